@@ -17,9 +17,11 @@ the same K steps are measured again as replays of a hipGraph of up to 16 env-ste
 of the two is reported (`config.exchange` says which; a failed or stalled attempt leaves the eager result).
 
 Rank 0 prints ONE JSON line.  `roofline` is for the step kernel against HBM (algorithmic bytes per
-env-step x envs / average kernel duration measured with HIP events on the kernel's stream);
-`cpu_baseline` is the CPU oracle (a scalar C port; the reference's engine, mujoco, is not installed)
-timed on this host.
+env-step x envs / average kernel duration measured with HIP events on the kernel's stream).
+A plain run does only what that line's headline needs: set-up, device wake-up, W warm-up steps, the K timed
+steps.  --full adds the measurements that take runs of their own: `cpu_baseline`, the CPU oracle (a scalar
+C port; the reference's engine, mujoco, is not installed) timed on this host, and for N > 1 `config4`.
+--dump-outputs DIR writes what the timed path returned in its last env-step (rank 0's shard) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -118,6 +120,23 @@ def cpu_baseline(n_envs: int, frame_skip: int, seconds: float):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs):
+    """`outs`: name -> array with the env on axis 0.  Beyond DUMP_LIMIT_BYTES in all, the same seeded sample of envs is taken from
+    every array, and its indices are written too (env_index.npy)."""
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(outs.values())))
+    total = sum(a.nbytes for a in outs.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, int(n * (DUMP_LIMIT_BYTES - 8 * n) / total), replace=False))
+        outs = {k: a[keep] for k, a in outs.items()}
+        outs["env_index"] = keep.astype(np.float64)
+    for name, a in outs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def _cpu_model():
     try:
         with open("/proc/cpuinfo") as fh:
@@ -141,8 +160,14 @@ def main():
     ap.add_argument("--joint-jitter", type=float, default=0.0, metavar="RAD",
                     help="BASELINE config 3 option: hinges restart at qpos0 + RAD * U(-1,1) at every (re)set")
     ap.add_argument("--sync-gather", action="store_true", help="do not overlap the RCCL gather with the next step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baseline (cpu_baseline) and, for N > 1, BASELINE config 4's "
+                         "shard (config4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last env-step (obs, reward, done of rank "
+                         "0's shard; a fixed sample of the envs beyond 64 MB) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--walking", action="store_true", help="time the walking task layer too (SURVEY 8 f1): pre + physics + post kernels per env-step")
     ap.add_argument("--rehearse-shared-gpu", action="store_true",
                     help="development only: every rank uses GPU 0 and the gather goes through gloo on CPU copies, to exercise the "
@@ -170,7 +195,7 @@ def main():
                     help="development only: skip the data.ctrl write-back (48 B/env) the reference's step maintains; such a line is "
                          "marked `ctrl_tracking: false` and is not the reported configuration")
     ap.add_argument("--config4-steps", type=int, default=-1, metavar="K4",
-                    help="N > 1 only: after the headline, BASELINE config 4's per-GPU shard (32 768 envs, random yaw, one gather of "
+                    help="N > 1 with --full only: after the headline, BASELINE config 4's per-GPU shard (32 768 envs, random yaw, one gather of "
                          "[32768, obs+2] f32 per env-step) is timed in the same process for K4 steps and attached as `config4`; "
                          "-1 (default) = max(--steps, 200), 0 = skip")
     ap.add_argument("--seq", type=int, default=0, metavar="S",
@@ -583,7 +608,7 @@ def main():
     # 262 144 envs over 8 GPUs = 32 768 per GPU, random yaw at every (re)set, per env-step ONE gather of the packed [32 768, obs + 2]
     # f32 rows (4.59 MB per rank) to rank 0, double-buffered and overlapped exactly like the headline's (eager issue from the host).
     k4 = args.config4_steps if args.config4_steps >= 0 else max(args.steps, 200)
-    if use_dist and native is None and walk is None and multi is None and k4 > 0 and gatherer is not None:
+    if args.full and use_dist and native is None and walk is None and multi is None and k4 > 0 and gatherer is not None:
         n4 = 32768
         t4 = _abi.default_task()
         t4.frame_skip, t4.obs_mode, t4.use_fall, t4.fall_height, t4.auto_reset = args.frame_skip, args.obs_mode, 1, 0.05, 1
@@ -717,7 +742,22 @@ def main():
         line["config4"] = config4
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            torch.cuda.synchronize(dev)
+            if walk is not None:
+                outs = {"obs": w_obs, "reward": w_rew, "done": w_done}
+            else:
+                if multi is not None:                    # env-step i of these forms writes slot i % slots
+                    last = rows_t[(args.warmup + args.steps - 1) % multi["slots"]]
+                elif native is not None:                 # every qg_comm_rollout call starts again at packed[0]
+                    last = packed[(args.steps - 1) & 1]
+                elif state["graph"] is not None:         # a replay of G env-steps ends on packed[(G - 1) & 1]
+                    last = packed[(state["G"] - 1) & 1]
+                else:
+                    last = packed[(args.warmup + args.steps - 1) & 1]
+                outs = {"obs": last[:, :od], "reward": last[:, od], "done": last[:, od + 1]}
+            dump_outputs(args.dump_outputs, {k: v.float().cpu().numpy() for k, v in outs.items()})
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(n, args.frame_skip, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if native is not None:

@@ -1,7 +1,26 @@
 """Shared helpers for the test-suite (state sampling, model variants)."""
+import lzma
+import os
+import shutil
+
 import numpy as np
 
 NQ, NV, NU = 19, 18, 12
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def reference_model(tmp_dir):
+    """The reference robot's MJCF scene, unpacked from tests/golden/quadruped_model (tools/make_model_fixture.py) into
+    `tmp_dir`: the two XML files and every mesh's vertex positions.  Returns the path of scene.xml."""
+    src = os.path.join(GOLDEN, "quadruped_model")
+    out = os.path.join(str(tmp_dir), "quadruped")
+    os.makedirs(os.path.join(out, "mesh"), exist_ok=True)
+    for name in ("scene.xml", "quadruped.xml"):
+        shutil.copyfile(os.path.join(src, name), os.path.join(out, name))
+    for name in os.listdir(os.path.join(src, "mesh")):
+        with lzma.open(os.path.join(src, "mesh", name)) as fh, open(os.path.join(out, "mesh", name[:-len(".xz")]), "wb") as dst:
+            dst.write(fh.read())
+    return os.path.join(out, "scene.xml")
 
 
 def random_state(rng, model, z=1.0, vel=1.0, joint_margin=0.05):

@@ -41,6 +41,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 CONTRACT_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -57,7 +58,7 @@ def _free_port():
 
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line_on_one_gpu():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "200", "--warmup", "20", "--cpu-seconds", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "200", "--warmup", "20", "--full", "--cpu-seconds", "1"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -106,7 +107,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(envs_per_gpu):
     gather of the packed [32 768, 35] f32 rows per step)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "60", "--warmup", "10",
-           "--envs-per-gpu", str(envs_per_gpu), "--rehearse-shared-gpu", "--no-cpu-baseline"]
+           "--envs-per-gpu", str(envs_per_gpu), "--rehearse-shared-gpu", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -154,3 +155,46 @@ def test_exchange_auto_reports_a_valid_line_whatever_the_graph_attempt_does(faul
     else:
         assert d["config"]["exchange"] == "eager" and "exchange_note" in d["config"]
         assert ("injected" in d["config"]["exchange_note"]) == (fault == "raise")
+
+
+def test_bench_offers_full_and_dump_outputs():
+    b = _bench()
+    assert b.DUMP_LIMIT_BYTES == 64 << 20
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60, cwd=ROOT)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+def test_dump_outputs_samples_the_same_envs_of_every_array_beyond_the_limit(tmp_path, monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 4096)
+    obs = np.arange(100 * 33, dtype=np.float32).reshape(100, 33)
+    rew = np.arange(100, dtype=np.float32)
+    b.dump_outputs(str(tmp_path / "a"), {"obs": obs, "reward": rew})
+    b.dump_outputs(str(tmp_path / "b"), {"obs": obs, "reward": rew})
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    o, r = np.load(tmp_path / "a" / "obs.npy"), np.load(tmp_path / "a" / "reward.npy")
+    assert idx.dtype == np.float64 and o.dtype == np.float32 and r.dtype == np.float32
+    assert o.nbytes + r.nbytes + idx.nbytes <= 4096 and len(idx) > 0 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(o, obs[idx.astype(int)]) and np.array_equal(r, rew[idx.astype(int)])
+    assert all(np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in ("obs.npy", "reward.npy", "env_index.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_lean_and_dumps_the_same_outputs_every_run(tmp_path):
+    """Without --full the line carries only the headline (no cpu_baseline); --steps is the number of timed steps; --dump-outputs writes
+    the last env-step's obs / reward / done, and two runs with the same arguments write the same bits."""
+    lines = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "7",
+                              "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0]))
+    for d in lines:
+        assert CONTRACT_KEYS <= set(d) and "cpu_baseline" not in d and d["steps"] == 50 and d["warmup"] == 7
+        assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for name, shape in (("obs", (4096, 33)), ("reward", (4096,)), ("done", (4096,))):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all()
+        assert np.array_equal(a, b), name
+    assert set(np.unique(np.load(tmp_path / "a" / "done.npy"))) <= {0.0, 1.0}
+    assert not os.path.exists(tmp_path / "a" / "env_index.npy")

@@ -6,7 +6,6 @@ oracle is pinned by physics identities instead: the parity
 of the oracle against MuJoCo itself is UNPINNED.
 """
 import math
-import os
 
 import numpy as np
 import pytest
@@ -435,15 +434,13 @@ def test_standing_height_at_the_joint_centre_command_follows_the_geometry(oracle
     assert q[2] - 0.13 > 0.012 and q[2] - 0.12 > 0.022              # walking_quad.py:243-247,369: not this robot's stance height
 
 
-REF_MODEL_DIR = "/root/reference/src/models/quadruped"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_MODEL_DIR), reason="reference checkout not present on this host")
-def test_standing_height_from_the_reference_meshes(oracle, model, task):
+def test_standing_height_from_the_reference_meshes(tmp_path, oracle, model, task):
     """The same geometric height from the reference's own files: every vertex of the convex hulls of the OBJ meshes, placed by the
-    XML's geom frames (model/compiler.py), instead of the eight sample points per body the model ships with."""
+    XML's geom frames (model/compiler.py), instead of the eight sample points per body the model ships with.  The files are
+    stored under tests/golden/quadruped_model (every mesh vertex, tools/make_model_fixture.py)."""
+    from helpers import reference_model
     from quadruped_gym_amd.model import compiler as MC
-    full = MC.compile_mjcf(os.path.join(REF_MODEL_DIR, "scene.xml"), keep_hulls=True)
+    full = MC.compile_mjcf(reference_model(tmp_path), keep_hulls=True)
     clouds = full.get("hull_clouds")
     assert clouds is not None and len(clouds) == 13
     h_full = _lowest_point_below_frame(oracle, model, np.array([0, 0, -0.78125] * 4), {b: np.asarray(clouds[b]) for b in range(13)})
