@@ -84,6 +84,7 @@ extern "C" {
 #define QG_RESET_RANDOM_YAW 1u   /* walking_quad.py:68-75: qpos[3:7] = [cos a/2, 0, 0, sin a/2], a ~ U(0, 2 pi) */
 #define QG_RESET_JOINT_JITTER 2u /* hinge j starts at qpos0 + reset_joint_jitter * U(-1, 1), clamped to its range (the reference's open
                                     "RANDOMIZE ENVIRONMENT - Starting pose, joints" item, TODO.md:8; SURVEY config 3 option) */
+#define QG_RESET_DYNAMICS 4u     /* draw a new per-env dynamics row (qg_set_dynamics_range) for the envs reset; refused without a range */
 
 /* Robot constants: what mujoco.MjModel.from_xml_path (quadruped.py:59) compiles
  * out of scene.xml.  Topology is fixed (body 0 = FRAME with the free joint, body
@@ -394,6 +395,54 @@ int qg_po_step_device(qg_po *po, const float *actions, float *obs, float *reward
 int64_t qg_po_state_bytes(const qg_po *po);
 int qg_po_get_state(qg_po *po, void *blob);
 int qg_po_set_state(qg_po *po, const void *blob);
+
+/* ---- per-env dynamics randomisation -----------------------------------------------------------------------------------------
+ * Every env of a handle runs one qg_model; with this mode on, each env also has a row of QG_NDYN f32 that changes the handle's model
+ * for that env alone (the reference's SubprocVecEnv gives each env its own MjModel; its TODO.md:8 "RANDOMIZE ENVIRONMENT ... etc."):
+ *   col  name                     effect on the handle's model for this env
+ *   0    friction                 contact_friction = value (absolute Coulomb mu)
+ *   1    payload_mass             point mass dm (kg, may be negative) rigidly fixed to the FRAME at ...
+ *   2-4  payload_pos              ... point p, FRAME body coordinates (m): m0' = m0 + dm, h0' = h0 + dm p, I0' = I0 + dm (|p|^2 E - p p^T)
+ *                                 (the FRAME's rigid inertia about its origin)
+ *   5    kp_scale                 act_kp[j] x value, all 12 servos
+ *   6    kv_scale                 act_kv[j] x value
+ *   7    force_scale              both ends of act_forcerange[j] x value (motor strength)
+ *   8    damping_scale            jnt_damping[j] x value (the 12 hinges, not the free joint)
+ *   9    contact_stiffness_scale  contact_stiffness x value
+ *   10   contact_damping_scale    contact_damping x value
+ * The identity row is (model.contact_friction, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1); with it an env computes the shared model's bits.
+ * Draws (QG_RESET_DYNAMICS in qg_reset / qg_walk_reset / qg_po_reset, or in task.reset_flags for auto-resets): column k of env i for
+ * episode e is lo[k] + (hi[k] - lo[k]) u, u = the uniform of stream 16 + k of the (seed, env_index_base + i, e) key -- the key the reset
+ * yaw of that episode uses (streams 0..15: yaw, hinge jitter, command; unchanged).  Without the flag rows persist across resets.
+ * Validation (QG_ERR_ARG): non-finite values, friction or a scale < 0, a FRAME mass m0 + dm <= 0, a rotational inertia about the new
+ * centre of mass that is not positive definite (a range: at its corners).
+ * While the mode is on the generic (table-driven) step kernels run in their per-env form, LINK up to 4096 envs and QUAD above (also for
+ * the compiled-in robot: qg_uses_baked_model returns 0); qg_step_device_seq and the resident form are refused, as are the PAIR and LANE
+ * mappings. */
+#define QG_NDYN 11
+#define QG_DYN_FRICTION 0
+#define QG_DYN_PAYLOAD_MASS 1
+#define QG_DYN_PAYLOAD_X 2
+#define QG_DYN_PAYLOAD_Y 3
+#define QG_DYN_PAYLOAD_Z 4
+#define QG_DYN_KP_SCALE 5
+#define QG_DYN_KV_SCALE 6
+#define QG_DYN_FORCE_SCALE 7
+#define QG_DYN_DAMPING_SCALE 8
+#define QG_DYN_CONTACT_STIFFNESS_SCALE 9
+#define QG_DYN_CONTACT_DAMPING_SCALE 10
+typedef struct { float lo[QG_NDYN], hi[QG_NDYN]; } qg_dynamics_range;
+/* Validates and stores the range QG_RESET_DYNAMICS draws from (lo <= hi per column); switches the mode on (identity rows until the
+ * first draw).  Like the other entry points that touch the per-env state, these four calls first wait for all work on the handle's
+ * device (the ordering contract at the top of this file). */
+int qg_set_dynamics_range(qg_sim *sim, const qg_dynamics_range *range);
+/* Sets rows explicitly (curricula, tests): rows is a host [n_envs][QG_NDYN] array; mask == NULL sets every env, else only
+ * mask[i] != 0 (the other rows are kept).  Switches the mode on. */
+int qg_set_dynamics(qg_sim *sim, const uint8_t *mask, const float *rows);
+/* The current rows into a host [n_envs][QG_NDYN] array; identity rows while the mode is off. */
+int qg_get_dynamics(qg_sim *sim, float *rows);
+/* Back to the shared model (the range is dropped too); the compiled-in robot's baked kernels run again. */
+int qg_clear_dynamics(qg_sim *sim);
 
 #ifdef __cplusplus
 }

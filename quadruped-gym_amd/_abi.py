@@ -13,6 +13,11 @@ NBODY, NJNT, NQ, NV, NU, NSENSOR, MAXCP, NREWARD = 13, 12, 19, 18, 12, 33, 12, 3
 OBS_FULL, OBS_IMU = 0, 1
 RESET_RANDOM_YAW = 1
 RESET_JOINT_JITTER = 2
+RESET_DYNAMICS = 4
+# per-env dynamics rows (QG_DYN_* of include/quadgym.h): column order of the [n, NDYN] arrays
+NDYN = 11
+DYN_COLUMNS = ("friction", "payload_mass", "payload_x", "payload_y", "payload_z", "kp_scale", "kv_scale", "force_scale",
+               "damping_scale", "contact_stiffness_scale", "contact_damping_scale")
 CMD_FIXED_HEADING, CMD_FIXED_VELOCITY_ANGLE, CMD_FIXED_SPEED = 1, 2, 4
 MAP_AUTO, MAP_LANE, MAP_QUAD, MAP_PAIR, MAP_LINK = 0, 1, 2, 3, 4
 OBS_DIM = {OBS_FULL: 33, OBS_IMU: 21}
@@ -73,6 +78,10 @@ class QgTask(C.Structure):
         ("default_ctrl", C.c_double * NU),
         ("reset_joint_jitter", C.c_double),
     ]
+
+
+class QgDynamicsRange(C.Structure):
+    _fields_ = [("lo", C.c_float * NDYN), ("hi", C.c_float * NDYN)]
 
 
 class QgCommandSampler(C.Structure):
@@ -222,6 +231,10 @@ def load_library():
     lib.qg_resident_step_device.argtypes = [vp, C.c_int32, vp]
     lib.qg_resident_ensure.argtypes = [vp]
     lib.qg_resident_status.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.qg_set_dynamics_range.argtypes = [vp, C.POINTER(QgDynamicsRange)]
+    lib.qg_set_dynamics.argtypes = [vp, vp, vp]
+    lib.qg_get_dynamics.argtypes = [vp, vp]
+    lib.qg_clear_dynamics.argtypes = [vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("qg_version", "qg_build_id", "qg_last_error", "qg_time_limit_substeps", "qg_walk_state_bytes", "qg_po_state_bytes",
@@ -245,6 +258,7 @@ EXPORTS = (
     "qg_get_reset_streams", "qg_set_reset_streams",
     "qg_step_device_seq", "qg_resident_start", "qg_resident_stop", "qg_resident_buffers", "qg_resident_step_device",
     "qg_resident_ensure", "qg_resident_status",
+    "qg_set_dynamics_range", "qg_set_dynamics", "qg_get_dynamics", "qg_clear_dynamics",
 )
 
 
@@ -262,6 +276,38 @@ def recommended_batch(n_envs: int, device: int = -1) -> int:
     """The batch size at the top of the step-time stair ``n_envs`` stands on (``qg_recommended_batch``): 4096, 16 384, then multiples
     of 32 768 on an MI355X.  ``device=-1`` assumes an MI355X (no GPU needed)."""
     return int(load_library().qg_recommended_batch(int(n_envs), int(device)))
+
+
+def identity_dynamics_row(model: QgModel):
+    """The row that leaves ``model`` as it is: ``(contact_friction, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1)`` (f32)."""
+    import numpy as np
+    row = np.ones(NDYN, np.float32)
+    row[0] = np.float32(model.contact_friction)
+    row[1:5] = 0.0
+    return row
+
+
+def dynamics_range(spec: dict, model: QgModel) -> QgDynamicsRange:
+    """``qg_dynamics_range`` from a dict: ``{"friction": (lo, hi), "payload_mass": (lo, hi), "payload_pos": ((lo, hi), (lo, hi),
+    (lo, hi)), "kp_scale": (lo, hi), ...}`` -- the column names of ``DYN_COLUMNS`` (``payload_pos`` for x, y, z).  Missing keys stay at
+    the identity."""
+    ident = identity_dynamics_row(model)
+    lo, hi = ident.copy(), ident.copy()
+    for key, val in spec.items():
+        if key == "payload_pos":
+            pairs = list(val)
+            if len(pairs) != 3:
+                raise ValueError("payload_pos: three (lo, hi) pairs, for x, y and z")
+            for d, pair in enumerate(pairs):
+                lo[2 + d], hi[2 + d] = pair
+        elif key in DYN_COLUMNS and key not in ("payload_x", "payload_y", "payload_z"):
+            lo[DYN_COLUMNS.index(key)], hi[DYN_COLUMNS.index(key)] = val
+        else:
+            raise ValueError(f"dynamics key {key!r}: one of friction, payload_mass, payload_pos, " + ", ".join(DYN_COLUMNS[5:]))
+    r = QgDynamicsRange()
+    for c in range(NDYN):
+        r.lo[c], r.hi[c] = float(lo[c]), float(hi[c])
+    return r
 
 
 def default_model() -> QgModel:

@@ -48,6 +48,13 @@ struct qg_sim {
     int32_t track_ctrl;
     int32_t link_helpers;     // walking forms of the one-link-per-lane kernel run with helper waves (QG_LINK_HELPERS at qg_create; default 1)
     int32_t baked;            // 1: the model equals the compiled-in default, the literal-constant kernel variant runs
+    int32_t model_baked;      // what `baked` is with the per-env dynamics off (the mode runs the table-driven kernels)
+    // per-env dynamics (qg_set_dynamics_range / qg_set_dynamics)
+    int32_t dyn;              // the mode is on: the per-env forms of the table-driven step kernels run
+    int32_t dyn_range_set;    // QG_RESET_DYNAMICS may draw
+    KDynRange dyn_range;
+    float *d_dyn;             // [QG_NDYN][n]
+    KModelDyn *d_model_dyn;   // the model tables and d_dyn: the per-env kernels' model pointer
     int32_t mapping;          // QG_MAP_AUTO / QG_MAP_LANE / QG_MAP_QUAD (request)
     int32_t creating;
     int32_t walk_bound;       // qg_walk layers bound to this handle (qg_set_task refuses while > 0)
@@ -153,7 +160,7 @@ extern "C" int qg_destroy(qg_sim *s) {
     (void)hipDeviceSynchronize();                  // steps may still be in flight on a caller's stream (the header's ordering contract)
     resident_free(s);
     void *ptrs[] = {s->d_model, s->d_task, s->st.qpos, s->st.qvel, s->st.act, s->st.ctrl, s->st.nstep, s->st.episode, s->d_actions,
-                    s->d_obs,   s->d_reward, s->d_comps, s->d_stage, s->d_done, s->d_mask};
+                    s->d_obs,   s->d_reward, s->d_comps, s->d_stage, s->d_done, s->d_mask, s->d_dyn, s->d_model_dyn};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->h_pin) (void)hipHostFree(s->h_pin);
@@ -204,6 +211,7 @@ extern "C" int qg_create(int32_t n_envs, int32_t device_id, const qg_model *mode
     {
         static const KModel baked = {QG_BAKED_FLOATS};
         s->baked = QG_BAKED_LEGS_IDENTICAL && memcmp(&km, &baked, sizeof km) == 0;
+        s->model_baked = s->baked;
     }
     size_t n = (size_t)n_envs;
 #define ALLOC(ptr, bytes)                                                                   \
@@ -266,6 +274,7 @@ extern "C" int qg_reset(qg_sim *s, const uint8_t *mask, uint64_t seed, uint32_t 
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
     // the seed keys the reset streams of EVERY env (auto-resets included): only a whole-batch reset may change it, a masked
     // reset draws from the streams already in force
+    if ((flags & QG_RESET_DYNAMICS) && !s->dyn_range_set) return fail(QG_ERR_ARG, "qg_reset: QG_RESET_DYNAMICS without a range (qg_set_dynamics_range)");
     if (!mask) s->seed = seed;
     else seed = s->seed;
     const uint8_t *dmask = nullptr;
@@ -274,6 +283,12 @@ extern "C" int qg_reset(qg_sim *s, const uint8_t *mask, uint64_t seed, uint32_t 
         dmask = s->d_mask;
     }
     int threads = 256, blocks = (s->n + threads - 1) / threads;
+    if (flags & QG_RESET_DYNAMICS) {                 // keyed by the episode that begins: the counter before the reset kernel advances it
+        const int total = QG_NDYN * s->n;
+        hipLaunchKernelGGL(qg_dyn_draw_kernel, dim3((total + threads - 1) / threads), dim3(threads), 0, s->stream, s->d_dyn, s->dyn_range,
+                           (const int32_t *)s->st.episode, s->n, dmask, (const uint8_t *)nullptr, (const float *)nullptr, 0, 0, seed, s->env_index_base);
+        HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
+    }
     hipLaunchKernelGGL(qg_reset_kernel, dim3(blocks), dim3(threads), 0, s->stream, s->d_model, s->d_task, s->st, s->n, dmask, seed,
                        s->env_index_base, flags, s->creating ? 0 : 1);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
@@ -358,7 +373,31 @@ static int launch_step(qg_sim *s, const float *d_actions, float *d_obs, float *d
         }
     }
     if (po && !(walk && po_fusable(s))) return fail(QG_ERR_ARG, "launch_step: no step kernel with the fused observation pack for this handle");
-    if (walk && emap == QG_MAP_LINK) {
+    const bool dyn_draw = s->task.auto_reset && (s->task.reset_flags & QG_RESET_DYNAMICS);
+    if (dyn_draw && !s->dyn_range_set) return fail(QG_ERR_ARG, "step: task.reset_flags has QG_RESET_DYNAMICS and no range is set (qg_set_dynamics_range)");
+    if (s->dyn) {
+        // per-env dynamics: the table-driven kernels' per-env forms, one link per lane up to 4096 envs (lagged sensors), one leg per lane
+        // above (qg_set_mapping refuses the other mappings while the mode is on)
+        const KModel *dm = &s->d_model_dyn->m;
+        if (emap == QG_MAP_LINK) {
+            const int per_block = QGK_LINK_ENVS * QGK_LINK_WAVES;
+            dim3 lg((s->n + per_block - 1) / per_block), lb(QGK_WAVE * QGK_LINK_WAVES);
+            if (po) hipLaunchKernelGGL((qg_step_kernel_link<true, true, false, false, true>), lg, lb, 0, stream, dm, s->d_task, P, *walk, *po);
+            else if (walk) hipLaunchKernelGGL((qg_step_kernel_link<true, false, false, false, true>), lg, lb, 0, stream, dm, s->d_task, P, *walk, KPoNone{});
+            else hipLaunchKernelGGL((qg_step_kernel_link<false, false, false, false, true>), lg, lb, 0, stream, dm, s->d_task, P, KWalkNone{}, KPoNone{});
+        } else if (emap == QG_MAP_QUAD) {
+            const int qblocks = (s->n + QGK_QUAD_ENVS - 1) / QGK_QUAD_ENVS;
+            const bool wg4 = qblocks > s->simds / 4;
+            dim3 g1(qblocks), b1(QGK_WAVE), g4((qblocks + 3) / 4), b4(QGK_WAVE * 4);
+            if (po) hipLaunchKernelGGL((qg_step_kernel_quad<1, false, true, 4, true, false, true>), g4, b4, 0, stream, dm, s->d_task, P, *walk, *po);
+            else if (walk && wg4) hipLaunchKernelGGL((qg_step_kernel_quad<1, false, true, 4, false, false, true>), g4, b4, 0, stream, dm, s->d_task, P, *walk, KPoNone{});
+            else if (walk) hipLaunchKernelGGL((qg_step_kernel_quad<1, false, true, 1, false, false, true>), g1, b1, 0, stream, dm, s->d_task, P, *walk, KPoNone{});
+            else if (wg4) hipLaunchKernelGGL((qg_step_kernel_quad<1, false, false, 4, false, false, true>), g4, b4, 0, stream, dm, s->d_task, P, KWalkNone{}, KPoNone{});
+            else hipLaunchKernelGGL((qg_step_kernel_quad<1, false, false, 1, false, false, true>), g1, b1, 0, stream, dm, s->d_task, P, KWalkNone{}, KPoNone{});
+        } else {
+            return fail(QG_ERR_ARG, "step: per-env dynamics run in the LINK and QUAD mappings only (mapping %d)", emap);
+        }
+    } else if (walk && emap == QG_MAP_LINK) {
         const int per_block = QGK_LINK_ENVS * QGK_LINK_WAVES;
         int lblocks = (s->n + per_block - 1) / per_block;
         dim3 lg(lblocks), lb(QGK_WAVE * QGK_LINK_WAVES);
@@ -443,6 +482,14 @@ static int launch_step(qg_sim *s, const float *d_actions, float *d_obs, float *d
                            (const uint8_t *)d_done, (const float *)d_packed, s->obs_dim + 2, s->seed, s->env_index_base);
         e = hipGetLastError();
         if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "qg_jitter_kernel launch: %s", hipGetErrorString(e));
+    }
+    if (dyn_draw) {     // new dynamics rows of the envs just auto-reset, keyed as their reset yaw (episode - 1 after the increment)
+        const int total = QG_NDYN * s->n, threads = 256;
+        hipLaunchKernelGGL(qg_dyn_draw_kernel, dim3((total + threads - 1) / threads), dim3(threads), 0, stream, s->d_dyn, s->dyn_range,
+                           (const int32_t *)s->st.episode, s->n, (const uint8_t *)nullptr, (const uint8_t *)d_done, (const float *)d_packed,
+                           s->obs_dim + 2, -1, s->seed, s->env_index_base);
+        e = hipGetLastError();
+        if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "qg_dyn_draw_kernel launch: %s", hipGetErrorString(e));
     }
     return QG_OK;
 }
@@ -648,6 +695,8 @@ extern "C" int qg_time_step_kernel(qg_sim *s, const float *d_actions, float *d_p
 
 extern "C" int qg_set_mapping(qg_sim *s, int32_t mapping) {
     if (!s) return fail(QG_ERR_ARG, "null handle");
+    if (s->dyn && (mapping == QG_MAP_PAIR || mapping == QG_MAP_LANE))
+        return fail(QG_ERR_ARG, "qg_set_mapping: per-env dynamics run in the LINK and QUAD mappings only (qg_clear_dynamics first)");
     if (mapping == QG_MAP_PAIR && !s->baked)
         return fail(QG_ERR_ARG, "qg_set_mapping: the two-legs-per-lane kernel serves the compiled-in robot only");
     if (mapping != QG_MAP_AUTO && mapping != QG_MAP_LANE && mapping != QG_MAP_QUAD && mapping != QG_MAP_PAIR && mapping != QG_MAP_LINK)
@@ -731,6 +780,7 @@ static dim3 multi_step_grid(const qg_sim *s) {
 
 extern "C" int qg_step_device_seq(qg_sim *s, const float *actions, float *packed, int32_t count, void *stream) {
     if (!s || !actions || !packed || count < 1) return fail(QG_ERR_ARG, "qg_step_device_seq: bad argument");
+    if (s->dyn) return fail(QG_ERR_ARG, "qg_step_device_seq: not available with per-env dynamics (qg_clear_dynamics first)");
     if (s->walk_bound) return fail(QG_ERR_ARG, "qg_step_device_seq: a walking task layer is bound to this handle");
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     int rc;
@@ -864,6 +914,7 @@ extern "C" int qg_resident_start(qg_sim *s, int32_t slots, int32_t idle_timeout_
     if (!s) return fail(QG_ERR_ARG, "null handle");
     if ((actions == nullptr) != (packed == nullptr)) return fail(QG_ERR_ARG, "qg_resident_start: pass both slot buffers or neither");
     if (s->res.active) return fail(QG_ERR_ARG, "qg_resident_start: already on");
+    if (s->dyn) return fail(QG_ERR_ARG, "qg_resident_start: not available with per-env dynamics (qg_clear_dynamics first)");
     if (slots < 1 || slots > 4096) return fail(QG_ERR_ARG, "qg_resident_start: slots must be 1..4096");
     if (idle_timeout_us == 0) idle_timeout_us = 2000;
     if (idle_timeout_us < 50 || idle_timeout_us > 100000) return fail(QG_ERR_ARG, "qg_resident_start: idle_timeout_us must be 50..100000 (0 = 2000)");
@@ -1316,6 +1367,7 @@ extern "C" int qg_walk_get_commands(qg_walk *w, float *velocity_xy, float *headi
 extern "C" int qg_walk_reset(qg_walk *w, const uint8_t *mask, uint64_t seed, uint32_t flags) {
     if (!w) return fail(QG_ERR_ARG, "null handle");
     qg_sim *s = w->sim;
+    if ((flags & QG_RESET_DYNAMICS) && !s->dyn_range_set) return fail(QG_ERR_ARG, "qg_walk_reset: QG_RESET_DYNAMICS without a range (qg_set_dynamics_range)");
     int rc = qg_reset(s, mask, seed, flags);           // uploads the mask into s->d_mask
     if (rc != QG_OK) return rc;
     int threads = 256, blocks = (s->n + threads - 1) / threads;
@@ -1592,6 +1644,8 @@ extern "C" int qg_po_create(qg_walk *w, int32_t obs_window, qg_po **out) {
 extern "C" int qg_po_reset(qg_po *p, const uint8_t *mask, uint64_t seed, uint32_t flags, float *obs) {
     if (!p) return fail(QG_ERR_ARG, "null handle");
     qg_sim *s = p->walk->sim;
+    // refused before anything is launched: a refused call leaves the observation pack as it was
+    if ((flags & QG_RESET_DYNAMICS) && !s->dyn_range_set) return fail(QG_ERR_ARG, "qg_po_reset: QG_RESET_DYNAMICS without a range (qg_set_dynamics_range)");
     // the reset frame shows the estimate and the command as they stand BEFORE the robots / commands are reset (:59-69)
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);   // device-pointer steps may be in flight on a caller's stream
@@ -1682,4 +1736,167 @@ extern "C" int qg_po_set_state(qg_po *p, const void *blob) {
     if (!p || !blob) return fail(QG_ERR_ARG, "qg_po_set_state: null argument");
     QgField f[QG_MAX_FIELDS];
     return blob_in(p->walk->sim, QG_BLOB_PO, p->kp.window, f, po_fields(p, f), blob, "qg_po_set_state");
+}
+
+// ------------------------------------------------------------------------------------------------------
+// per-env dynamics (include/quadgym.h, QG_NDYN columns)
+// ------------------------------------------------------------------------------------------------------
+static void dyn_identity_row(const qg_sim *s, float row[QG_NDYN]) {
+    for (int c = 0; c < QG_NDYN; c++) row[c] = 1.f;
+    row[QG_DYN_FRICTION] = (float)s->model.contact_friction;
+    row[QG_DYN_PAYLOAD_MASS] = row[QG_DYN_PAYLOAD_X] = row[QG_DYN_PAYLOAD_Y] = row[QG_DYN_PAYLOAD_Z] = 0.f;
+}
+// one row against the model: finite, friction and scales >= 0, FRAME mass > 0, rotational inertia about the new centre of mass positive
+// definite (f64; what the payload does to the FRAME's rigid inertia, the same rule as the kernels' dyn_load)
+static int dyn_check_row(const qg_sim *s, const float *row, const char *who, const char *what) {
+    for (int c = 0; c < QG_NDYN; c++) {      // (exponent bits: the device pass, which parses this too, assumes finite math)
+        uint32_t bits;
+        memcpy(&bits, row + c, 4);
+        if (((bits >> 23) & 0xFFu) == 0xFFu) return fail(QG_ERR_ARG, "%s: %s: column %d is not finite", who, what, c);
+    }
+    if (row[QG_DYN_FRICTION] < 0) return fail(QG_ERR_ARG, "%s: %s: friction %g < 0", who, what, (double)row[QG_DYN_FRICTION]);
+    for (int c = QG_DYN_KP_SCALE; c < QG_NDYN; c++)
+        if (row[c] < 0) return fail(QG_ERR_ARG, "%s: %s: scale column %d is %g < 0", who, what, c, (double)row[c]);
+    const qg_model &m = s->model;
+    const double dm = row[QG_DYN_PAYLOAD_MASS], p[3] = {row[QG_DYN_PAYLOAD_X], row[QG_DYN_PAYLOAD_Y], row[QG_DYN_PAYLOAD_Z]};
+    const double m1 = m.body_mass[0] + dm;
+    if (!(m1 > 0)) return fail(QG_ERR_ARG, "%s: %s: FRAME mass %g + payload %g <= 0", who, what, m.body_mass[0], dm);
+    // about the FRAME origin: body inertia (about its COM) shifted there, plus the point mass
+    const double *c0 = m.body_ipos[0], *I = m.body_inertia[0], m0 = m.body_mass[0];
+    double J[3][3] = {{I[0], I[3], I[4]}, {I[3], I[1], I[5]}, {I[4], I[5], I[2]}};
+    const double cc = c0[0] * c0[0] + c0[1] * c0[1] + c0[2] * c0[2], pp = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+    double h[3];
+    for (int a = 0; a < 3; a++) {
+        h[a] = m0 * c0[a] + dm * p[a];
+        for (int b = 0; b < 3; b++) J[a][b] += m0 * ((a == b ? cc : 0) - c0[a] * c0[b]) + dm * ((a == b ? pp : 0) - p[a] * p[b]);
+    }
+    // back to the new centre of mass c1 = h / m1
+    const double c1[3] = {h[0] / m1, h[1] / m1, h[2] / m1}, c1c1 = c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2];
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) J[a][b] -= m1 * ((a == b ? c1c1 : 0) - c1[a] * c1[b]);
+    const double d1 = J[0][0], d2 = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+    const double d3 = J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0]) +
+                      J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+    if (!(d1 > 0 && d2 > 0 && d3 > 0))
+        return fail(QG_ERR_ARG, "%s: %s: the FRAME's rotational inertia about its centre of mass is not positive definite with payload %g kg at (%g, %g, %g)",
+                    who, what, dm, p[0], p[1], p[2]);
+    return QG_OK;
+}
+// switch the mode on: the row buffer (identity rows) and the per-env kernels' model pointer, the table-driven kernels
+static int dyn_enable(qg_sim *s, const char *who) {
+    if (s->dyn) return QG_OK;
+    if (s->mapping == QG_MAP_LANE || s->mapping == QG_MAP_PAIR)
+        return fail(QG_ERR_ARG, "%s: per-env dynamics run in the LINK and QUAD mappings only (qg_set_mapping AUTO, LINK or QUAD first)", who);
+    if (s->res.active) return fail(QG_ERR_ARG, "%s: the resident step mode is on (qg_resident_stop first)", who);
+    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);        // steps of the shared model may be in flight on a caller's stream
+    const size_t n = (size_t)s->n;
+    if (!s->d_dyn) HIP_TRY(hipMalloc((void **)&s->d_dyn, n * QG_NDYN * sizeof(float)), QG_ERR_ALLOC);
+    if (!s->d_model_dyn) HIP_TRY(hipMalloc((void **)&s->d_model_dyn, sizeof(KModelDyn)), QG_ERR_ALLOC);
+    HIP_TRY(hipMemcpy(&s->d_model_dyn->m, s->d_model, sizeof(KModel), hipMemcpyDeviceToDevice), QG_ERR_DEVICE);
+    const float *rows = s->d_dyn;
+    HIP_TRY(hipMemcpy(&s->d_model_dyn->rows, &rows, sizeof rows, hipMemcpyHostToDevice), QG_ERR_DEVICE);
+    float id[QG_NDYN];
+    dyn_identity_row(s, id);
+    float *h = (float *)malloc(n * QG_NDYN * sizeof(float));
+    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
+    for (int c = 0; c < QG_NDYN; c++)
+        for (size_t i = 0; i < n; i++) h[c * n + i] = id[c];
+    hipError_t e = hipMemcpy(s->d_dyn, h, n * QG_NDYN * sizeof(float), hipMemcpyHostToDevice);
+    free(h);
+    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    s->dyn = 1;
+    s->baked = 0;
+    return QG_OK;
+}
+
+extern "C" int qg_set_dynamics_range(qg_sim *s, const qg_dynamics_range *r) {
+    if (!s || !r) return fail(QG_ERR_ARG, "qg_set_dynamics_range: null argument");
+    for (int c = 0; c < QG_NDYN; c++)
+        if (!(r->lo[c] <= r->hi[c])) return fail(QG_ERR_ARG, "qg_set_dynamics_range: column %d: lo %g > hi %g (or not a number)", c, (double)r->lo[c], (double)r->hi[c]);
+    // every corner of (payload mass, x, y, z) and both ends of the other columns
+    for (int corner = 0; corner < 16; corner++) {
+        float row[QG_NDYN];
+        for (int c = 0; c < QG_NDYN; c++) row[c] = r->lo[c];
+        for (int b = 0; b < 4; b++) row[QG_DYN_PAYLOAD_MASS + b] = (corner >> b) & 1 ? r->hi[QG_DYN_PAYLOAD_MASS + b] : r->lo[QG_DYN_PAYLOAD_MASS + b];
+        int rc = dyn_check_row(s, row, "qg_set_dynamics_range", "lo corner");
+        if (rc != QG_OK) return rc;
+        for (int c = 0; c < QG_NDYN; c++)
+            if (c < QG_DYN_PAYLOAD_MASS || c > QG_DYN_PAYLOAD_Z) row[c] = r->hi[c];
+        rc = dyn_check_row(s, row, "qg_set_dynamics_range", "hi corner");
+        if (rc != QG_OK) return rc;
+    }
+    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
+    int rc = dyn_enable(s, "qg_set_dynamics_range");
+    if (rc != QG_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);        // (the range takes effect from the next call that draws)
+    memcpy(s->dyn_range.lo, r->lo, sizeof r->lo);
+    memcpy(s->dyn_range.hi, r->hi, sizeof r->hi);
+    s->dyn_range_set = 1;
+    return QG_OK;
+}
+
+extern "C" int qg_get_dynamics(qg_sim *s, float *rows) {
+    if (!s || !rows) return fail(QG_ERR_ARG, "qg_get_dynamics: null argument");
+    const size_t n = (size_t)s->n;
+    if (!s->dyn) {
+        float id[QG_NDYN];
+        dyn_identity_row(s, id);
+        for (size_t i = 0; i < n; i++) memcpy(rows + i * QG_NDYN, id, sizeof id);
+        return QG_OK;
+    }
+    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
+    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    float *h = (float *)malloc(n * QG_NDYN * sizeof(float));
+    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
+    hipError_t e = hipMemcpy(h, s->d_dyn, n * QG_NDYN * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        for (int c = 0; c < QG_NDYN; c++)
+            for (size_t i = 0; i < n; i++) rows[i * QG_NDYN + c] = h[c * n + i];
+    free(h);
+    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_get_dynamics: %s", hipGetErrorString(e));
+    return QG_OK;
+}
+
+extern "C" int qg_set_dynamics(qg_sim *s, const uint8_t *mask, const float *rows) {
+    if (!s || !rows) return fail(QG_ERR_ARG, "qg_set_dynamics: null argument");
+    const size_t n = (size_t)s->n;
+    char what[48];
+    for (size_t i = 0; i < n; i++) {
+        if (mask && !mask[i]) continue;
+        snprintf(what, sizeof what, "env %zu", i);
+        int rc = dyn_check_row(s, rows + i * QG_NDYN, "qg_set_dynamics", what);
+        if (rc != QG_OK) return rc;
+    }
+    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
+    int rc = dyn_enable(s, "qg_set_dynamics");
+    if (rc != QG_OK) return rc;
+    // read-modify-write of the rows: steps (and their auto-reset draws) may be in flight on a caller's stream even when the mode was
+    // already on (dyn_enable then returns at once) -- the header's ordering contract
+    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    float *h = (float *)malloc(n * QG_NDYN * sizeof(float));
+    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
+    hipError_t e = hipMemcpy(h, s->d_dyn, n * QG_NDYN * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) {
+        for (size_t i = 0; i < n; i++)
+            if (!mask || mask[i])
+                for (int c = 0; c < QG_NDYN; c++) h[c * n + i] = rows[i * QG_NDYN + c];
+        e = hipMemcpy(s->d_dyn, h, n * QG_NDYN * sizeof(float), hipMemcpyHostToDevice);
+    }
+    free(h);
+    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_set_dynamics: %s", hipGetErrorString(e));
+    return QG_OK;
+}
+
+extern "C" int qg_clear_dynamics(qg_sim *s) {
+    if (!s) return fail(QG_ERR_ARG, "null handle");
+    if (!s->dyn) return QG_OK;
+    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);        // per-env steps may be in flight on a caller's stream
+    s->dyn = 0;
+    s->dyn_range_set = 0;
+    s->baked = s->model_baked;
+    return QG_OK;
 }

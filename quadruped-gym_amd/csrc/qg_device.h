@@ -37,6 +37,22 @@ struct KModel {
     KLink link[QGK_NLINK];
 };
 
+// Per-env dynamics (qg_set_dynamics_range / qg_set_dynamics): QG_NDYN f32 columns per env in HBM, field-major, env-minor ([11][n],
+// the state's layout).  The per-env-dynamics variants of the generic step kernels get a KModelDyn as their model pointer: the shared
+// tables followed by the rows' address -- the kernel arguments (and so the existing variants' code) stay as they are.
+#define QGK_NDYN 11
+struct KModelDyn {
+    KModel m;
+    const float *rows;        // [QGK_NDYN][n]
+};
+// what one lane holds of its env's row: the replaced contact constants, the servo / hinge scales, the FRAME's rigid inertia about its
+// origin with the payload added
+struct KDyn {
+    float mu, kc, cc;                         // contact friction, stiffness, damping
+    float kp, kv, force, damping;             // scales of act_kp, act_kv, act_forcerange, jnt_damping
+    float m0, h0[3], I0[6];
+};
+
 struct KTask {
     int32_t frame_skip;
     int32_t limit_substeps;   // substep count at which data.time >= max_time (f64 accumulation), or INT32_MAX

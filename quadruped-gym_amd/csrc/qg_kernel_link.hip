@@ -132,9 +132,11 @@ DEV V3 sel3(int r, V3 a, V3 b, V3 c) { return v3(sel3(r, a.x, b.x, c.x), sel3(r,
 //   * velocity and bias acceleration are PREFIX SUMS over the leg's lanes of one term per lane, qd_r S_r and qd_r (v_r x S_r):
 //     two fused DPP adds per value instead of every lane walking the chain;
 //   * the FRAME's twelve contact sample points are shared out one per link lane (the spare lane alone used to evaluate three).
-template <bool BAKED>
+// DYN: per-env dynamics -- contact constants and the FRAME's rigid inertia of this lane's env from D (the servo / hinge scales are
+// already in K)
+template <bool BAKED, bool DYN = false>
 DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env, BaseState &B, HingeLane &J, const LinkRegs &K,
-                      bool want_sensors, float *__restrict__ row, int kleg, float &zaxis_z) {
+                      bool want_sensors, float *__restrict__ row, int kleg, float &zaxis_z, const KDyn &D = KDyn{}) {
     using namespace pk3;
     const float h = C.h;
     const BaseCtx bc = pk3::base_prelude_unit(C, B); // the quaternion is of unit length here (normalised at load, then by base_integrate)
@@ -246,7 +248,8 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
         wsum *= K.ml;                               // the spare lane is no link (its mass and inertia are zero as well)
         SV fe;
         ContactDampT<float> cd;
-        pk3::contact_eval(wsum, s, Ep, pp, nb, vp, C.contact_k, C.contact_c, C.contact_inv_ramp, C.contact_mu, h, fe, cd);
+        if constexpr (DYN) pk3::contact_eval(wsum, s, Ep, pp, nb, vp, D.kc, D.cc, C.contact_inv_ramp, D.mu, h, fe, cd);
+        else pk3::contact_eval(wsum, s, Ep, pp, nb, vp, C.contact_k, C.contact_c, C.contact_inv_ramp, C.contact_mu, h, fe, cd);
         f.a = f.a - fe.a;
         f.l = f.l - fe.l;
         pk3::add_contact_damping(A, cd.mc, cd.w, cd.P, nb);
@@ -362,7 +365,7 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
     {
         SV p0;
         Sym6 Ic0;
-        pk3::frame_body_pk(C, bc, h, p0, Ic0);
+        pk3::frame_body_pk<DYN>(C, bc, h, p0, Ic0, D);
         // the block's non-zero literals (the FRAME's inertia + armature) come from registers filled once per launch (K.fb): a DPP add
         // takes no literal, so each of the eight sums below was a DPP move and an add with a literal; with a register operand it is
         // one v_add_f32_dpp
@@ -389,7 +392,8 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
             sF = env_sum(sF);
             Fr E0 = {v3(1.f, 0.f, 0.f), v3(0.f, 1.f, 0.f), v3(0.f, 0.f, 1.f)};
             SV fe;
-            contact_finish(wsumF, sF, E0, v3(0.f, 0.f, 0.f), bc.n, bc.V0, C.contact_k, C.contact_c, C.contact_inv_ramp, C.contact_mu, h, fe, Ic0);
+            if constexpr (DYN) contact_finish(wsumF, sF, E0, v3(0.f, 0.f, 0.f), bc.n, bc.V0, D.kc, D.cc, C.contact_inv_ramp, D.mu, h, fe, Ic0);
+            else contact_finish(wsumF, sF, E0, v3(0.f, 0.f, 0.f), bc.n, bc.V0, C.contact_k, C.contact_c, C.contact_inv_ramp, C.contact_mu, h, fe, Ic0);
             b.a = b.a + fe.a;
             b.l = b.l + fe.l;
         }
@@ -433,12 +437,15 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
 // physics wave, which alone uses its SIMD's issue slots every fourth cycle only, goes straight into the substep loop; the estimates
 // come back through LDS behind one workgroup barrier after the loop.  Same lane mapping in both waves (lane r < 3 of leg k = channel
 // 3k + r of env el of wave w).
-template <bool WALK = false, bool PO = false, bool BAKED = true, bool HELP = false>
+// DYN (generic tables only): per-env dynamics -- `Mp` is a KModelDyn; each lane takes its env's row into registers once per launch
+// (dyn_load) and scales its servo / hinge constants in K with it.
+template <bool WALK = false, bool PO = false, bool BAKED = true, bool HELP = false, bool DYN = false>
 __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void qg_step_kernel_link(const KModel *__restrict__ Mp, const KTask *__restrict__ T, KStepArgs P,
                                                                                   const typename WalkArgT<WALK>::type WK,
                                                                                   const typename PoArgT<PO>::type PK) {
     static_assert(WALK || !PO, "the observation pack rides on the walking task layer");
     static_assert(WALK || !HELP, "the helper waves carry the walking task layer's estimator");
+    static_assert(!DYN || (!BAKED && !HELP), "per-env dynamics: the table-driven variants");
     static_assert(QGK_LINK_ENVS * QGK_LINK_WAVES == QG_PO_ENVS && QGK_WAVE * QGK_LINK_WAVES == QG_PO_THREADS, "workgroup layout of qg_po_dev.h");
     __shared__ float tile_all[QGK_LINK_WAVES][QGK_LINK_ENVS * 35];
     __shared__ KModel smodel;
@@ -560,6 +567,11 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
     }
 
 #include "qg_link_regs.inc"
+    KDyn D = {};
+    if constexpr (DYN) {
+        D = dyn_load(Mp, C, n, env);
+        K.kp *= D.kp; K.kv *= D.kv; K.force_lo *= D.force; K.force_hi *= D.force; K.damping *= D.damping;
+    }
 
     BaseState B;
     const unsigned n4 = 4u * (unsigned)n, e4 = 4u * (unsigned)env;        // byte strides of the [field][n] state arrays
@@ -644,7 +656,7 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
     QG_MARK(1);                                      // state in registers, prologue stores issued
     asm volatile(".p2align 6");
 #pragma unroll 1
-    for (int s = 0; s < fs; ++s) substep_link<BAKED>(C, cm, sm, r, lead_env, B, J, K, s == fs - 1, srow, k, zaxis_z);
+    for (int s = 0; s < fs; ++s) substep_link<BAKED, DYN>(C, cm, sm, r, lead_env, B, J, K, s == fs - 1, srow, k, zaxis_z, D);
     int nstep = nstep0 + fs;
     QG_MARK(2);                                      // physics done
 

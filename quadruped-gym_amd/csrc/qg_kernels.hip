@@ -522,8 +522,11 @@ DEV BaseCtx base_prelude(const KModel &C, const BaseState &B) {
 }
 // FRAME body: bias force, rigid inertia, free-joint damping and armature on all six base DoFs
 // (quadruped.xml:9,62-63).  Contact of the FRAME is added by the caller.
-DEV void frame_body(const KModel &C, const BaseCtx &c, float h, SV &p0, Sym6 &Ic0) {
-    Rigid I0 = {C.m0, ld3(C.h0), {C.I0[0], C.I0[1], C.I0[2], C.I0[3], C.I0[4], C.I0[5]}};
+// DYN: the FRAME's rigid inertia of this env (payload included, KDyn) instead of the shared one
+template <bool DYN = false>
+DEV void frame_body(const KModel &C, const BaseCtx &c, float h, SV &p0, Sym6 &Ic0, const KDyn &D = KDyn{}) {
+    Rigid I0 = DYN ? Rigid{D.m0, ld3(D.h0), {D.I0[0], D.I0[1], D.I0[2], D.I0[3], D.I0[4], D.I0[5]}}
+                   : Rigid{C.m0, ld3(C.h0), {C.I0[0], C.I0[1], C.I0[2], C.I0[3], C.I0[4], C.I0[5]}};
     SV Iv0 = mul(I0, c.V0), Ia0 = mul(I0, c.A0);
     p0.a = Ia0.a + cross(c.V0.a, Iv0.a) + cross(c.V0.l, Iv0.l);
     p0.l = Ia0.l + cross(c.V0.a, Iv0.l);
@@ -537,8 +540,10 @@ DEV void frame_body(const KModel &C, const BaseCtx &c, float h, SV &p0, Sym6 &Ic
 namespace pk3 {
 // the same with the velocity-product terms as packed cross products (the inertia products keep the plain templates: the compiled-in
 // robot's FRAME inertia is literals, which fold there and would have to be materialised for a packed operand)
-DEV void frame_body_pk(const KModel &C, const BaseCtx &c, float h, SV &p0, Sym6 &Ic0) {
-    Rigid I0 = {C.m0, ld3(C.h0), {C.I0[0], C.I0[1], C.I0[2], C.I0[3], C.I0[4], C.I0[5]}};
+template <bool DYN = false>
+DEV void frame_body_pk(const KModel &C, const BaseCtx &c, float h, SV &p0, Sym6 &Ic0, const KDyn &D = KDyn{}) {
+    Rigid I0 = DYN ? Rigid{D.m0, ld3(D.h0), {D.I0[0], D.I0[1], D.I0[2], D.I0[3], D.I0[4], D.I0[5]}}
+                   : Rigid{C.m0, ld3(C.h0), {C.I0[0], C.I0[1], C.I0[2], C.I0[3], C.I0[4], C.I0[5]}};
     SV Iv0 = ::mul<float>(I0, c.V0), Ia0 = ::mul<float>(I0, c.A0);
     p0.a = cross_add(c.V0.l, Iv0.l, cross_add(c.V0.a, Iv0.a, Ia0.a));
     p0.l = cross_add(c.V0.a, Iv0.l, Ia0.l);
@@ -550,6 +555,34 @@ DEV void frame_body_pk(const KModel &C, const BaseCtx &c, float h, SV &p0, Sym6 
     p0.l = fma3(C.free_damping, c.V0.l, p0.l);
 }
 }  // namespace pk3
+
+// Per-env dynamics: env `env`'s row (QG_DYN_* columns of include/quadgym.h) into registers, once per launch.  `Mp` is a KModelDyn,
+// `C` the shared tables (staged in LDS).  The payload dm at p (FRAME coordinates) is added to the FRAME's rigid inertia about its
+// origin here: m0 + dm, h0 + dm p, I0 + dm (|p|^2 E - p p^T) -- twelve multiply-adds, against ten more per-lane loads for derived
+// columns.  With the identity row every product below is exact (x * 1, x + 0 * y), so the variant computes the shared model's bits.
+DEV KDyn dyn_load(const KModel *Mp, const KModel &C, int n, int env) {
+    const float *rows = reinterpret_cast<const KModelDyn *>(Mp)->rows;
+    float v[QGK_NDYN];
+#pragma unroll
+    for (int c = 0; c < QGK_NDYN; ++c) v[c] = rows[(size_t)c * n + env];
+    KDyn D;
+    D.mu = v[0];
+    D.kc = C.contact_k * v[9];
+    D.cc = C.contact_c * v[10];
+    D.kp = v[5]; D.kv = v[6]; D.force = v[7]; D.damping = v[8];
+    const float dm = v[1], px = v[2], py = v[3], pz = v[4];
+    D.m0 = C.m0 + dm;
+    D.h0[0] = fmaf(dm, px, C.h0[0]); D.h0[1] = fmaf(dm, py, C.h0[1]); D.h0[2] = fmaf(dm, pz, C.h0[2]);
+    D.I0[0] = fmaf(dm, fmaf(py, py, pz * pz), C.I0[0]);
+    D.I0[1] = fmaf(dm, fmaf(px, px, pz * pz), C.I0[1]);
+    D.I0[2] = fmaf(dm, fmaf(px, px, py * py), C.I0[2]);
+    D.I0[3] = fmaf(-dm, px * py, C.I0[3]);
+    D.I0[4] = fmaf(-dm, px * pz, C.I0[4]);
+    D.I0[5] = fmaf(-dm, py * pz, C.I0[5]);
+    return D;
+}
+// a servo / hinge constant of the shared table, times this env's scale in the per-env-dynamics variants
+#define QG_DYN_SCALE(x, s) (DYN ? (x) * D.s : (x))
 
 // ------------------------------------------------------------------------------------------
 // one leg: kinematics of fema / shin / foot, recursive Newton-Euler bias forces, ground contact,
@@ -565,9 +598,11 @@ DEV void frame_body_pk(const KModel &C, const BaseCtx &c, float h, SV &p0, Sym6 
 // register-capped (3 and 4 waves per SIMD) instantiations of the one-leg-per-lane kernel.
 // sc: sin / cos of the three hinge rotations carried by the caller (advanced by each substep's small rotation, see hinge_advance),
 // or NULL: evaluate the polynomials here.
-template <class T, bool BAKED, bool QUAD, bool CULL_FEMUR = false, bool COMPACT = false>
+// DYN: contact constants and servo / hinge scales of this lane's env from D (per-env dynamics)
+template <class T, bool BAKED, bool QUAD, bool CULL_FEMUR = false, bool COMPACT = false, bool DYN = false>
 DEV void leg_pass(const KModel &C, int k, FrT<T> Ep, const T q[3], const T qd[3], const T act[3], const BaseCtx &bc, float zbase_f,
-                  float h, Sym6T<T> &Ic, SVT<T> &fc, SVT<T> F[3], T Hd[3], T &H01, T &H02, T &H12, T bj[3], const T *sc = nullptr) {
+                  float h, Sym6T<T> &Ic, SVT<T> &fc, SVT<T> F[3], T Hd[3], T &H01, T &H02, T &H12, T bj[3], const T *sc = nullptr,
+                  const KDyn &D = KDyn{}) {
     const T zero = T(0.f);
     V3T<T> pp = v3<T>(zero, zero, zero);
     const V3T<T> nb = splat3<T>(bc.n);
@@ -640,6 +675,8 @@ DEV void leg_pass(const KModel &C, int k, FrT<T> Ep, const T q[3], const T qd[3]
             if constexpr (COMPACT)
                 body_contact_compact<T, QGK_CP_LINK>(L.cp, E, p, zo, nb, v, C.contact_k, C.contact_c, C.contact_inv_ramp,
                                                      C.contact_margin, C.contact_mu, h, fe, Cd[i]);
+            else if constexpr (DYN)
+                body_contact<T, QGK_CP_LINK>(L.cp, E, p, zo, nb, v, D.kc, D.cc, C.contact_inv_ramp, C.contact_margin, D.mu, h, fe, Ag[i]);
             else
                 body_contact<T, QGK_CP_LINK>(L.cp, E, p, zo, nb, v, C.contact_k, C.contact_c, C.contact_inv_ramp,
                                              C.contact_margin, C.contact_mu, h, fe, Ag[i]);
@@ -687,11 +724,11 @@ DEV void leg_pass(const KModel &C, int k, FrT<T> Ep, const T q[3], const T qd[3]
     for (int i = 0; i < 3; ++i) {
         const KLink &L = link_of<BAKED>(C, k, i);
         // position servo (quadruped.xml:10-37): force from the PRE-update activation
-        T force = L.kp * (act[i] - L.gear * q[i]) - (L.kv * L.gear) * qd[i];
-        auto clamped = m_or(force <= T(L.force_lo), force >= T(L.force_hi));
-        force = min_(max_(force, T(L.force_lo)), T(L.force_hi));
-        T dimp = T(L.damping) + sel(clamped, zero, T(L.kv * L.gear * L.gear));
-        T tau = L.gear * force - L.damping * qd[i];
+        T force = QG_DYN_SCALE(L.kp, kp) * (act[i] - L.gear * q[i]) - (QG_DYN_SCALE(L.kv, kv) * L.gear) * qd[i];
+        auto clamped = m_or(force <= T(QG_DYN_SCALE(L.force_lo, force)), force >= T(QG_DYN_SCALE(L.force_hi, force)));
+        force = min_(max_(force, T(QG_DYN_SCALE(L.force_lo, force))), T(QG_DYN_SCALE(L.force_hi, force)));
+        T dimp = T(QG_DYN_SCALE(L.damping, damping)) + sel(clamped, zero, T(QG_DYN_SCALE(L.kv, kv) * L.gear * L.gear));
+        T tau = L.gear * force - QG_DYN_SCALE(L.damping, damping) * qd[i];
         // soft joint limits: one-sided spring + damper that ramps in with the penetration (continuous torque)
         T below = T(L.lo) - q[i], above = q[i] - T(L.hi);
         T pen = max_(max_(below, above), zero);
@@ -1286,8 +1323,9 @@ template <bool PKQ> DEV void quad_integrate(const BaseCtx &c, float h, V3 wdot, 
 // share a SIMD (register cap 256), costs ~2 % when a wave has the register file to itself.
 // BAKED: the compiled-in robot, constants are literals and the lane works in its leg's quarter-turn frame.  Otherwise `C`
 // is the model table staged in LDS and every lane reads the constants of its own leg (k) from it -- any model numbers.
-template <bool BAKED, bool LOWREG>
-DEV void substep_quad(const KModel &C, float cm, float sm, BaseState &B, LegState &L, bool want_sensors, float *__restrict__ row, int k, float &zaxis_z) {
+template <bool BAKED, bool LOWREG, bool DYN = false>
+DEV void substep_quad(const KModel &C, float cm, float sm, BaseState &B, LegState &L, bool want_sensors, float *__restrict__ row, int k, float &zaxis_z,
+                      const KDyn &D = KDyn{}) {
     const float h = C.h;
     const BaseCtx bc0 = quad_prelude<BAKED && !LOWREG>(C, B);
     V3 gb_keep;
@@ -1318,7 +1356,7 @@ DEV void substep_quad(const KModel &C, float cm, float sm, BaseState &B, LegStat
             leg_pass<float, true, true, LOWREG, false>(C, 0, Ek, L.q, L.qd, L.act, bc, B.pw.z, h, Ic, fc, F, Hd, H01, H02, H12, bj, L.sc);
         } else {
             Fr E0 = {v3(1.f, 0.f, 0.f), v3(0.f, 1.f, 0.f), v3(0.f, 0.f, 1.f)};
-            leg_pass<float, false, false, LOWREG, false>(C, k, E0, L.q, L.qd, L.act, bc, B.pw.z, h, Ic, fc, F, Hd, H01, H02, H12, bj, L.sc);
+            leg_pass<float, false, false, LOWREG, false, DYN>(C, k, E0, L.q, L.qd, L.act, bc, B.pw.z, h, Ic, fc, F, Hd, H01, H02, H12, bj, L.sc, D);
         }
         leg_eliminate(F, Hd, H01, H02, H12, bj, Y0, Y1, Y2, u, YFt, Fu);
         sub(Ic, YFt);                       // this leg's Schur complement
@@ -1328,7 +1366,7 @@ DEV void substep_quad(const KModel &C, float cm, float sm, BaseState &B, LegStat
         const BaseCtx bc = LOWREG ? quad_prelude<BAKED && !LOWREG>(C, B) : bc0;      // rebuilt (cheap) rather than kept alive across the leg pass
         SV p0;
         Sym6 Ic0;
-        frame_body(C, bc, h, p0, Ic0);
+        frame_body<DYN>(C, bc, h, p0, Ic0, D);
         SV b;
         {   // FRAME contact: this lane evaluates its quarter turn of the three base sample points
             float wsum = 0.f;
@@ -1362,7 +1400,8 @@ DEV void substep_quad(const KModel &C, float cm, float sm, BaseState &B, LegStat
                 s = quad_sum(s);
                 Fr E0 = {v3(1.f, 0.f, 0.f), v3(0.f, 1.f, 0.f), v3(0.f, 0.f, 1.f)};
                 SV fe;
-                contact_finish(wsum, s, E0, v3(0.f, 0.f, 0.f), bc.n, bc.V0, C.contact_k, C.contact_c, C.contact_inv_ramp, C.contact_mu, h, fe, Ic0);
+                if constexpr (DYN) contact_finish(wsum, s, E0, v3(0.f, 0.f, 0.f), bc.n, bc.V0, D.kc, D.cc, C.contact_inv_ramp, D.mu, h, fe, Ic0);
+                else contact_finish(wsum, s, E0, v3(0.f, 0.f, 0.f), bc.n, bc.V0, C.contact_k, C.contact_c, C.contact_inv_ramp, C.contact_mu, h, fe, Ic0);
                 b.a = b.a + fe.a;
                 b.l = b.l + fe.l;
             }
@@ -1450,13 +1489,15 @@ DEV void po_wave_epilogue(const KPoLaunch &PK, const KWalkLaunch &WK, const KSte
 // copies the history rows ring -> out (po_copy_history_now), so that nothing of the copy rides on the physics wave's substep loop: the
 // first version, which kept the in-loop copy with the physics wave, lost to the one-role kernel (48.6 against 46.9 us per step at
 // 16 384 envs, frame_skip 10: at this register budget the copy cannot park in AGPRs across a substep); this one measures 45.4.
-template <int WPE, bool BAKED, bool WALK = false, int WAVES = 1, bool PO = false, bool HELP = false>
+// DYN (generic tables only): per-env dynamics -- `Mp` is a KModelDyn and each lane takes its env's row into registers (dyn_load)
+template <int WPE, bool BAKED, bool WALK = false, int WAVES = 1, bool PO = false, bool HELP = false, bool DYN = false>
 __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_step_kernel_quad(const KModel *__restrict__ Mp, const KTask *__restrict__ T, KStepArgs P,
                                                                              const typename WalkArgT<WALK>::type WK,
                                                                              const typename PoArgT<PO>::type PK) {
     static_assert(WALK || !PO, "the observation pack rides on the walking task layer");
     static_assert(WPE == 1 || WPE == 2, "register budget: one wave per SIMD (all 512 registers) or two");
     static_assert(!HELP || (WALK && WPE == 2), "helper waves: the walking forms at the two-waves-per-SIMD register budget");
+    static_assert(!DYN || (!BAKED && !HELP), "per-env dynamics: the table-driven variants");
     constexpr bool PO_COPY = PO && !HELP;          // HELP: the helper wave copies the history rows, nothing of it rides on the substep loop
     __shared__ float tile_all[WAVES][QGK_QUAD_ENVS * 35];
     __shared__ KModel smodel;                       // generic variant: the link / joint tables staged in LDS (3.2 KB)
@@ -1486,6 +1527,8 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
     // quarter turn of this lane's leg: (cos, sin)(90 deg * k)
     const float cm = (k == 0) ? 1.f : (k == 2) ? -1.f : 0.f;
     const float sm = (k == 1) ? 1.f : (k == 3) ? -1.f : 0.f;
+    KDyn D = {};
+    if constexpr (DYN) D = dyn_load(Mp, C, n, env);     // this env's dynamics row, once per launch
 
     if constexpr (HELP) {
         if (helper) {
@@ -1659,7 +1702,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
             PoCopyRegs<PO ? QG_PO_COPY_K : 1> pcr;
             if constexpr (PO_COPY) po_row_copy_load<QG_PO_COPY_K, 4>(PK.P, po_ring, k, s == 0, pcs, pcr);
             if constexpr (PO_COPY && !PO_DEFER) po_row_copy_store<QG_PO_COPY_K, 4>(PK.P, po_out, live, k, s == 0, pcs, pcr);
-            substep_quad<BAKED, (WPE > 1)>(C, cm, sm, B, L, lag && (s == fs - 1), srow, k, zaxis_z);
+            substep_quad<BAKED, (WPE > 1), DYN>(C, cm, sm, B, L, lag && (s == fs - 1), srow, k, zaxis_z, D);
             if constexpr (PO_DEFER) po_row_copy_store<QG_PO_COPY_K, 4>(PK.P, po_out, live, k, s == 0, pcs, pcr);
         }
         if constexpr (PO_COPY) po_row_copy_rest<QG_PO_COPY_K, 4>(PK.P, po_ring, po_out, live, k, pcs);
@@ -1670,7 +1713,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
         if (!lag) {   // un-lagged sensors (task.sensor_lag = 0): one extra forward pass on a scratch copy of the state
             BaseState B2 = B;
             LegState L2 = L;
-            substep_quad<BAKED, (WPE > 1)>(C, cm, sm, B2, L2, true, srow, k, zaxis_z);
+            substep_quad<BAKED, (WPE > 1), DYN>(C, cm, sm, B2, L2, true, srow, k, zaxis_z, D);
         }
         nstep = nstep0 + fs;
 #pragma unroll
@@ -2252,6 +2295,28 @@ __global__ void qg_jitter_kernel(const KModel *__restrict__ M, const KTask *__re
     if (!was_reset) return;
     st.qpos[(7 + j) * n + env] = jittered_hinge(M->qpos0[7 + j], M->link[j].lo, M->link[j].hi, T->reset_joint_jitter, seed,
                                                 env_index_base + (uint64_t)env, st.episode[env] - 1, j);
+}
+
+// QG_RESET_DYNAMICS: column c of env i drawn for episode e as lo + (hi - lo) u, u = uniform24s(seed, base + i, e, 16 + c) -- streams of
+// their own, so the yaw (0), hinge (1..12) and command (13..15) draws are the same with the flag as without.  One thread per (column,
+// env).  Behind qg_reset (`mask`: the envs reset, NULL: all; key = the episode counter before the reset advances it, key_offset 0) and,
+// as qg_jitter_kernel and for its reason, as a launch of its own behind a step that auto-resets (`done` bytes or the packed rows' last
+// column: the envs that finished; their counter has advanced, key_offset -1).
+#define QG_STREAM_DYNAMICS 16u
+struct KDynRange { float lo[QGK_NDYN], hi[QGK_NDYN]; };
+__global__ void qg_dyn_draw_kernel(float *__restrict__ rows, KDynRange R, const int32_t *__restrict__ episode, int n, const uint8_t *__restrict__ mask,
+                                   const uint8_t *__restrict__ done, const float *__restrict__ packed, int row, int key_offset, uint64_t seed,
+                                   uint64_t env_index_base) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= QGK_NDYN * n) return;
+    const int c = t / n, env = t - c * n;
+    if (mask && !mask[env]) return;
+    if (!mask && (done || packed)) {
+        const bool was_reset = done ? (done[env] != 0) : (packed[(size_t)env * row + (row - 1)] > 0.5f);
+        if (!was_reset) return;
+    }
+    const float u = uniform24s(seed, env_index_base + (uint64_t)env, (uint64_t)(episode[env] + key_offset), QG_STREAM_DYNAMICS + (uint32_t)c);
+    rows[(size_t)c * n + env] = fmaf(R.hi[c] - R.lo[c], u, R.lo[c]);
 }
 
 // env-major [n][w] <-> field-major [w][n] (state snapshot / restore at the ABI)

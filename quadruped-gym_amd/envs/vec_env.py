@@ -146,7 +146,7 @@ class QuadrupedVecEnv(_VecEnvBase):
     def __init__(self, num_envs: int, model_path: str | None = "builtin", max_time: float = 10.0, frame_skip: int = 4,
                  reward_fns: dict | None = None, termination_fns: dict | None = None, use_default_termination: bool = True,
                  obs_mode: int = _abi.OBS_FULL, random_init: bool = False, device: int = 0, env_index_base: int = 0,
-                 seed: int = 0, callable_mode: str = "per_env", infos_mode: str = "lazy"):
+                 seed: int = 0, callable_mode: str = "per_env", infos_mode: str = "lazy", dynamics_randomization: dict | None = None):
         if callable_mode not in ("per_env", "batched"):
             raise ValueError("callable_mode must be 'per_env' or 'batched'")
         if infos_mode not in ("lazy", "finished"):
@@ -164,9 +164,13 @@ class QuadrupedVecEnv(_VecEnvBase):
         if use_default_termination:
             self.termination_fns["default"] = self._default_termination
         self._reset_flags = _abi.RESET_RANDOM_YAW if random_init else 0
+        if dynamics_randomization is not None:      # a new dynamics row per env at every reset and auto-reset
+            self._reset_flags |= _abi.RESET_DYNAMICS
         self._obs_mode = obs_mode
         task, self._host_rewards, self._host_terms = self._plan()
         self._sim = BatchedSim(self.num_envs, device=device, model=qg_model, task=task, env_index_base=env_index_base)
+        if dynamics_randomization is not None:
+            self._sim.set_dynamics_range(dynamics_randomization)
         self._task_key = self._key(task)
         self._seed = int(seed)
         self.obs_dim = self._sim.obs_dim
@@ -253,6 +257,10 @@ class QuadrupedVecEnv(_VecEnvBase):
 
     def step_async(self, actions):
         self._actions = np.asarray(actions, dtype=np.float32)
+
+    def dynamics(self):
+        """``[num_envs, 11]`` f32: each env's dynamics row (columns ``_abi.DYN_COLUMNS``; identity rows without randomisation)."""
+        return self._sim.get_dynamics()
 
     def _eval_callables(self, obs, state=None):
         """Host evaluation of the Python callables over ``self.data``; returns (components {name: [N]}, done [N])."""

@@ -68,7 +68,8 @@ class WalkingQuadrupedVecEnv(_VecEnvBase):      # SB3's VecEnv where that packag
 
     def __init__(self, num_envs, settling_time=0, random_controls=False, random_init=False, reset_options=None,
                  model_path="builtin", max_time=10.0, frame_skip=4, device=0, env_index_base=0, seed=0, walk_params=None,
-                 device_commands=False, auto_reset=True, use_default_termination=True, infos_mode="lazy", nan_direction=True):
+                 device_commands=False, auto_reset=True, use_default_termination=True, infos_mode="lazy", nan_direction=True,
+                 dynamics_randomization=None):
         if infos_mode not in ("lazy", "finished"):
             raise ValueError("infos_mode must be 'lazy' (every env's component dict, built when touched) or 'finished' (content "
                              "for the envs that finished only; `last_components` holds every env's components as one array)")
@@ -89,7 +90,11 @@ class WalkingQuadrupedVecEnv(_VecEnvBase):      # SB3's VecEnv where that packag
         self.auto_reset = bool(auto_reset)
         task.auto_reset = 1 if self.auto_reset else 0
         task.reset_flags = _abi.RESET_RANDOM_YAW if random_init else 0     # walking_quad.py:68-75,118-119
+        if dynamics_randomization is not None:      # a new dynamics row per env at every reset and auto-reset
+            task.reset_flags |= _abi.RESET_DYNAMICS
         self._sim = BatchedSim(self.num_envs, device=device, model=qg_model, task=task, env_index_base=env_index_base)
+        if dynamics_randomization is not None:
+            self._sim.set_dynamics_range(dynamics_randomization)
         self._lib = _abi.load_library()
         self.params = walk_params if walk_params is not None else default_walk_params()
         self.params.settling_time = float(settling_time)
@@ -130,6 +135,10 @@ class WalkingQuadrupedVecEnv(_VecEnvBase):      # SB3's VecEnv where that packag
         """``(velocity_xy, heading_xy)`` as they stand on the device, ``[num_envs, 2]`` each."""
         check(self._lib.qg_walk_get_commands(self._w, self.velocity.ctypes.data, self.heading.ctypes.data), "qg_walk_get_commands")
         return self.velocity, self.heading
+
+    def dynamics(self):
+        """``[num_envs, 11]`` f32: each env's dynamics row (columns ``_abi.DYN_COLUMNS``; identity rows without randomisation)."""
+        return self._sim.get_dynamics()
 
     # -- checkpoint / resume (SURVEY section 5; the reference resumes the policy only, train_quadruped.py:114-141) -------------------
     def snapshot(self):

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import NQ, NV, NU, NREWARD, QgModel, QgTask, check
+from ._abi import NDYN, NQ, NV, NU, NREWARD, QgModel, QgTask, check
 
 
 class BatchedSim:
@@ -253,14 +253,86 @@ class BatchedSim:
         check(self._lib.qg_set_reset_streams(self._h, ep.ctypes.data, int(seed)), "qg_set_reset_streams")
 
     def snapshot(self):
-        """Everything the simulator keeps per env: ``dict`` of NumPy arrays (physics state + reset streams)."""
+        """Everything the simulator keeps per env: ``dict`` of NumPy arrays (physics state + reset streams, and the per-env dynamics
+        rows under ``"dynamics"`` while that mode is on)."""
         qpos, qvel, act, ctrl, nstep = self.get_state()
         ep, seed = self.get_reset_streams()
-        return {"qpos": qpos, "qvel": qvel, "act": act, "ctrl": ctrl, "nstep": nstep, "episode": ep, "seed": seed}
+        snap = {"qpos": qpos, "qvel": qvel, "act": act, "ctrl": ctrl, "nstep": nstep, "episode": ep, "seed": seed}
+        if self.dynamics_on:
+            snap["dynamics"] = self.get_dynamics()
+            if self._dyn_range is not None:         # what later draws take their rows from
+                snap["dynamics_range"] = np.array([self._dyn_range.lo[:], self._dyn_range.hi[:]], np.float32)
+        return snap
 
     def restore(self, snap):
+        """All-or-nothing as far as the checks go: shapes and the dynamics mode are checked, and the per-env dynamics (which the
+        library may still refuse, e.g. on the LANE mapping) are applied, before the state is written."""
+        shapes = {"qpos": (self.n, NQ), "qvel": (self.n, NV), "act": (self.n, NU), "ctrl": (self.n, NU), "nstep": (self.n,),
+                  "episode": (self.n,)}
+        for key, shape in shapes.items():
+            if np.asarray(snap[key]).shape != shape:
+                raise ValueError(f"the snapshot's {key} has shape {np.asarray(snap[key]).shape}, expected {shape}")
+        if "dynamics" in snap:
+            if np.asarray(snap["dynamics"]).shape != (self.n, NDYN):
+                raise ValueError(f"the snapshot's dynamics rows have shape {np.asarray(snap['dynamics']).shape}, expected ({self.n}, {NDYN})")
+            rng = snap.get("dynamics_range")
+            if rng is not None:
+                rng = np.asarray(rng, np.float32)
+                if rng.shape != (2, NDYN):
+                    raise ValueError(f"the snapshot's dynamics range has shape {rng.shape}, expected (2, {NDYN})")
+                r = _abi.QgDynamicsRange()
+                for c in range(NDYN):
+                    r.lo[c], r.hi[c] = float(rng[0, c]), float(rng[1, c])
+                check(self._lib.qg_set_dynamics_range(self._h, C.byref(r)), "qg_set_dynamics_range")
+                self._dyn_range = r
+            self.set_dynamics(snap["dynamics"])
+        elif self.dynamics_on:
+            raise ValueError("the snapshot was taken with the shared model, this handle has per-env dynamics on (clear_dynamics() first)")
         self.set_state(snap["qpos"], snap["qvel"], snap["act"], snap["ctrl"], snap["nstep"])
         self.set_reset_streams(snap["episode"], snap["seed"])
+
+    # -- per-env dynamics (qg_set_dynamics_range / qg_set_dynamics, include/quadgym.h) ----------------------------------------
+    dynamics_on = False
+    _dyn_range = None
+
+    def set_dynamics_range(self, spec: dict):
+        """The range ``RESET_DYNAMICS`` draws each env's row from: ``{"friction": (lo, hi), "payload_mass": (lo, hi), "payload_pos":
+        ((lo, hi),) * 3, "kp_scale": (lo, hi), "kv_scale", "force_scale", "damping_scale", "contact_stiffness_scale",
+        "contact_damping_scale"}``; missing keys stay at the identity.  Switches the per-env mode on (identity rows until a draw)."""
+        r = _abi.dynamics_range(spec, self.model)
+        check(self._lib.qg_set_dynamics_range(self._h, C.byref(r)), "qg_set_dynamics_range")
+        self._dyn_range = r
+        self._dynamics_mode(True)
+
+    def set_dynamics(self, rows, mask=None):
+        """Set the rows ``[n, 11]`` (columns ``_abi.DYN_COLUMNS``) of every env, or of the envs where ``mask`` is true."""
+        r = np.ascontiguousarray(rows, dtype=np.float32)
+        if r.shape != (self.n, NDYN):
+            raise ValueError(f"expected shape ({self.n}, {NDYN}), got {r.shape}")
+        mp = None
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.shape != (self.n,):
+                raise ValueError(f"mask: expected shape ({self.n},), got {mask.shape}")
+            mp = mask.ctypes.data
+        check(self._lib.qg_set_dynamics(self._h, mp, r.ctypes.data), "qg_set_dynamics")
+        self._dynamics_mode(True)
+
+    def get_dynamics(self):
+        """``[n, 11]`` f32: every env's row (identity rows while the mode is off)."""
+        out = np.empty((self.n, NDYN), np.float32)
+        check(self._lib.qg_get_dynamics(self._h, out.ctypes.data), "qg_get_dynamics")
+        return out
+
+    def clear_dynamics(self):
+        """Back to the one shared model (the range is dropped as well)."""
+        check(self._lib.qg_clear_dynamics(self._h), "qg_clear_dynamics")
+        self._dyn_range = None
+        self._dynamics_mode(False)
+
+    def _dynamics_mode(self, on: bool):
+        self.dynamics_on = on
+        self.baked = bool(self._lib.qg_uses_baked_model(self._h))
 
     def set_state(self, qpos=None, qvel=None, act=None, ctrl=None, nstep=None):
         def f32(x, w):

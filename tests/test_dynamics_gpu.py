@@ -1,0 +1,567 @@
+"""Per-env dynamics randomisation (qg_set_dynamics_range / qg_set_dynamics, include/quadgym.h): every env of a heterogeneous batch
+against the CPU oracle run on THAT env's own qg_model, derived here from the row table of the header (not by product code)."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from quadruped_gym_amd import _abi
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_parity_gpu import TOL, close  # noqa: E402
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+
+WIDE = {"friction": (0.3, 1.5), "payload_mass": (-0.1, 0.3), "payload_pos": ((-0.015, 0.015),) * 3, "kp_scale": (0.6, 1.4),
+        "kv_scale": (0.6, 1.4), "force_scale": (0.6, 1.4), "damping_scale": (0.6, 1.4), "contact_stiffness_scale": (0.5, 2.0),
+        "contact_damping_scale": (0.5, 2.0)}
+# (payload -0.1 .. 0.3 kg: at +-2 cm the -0.1 kg corners leave the 0.242 kg FRAME with an inertia about its centre of mass that is not
+# positive definite -- smallest eigenvalue -1.2e-5 kg m^2 -- which qg_set_dynamics_range refuses (test_refusals); +-1.5 cm passes)
+MAPS = {"link": _abi.MAP_LINK, "quad": _abi.MAP_QUAD}
+
+
+def test_header_columns_match_the_binding():
+    """QG_NDYN / QG_DYN_* / QG_RESET_DYNAMICS of the header and the Python column names agree (no GPU)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "include", "quadgym.h")).read()
+    import re
+    assert int(re.search(r"#define QG_NDYN (\d+)", text).group(1)) == _abi.NDYN == len(_abi.DYN_COLUMNS)
+    assert re.search(r"#define QG_RESET_DYNAMICS (\d+)u", text).group(1) == str(_abi.RESET_DYNAMICS)
+    for i, name in enumerate(_abi.DYN_COLUMNS):
+        assert int(re.search(r"#define QG_DYN_%s (\d+)" % name.upper(), text).group(1)) == i
+    m = _abi.default_model()
+    r = _abi.dynamics_range({"friction": (0.2, 0.9), "payload_pos": ((1, 2), (3, 4), (5, 6))}, m)
+    assert r.lo[0] == np.float32(0.2) and r.hi[4] == 6 and r.lo[5] == 1 and r.hi[1] == 0
+    with pytest.raises(ValueError):
+        _abi.dynamics_range({"gravity": (0, 1)}, m)
+
+
+def test_dynamics_range_layout_matches_the_c_side(tmp_path):
+    """sizeof(qg_dynamics_range) and the offset of `hi`, compiled from the header, equal the ctypes mirror's (no GPU)."""
+    import shutil
+    import subprocess
+    cc = shutil.which("gcc") or shutil.which("cc")
+    if cc is None:
+        pytest.fail("no C compiler to compile the header with")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "quadgym.h"\n'
+                   'int main(void) { printf("%zu %zu\\n", sizeof(qg_dynamics_range), offsetof(qg_dynamics_range, hi)); return 0; }\n')
+    exe = tmp_path / "layout"
+    subprocess.run([cc, "-I", os.path.join(root, "include"), "-o", str(exe), str(src)], check=True)
+    size, off_hi = map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
+    assert size == C.sizeof(_abi.QgDynamicsRange)
+    assert off_hi == _abi.QgDynamicsRange.hi.offset
+
+
+def env_model(oracle, base, row):
+    """The qg_model one env runs with `row` (f32 values, the table of include/quadgym.h), in f64: the payload combined with the FRAME
+    by the parallel-axis rule, the FRAME's inertia expressed about the new centre of mass."""
+    m = oracle.default_model()
+    C.memmove(C.byref(m), C.byref(base), C.sizeof(m))
+    row = np.asarray(row, np.float64)
+    m.contact_friction = row[0]
+    dm, p = row[1], row[2:5]
+    m0, c0 = base.body_mass[0], np.array(base.body_ipos[0][:])
+    I = base.body_inertia[0]
+    I0 = np.array([[I[0], I[3], I[4]], [I[3], I[1], I[5]], [I[4], I[5], I[2]]])
+    m1 = m0 + dm
+    c1 = (m0 * c0 + dm * p) / m1
+
+    def shift(mass, d):
+        return mass * (np.dot(d, d) * np.eye(3) - np.outer(d, d))
+    I1 = I0 + shift(m0, c0 - c1) + shift(dm, p - c1)
+    m.body_mass[0] = m1
+    for i in range(3):
+        m.body_ipos[0][i] = c1[i]
+    for i, v in enumerate([I1[0, 0], I1[1, 1], I1[2, 2], I1[0, 1], I1[0, 2], I1[1, 2]]):
+        m.body_inertia[0][i] = v
+    for j in range(12):
+        m.act_kp[j] = base.act_kp[j] * row[5]
+        m.act_kv[j] = base.act_kv[j] * row[6]
+        m.act_forcerange[j][0] = base.act_forcerange[j][0] * row[7]
+        m.act_forcerange[j][1] = base.act_forcerange[j][1] * row[7]
+        m.jnt_damping[j] = base.jnt_damping[j] * row[8]
+    m.contact_stiffness = base.contact_stiffness * row[9]
+    m.contact_damping = base.contact_damping * row[10]
+    return m
+
+
+def oracle_per_env(oracle, base, task, rows, state, actions):
+    """One env-step of every env on its own model; returns (obs, reward, comps, qpos, qvel, act) stacked."""
+    qpos, qvel, act, nstep = state
+    outs = []
+    for i in range(len(rows)):
+        b = oracle.Batch(env_model(oracle, base, rows[i]), task, 1)
+        b.set_state(qpos[i:i + 1].astype(np.float64), qvel[i:i + 1].astype(np.float64), act[i:i + 1].astype(np.float64), None, nstep[i:i + 1])
+        obs, rew, done, comps = b.step(actions[i:i + 1].astype(np.float64))
+        q, v, a, _, _ = b.get_state()
+        outs.append((obs[0], rew[0], comps[0], q[0], v[0], a[0]))
+    return [np.array(x) for x in zip(*outs)]
+
+
+def sampled(oracle, n, seed):
+    from make_golden import sample_states
+    return sample_states(oracle.default_model(), oracle.default_task(), n, seed=seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fs", [1, 4])
+@pytest.mark.parametrize("mapping", ["link", "quad"])
+def test_heterogeneous_batch_matches_per_env_oracle(oracle, mapping, fs):
+    from quadruped_gym_amd.sim import BatchedSim
+    n = 256
+    task = _abi.default_task()
+    task.frame_skip = fs
+    otask = oracle.default_task()
+    otask.frame_skip = fs
+    sim = BatchedSim(n, task=task)
+    sim.set_mapping(MAPS[mapping])
+    sim.set_dynamics_range(WIDE)
+    assert sim.mapping == MAPS[mapping] and not sim.baked
+    sim.reset(seed=11, flags=_abi.RESET_DYNAMICS)
+    rows = sim.get_dynamics()
+    assert np.unique(rows[:, 0]).size > n // 2                      # the rows differ from env to env
+    state = sampled(oracle, n, seed=77)
+    actions = np.random.default_rng(3).uniform(-1.2, 1.2, (n, 12)).astype(np.float32)
+    sim.set_state(state[0], state[1], state[2], None, state[3])
+    obs, rew, done, comps = sim.step(actions, want_components=True)
+    q1, v1, a1, _, _ = sim.get_state()
+    sim.close()
+    obs_o, rew_o, comps_o, q_o, v_o, a_o = oracle_per_env(oracle, oracle.default_model(), otask, rows, state, actions)
+    t = TOL["A"]
+    mask = np.ones(33, bool)
+    mask[12:15] = False
+    what = f"{mapping} fs {fs}: "
+    close(q1, q_o, t["qpos"], what + "qpos")
+    close(v1, v_o, t["qvel"], what + "qvel")
+    close(a1, a_o, t["act"], what + "act")
+    close(obs[:, mask], obs_o[:, mask], t["obs"], what + "obs")
+    close(obs[:, 12:15], obs_o[:, 12:15], t["accel"], what + "accelerometer")
+    close(rew, rew_o, t["reward"], what + "reward")
+    close(comps, comps_o, t["reward"], what + "reward components")
+    # control: the shared model misses most envs -- the rows take effect
+    b = oracle.Batch(oracle.default_model(), otask, n)
+    b.set_state(state[0].astype(np.float64), state[1].astype(np.float64), state[2].astype(np.float64), None, state[3])
+    b.step(actions.astype(np.float64))
+    q_s, v_s = b.get_state()[:2]
+    atol, rtol = t["qvel"]
+    off = (np.abs(v1 - v_s) > atol + rtol * np.abs(v_s)).any(axis=1)
+    assert off.mean() > 0.5, f"only {off.mean():.2f} of the envs differ from the shared model"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("po", [False, True])
+def test_walking_and_po_steps_with_per_env_dynamics(oracle, po):
+    from quadruped_gym_amd.envs.walking import POWalkingQuadrupedVecEnv, WalkingQuadrupedVecEnv
+    n = 256
+    kw = dict(nan_direction=False, dynamics_randomization=WIDE, seed=5)
+    env = POWalkingQuadrupedVecEnv(n, **kw) if po else WalkingQuadrupedVecEnv(n, **kw)
+    env.reset()
+    rows = env.dynamics()
+    assert rows.shape == (n, 11) and np.unique(rows[:, 5]).size > n // 2
+    state = sampled(oracle, n, seed=91)
+    env._sim.set_state(state[0], state[1], state[2], None, state[3])
+    actions = np.random.default_rng(8).uniform(-1, 1, (n, 12)).astype(np.float32)
+    _, rew, done, _ = env.step(actions)
+    q1, v1, a1, _, _ = env._sim.get_state()
+    env.close()
+    assert np.isfinite(rew).all()
+    _, _, _, q_o, v_o, a_o = oracle_per_env(oracle, oracle.default_model(), oracle.default_task(), rows, state, actions)
+    keep = ~np.asarray(done, bool)                   # envs that finished were auto-reset
+    assert keep.sum() > n // 2
+    t = TOL["A"]
+    close(q1[keep], q_o[keep], t["qpos"], "qpos")
+    close(v1[keep], v_o[keep], t["qvel"], "qvel")
+    close(a1[keep], a_o[keep], t["act"], "act")
+
+
+def tweaked_model():
+    m = _abi.default_model()
+    for j in range(12):
+        m.act_kp[j] *= 1.1
+    m.body_mass[0] *= 1.05
+    m.contact_stiffness *= 0.9
+    return m
+
+
+def run_sim(sim, steps, seed):
+    rng = np.random.default_rng(seed)
+    outs = []
+    for _ in range(steps):
+        a = rng.uniform(-1, 1, (sim.n, 12)).astype(np.float32)
+        outs.append(sim.step(a, want_components=True))
+    return outs, sim.get_state()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mapping", ["link", "quad"])
+def test_identity_rows_change_nothing(mapping):
+    from quadruped_gym_amd.sim import BatchedSim
+    n = 192
+    task = _abi.default_task()
+    task.max_time = 0.2                                   # auto-resets inside the 50 steps
+    task.auto_reset, task.reset_flags = 1, _abi.RESET_RANDOM_YAW | _abi.RESET_JOINT_JITTER
+    model = tweaked_model()
+    a, b = BatchedSim(n, model=model, task=task), BatchedSim(n, model=model, task=task)
+    for s in (a, b):
+        s.set_mapping(MAPS[mapping])
+        s.reset(seed=3, flags=_abi.RESET_RANDOM_YAW | _abi.RESET_JOINT_JITTER)
+    b.set_dynamics(np.tile(_abi.identity_dynamics_row(model), (n, 1)))
+    assert b.dynamics_on and a.mapping == b.mapping
+    oa, sa = run_sim(a, 50, 9)
+    ob, sb = run_sim(b, 50, 9)
+    for x, y in zip(oa, ob):
+        for u, v in zip(x, y):
+            assert np.array_equal(np.asarray(u), np.asarray(v))
+    for u, v in zip(sa, sb):
+        assert np.array_equal(u, v)
+    a.close(); b.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("po", [False, True])
+@pytest.mark.parametrize("n", [128, 5000])
+def test_identity_rows_change_nothing_walking(po, n, tmp_path):
+    """Walking / PO envs on a tweaked robot (LINK at 128 envs, QUAD at 5000): identity rows give the bits of the handle without the
+    mode, auto-resets included."""
+    import json
+    from quadruped_gym_amd.envs.walking import POWalkingQuadrupedVecEnv, WalkingQuadrupedVecEnv
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = json.load(open(os.path.join(root, "quadruped-gym_amd", "model", "quadruped_model.json")))
+    for act in d["actuators"]:
+        act["kp"] *= 1.1
+    d["contact"]["stiffness"] *= 0.9
+    path = str(tmp_path / "tweaked.json")
+    json.dump(d, open(path, "w"))
+    res = []
+    for with_rows in (False, True):
+        cls = POWalkingQuadrupedVecEnv if po else WalkingQuadrupedVecEnv
+        env = cls(n, nan_direction=False, random_init=True, max_time=0.3, seed=4, model_path=path)
+        assert not env._sim.baked
+        if with_rows:
+            env._sim.set_dynamics(np.tile(_abi.identity_dynamics_row(env._sim.model), (n, 1)))
+        env.reset()
+        rng = np.random.default_rng(2)
+        trace = []
+        for _ in range(50):
+            o, r, dn, _ = env.step(rng.uniform(-1, 1, (n, 12)).astype(np.float32))
+            trace.append((np.array(o), np.array(r), np.array(dn)))
+        trace.append(env._sim.get_state())
+        res.append(trace)
+        env.close()
+    assert any(t[2].any() for t in res[0][:-1]), "auto-resets inside the 50 steps"
+    for x, y in zip(res[0], res[1]):
+        for u, v in zip(x, y):
+            assert np.array_equal(u, v, equal_nan=True)
+
+
+@pytest.mark.gpu
+def test_clear_dynamics_restores_the_baked_kernel():
+    from quadruped_gym_amd.sim import BatchedSim
+    n = 64
+    a, b = BatchedSim(n), BatchedSim(n)
+    assert a.baked
+    a.set_dynamics_range(WIDE)
+    a.reset(seed=1, flags=_abi.RESET_DYNAMICS)
+    assert not a.baked and a._lib.qg_uses_baked_model(a._h) == 0
+    a.step(np.zeros((n, 12), np.float32))
+    a.clear_dynamics()
+    assert a.baked and a._lib.qg_uses_baked_model(a._h) == 1
+    assert np.array_equal(a.get_dynamics(), np.tile(_abi.identity_dynamics_row(a.model), (n, 1)))
+    a.set_reset_streams(np.zeros(n, np.int32), 0)         # the same reset keys as the fresh handle
+    for s in (a, b):
+        s.reset(seed=2, flags=_abi.RESET_RANDOM_YAW)
+    oa, sa = run_sim(a, 10, 4)
+    ob, sb = run_sim(b, 10, 4)
+    for x, y in zip(oa + [sa], ob + [sb]):
+        for u, v in zip(x, y):
+            assert np.array_equal(np.asarray(u), np.asarray(v))
+    a.close(); b.close()
+
+
+def expected_rows(oracle, spec, model, seed, envs, episodes):
+    """lo + (hi - lo) u per column, u of stream 16 + k of the (seed, env, episode) key; in f64 from the f32 lo, hi - lo and u."""
+    r = _abi.dynamics_range(spec, model)
+    lo, hi = np.array(r.lo[:], np.float32), np.array(r.hi[:], np.float32)
+    L = oracle.lib()
+    out = np.empty((len(envs), 11), np.float64)
+    for i, (e, ep) in enumerate(zip(envs, episodes)):
+        for k in range(11):
+            u = np.float32(L.qgo_uniform_stream(seed, int(e), int(ep), 16 + k))
+            out[i, k] = np.float64(lo[k]) + np.float64(hi[k] - lo[k]) * np.float64(u)
+    return out
+
+
+def ulp_close(a, b):
+    """within one f32 ulp of the exact value"""
+    return bool(np.all(np.abs(a.astype(np.float64) - b) <= np.spacing(np.abs(b).astype(np.float32)).astype(np.float64)))
+
+
+@pytest.mark.gpu
+def test_draw_stream(oracle):
+    from quadruped_gym_amd.sim import BatchedSim
+    n, seed = 300, 21
+    sim = BatchedSim(n)
+    sim.set_dynamics_range(WIDE)
+    sim.reset(seed=seed, flags=_abi.RESET_DYNAMICS)
+    rows = sim.get_dynamics()
+    want = expected_rows(oracle, WIDE, sim.model, seed, range(n), [0] * n)
+    assert ulp_close(rows, want)
+    # two shards give the rows of one handle
+    halves = []
+    for base in (0, n // 2):
+        s = BatchedSim(n // 2, env_index_base=base)
+        s.set_dynamics_range(WIDE)
+        s.reset(seed=seed, flags=_abi.RESET_DYNAMICS)
+        halves.append(s.get_dynamics())
+        s.close()
+    assert np.array_equal(np.concatenate(halves), rows)
+    # masked reset: only masked envs redraw (episode 1 key); a reset without the flag keeps every row
+    mask = np.zeros(n, np.uint8)
+    mask[::3] = 1
+    sim.reset(mask=mask, flags=_abi.RESET_DYNAMICS)
+    r2 = sim.get_dynamics()
+    assert np.array_equal(r2[mask == 0], rows[mask == 0])
+    idx = np.nonzero(mask)[0]
+    assert ulp_close(r2[idx], expected_rows(oracle, WIDE, sim.model, seed, idx, [1] * len(idx)))
+    sim.reset(flags=0, seed=seed)
+    assert np.array_equal(sim.get_dynamics(), r2)
+    # yaw and jitter draws are the same with the flag added (fresh handles: episode 0 for both)
+    plain, flagged = BatchedSim(n), BatchedSim(n)
+    flagged.set_dynamics_range(WIDE)
+    plain.reset(seed=seed, flags=_abi.RESET_RANDOM_YAW | _abi.RESET_JOINT_JITTER)
+    flagged.reset(seed=seed, flags=_abi.RESET_RANDOM_YAW | _abi.RESET_JOINT_JITTER | _abi.RESET_DYNAMICS)
+    assert np.array_equal(plain.get_state()[0], flagged.get_state()[0])
+    assert np.array_equal(flagged.get_dynamics(), rows)
+    flagged.close()
+    plain.close()
+    sim.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [256, 6000])
+def test_auto_reset_draws_for_finished_envs_only(oracle, n):
+    from quadruped_gym_amd.sim import BatchedSim
+    task = _abi.default_task()
+    task.max_time = 0.05
+    task.auto_reset, task.reset_flags = 1, _abi.RESET_RANDOM_YAW | _abi.RESET_DYNAMICS
+    sim = BatchedSim(n, task=task)
+    sim.set_dynamics_range(WIDE)
+    seed = 8
+    sim.reset(seed=seed, flags=_abi.RESET_RANDOM_YAW | _abi.RESET_DYNAMICS)
+    rng = np.random.default_rng(1)
+    # stagger the episodes: half the envs start later in their episode
+    q, v, a, c, ns = sim.get_state()
+    ns[::2] = 10
+    sim.set_state(q, v, a, c, ns)
+    before = sim.get_dynamics()
+    _, _, done, _ = sim.step(rng.uniform(-1, 1, (n, 12)).astype(np.float32))
+    for _ in range(3):
+        if np.asarray(done).any():
+            break
+        before = sim.get_dynamics()
+        _, _, done, _ = sim.step(rng.uniform(-1, 1, (n, 12)).astype(np.float32))
+    done = np.asarray(done, bool)
+    assert done.any() and not done.all()
+    after = sim.get_dynamics()
+    assert np.array_equal(after[~done], before[~done])
+    ep, _ = sim.get_reset_streams()
+    idx = np.nonzero(done)[0]
+    assert ulp_close(after[idx], expected_rows(oracle, WIDE, sim.model, seed, idx, ep[idx] - 1))
+    sim.close()
+
+
+@pytest.mark.gpu
+def test_po_snapshot_restore_is_bit_identical():
+    from quadruped_gym_amd.envs.walking import POWalkingQuadrupedVecEnv
+    n = 128
+    kw = dict(nan_direction=False, dynamics_randomization=WIDE, random_init=True, max_time=0.2, seed=6, device_commands=True,
+              random_controls=True)
+    env = POWalkingQuadrupedVecEnv(n, **kw)
+    env.reset()
+    rng = np.random.default_rng(0)
+    for _ in range(20):
+        env.step(rng.uniform(-1, 1, (n, 12)).astype(np.float32))
+    snap = env.snapshot()
+    assert "dynamics" in snap["sim"]
+    acts = [rng.uniform(-1, 1, (n, 12)).astype(np.float32) for _ in range(60)]
+    first = [env.step(a)[:3] for a in acts] + [(env.dynamics(),)]
+    other = POWalkingQuadrupedVecEnv(n, **kw)
+    other.reset()
+    other.restore(snap)
+    second = [other.step(a)[:3] for a in acts] + [(other.dynamics(),)]
+    for x, y in zip(first, second):
+        for u, v in zip(x, y):
+            assert np.array_equal(np.asarray(u), np.asarray(v))
+    env.close(); other.close()
+
+
+@pytest.mark.gpu
+def test_scale_32768_envs(oracle):
+    from quadruped_gym_amd.sim import BatchedSim
+    import torch
+    n = 32768
+    sim = BatchedSim(n)
+    sim.set_dynamics_range(WIDE)
+    sim.reset(seed=5, flags=_abi.RESET_RANDOM_YAW | _abi.RESET_DYNAMICS)
+    assert sim.mapping == _abi.MAP_QUAD
+    dev = torch.device("cuda:0")
+    packed = torch.empty((n, 35), device=dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    for _ in range(200):
+        sim.step_device_packed(torch.rand((n, 12), device=dev, generator=g) * 2 - 1, packed)
+    torch.cuda.synchronize()
+    q, v, a, c, ns = sim.get_state()
+    assert np.isfinite(q).all() and np.isfinite(v).all()
+    assert np.allclose(np.linalg.norm(q[:, 3:7], axis=1), 1, atol=1e-5)
+    rows = sim.get_dynamics()
+    pick = np.arange(0, n, 257)
+    actions = np.random.default_rng(2).uniform(-1, 1, (n, 12)).astype(np.float32)
+    _ = sim.step(actions)
+    q1, v1, a1, _, _ = sim.get_state()
+    sim.close()
+    state = (q[pick], v[pick], a[pick], ns[pick])
+    live = ns[pick] + 4 < 5000                             # no time-limit reset inside the step (max_time 10 s)
+    _, _, _, q_o, v_o, a_o = oracle_per_env(oracle, oracle.default_model(), oracle.default_task(), rows[pick], state, actions[pick])
+    t = TOL["A"]
+    close(q1[pick][live], q_o[live], t["qpos"], "qpos")
+    close(v1[pick][live], v_o[live], t["qvel"], "qvel")
+
+
+@pytest.mark.gpu
+def test_refusals():
+    from quadruped_gym_amd.sim import BatchedSim
+    import torch
+    lib = _abi.load_library()
+    n = 64
+    sim = BatchedSim(n)
+    # a flagged reset without a range
+    assert lib.qg_reset(sim._h, None, 0, _abi.RESET_DYNAMICS) == -1
+    assert b"range" in lib.qg_last_error()
+    model = sim.model
+    bad = [{"friction": (-0.1, 0.5)}, {"payload_mass": (-0.1, 0.3), "payload_pos": ((-0.02, 0.02),) * 3}, {"payload_mass": (-model.body_mass[0] - 0.01, 0.0)}, {"kp_scale": (float("nan"), 1.0)},
+           {"kv_scale": (-1.0, 1.0)}]
+    for spec in bad:
+        r = _abi.dynamics_range(spec, model)
+        assert lib.qg_set_dynamics_range(sim._h, C.byref(r)) == -1, spec
+        assert len(lib.qg_last_error()) > 0
+    row = np.tile(_abi.identity_dynamics_row(model), (n, 1))
+    row[3, 1] = -model.body_mass[0]
+    assert lib.qg_set_dynamics(sim._h, None, row.ctypes.data) == -1
+    row[3, 1] = 0
+    row[5, 0] = np.nan
+    assert lib.qg_set_dynamics(sim._h, None, row.ctypes.data) == -1
+    assert not sim.baked or lib.qg_uses_baked_model(sim._h) == 1      # nothing switched on by a refused call
+    sim.set_dynamics_range(WIDE)
+    for m in (_abi.MAP_PAIR, _abi.MAP_LANE):
+        assert lib.qg_set_mapping(sim._h, m) == -1
+        assert b"LINK and QUAD" in lib.qg_last_error()
+    dev = torch.device("cuda:0")
+    acts = torch.zeros((2, n, 12), device=dev)
+    packed = torch.empty((2, n, 35), device=dev)
+    assert lib.qg_step_device_seq(sim._h, C.c_void_p(acts.data_ptr()), C.c_void_p(packed.data_ptr()), 2, None) == -1
+    assert lib.qg_resident_start(sim._h, 2, 0, None, None) == -1
+    sim.close()
+    # a handle on the LANE mapping cannot switch the mode on
+    s2 = BatchedSim(n)
+    s2.set_mapping(_abi.MAP_LANE)
+    with pytest.raises(_abi.QuadGymError):
+        s2.set_dynamics_range(WIDE)
+    s2.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("host_reset", [False, True])
+def test_quadruped_vec_env_dynamics(oracle, host_reset):
+    """QuadrupedVecEnv(dynamics_randomization=...): the flag reaches the reset and the auto-reset (in-kernel, or -- with a host
+    termination callable -- the host's masked reset), and dynamics() shows rows keyed by each env's episode."""
+    from quadruped_gym_amd.envs.vec_env import QuadrupedVecEnv
+    n, seed = 64, 3
+    holder = {}
+    kw = dict(dynamics_randomization=WIDE, seed=seed, random_init=True, max_time=0.05)
+    if host_reset:
+        kw["termination_fns"] = {"short": lambda: holder["env"].data.time >= 0.03}
+        kw["callable_mode"] = "batched"
+    env = QuadrupedVecEnv(n, **kw)
+    holder["env"] = env
+    assert env._reset_flags & _abi.RESET_DYNAMICS
+    assert bool(env._sim.task.auto_reset) == (not host_reset)
+    env.reset()
+    rows = env.dynamics()
+    assert rows.shape == (n, 11) and rows.dtype == np.float32
+    assert ulp_close(rows, expected_rows(oracle, WIDE, env._sim.model, seed, range(n), [0] * n))
+    rng = np.random.default_rng(0)
+    done = np.zeros(n, bool)
+    for _ in range(40):
+        _, _, done, _ = env.step(rng.uniform(-1, 1, (n, 12)).astype(np.float32))
+        done = np.asarray(done, bool)
+        if done.any():
+            break
+    assert done.any()
+    after = env.dynamics()
+    assert np.array_equal(after[~done], rows[~done])
+    ep, _ = env._sim.get_reset_streams()
+    idx = np.nonzero(done)[0]
+    assert (ep[idx] == 2).all()
+    assert ulp_close(after[idx], expected_rows(oracle, WIDE, env._sim.model, seed, idx, ep[idx] - 1))
+    env.close()
+
+
+@pytest.mark.gpu
+def test_restore_checks_before_writing():
+    """A snapshot without rows into a handle with the mode on is refused with nothing written; a snapshot with rows carries the
+    range, so the restored handle draws what the original would."""
+    from quadruped_gym_amd.sim import BatchedSim
+    n = 64
+    plain, dyn = BatchedSim(n), BatchedSim(n)
+    dyn.set_dynamics_range(WIDE)
+    dyn.reset(seed=4, flags=_abi.RESET_DYNAMICS)
+    before = dyn.snapshot()
+    with pytest.raises(ValueError):
+        dyn.restore(plain.snapshot())
+    after = dyn.snapshot()
+    for k in ("qpos", "qvel", "act", "nstep", "episode", "dynamics"):
+        assert np.array_equal(before[k], after[k])
+    fresh = BatchedSim(n)
+    fresh.restore(before)
+    assert fresh.dynamics_on and np.array_equal(fresh.get_dynamics(), before["dynamics"])
+    for s in (fresh, dyn):
+        s.reset(mask=np.ones(n, np.uint8), flags=_abi.RESET_DYNAMICS)
+    assert np.array_equal(fresh.get_dynamics(), dyn.get_dynamics())
+    for s in (plain, dyn, fresh):
+        s.close()
+
+
+@pytest.mark.gpu
+def test_set_dynamics_waits_for_device_pointer_steps():
+    """qg_set_dynamics after device-pointer steps on a caller's stream (with auto-reset draws in them): the rows written are the ones
+    read back, and the draws that happened before the call are kept for the unmasked envs."""
+    from quadruped_gym_amd.sim import BatchedSim
+    import torch
+    n = 4096
+    task = _abi.default_task()
+    task.max_time = 0.02
+    task.auto_reset, task.reset_flags = 1, _abi.RESET_DYNAMICS
+    sim = BatchedSim(n, task=task)
+    sim.set_dynamics_range(WIDE)
+    sim.reset(seed=9, flags=_abi.RESET_DYNAMICS)
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.Stream(device=dev)
+    acts = torch.zeros((n, 12), device=dev)
+    packed = torch.empty((n, 35), device=dev)
+    with torch.cuda.stream(stream):
+        for _ in range(40):
+            sim.step_device_packed(acts, packed, stream=stream)
+    mask = np.zeros(n, np.uint8)
+    mask[::2] = 1
+    new = np.tile(_abi.identity_dynamics_row(sim.model), (n, 1))
+    sim.set_dynamics(new, mask=mask)          # no explicit synchronisation: the call has to wait itself
+    torch.cuda.synchronize()
+    ep, _ = sim.get_reset_streams()
+    got = sim.get_dynamics()
+    assert np.array_equal(got[::2], new[::2])
+    assert (ep > 1).all()                      # every env went through auto-resets before the call
+    sim.close()
