@@ -153,6 +153,14 @@ extern "C" int qg_default_task(qg_task *out) {
 
 extern "C" int64_t qg_time_limit_substeps(double timestep, double max_time) { return qg_time_limit_substeps_impl(timestep, max_time); }
 
+// the resident kernel hands the state back, then whatever is in flight on any stream -- a caller's included -- has run
+static int retire_and_sync(qg_sim *s) {
+    int rc = resident_retire(s);
+    if (rc != QG_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    return QG_OK;
+}
+
 extern "C" int qg_destroy(qg_sim *s) {
     if (!s) return QG_OK;
     (void)hipSetDevice(s->device);
@@ -270,8 +278,7 @@ extern "C" int qg_reset(qg_sim *s, const uint8_t *mask, uint64_t seed, uint32_t 
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     // steps may be in flight on a caller's stream (qg_step_device*): the reset runs on the library's own non-blocking stream
     // and must not overlap them (a resident step kernel first stores the state it holds in registers and leaves)
-    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
-    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }
     // the seed keys the reset streams of EVERY env (auto-resets included): only a whole-batch reset may change it, a masked
     // reset draws from the streams already in force
     if ((flags & QG_RESET_DYNAMICS) && !s->dyn_range_set) return fail(QG_ERR_ARG, "qg_reset: QG_RESET_DYNAMICS without a range (qg_set_dynamics_range)");
@@ -322,18 +329,147 @@ static int effective_mapping(const qg_sim *s) {
     return QG_MAP_QUAD;
 }
 
+// ---- step-kernel grids ------------------------------------------------------------------------------------------------------------
+// The size predicates every step-kernel choice reads (po_fusable, launch_step, qg_step_device_seq), and the launchers: one per kernel
+// family, each deriving grid and block from the instantiation it launches, as the kernel's __launch_bounds__ does.
+static int link_blocks(const qg_sim *s) { return (s->n + QGK_LINK_ENVS * QGK_LINK_WAVES - 1) / (QGK_LINK_ENVS * QGK_LINK_WAVES); }
+static int quad_blocks(const qg_sim *s) { return (s->n + QGK_QUAD_ENVS - 1) / QGK_QUAD_ENVS; }    // one wave each
+static int pair_blocks(const qg_sim *s) { return (s->n + QGK_PAIR_ENVS - 1) / QGK_PAIR_ENVS; }
+// four-wave workgroups for grids of more than one wave per compute unit
+static bool quad_wg4(const qg_sim *s) { return quad_blocks(s) > s->simds / 4; }
+static bool pair_wg4(const qg_sim *s) { return pair_blocks(s) > s->simds / 4; }
+// at most one wave per SIMD (256 CUs x 4 on an MI355X): give each wave the whole register file
+static bool quad_one_wave(const qg_sim *s) { return quad_blocks(s) <= s->simds; }
+static dim3 wave_grid(int waves, int per_group) { return dim3(per_group == 4 ? (waves + 3) / 4 : waves); }
+
+// what every per-launch step kernel takes, and where it goes
+struct StepLaunch {
+    const qg_sim *s;
+    const KModel *model;      // the model tables (per-env dynamics: the KModelDyn in front of the rows)
+    KStepArgs P;
+    hipStream_t stream;
+    const KWalkLaunch *walk;
+    const KPoLaunch *po;
+};
+template <bool WALK> static typename WalkArgT<WALK>::type walk_arg(const KWalkLaunch *w) {
+    if constexpr (WALK) return *w;
+    else return {};
+}
+template <bool PO> static typename PoArgT<PO>::type po_arg(const KPoLaunch *p) {
+    if constexpr (PO) return *p;
+    else return {};
+}
+
+template <bool BAKED> static void launch_lane(const StepLaunch &L) {
+    hipLaunchKernelGGL(qg_step_kernel<BAKED>, dim3((L.s->n + QGK_WAVE - 1) / QGK_WAVE), dim3(QGK_WAVE), 0, L.stream, L.model, L.s->d_task, L.P);
+}
+template <bool WALK, bool PO, bool BAKED, bool HELP = false, bool DYN = false> static void launch_link(const StepLaunch &L) {
+    hipLaunchKernelGGL((qg_step_kernel_link<WALK, PO, BAKED, HELP, DYN>), dim3(link_blocks(L.s)), dim3(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1)), 0,
+                       L.stream, L.model, L.s->d_task, L.P, walk_arg<WALK>(L.walk), po_arg<PO>(L.po));
+}
+template <int WPE, bool BAKED, bool WALK, int WAVES, bool PO = false, bool HELP = false, bool DYN = false> static void launch_quad(const StepLaunch &L) {
+    static_assert(WAVES == 1 || WAVES == 4, "one-wave or four-wave workgroups");
+    hipLaunchKernelGGL((qg_step_kernel_quad<WPE, BAKED, WALK, WAVES, PO, HELP, DYN>), wave_grid(quad_blocks(L.s), WAVES),
+                       dim3(QGK_WAVE * WAVES * (HELP ? 2 : 1)), 0, L.stream, L.model, L.s->d_task, L.P, walk_arg<WALK>(L.walk), po_arg<PO>(L.po));
+}
+template <int WAVES, bool WALK, bool PO = false> static void launch_pair(const StepLaunch &L) {
+    static_assert(WAVES == 1 || WAVES == 4, "one-wave or four-wave workgroups");
+    hipLaunchKernelGGL((qg_step_kernel_pair<WAVES, WALK, PO>), wave_grid(pair_blocks(L.s), WAVES), dim3(QGK_WAVE * WAVES), 0, L.stream, L.s->d_task,
+                       L.P, walk_arg<WALK>(L.walk), po_arg<PO>(L.po));
+}
+// the many-env-steps-per-launch forms (qg_kernel_resident.hip)
+template <bool BAKED, bool DOOR> static void launch_link_multi(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
+    hipLaunchKernelGGL((qg_step_kernel_link_multi<BAKED, DOOR>), dim3(link_blocks(s)), dim3(QGK_WAVE * QGK_LINK_WAVES), 0, st, s->d_model, s->d_task, P, R);
+}
+template <int WPE, bool BAKED> static void launch_quad_multi(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
+    hipLaunchKernelGGL((qg_step_kernel_quad_multi<WPE, BAKED>), wave_grid(quad_blocks(s), 4), dim3(QGK_WAVE * 4), 0, st, s->d_model, s->d_task, P, R);
+}
+template <int WAVES> static void launch_pair_multi(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
+    static_assert(WAVES == 1 || WAVES == 4, "one-wave or four-wave workgroups");
+    hipLaunchKernelGGL((qg_step_kernel_pair_multi<WAVES>), wave_grid(pair_blocks(s), WAVES), dim3(QGK_WAVE * WAVES), 0, st, s->d_task, P, R);
+}
+
 // Which step kernels carry the fused observation pack (KPoLaunch): the one-link-per-lane kernel, and -- round 3 -- the four-wave-workgroup
 // forms of the two-legs-per-lane and one-leg-per-lane kernels that AUTO runs above 4096 envs (explicit mapping requests on small
 // grids, which launch the one-wave-workgroup forms, keep the observation pack a launch of its own).
 static bool po_fusable(const qg_sim *s) {
     const int emap = effective_mapping(s);
     if (emap == QG_MAP_LINK) return true;
-    if (emap == QG_MAP_PAIR) return (s->n + QGK_PAIR_ENVS - 1) / QGK_PAIR_ENVS > s->simds / 4;
-    if (emap == QG_MAP_QUAD) {
-        const int qblocks = (s->n + QGK_QUAD_ENVS - 1) / QGK_QUAD_ENVS;
-        return qblocks > s->simds / 4;
-    }
+    if (emap == QG_MAP_PAIR) return pair_wg4(s);
+    if (emap == QG_MAP_QUAD) return quad_wg4(s);
     return false;
+}
+
+static bool jitter_at_reset(const qg_sim *s) { return s->task.auto_reset && (s->task.reset_flags & QG_RESET_JOINT_JITTER); }
+
+// A device-pointer step enqueued on a caller's stream: the next host-pointer call waits for the whole device, and from the first one
+// that is CAPTURED on (sticky) every host-pointer call does.  (Not asked of the legacy NULL stream: while ANOTHER stream is in
+// global-mode capture that query itself is a capture-implicit error and invalidates the capture in progress; a failed query counts
+// as "captured" and its error is cleared.)
+static void note_caller_stream(qg_sim *s, hipStream_t stream) {
+    if (stream == s->stream) return;
+    s->caller_inflight = 1;
+    if (s->captured_once || !stream) return;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); s->captured_once = 1; }
+    else if (cs == hipStreamCaptureStatusActive) s->captured_once = 1;
+}
+
+// One decision per mapping; every leaf names the instantiation it launches.  DYN: per-env dynamics, which run the table-driven
+// (!baked) leaves of the LINK and QUAD mappings only.
+template <bool DYN> static void select_step(const StepLaunch &L, int emap) {
+    const qg_sim *s = L.s;
+    const bool walk = L.walk, po = L.po;
+    switch (emap) {
+    case QG_MAP_LINK:
+        if (!s->baked) {
+            if (po) launch_link<true, true, false, false, DYN>(L);
+            else if (walk) launch_link<true, false, false, false, DYN>(L);
+            else launch_link<false, false, false, false, DYN>(L);
+        } else if (walk && s->link_helpers) {
+            // helper waves (qg_step_kernel_link<.., HELP>): the compiled-in robot's walking forms; QG_LINK_HELPERS=0 at qg_create keeps the one-role kernels
+            if (po) launch_link<true, true, true, true>(L);
+            else launch_link<true, false, true, true>(L);
+        } else if (po) launch_link<true, true, true>(L);
+        else if (walk) launch_link<true, false, true>(L);
+        else launch_link<false, false, true>(L);
+        break;
+    case QG_MAP_QUAD:
+        if (!s->baked) {
+            // tables in LDS: the 256-register cap spills 888 B per lane and measured 2x slower at every grid size (363 vs 741 us
+            // at 262 144 envs), so any other robot runs the one-wave-per-SIMD form throughout
+            if (po) launch_quad<1, false, true, 4, true, false, DYN>(L);     // po_fusable(): four-wave workgroups
+            else if (walk && quad_wg4(s)) launch_quad<1, false, true, 4, false, false, DYN>(L);
+            else if (walk) launch_quad<1, false, true, 1, false, false, DYN>(L);
+            else if (quad_wg4(s)) launch_quad<1, false, false, 4, false, false, DYN>(L);
+            else launch_quad<1, false, false, 1, false, false, DYN>(L);
+        } else if (po) {            // po_fusable(): four-wave workgroups, register cap for one or two waves per SIMD
+            if (quad_one_wave(s) && s->link_helpers) launch_quad<2, true, true, 4, true, true>(L);
+            else if (quad_one_wave(s)) launch_quad<1, true, true, 4, true>(L);
+            else launch_quad<2, true, true, 4, true>(L);
+        } else if (walk) {
+            // at most one physics wave per SIMD: helper waves beside them (QG_LINK_HELPERS, as for the one-link-per-lane kernel)
+            if (quad_one_wave(s) && s->link_helpers) launch_quad<2, true, true, 4, false, true>(L);
+            else if (quad_one_wave(s) && quad_wg4(s)) launch_quad<1, true, true, 4>(L);
+            else if (quad_one_wave(s)) launch_quad<1, true, true, 1>(L);
+            else launch_quad<2, true, true, 4>(L);
+        } else if (quad_one_wave(s)) {
+            if (quad_wg4(s)) launch_quad<1, true, false, 4>(L);
+            else launch_quad<1, true, false, 1>(L);
+        } else if (quad_wg4(s)) launch_quad<2, true, false, 4>(L);
+        else launch_quad<2, true, false, 1>(L);
+        break;
+    case QG_MAP_PAIR:                       // (the compiled-in robot only)
+        if (po) launch_pair<4, true, true>(L);                             // po_fusable(): four-wave workgroups
+        else if (walk && pair_wg4(s)) launch_pair<4, true>(L);
+        else if (walk) launch_pair<1, true>(L);
+        else if (pair_wg4(s)) launch_pair<4, false>(L);
+        else launch_pair<1, false>(L);
+        break;
+    default:                                // QG_MAP_LANE
+        if (s->baked) launch_lane<true>(L);
+        else launch_lane<false>(L);
+    }
 }
 
 // `walk` != NULL: the fused walking launch (one-leg-per-lane kernel with the task layer folded in); walk_comps / walk_sample go
@@ -353,130 +489,26 @@ static int launch_step(qg_sim *s, const float *d_actions, float *d_obs, float *d
     P.packed = d_packed;
     P.seed = s->seed;
     P.env_index_base = s->env_index_base;
-    int blocks = (s->n + QGK_WAVE - 1) / QGK_WAVE;
+    const StepLaunch L = {s, s->dyn ? &s->d_model_dyn->m : s->d_model, P, stream, walk, po};
     const int emap = effective_mapping(s);
     if (s->res.launched) {            // a per-launch step while the resident kernel holds the state in registers: it has to hand it back first
         int rr = resident_retire(s);
         if (rr != QG_OK) return rr;
     }
-    if (stream != s->stream) {
-        s->caller_inflight = 1;
-        if (!s->captured_once) {
-            // (not asked of the legacy NULL stream: while ANOTHER stream is in global-mode capture that query itself is a
-            // capture-implicit error and invalidates the capture in progress; a failed query counts as "captured")
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (stream) {
-                const hipError_t qe = hipStreamIsCapturing(stream, &cs);
-                if (qe != hipSuccess) { (void)hipGetLastError(); s->captured_once = 1; }
-                else if (cs == hipStreamCaptureStatusActive) s->captured_once = 1;
-            }
-        }
-    }
+    note_caller_stream(s, stream);
     if (po && !(walk && po_fusable(s))) return fail(QG_ERR_ARG, "launch_step: no step kernel with the fused observation pack for this handle");
+    if (walk && emap == QG_MAP_LANE) return fail(QG_ERR_ARG, "launch_step: no step kernel with the fused walking task layer for this handle");
     const bool dyn_draw = s->task.auto_reset && (s->task.reset_flags & QG_RESET_DYNAMICS);
     if (dyn_draw && !s->dyn_range_set) return fail(QG_ERR_ARG, "step: task.reset_flags has QG_RESET_DYNAMICS and no range is set (qg_set_dynamics_range)");
-    if (s->dyn) {
-        // per-env dynamics: the table-driven kernels' per-env forms, one link per lane up to 4096 envs (lagged sensors), one leg per lane
-        // above (qg_set_mapping refuses the other mappings while the mode is on)
-        const KModel *dm = &s->d_model_dyn->m;
-        if (emap == QG_MAP_LINK) {
-            const int per_block = QGK_LINK_ENVS * QGK_LINK_WAVES;
-            dim3 lg((s->n + per_block - 1) / per_block), lb(QGK_WAVE * QGK_LINK_WAVES);
-            if (po) hipLaunchKernelGGL((qg_step_kernel_link<true, true, false, false, true>), lg, lb, 0, stream, dm, s->d_task, P, *walk, *po);
-            else if (walk) hipLaunchKernelGGL((qg_step_kernel_link<true, false, false, false, true>), lg, lb, 0, stream, dm, s->d_task, P, *walk, KPoNone{});
-            else hipLaunchKernelGGL((qg_step_kernel_link<false, false, false, false, true>), lg, lb, 0, stream, dm, s->d_task, P, KWalkNone{}, KPoNone{});
-        } else if (emap == QG_MAP_QUAD) {
-            const int qblocks = (s->n + QGK_QUAD_ENVS - 1) / QGK_QUAD_ENVS;
-            const bool wg4 = qblocks > s->simds / 4;
-            dim3 g1(qblocks), b1(QGK_WAVE), g4((qblocks + 3) / 4), b4(QGK_WAVE * 4);
-            if (po) hipLaunchKernelGGL((qg_step_kernel_quad<1, false, true, 4, true, false, true>), g4, b4, 0, stream, dm, s->d_task, P, *walk, *po);
-            else if (walk && wg4) hipLaunchKernelGGL((qg_step_kernel_quad<1, false, true, 4, false, false, true>), g4, b4, 0, stream, dm, s->d_task, P, *walk, KPoNone{});
-            else if (walk) hipLaunchKernelGGL((qg_step_kernel_quad<1, false, true, 1, false, false, true>), g1, b1, 0, stream, dm, s->d_task, P, *walk, KPoNone{});
-            else if (wg4) hipLaunchKernelGGL((qg_step_kernel_quad<1, false, false, 4, false, false, true>), g4, b4, 0, stream, dm, s->d_task, P, KWalkNone{}, KPoNone{});
-            else hipLaunchKernelGGL((qg_step_kernel_quad<1, false, false, 1, false, false, true>), g1, b1, 0, stream, dm, s->d_task, P, KWalkNone{}, KPoNone{});
-        } else {
-            return fail(QG_ERR_ARG, "step: per-env dynamics run in the LINK and QUAD mappings only (mapping %d)", emap);
-        }
-    } else if (walk && emap == QG_MAP_LINK) {
-        const int per_block = QGK_LINK_ENVS * QGK_LINK_WAVES;
-        int lblocks = (s->n + per_block - 1) / per_block;
-        dim3 lg(lblocks), lb(QGK_WAVE * QGK_LINK_WAVES);
-        // helper waves (qg_step_kernel_link<.., HELP>): the compiled-in robot's walking forms; QG_LINK_HELPERS=0 at qg_create keeps the one-role kernels
-        const int helpers = s->link_helpers;
-        const dim3 lb2(2 * QGK_WAVE * QGK_LINK_WAVES);
-        if (helpers && po && s->baked) hipLaunchKernelGGL((qg_step_kernel_link<true, true, true, true>), lg, lb2, 0, stream, s->d_model, s->d_task, P, *walk, *po);
-        else if (helpers && s->baked) hipLaunchKernelGGL((qg_step_kernel_link<true, false, true, true>), lg, lb2, 0, stream, s->d_model, s->d_task, P, *walk, KPoNone{});
-        else if (po && s->baked) hipLaunchKernelGGL((qg_step_kernel_link<true, true, true>), lg, lb, 0, stream, s->d_model, s->d_task, P, *walk, *po);
-        else if (po) hipLaunchKernelGGL((qg_step_kernel_link<true, true, false>), lg, lb, 0, stream, s->d_model, s->d_task, P, *walk, *po);
-        else if (s->baked) hipLaunchKernelGGL((qg_step_kernel_link<true, false, true>), lg, lb, 0, stream, s->d_model, s->d_task, P, *walk, KPoNone{});
-        else hipLaunchKernelGGL((qg_step_kernel_link<true, false, false>), lg, lb, 0, stream, s->d_model, s->d_task, P, *walk, KPoNone{});
-    } else if (walk && emap == QG_MAP_PAIR) {
-        int pblocks = (s->n + QGK_PAIR_ENVS - 1) / QGK_PAIR_ENVS;
-        if (po)
-            hipLaunchKernelGGL((qg_step_kernel_pair<4, true, true>), dim3((pblocks + 3) / 4), dim3(QGK_WAVE * 4), 0, stream, s->d_task, P, *walk, *po);
-        else if (pblocks > s->simds / 4)
-            hipLaunchKernelGGL((qg_step_kernel_pair<4, true>), dim3((pblocks + 3) / 4), dim3(QGK_WAVE * 4), 0, stream, s->d_task, P, *walk, KPoNone{});
-        else
-            hipLaunchKernelGGL((qg_step_kernel_pair<1, true>), dim3(pblocks), dim3(QGK_WAVE), 0, stream, s->d_task, P, *walk, KPoNone{});
-    } else if (walk) {
-        int qblocks = (s->n + QGK_QUAD_ENVS - 1) / QGK_QUAD_ENVS;
-        const int wpe = qblocks <= s->simds ? 1 : 2;
-        const bool wg4 = qblocks > s->simds / 4;    // four-wave workgroups for grids of more than one wave per compute unit
-        dim3 g1(qblocks), b1(QGK_WAVE), g4((qblocks + 3) / 4), b4(QGK_WAVE * 4);
-        if (po) {                                   // po_fusable(): four-wave workgroups, register cap for one or two waves per SIMD
-            if (!s->baked) hipLaunchKernelGGL((qg_step_kernel_quad<1, false, true, 4, true>), g4, b4, 0, stream, s->d_model, s->d_task, P, *walk, *po);
-            else if (wpe == 1 && s->link_helpers)
-                hipLaunchKernelGGL((qg_step_kernel_quad<2, true, true, 4, true, true>), g4, dim3(QGK_WAVE * 8), 0, stream, s->d_model, s->d_task, P, *walk, *po);
-            else if (wpe == 1) hipLaunchKernelGGL((qg_step_kernel_quad<1, true, true, 4, true>), g4, b4, 0, stream, s->d_model, s->d_task, P, *walk, *po);
-            else hipLaunchKernelGGL((qg_step_kernel_quad<2, true, true, 4, true>), g4, b4, 0, stream, s->d_model, s->d_task, P, *walk, *po);
-        } else if (!s->baked) {
-            if (wg4) hipLaunchKernelGGL((qg_step_kernel_quad<1, false, true, 4>), g4, b4, 0, stream, s->d_model, s->d_task, P, *walk, KPoNone{});
-            else hipLaunchKernelGGL((qg_step_kernel_quad<1, false, true, 1>), g1, b1, 0, stream, s->d_model, s->d_task, P, *walk, KPoNone{});
-        } else if (wpe == 1) {
-            // at most one physics wave per SIMD: helper waves beside them (QG_LINK_HELPERS, as for the one-link-per-lane kernel)
-            if (s->link_helpers)
-                hipLaunchKernelGGL((qg_step_kernel_quad<2, true, true, 4, false, true>), g4, dim3(QGK_WAVE * 8), 0, stream, s->d_model, s->d_task, P, *walk, KPoNone{});
-            else if (wg4) hipLaunchKernelGGL((qg_step_kernel_quad<1, true, true, 4>), g4, b4, 0, stream, s->d_model, s->d_task, P, *walk, KPoNone{});
-            else hipLaunchKernelGGL((qg_step_kernel_quad<1, true, true, 1>), g1, b1, 0, stream, s->d_model, s->d_task, P, *walk, KPoNone{});
-        } else {
-            hipLaunchKernelGGL((qg_step_kernel_quad<2, true, true, 4>), g4, b4, 0, stream, s->d_model, s->d_task, P, *walk, KPoNone{});
-        }
-    } else if (emap == QG_MAP_LINK) {
-        const int per_block = QGK_LINK_ENVS * QGK_LINK_WAVES;
-        int lblocks = (s->n + per_block - 1) / per_block;
-        dim3 lg(lblocks), lb(QGK_WAVE * QGK_LINK_WAVES);
-        if (s->baked) hipLaunchKernelGGL((qg_step_kernel_link<false, false, true>), lg, lb, 0, stream, s->d_model, s->d_task, P, KWalkNone{}, KPoNone{});
-        else hipLaunchKernelGGL((qg_step_kernel_link<false, false, false>), lg, lb, 0, stream, s->d_model, s->d_task, P, KWalkNone{}, KPoNone{});
-    } else if (emap == QG_MAP_PAIR) {
-        int pblocks = (s->n + QGK_PAIR_ENVS - 1) / QGK_PAIR_ENVS;
-        if (pblocks > s->simds / 4)
-            hipLaunchKernelGGL((qg_step_kernel_pair<4, false>), dim3((pblocks + 3) / 4), dim3(QGK_WAVE * 4), 0, stream, s->d_task, P, KWalkNone{}, KPoNone{});
-        else
-            hipLaunchKernelGGL((qg_step_kernel_pair<1, false>), dim3(pblocks), dim3(QGK_WAVE), 0, stream, s->d_task, P, KWalkNone{}, KPoNone{});
-    } else if (emap == QG_MAP_QUAD) {
-        int qblocks = (s->n + QGK_QUAD_ENVS - 1) / QGK_QUAD_ENVS;
-        const bool one_wave = qblocks <= s->simds;  // at most one wave per SIMD (256 CUs x 4 on an MI355X): give each wave the whole register file
-        const bool wg4 = qblocks > s->simds / 4;    // four-wave workgroups for grids of more than one wave per compute unit
-        dim3 g1(qblocks), b1(QGK_WAVE), g4((qblocks + 3) / 4), b4(QGK_WAVE * 4);
-        if (s->baked) {
-            const int wpe = one_wave ? 1 : 2;
-            if (wpe == 1 && !wg4) hipLaunchKernelGGL((qg_step_kernel_quad<1, true, false, 1>), g1, b1, 0, stream, s->d_model, s->d_task, P, KWalkNone{}, KPoNone{});
-            else if (wpe == 1) hipLaunchKernelGGL((qg_step_kernel_quad<1, true, false, 4>), g4, b4, 0, stream, s->d_model, s->d_task, P, KWalkNone{}, KPoNone{});
-            else if (!wg4) hipLaunchKernelGGL((qg_step_kernel_quad<2, true, false, 1>), g1, b1, 0, stream, s->d_model, s->d_task, P, KWalkNone{}, KPoNone{});
-            else hipLaunchKernelGGL((qg_step_kernel_quad<2, true, false, 4>), g4, b4, 0, stream, s->d_model, s->d_task, P, KWalkNone{}, KPoNone{});
-        } else {
-            // tables in LDS: the 256-register cap spills 888 B per lane and measured 2x slower at every grid size (363 vs 741 us
-            // at 262 144 envs), so any other robot runs the one-wave-per-SIMD form throughout
-            if (wg4) hipLaunchKernelGGL((qg_step_kernel_quad<1, false, false, 4>), g4, b4, 0, stream, s->d_model, s->d_task, P, KWalkNone{}, KPoNone{});
-            else hipLaunchKernelGGL((qg_step_kernel_quad<1, false, false, 1>), g1, b1, 0, stream, s->d_model, s->d_task, P, KWalkNone{}, KPoNone{});
-        }
-    } else if (s->baked)
-        hipLaunchKernelGGL(qg_step_kernel<true>, dim3(blocks), dim3(QGK_WAVE), 0, stream, s->d_model, s->d_task, P);
-    else
-        hipLaunchKernelGGL(qg_step_kernel<false>, dim3(blocks), dim3(QGK_WAVE), 0, stream, s->d_model, s->d_task, P);
+    // per-env dynamics: the table-driven kernels' per-env forms, one link per lane up to 4096 envs (lagged sensors), one leg per lane
+    // above (qg_set_mapping refuses the other mappings while the mode is on)
+    if (s->dyn && emap != QG_MAP_LINK && emap != QG_MAP_QUAD)
+        return fail(QG_ERR_ARG, "step: per-env dynamics run in the LINK and QUAD mappings only (mapping %d)", emap);
+    if (s->dyn) select_step<true>(L, emap);
+    else select_step<false>(L, emap);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "qg_step_kernel launch: %s", hipGetErrorString(e));
-    if (s->task.auto_reset && (s->task.reset_flags & QG_RESET_JOINT_JITTER)) {     // start-pose randomisation of the envs just auto-reset
+    if (jitter_at_reset(s)) {         // start-pose randomisation of the envs just auto-reset
         const int total = 12 * s->n, threads = 256;
         hipLaunchKernelGGL(qg_jitter_kernel, dim3((total + threads - 1) / threads), dim3(threads), 0, stream, s->d_model, s->d_task, s->st, s->n,
                            (const uint8_t *)d_done, (const float *)d_packed, s->obs_dim + 2, s->seed, s->env_index_base);
@@ -552,29 +584,6 @@ static int wait_for_caller_streams(qg_sim *s) {
     return QG_OK;
 }
 
-extern "C" int qg_step(qg_sim *s, const float *actions, float *obs, float *reward, uint8_t *done, float *comps) {
-    if (!s || !actions || !obs || !reward || !done) return fail(QG_ERR_ARG, "qg_step: null argument");
-    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    { int rc0 = wait_for_caller_streams(s); if (rc0 != QG_OK) return rc0; }
-    size_t n = (size_t)s->n;
-    size_t off = pin_align(n * QG_NU * sizeof(float));
-    PinOut o_obs = {obs, off, n * s->obs_dim * sizeof(float)};       off += pin_align(o_obs.bytes);
-    PinOut o_rew = {reward, off, n * sizeof(float)};                   off += pin_align(o_rew.bytes);
-    PinOut o_done = {done, off, n};                                    off += pin_align(o_done.bytes);
-    PinOut o_comp = {comps, off, n * QG_NREWARD * sizeof(float)};      off += pin_align(o_comp.bytes);
-    int rc = pin_reserve(s, off);
-    if (rc == QG_OK) rc = pin_actions_in(s, actions, s->d_actions);
-    if (rc == QG_OK) rc = launch_step(s, s->d_actions, s->d_obs, s->d_reward, s->d_done, comps ? s->d_comps : nullptr, nullptr, s->stream);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_obs, s->d_obs);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_rew, s->d_reward);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_done, s->d_done);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_comp, s->d_comps);
-    if (rc != QG_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream), QG_ERR_LAUNCH);
-    pin_out_finish(s, o_obs); pin_out_finish(s, o_rew); pin_out_finish(s, o_done); pin_out_finish(s, o_comp);
-    return QG_OK;
-}
-
 static int copy_in(qg_sim *s, const float *host, float *field_major, int w) {
     if (!host) return QG_OK;
     int total = s->n * w, threads = 256;
@@ -587,13 +596,14 @@ static int copy_in(qg_sim *s, const float *host, float *field_major, int w) {
 
 // State snapshot, part 1: where the five outputs land in the page-locked arena (from `off` on); part 2: the four transposes into their
 // own regions of the staging buffer and every transfer, enqueued on the library's stream (no synchronisation in here).
+struct StateDst { float *qpos, *qvel, *act, *ctrl; int32_t *nstep; };
 struct StateOut { PinOut o[5]; };
-static size_t state_out_layout(qg_sim *s, float *qpos, float *qvel, float *act, float *ctrl, int32_t *nstep, size_t off, StateOut &so) {
+static size_t state_out_layout(qg_sim *s, const StateDst &d, size_t off, StateOut &so) {
     const size_t n = (size_t)s->n;
-    float *dst[4] = {qpos, qvel, act, ctrl};
+    float *dst[4] = {d.qpos, d.qvel, d.act, d.ctrl};
     const int w[4] = {QG_NQ, QG_NV, QG_NU, QG_NU};
     for (int f = 0; f < 4; f++) { so.o[f] = {dst[f], off, n * w[f] * sizeof(float)}; off += pin_align(so.o[f].bytes); }
-    so.o[4] = {nstep, off, n * sizeof(int32_t)};
+    so.o[4] = {d.nstep, off, n * sizeof(int32_t)};
     return off + pin_align(so.o[4].bytes);
 }
 static int state_out_enqueue(qg_sim *s, const StateOut &so) {
@@ -617,17 +627,55 @@ static int state_out_enqueue(qg_sim *s, const StateOut &so) {
 extern "C" int qg_get_state(qg_sim *s, float *qpos, float *qvel, float *act, float *ctrl, int32_t *nstep) {
     if (!s) return fail(QG_ERR_ARG, "null handle");
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
-    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);   // steps may be in flight on a caller's stream
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }   // steps may be in flight on a caller's stream
     // every transfer enqueued, ONE synchronisation (five synchronised round trips made the single-env facade's mirror of the state
     // 120 us of a 160 us step)
     StateOut so;
-    int rc = pin_reserve(s, state_out_layout(s, qpos, qvel, act, ctrl, nstep, 0, so));
+    int rc = pin_reserve(s, state_out_layout(s, {qpos, qvel, act, ctrl, nstep}, 0, so));
     if (rc == QG_OK) rc = state_out_enqueue(s, so);
     if (rc != QG_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s->stream), QG_ERR_LAUNCH);
     for (int f = 0; f < 5; f++) pin_out_finish(s, so.o[f]);
     return QG_OK;
+}
+
+// One host-pointer step: the actions in through the arena's first bytes, `step` enqueues the device-pointer step from `d_actions` on
+// the library's stream, the four outputs (obs, reward, done, components: the caller's array, its device source, its size) -- and for
+// qg_step_mirror the state snapshot -- come back through the arena behind the actions, with ONE synchronisation.
+struct HostOut { void *user; const void *dev; size_t bytes; };
+template <class Step>
+static int host_step(qg_sim *s, const float *actions, float *d_actions, const HostOut (&out)[4], Step step, const StateDst *state = nullptr) {
+    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
+    { int rc0 = wait_for_caller_streams(s); if (rc0 != QG_OK) return rc0; }
+    size_t off = pin_align((size_t)s->n * QG_NU * sizeof(float));
+    PinOut o[4];
+    for (int i = 0; i < 4; i++) { o[i] = {out[i].user, off, out[i].bytes}; off += pin_align(o[i].bytes); }
+    StateOut so;
+    if (state) off = state_out_layout(s, *state, off, so);
+    int rc = pin_reserve(s, off);
+    if (rc == QG_OK) rc = pin_actions_in(s, actions, d_actions);
+    if (rc == QG_OK) rc = step();
+    for (int i = 0; i < 4 && rc == QG_OK; i++) rc = pin_out_enqueue(s, o[i], out[i].dev);
+    if (rc == QG_OK && state) rc = state_out_enqueue(s, so);
+    if (rc != QG_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream), QG_ERR_LAUNCH);
+    for (int i = 0; i < 4; i++) pin_out_finish(s, o[i]);
+    if (state)
+        for (int f = 0; f < 5; f++) pin_out_finish(s, so.o[f]);
+    return QG_OK;
+}
+static int sim_host_step(qg_sim *s, const float *actions, float *obs, float *reward, uint8_t *done, float *comps, const StateDst *state) {
+    const size_t n = (size_t)s->n;
+    const HostOut out[4] = {{obs, s->d_obs, n * s->obs_dim * sizeof(float)}, {reward, s->d_reward, n * sizeof(float)}, {done, s->d_done, n},
+                            {comps, s->d_comps, n * QG_NREWARD * sizeof(float)}};
+    return host_step(s, actions, s->d_actions, out, [&] {
+        return launch_step(s, s->d_actions, s->d_obs, s->d_reward, s->d_done, comps ? s->d_comps : nullptr, nullptr, s->stream);
+    }, state);
+}
+
+extern "C" int qg_step(qg_sim *s, const float *actions, float *obs, float *reward, uint8_t *done, float *comps) {
+    if (!s || !actions || !obs || !reward || !done) return fail(QG_ERR_ARG, "qg_step: null argument");
+    return sim_host_step(s, actions, obs, reward, done, comps, nullptr);
 }
 
 // qg_step and qg_get_state in one call and one synchronisation: what an env that mirrors the state on the host after every step
@@ -635,36 +683,14 @@ extern "C" int qg_get_state(qg_sim *s, float *qpos, float *qvel, float *act, flo
 extern "C" int qg_step_mirror(qg_sim *s, const float *actions, float *obs, float *reward, uint8_t *done, float *comps, float *qpos, float *qvel,
                               float *act, float *ctrl, int32_t *nstep) {
     if (!s || !actions || !obs || !reward || !done) return fail(QG_ERR_ARG, "qg_step_mirror: null argument");
-    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    { int rc0 = wait_for_caller_streams(s); if (rc0 != QG_OK) return rc0; }
-    size_t n = (size_t)s->n;
-    size_t off = pin_align(n * QG_NU * sizeof(float));
-    PinOut o_obs = {obs, off, n * s->obs_dim * sizeof(float)};       off += pin_align(o_obs.bytes);
-    PinOut o_rew = {reward, off, n * sizeof(float)};                   off += pin_align(o_rew.bytes);
-    PinOut o_done = {done, off, n};                                    off += pin_align(o_done.bytes);
-    PinOut o_comp = {comps, off, n * QG_NREWARD * sizeof(float)};      off += pin_align(o_comp.bytes);
-    StateOut so;
-    off = state_out_layout(s, qpos, qvel, act, ctrl, nstep, off, so);
-    int rc = pin_reserve(s, off);
-    if (rc == QG_OK) rc = pin_actions_in(s, actions, s->d_actions);
-    if (rc == QG_OK) rc = launch_step(s, s->d_actions, s->d_obs, s->d_reward, s->d_done, comps ? s->d_comps : nullptr, nullptr, s->stream);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_obs, s->d_obs);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_rew, s->d_reward);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_done, s->d_done);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_comp, s->d_comps);
-    if (rc == QG_OK) rc = state_out_enqueue(s, so);
-    if (rc != QG_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream), QG_ERR_LAUNCH);
-    pin_out_finish(s, o_obs); pin_out_finish(s, o_rew); pin_out_finish(s, o_done); pin_out_finish(s, o_comp);
-    for (int f = 0; f < 5; f++) pin_out_finish(s, so.o[f]);
-    return QG_OK;
+    const StateDst state = {qpos, qvel, act, ctrl, nstep};
+    return sim_host_step(s, actions, obs, reward, done, comps, &state);
 }
 
 extern "C" int qg_set_state(qg_sim *s, const float *qpos, const float *qvel, const float *act, const float *ctrl, const int32_t *nstep) {
     if (!s) return fail(QG_ERR_ARG, "null handle");
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
-    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }
     int rc;
     if ((rc = copy_in(s, qpos, s->st.qpos, QG_NQ)) != QG_OK) return rc;
     if ((rc = copy_in(s, qvel, s->st.qvel, QG_NV)) != QG_OK) return rc;
@@ -677,8 +703,7 @@ extern "C" int qg_set_state(qg_sim *s, const float *qpos, const float *qvel, con
 extern "C" int qg_time_step_kernel(qg_sim *s, const float *d_actions, float *d_packed, int32_t iters, float *ms_per_launch) {
     if (!s || !d_actions || !d_packed || iters < 1 || !ms_per_launch) return fail(QG_ERR_ARG, "qg_time_step_kernel: bad argument");
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
-    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }
     // the launches are exactly what qg_step_device_packed enqueues (data.ctrl write-back as the handle has it set)
     HIP_TRY(hipEventRecord(s->ev0, s->stream), QG_ERR_DEVICE);
     for (int i = 0; i < iters; i++) {
@@ -719,8 +744,7 @@ extern "C" int qg_set_task(qg_sim *s, const qg_task *task) {
     int rc = build_tables(&s->model, task, &km, &kt);
     if (rc != QG_OK) return rc;
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
-    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);   // steps reading the old task may be in flight on a caller's stream
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }   // steps reading the old task may be in flight on a caller's stream
     HIP_TRY(hipMemcpy(s->d_task, &kt, sizeof kt, hipMemcpyHostToDevice), QG_ERR_DEVICE);
     s->task = *task;
     return QG_OK;
@@ -760,7 +784,7 @@ static int multi_step_usable(const qg_sim *s, const char *who) {
         return fail(QG_ERR_ARG, "%s: needs the one-link-per-lane mapping (AUTO up to 4096 envs, lagged sensors)", who);
     if (s->n > s->simds * QGK_LINK_ENVS) return fail(QG_ERR_ARG, "%s: at most %d envs (one wave per SIMD)", who, s->simds * QGK_LINK_ENVS);
     if (s->walk_bound) return fail(QG_ERR_ARG, "%s: a walking task layer is bound to this handle", who);
-    if (s->task.auto_reset && (s->task.reset_flags & QG_RESET_JOINT_JITTER))
+    if (jitter_at_reset(s))
         return fail(QG_ERR_ARG, "%s: hinge jitter at auto-reset is a launch of its own behind every step; not available in this form", who);
     return QG_OK;
 }
@@ -773,11 +797,6 @@ static KStepArgs multi_step_args(const qg_sim *s) {
     P.env_index_base = s->env_index_base;
     return P;
 }
-static dim3 multi_step_grid(const qg_sim *s) {
-    const int per_block = QGK_LINK_ENVS * QGK_LINK_WAVES;
-    return dim3((s->n + per_block - 1) / per_block);
-}
-
 extern "C" int qg_step_device_seq(qg_sim *s, const float *actions, float *packed, int32_t count, void *stream) {
     if (!s || !actions || !packed || count < 1) return fail(QG_ERR_ARG, "qg_step_device_seq: bad argument");
     if (s->dyn) return fail(QG_ERR_ARG, "qg_step_device_seq: not available with per-env dynamics (qg_clear_dynamics first)");
@@ -786,56 +805,12 @@ extern "C" int qg_step_device_seq(qg_sim *s, const float *actions, float *packed
     int rc;
     if (s->res.launched && (rc = resident_retire(s)) != QG_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool seq_pair = effective_mapping(s) == QG_MAP_PAIR && s->baked && s->task.sensor_lag &&
-                          !(s->task.auto_reset && (s->task.reset_flags & QG_RESET_JOINT_JITTER));
-    if (seq_pair) {                   // the two-legs-per-lane mapping (16 385 .. 32 768 envs, >= 57 344): its own one-launch form
-        if (st != s->stream) {
-            s->caller_inflight = 1;
-            if (!s->captured_once) {
-                hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                if (st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) s->captured_once = 1;
-            }
-        }
-        KResident R = {};
-        R.actions = actions;
-        R.packed = packed;
-        R.count = count;
-        R.slots = 1;
-        const KStepArgs P = multi_step_args(s);
-        const int pblocks = (s->n + QGK_PAIR_ENVS - 1) / QGK_PAIR_ENVS;
-        if (pblocks > s->simds / 4) hipLaunchKernelGGL((qg_step_kernel_pair_multi<4>), dim3((pblocks + 3) / 4), dim3(QGK_WAVE * 4), 0, st, s->d_task, P, R);
-        else hipLaunchKernelGGL((qg_step_kernel_pair_multi<1>), dim3(pblocks), dim3(QGK_WAVE), 0, st, s->d_task, P, R);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "qg_step_kernel_pair_multi launch: %s", hipGetErrorString(e));
-        return QG_OK;
-    }
-    const int qblocks_seq = (s->n + QGK_QUAD_ENVS - 1) / QGK_QUAD_ENVS;
-    const bool seq_quad = effective_mapping(s) == QG_MAP_QUAD && s->task.sensor_lag && qblocks_seq > s->simds / 4 &&
-                          !(s->task.auto_reset && (s->task.reset_flags & QG_RESET_JOINT_JITTER));
-    if (seq_quad) {                   // the one-leg-per-lane mapping on the grids AUTO gives it (four-wave workgroups): its own one-launch form
-        if (st != s->stream) {
-            s->caller_inflight = 1;
-            if (!s->captured_once) {
-                hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                if (st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) s->captured_once = 1;
-            }
-        }
-        KResident R = {};
-        R.actions = actions;
-        R.packed = packed;
-        R.count = count;
-        R.slots = 1;
-        const KStepArgs P = multi_step_args(s);
-        const dim3 g4((qblocks_seq + 3) / 4), b4(QGK_WAVE * 4);
-        const bool one_wave = qblocks_seq <= s->simds;          // as launch_step: the whole register file while the grid is one wave per SIMD
-        if (!s->baked) hipLaunchKernelGGL((qg_step_kernel_quad_multi<1, false>), g4, b4, 0, st, s->d_model, s->d_task, P, R);   // (tables in LDS: always the one-wave form)
-        else if (one_wave) hipLaunchKernelGGL((qg_step_kernel_quad_multi<1, true>), g4, b4, 0, st, s->d_model, s->d_task, P, R);
-        else hipLaunchKernelGGL((qg_step_kernel_quad_multi<2, true>), g4, b4, 0, st, s->d_model, s->d_task, P, R);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "qg_step_kernel_quad_multi launch: %s", hipGetErrorString(e));
-        return QG_OK;
-    }
-    if (multi_step_usable(s, "qg_step_device_seq") != QG_OK) {
+    const int emap = effective_mapping(s);
+    // the two-legs-per-lane mapping (16 385 .. 32 768 envs, >= 57 344) and the one-leg-per-lane mapping on the grids AUTO gives it
+    // (four-wave workgroups) have one-launch forms of their own
+    const bool seq_pair = emap == QG_MAP_PAIR && s->baked && s->task.sensor_lag && !jitter_at_reset(s);
+    const bool seq_quad = emap == QG_MAP_QUAD && s->task.sensor_lag && quad_wg4(s) && !jitter_at_reset(s);
+    if (!seq_pair && !seq_quad && multi_step_usable(s, "qg_step_device_seq") != QG_OK) {
         // another mapping (more than one wave per SIMD of the one-link-per-lane kernel), or hinge jitter behind every step: the same
         // rows from `count` per-step launches -- the call means the same thing for every handle, the one-launch form is the fast path
         const size_t arow = (size_t)s->n * QG_NU, prow = (size_t)s->n * (s->obs_dim + 2);
@@ -843,24 +818,24 @@ extern "C" int qg_step_device_seq(qg_sim *s, const float *actions, float *packed
             if ((rc = launch_step(s, actions + k * arow, nullptr, nullptr, nullptr, nullptr, packed + k * prow, st)) != QG_OK) return rc;
         return QG_OK;
     }
-    if (st != s->stream) {
-        s->caller_inflight = 1;
-        if (!s->captured_once) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) s->captured_once = 1;
-        }
-    }
+    note_caller_stream(s, st);
     KResident R = {};
     R.actions = actions;
     R.packed = packed;
     R.count = count;
     R.slots = 1;
     const KStepArgs P = multi_step_args(s);
-    const dim3 g = multi_step_grid(s), b(QGK_WAVE * QGK_LINK_WAVES);
-    if (s->baked) hipLaunchKernelGGL((qg_step_kernel_link_multi<true, false>), g, b, 0, st, s->d_model, s->d_task, P, R);
-    else hipLaunchKernelGGL((qg_step_kernel_link_multi<false, false>), g, b, 0, st, s->d_model, s->d_task, P, R);
+    if (seq_pair) {
+        if (pair_wg4(s)) launch_pair_multi<4>(s, st, P, R);
+        else launch_pair_multi<1>(s, st, P, R);
+    } else if (seq_quad) {              // as launch_step: the whole register file while the grid is one wave per SIMD
+        if (!s->baked) launch_quad_multi<1, false>(s, st, P, R);       // (tables in LDS: always the one-wave form)
+        else if (quad_one_wave(s)) launch_quad_multi<1, true>(s, st, P, R);
+        else launch_quad_multi<2, true>(s, st, P, R);
+    } else if (s->baked) launch_link_multi<true, false>(s, st, P, R);
+    else launch_link_multi<false, false>(s, st, P, R);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "qg_step_kernel_link_multi launch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "qg_step_device_seq launch: %s", hipGetErrorString(e));
     return QG_OK;
 }
 
@@ -898,10 +873,9 @@ static int resident_launch(qg_sim *s) {
     s->res.hstat[0] = QG_RES_RUNNING;
     hipLaunchKernelGGL(qg_resident_ctl_kernel, dim3(1), dim3(64), 0, s->stream, s->res.k.door, 1);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
-    KStepArgs P = multi_step_args(s);
-    const dim3 g = multi_step_grid(s), b(QGK_WAVE * QGK_LINK_WAVES);
-    if (s->baked) hipLaunchKernelGGL((qg_step_kernel_link_multi<true, true>), g, b, 0, s->stream, s->d_model, s->d_task, P, s->res.k);
-    else hipLaunchKernelGGL((qg_step_kernel_link_multi<false, true>), g, b, 0, s->stream, s->d_model, s->d_task, P, s->res.k);
+    const KStepArgs P = multi_step_args(s);
+    if (s->baked) launch_link_multi<true, true>(s, s->stream, P, s->res.k);
+    else launch_link_multi<false, true>(s, s->stream, P, s->res.k);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "resident kernel launch: %s", hipGetErrorString(e));
     s->res.launched = 1;
@@ -963,9 +937,8 @@ extern "C" int qg_resident_stop(qg_sim *s) {
     if (!s) return fail(QG_ERR_ARG, "null handle");
     if (!s->res.active) return QG_OK;
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    int rc = resident_retire(s);
+    int rc = retire_and_sync(s);
     if (rc != QG_OK) return rc;
-    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
     resident_free(s);
     return QG_OK;
 }
@@ -1018,7 +991,7 @@ extern "C" int qg_resident_step_device(qg_sim *s, int32_t count, void *stream) {
     int rc = resident_check_reports(s, "qg_resident_step_device");
     if (rc != QG_OK) return rc;
     if ((rc = qg_resident_ensure(s)) != QG_OK) return rc;
-    const unsigned nwaves = multi_step_grid(s).x * QGK_LINK_WAVES;
+    const unsigned nwaves = link_blocks(s) * QGK_LINK_WAVES;
     hipLaunchKernelGGL(qg_resident_ring_kernel, dim3(1), dim3(QGK_WAVE), 0, (hipStream_t)stream, s->res.k, (unsigned)count, nwaves,
                        (unsigned long long)s->res.rung);
     hipError_t e = hipGetLastError();
@@ -1419,25 +1392,12 @@ extern "C" int qg_walk_step_device(qg_walk *w, const float *actions, float *obs,
 extern "C" int qg_walk_step(qg_walk *w, const float *actions, float *obs, float *reward, uint8_t *done, float *components) {
     if (!w || !actions || !obs || !reward || !done) return fail(QG_ERR_ARG, "qg_walk_step: null argument");
     qg_sim *s = w->sim;
-    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    { int rc0 = wait_for_caller_streams(s); if (rc0 != QG_OK) return rc0; }
-    size_t n = (size_t)s->n;
-    size_t off = pin_align(n * QG_NU * sizeof(float));
-    PinOut o_obs = {obs, off, n * QG_NSENSOR * 4};                     off += pin_align(o_obs.bytes);
-    PinOut o_rew = {reward, off, n * 4};                               off += pin_align(o_rew.bytes);
-    PinOut o_done = {done, off, n};                                    off += pin_align(o_done.bytes);
-    PinOut o_comp = {components, off, n * QG_NWALKREWARD * 4};         off += pin_align(o_comp.bytes);
-    int rc = pin_reserve(s, off);
-    if (rc == QG_OK) rc = pin_actions_in(s, actions, w->d_actions);
-    if (rc == QG_OK) rc = qg_walk_step_device(w, w->d_actions, w->d_obs, w->d_reward, w->d_done, components ? w->d_comps : nullptr, s->stream);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_obs, w->d_obs);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_rew, w->d_reward);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_done, w->d_done);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_comp, w->d_comps);
-    if (rc != QG_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream), QG_ERR_LAUNCH);
-    pin_out_finish(s, o_obs); pin_out_finish(s, o_rew); pin_out_finish(s, o_done); pin_out_finish(s, o_comp);
-    return QG_OK;
+    const size_t n = (size_t)s->n;
+    const HostOut out[4] = {{obs, w->d_obs, n * QG_NSENSOR * 4}, {reward, w->d_reward, n * 4}, {done, w->d_done, n},
+                            {components, w->d_comps, n * QG_NWALKREWARD * 4}};
+    return host_step(s, actions, w->d_actions, out, [&] {
+        return qg_walk_step_device(w, w->d_actions, w->d_obs, w->d_reward, w->d_done, components ? w->d_comps : nullptr, s->stream);
+    });
 }
 
 extern "C" int qg_walk_get_estimates(qg_walk *w, float *f_est, float *a_est, float *ideal_xy) {
@@ -1539,8 +1499,7 @@ extern "C" int qg_walk_set_state(qg_walk *w, const void *blob) {
 extern "C" int qg_get_reset_streams(qg_sim *s, int32_t *episode, uint64_t *seed) {
     if (!s) return fail(QG_ERR_ARG, "null handle");
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
-    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }
     if (episode) HIP_TRY(hipMemcpy(episode, s->st.episode, (size_t)s->n * sizeof(int32_t), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
     if (seed) *seed = s->seed;
     return QG_OK;
@@ -1548,8 +1507,7 @@ extern "C" int qg_get_reset_streams(qg_sim *s, int32_t *episode, uint64_t *seed)
 extern "C" int qg_set_reset_streams(qg_sim *s, const int32_t *episode, uint64_t seed) {
     if (!s) return fail(QG_ERR_ARG, "null handle");
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
-    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }
     if (episode) HIP_TRY(hipMemcpy(s->st.episode, episode, (size_t)s->n * sizeof(int32_t), hipMemcpyHostToDevice), QG_ERR_DEVICE);
     s->seed = seed;
     return QG_OK;
@@ -1686,25 +1644,14 @@ extern "C" int qg_po_step(qg_po *p, const float *actions, float *obs, float *rew
     if (!p || !actions || !obs || !reward || !done) return fail(QG_ERR_ARG, "qg_po_step: null argument");
     qg_walk *w = p->walk;
     qg_sim *s = w->sim;
-    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    { int rc0 = wait_for_caller_streams(s); if (rc0 != QG_OK) return rc0; }
-    size_t n = (size_t)s->n, width = (size_t)p->kp.window * QG_PO_FRAME;
-    size_t off = pin_align(n * QG_NU * sizeof(float));
-    PinOut o_obs = {obs, off, n * width * 4};                          off += pin_align(o_obs.bytes);
-    PinOut o_rew = {reward, off, n * 4};                               off += pin_align(o_rew.bytes);
-    PinOut o_done = {done, off, n};                                    off += pin_align(o_done.bytes);
-    PinOut o_comp = {components, off, n * QG_NWALKREWARD * 4};         off += pin_align(o_comp.bytes);
-    int rc = pin_reserve(s, off);
-    if (rc == QG_OK) rc = pin_actions_in(s, actions, w->d_actions);
-    if (rc == QG_OK) rc = qg_po_step_device(p, w->d_actions, p->d_out, w->d_reward, w->d_done, components ? w->d_comps : nullptr,
-                                            terminal_obs ? p->d_term : nullptr, s->stream);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_obs, p->d_out);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_rew, w->d_reward);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_done, w->d_done);
-    if (rc == QG_OK) rc = pin_out_enqueue(s, o_comp, w->d_comps);
+    const size_t n = (size_t)s->n, width = (size_t)p->kp.window * QG_PO_FRAME;
+    const HostOut out[4] = {{obs, p->d_out, n * width * 4}, {reward, w->d_reward, n * 4}, {done, w->d_done, n},
+                            {components, w->d_comps, n * QG_NWALKREWARD * 4}};
+    int rc = host_step(s, actions, w->d_actions, out, [&] {
+        return qg_po_step_device(p, w->d_actions, p->d_out, w->d_reward, w->d_done, components ? w->d_comps : nullptr,
+                                 terminal_obs ? p->d_term : nullptr, s->stream);
+    });
     if (rc != QG_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream), QG_ERR_LAUNCH);
-    pin_out_finish(s, o_obs); pin_out_finish(s, o_rew); pin_out_finish(s, o_done); pin_out_finish(s, o_comp);
     if (terminal_obs) {
         // the terminal stacks only exist for envs that finished: the [n][obs_dim] transfer (4.3 MB at 4096 envs and window 10 -- as much
         // as the observation itself) is skipped on the steps where none did
@@ -1788,8 +1735,7 @@ static int dyn_enable(qg_sim *s, const char *who) {
     if (s->mapping == QG_MAP_LANE || s->mapping == QG_MAP_PAIR)
         return fail(QG_ERR_ARG, "%s: per-env dynamics run in the LINK and QUAD mappings only (qg_set_mapping AUTO, LINK or QUAD first)", who);
     if (s->res.active) return fail(QG_ERR_ARG, "%s: the resident step mode is on (qg_resident_stop first)", who);
-    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
-    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);        // steps of the shared model may be in flight on a caller's stream
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }   // steps of the shared model may be in flight on a caller's stream
     const size_t n = (size_t)s->n;
     if (!s->d_dyn) HIP_TRY(hipMalloc((void **)&s->d_dyn, n * QG_NDYN * sizeof(float)), QG_ERR_ALLOC);
     if (!s->d_model_dyn) HIP_TRY(hipMalloc((void **)&s->d_model_dyn, sizeof(KModelDyn)), QG_ERR_ALLOC);
@@ -1846,8 +1792,7 @@ extern "C" int qg_get_dynamics(qg_sim *s, float *rows) {
         return QG_OK;
     }
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
-    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }
     float *h = (float *)malloc(n * QG_NDYN * sizeof(float));
     if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
     hipError_t e = hipMemcpy(h, s->d_dyn, n * QG_NDYN * sizeof(float), hipMemcpyDeviceToHost);
@@ -1874,8 +1819,7 @@ extern "C" int qg_set_dynamics(qg_sim *s, const uint8_t *mask, const float *rows
     if (rc != QG_OK) return rc;
     // read-modify-write of the rows: steps (and their auto-reset draws) may be in flight on a caller's stream even when the mode was
     // already on (dyn_enable then returns at once) -- the header's ordering contract
-    { int rr = resident_retire(s); if (rr != QG_OK) return rr; }
-    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }
     float *h = (float *)malloc(n * QG_NDYN * sizeof(float));
     if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
     hipError_t e = hipMemcpy(h, s->d_dyn, n * QG_NDYN * sizeof(float), hipMemcpyDeviceToHost);
