@@ -213,8 +213,9 @@ int qg_time_step_kernel(qg_sim *sim, const float *d_actions, float *d_packed, in
 
 /* Replace the task constants of a live handle -- what assigning env.reward_fns / env.termination_fns / env.max_time after
  * construction does in the reference (README.md:74-89): reward weights, fall / flip / time-limit terminations, auto-reset
- * and its flags, frame_skip.  obs_mode is fixed at qg_create.  Refused while a walking task layer is bound.  Takes effect
- * from the next step; waits for steps in flight. */
+ * and its flags, frame_skip.  obs_mode is fixed at qg_create.  Refused while a walking task layer is bound, and while the
+ * resident step mode is on for a task the resident kernel cannot run (unlagged sensors, hinge jitter at auto-reset): the
+ * handle keeps its task.  Takes effect from the next step; waits for steps in flight. */
 int qg_set_task(qg_sim *sim, const qg_task *task);
 int qg_get_task(const qg_sim *sim, qg_task *out);
 
@@ -224,6 +225,10 @@ int qg_set_track_ctrl(qg_sim *sim, int32_t on);
 /* Development builds only (make CXXFLAGS+=-DQG_PHASE_TIMES; tools/phase_times.py): the 100 MHz clock stamps the first wave of the last
  * one-link-per-lane launch took at its phase marks.  Production builds carry no such code and return QG_ERR_ARG. */
 int qg_debug_phase_times(uint64_t out[16]);
+/* The step-kernel instantiation the handle's latest step launch enqueued, every template argument written out (defaults included,
+ * bool as 0/1), e.g. "qg_step_kernel_quad<2,1,1,4,0,1,0>"; the many-env-steps forms are named too ("qg_step_kernel_link_multi<1,1>").
+ * QG_ERR_ARG before the first step, or when `len` cannot hold the name and its terminating zero.  Host-side bookkeeping only. */
+int32_t qg_debug_last_step_kernel(const qg_sim *sim, char *buf, int32_t len);
 
 /* 1 when the handle's model equals the compiled-in default (include/qg_model_data.h) and the
  * kernel variant with those constants baked into the instruction stream runs; 0 for any other

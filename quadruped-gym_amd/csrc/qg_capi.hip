@@ -61,6 +61,7 @@ struct qg_sim {
     int32_t po_unfused;       // env QG_PO_UNFUSED=1: keep the observation pack of qg_po_step a launch of its own (A/B, parity test)
     int32_t simds;            // SIMDs of the handle's GPU (hipDeviceProp: compute units x 4; 1024 on an MI355X): AUTO's thresholds are
                               // "one wave per SIMD" sizes
+    mutable uint32_t last_step_kernel;    // the step-kernel instantiation the latest launcher enqueued (step_kernel_code; 0: none yet)
     // resident form of the one-link-per-lane step (qg_resident_*, qg_kernel_resident.hip)
     struct {
         int32_t active;       // qg_resident_start has set the mailbox up (the mode is on until qg_resident_stop)
@@ -77,6 +78,7 @@ struct qg_sim {
 };
 static int resident_retire(qg_sim *s);
 static void resident_free(qg_sim *s);
+static int multi_step_usable(const qg_sim *s, const char *who);
 
 static thread_local char g_err[512] = "";
 
@@ -360,32 +362,48 @@ template <bool PO> static typename PoArgT<PO>::type po_arg(const KPoLaunch *p) {
     else return {};
 }
 
+// Which instantiation a launcher enqueued, for qg_debug_last_step_kernel: the family in the low nibble, then one nibble per template
+// argument in declaration order (every argument is 0 .. 4).  A store of a constant on the launch path; the name is formatted on request.
+enum StepFamily : uint32_t { KF_NONE, KF_LANE, KF_LINK, KF_QUAD, KF_PAIR, KF_LINK_MULTI, KF_QUAD_MULTI, KF_PAIR_MULTI };
+template <int... A> static constexpr uint32_t step_kernel_code(StepFamily fam) {
+    uint32_t code = fam, shift = 4;
+    ((code |= (uint32_t)A << shift, shift += 4), ...);
+    return code;
+}
+
 template <bool BAKED> static void launch_lane(const StepLaunch &L) {
+    L.s->last_step_kernel = step_kernel_code<BAKED>(KF_LANE);
     hipLaunchKernelGGL(qg_step_kernel<BAKED>, dim3((L.s->n + QGK_WAVE - 1) / QGK_WAVE), dim3(QGK_WAVE), 0, L.stream, L.model, L.s->d_task, L.P);
 }
 template <bool WALK, bool PO, bool BAKED, bool HELP = false, bool DYN = false> static void launch_link(const StepLaunch &L) {
+    L.s->last_step_kernel = step_kernel_code<WALK, PO, BAKED, HELP, DYN>(KF_LINK);
     hipLaunchKernelGGL((qg_step_kernel_link<WALK, PO, BAKED, HELP, DYN>), dim3(link_blocks(L.s)), dim3(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1)), 0,
                        L.stream, L.model, L.s->d_task, L.P, walk_arg<WALK>(L.walk), po_arg<PO>(L.po));
 }
 template <int WPE, bool BAKED, bool WALK, int WAVES, bool PO = false, bool HELP = false, bool DYN = false> static void launch_quad(const StepLaunch &L) {
     static_assert(WAVES == 1 || WAVES == 4, "one-wave or four-wave workgroups");
+    L.s->last_step_kernel = step_kernel_code<WPE, BAKED, WALK, WAVES, PO, HELP, DYN>(KF_QUAD);
     hipLaunchKernelGGL((qg_step_kernel_quad<WPE, BAKED, WALK, WAVES, PO, HELP, DYN>), wave_grid(quad_blocks(L.s), WAVES),
                        dim3(QGK_WAVE * WAVES * (HELP ? 2 : 1)), 0, L.stream, L.model, L.s->d_task, L.P, walk_arg<WALK>(L.walk), po_arg<PO>(L.po));
 }
 template <int WAVES, bool WALK, bool PO = false> static void launch_pair(const StepLaunch &L) {
     static_assert(WAVES == 1 || WAVES == 4, "one-wave or four-wave workgroups");
+    L.s->last_step_kernel = step_kernel_code<WAVES, WALK, PO>(KF_PAIR);
     hipLaunchKernelGGL((qg_step_kernel_pair<WAVES, WALK, PO>), wave_grid(pair_blocks(L.s), WAVES), dim3(QGK_WAVE * WAVES), 0, L.stream, L.s->d_task,
                        L.P, walk_arg<WALK>(L.walk), po_arg<PO>(L.po));
 }
 // the many-env-steps-per-launch forms (qg_kernel_resident.hip)
 template <bool BAKED, bool DOOR> static void launch_link_multi(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
+    s->last_step_kernel = step_kernel_code<BAKED, DOOR>(KF_LINK_MULTI);
     hipLaunchKernelGGL((qg_step_kernel_link_multi<BAKED, DOOR>), dim3(link_blocks(s)), dim3(QGK_WAVE * QGK_LINK_WAVES), 0, st, s->d_model, s->d_task, P, R);
 }
 template <int WPE, bool BAKED> static void launch_quad_multi(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
+    s->last_step_kernel = step_kernel_code<WPE, BAKED>(KF_QUAD_MULTI);
     hipLaunchKernelGGL((qg_step_kernel_quad_multi<WPE, BAKED>), wave_grid(quad_blocks(s), 4), dim3(QGK_WAVE * 4), 0, st, s->d_model, s->d_task, P, R);
 }
 template <int WAVES> static void launch_pair_multi(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
     static_assert(WAVES == 1 || WAVES == 4, "one-wave or four-wave workgroups");
+    s->last_step_kernel = step_kernel_code<WAVES>(KF_PAIR_MULTI);
     hipLaunchKernelGGL((qg_step_kernel_pair_multi<WAVES>), wave_grid(pair_blocks(s), WAVES), dim3(QGK_WAVE * WAVES), 0, st, s->d_task, P, R);
 }
 
@@ -456,8 +474,7 @@ template <bool DYN> static void select_step(const StepLaunch &L, int emap) {
         } else if (quad_one_wave(s)) {
             if (quad_wg4(s)) launch_quad<1, true, false, 4>(L);
             else launch_quad<1, true, false, 1>(L);
-        } else if (quad_wg4(s)) launch_quad<2, true, false, 4>(L);
-        else launch_quad<2, true, false, 1>(L);
+        } else launch_quad<2, true, false, 4>(L);       // (more than one wave per SIMD is more than one per compute unit: quad_wg4)
         break;
     case QG_MAP_PAIR:                       // (the compiled-in robot only)
         if (po) launch_pair<4, true, true>(L);                             // po_fusable(): four-wave workgroups
@@ -739,6 +756,17 @@ extern "C" int qg_set_task(qg_sim *s, const qg_task *task) {
     if (!s || !task) return fail(QG_ERR_ARG, "qg_set_task: null argument");
     if (s->walk_bound) return fail(QG_ERR_ARG, "qg_set_task: a walking task layer is bound to this handle (it holds a copy of the task)");
     if (task->obs_mode != s->task.obs_mode) return fail(QG_ERR_ARG, "qg_set_task: obs_mode is fixed at qg_create (it sizes the output rows)");
+    if (s->res.active) {              // the next ring relaunches the resident kernel: it has to be able to run the new task
+        const qg_task old = s->task;
+        s->task = *task;
+        const int rc = multi_step_usable(s, "the resident step mode");
+        s->task = old;
+        if (rc != QG_OK) {
+            char why[256];
+            snprintf(why, sizeof why, "%s", g_err);
+            return fail(QG_ERR_ARG, "qg_set_task: %s (qg_resident_stop first)", why);
+        }
+    }
     KModel km;
     KTask kt;
     int rc = build_tables(&s->model, task, &km, &kt);
@@ -753,6 +781,22 @@ extern "C" int qg_set_task(qg_sim *s, const qg_task *task) {
 extern "C" int qg_get_task(const qg_sim *s, qg_task *out) {
     if (!s || !out) return fail(QG_ERR_ARG, "qg_get_task: null argument");
     *out = s->task;
+    return QG_OK;
+}
+
+extern "C" int32_t qg_debug_last_step_kernel(const qg_sim *s, char *buf, int32_t len) {
+    if (!s || !buf || len < 1) return fail(QG_ERR_ARG, "qg_debug_last_step_kernel: bad argument");
+    static const struct { const char *name; int nargs; } fam[] = {
+        {nullptr, 0}, {"qg_step_kernel", 1}, {"qg_step_kernel_link", 5}, {"qg_step_kernel_quad", 7}, {"qg_step_kernel_pair", 3},
+        {"qg_step_kernel_link_multi", 2}, {"qg_step_kernel_quad_multi", 2}, {"qg_step_kernel_pair_multi", 1}};
+    const uint32_t code = s->last_step_kernel, f = code & 15u;
+    if (f == KF_NONE || f > KF_PAIR_MULTI) return fail(QG_ERR_ARG, "qg_debug_last_step_kernel: no step kernel launched yet");
+    char name[96];
+    int k = snprintf(name, sizeof name, "%s<", fam[f].name);
+    for (int a = 0; a < fam[f].nargs; a++) k += snprintf(name + k, sizeof name - k, a ? ",%u" : "%u", (code >> (4 + 4 * a)) & 15u);
+    snprintf(name + k, sizeof name - k, ">");
+    if ((int)strlen(name) >= len) return fail(QG_ERR_ARG, "qg_debug_last_step_kernel: need a buffer of %d bytes", (int)strlen(name) + 1);
+    memcpy(buf, name, strlen(name) + 1);
     return QG_OK;
 }
 
@@ -870,6 +914,8 @@ static int resident_retire(qg_sim *s) {
 
 // (re)launch on the library's stream: clear STOP, then the kernel; it starts at the env-step the previous launch left off at
 static int resident_launch(qg_sim *s) {
+    int rc = multi_step_usable(s, "resident kernel launch");
+    if (rc != QG_OK) return rc;
     s->res.hstat[0] = QG_RES_RUNNING;
     hipLaunchKernelGGL(qg_resident_ctl_kernel, dim3(1), dim3(64), 0, s->stream, s->res.k.door, 1);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);

@@ -218,12 +218,26 @@ class BatchedSim:
     def mapping(self) -> int:
         return int(self._lib.qg_get_mapping(self._h))
 
+    @property
+    def last_step_kernel(self) -> str:
+        """The step-kernel instantiation the latest step launch ran (``qg_debug_last_step_kernel``), e.g.
+        ``"qg_step_kernel_quad<2,1,1,4,0,1,0>"``."""
+        buf = C.create_string_buffer(128)
+        check(self._lib.qg_debug_last_step_kernel(self._h, buf, len(buf)), "qg_debug_last_step_kernel")
+        return buf.value.decode()
+
     def set_task(self, task: QgTask):
         """Replace the task constants of the live handle (``qg_set_task``): reward weights, terminations, auto-reset,
         frame_skip -- what assigning ``env.reward_fns`` / ``env.termination_fns`` after construction does in the reference."""
         check(self._lib.qg_set_task(self._h, C.byref(task)), "qg_set_task")
         self.task = task
         self.limit_substeps = int(self._lib.qg_time_limit_substeps(self.model.timestep, self.task.max_time))
+
+    def get_task(self) -> QgTask:
+        """The task constants the handle runs (``qg_get_task``)."""
+        t = QgTask()
+        check(self._lib.qg_get_task(self._h, C.byref(t)), "qg_get_task")
+        return t
 
     def set_track_ctrl(self, on: bool):
         check(self._lib.qg_set_track_ctrl(self._h, 1 if on else 0), "qg_set_track_ctrl")

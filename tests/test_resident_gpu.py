@@ -3,6 +3,7 @@ bits of the per-launch one-link-per-lane kernel -- they run the same substep cod
 (/root/reference keeps it in MjData across steps the same way, src/envs/quadruped.py:163-165) -- and the resident kernel must never
 be able to hang: it leaves by itself when nobody rings, and every entry point that needs the state in memory retires it first."""
 import os
+import sys
 import time
 
 import numpy as np
@@ -13,6 +14,8 @@ from quadruped_gym_amd import _abi
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "step_vectors.npz")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_leaves import TWIN_PAIRS  # noqa: E402
 
 
 def _task(frame_skip=4, imu=False, max_time=0.2, yaw=True):
@@ -77,6 +80,7 @@ def test_sequence_launch_is_bit_identical_to_per_step_launches(n, fs, imu):
             b.step_device_packed(acts[k], pb[k])
         torch.cuda.synchronize()
         assert torch.equal(pa, pb), rnd
+        assert (a.last_step_kernel, b.last_step_kernel) in TWIN_PAIRS     # the one-launch form and the leaf tests/kernel_leaves.py pins it to
         finished += int(pa[:, :, -1].sum())
     episodes = 2 if n <= 4096 else 1                  # (the large batches run 36 env-steps: one time limit of 25, or of 12 - 13 at frame_skip 8 / 20)
     assert finished >= episodes * n
@@ -138,6 +142,7 @@ def test_resident_closed_loop_is_bit_identical_to_per_step_launches(n, slots):
         b.step_device_packed(act, pb)
         _sync()
         assert torch.equal(got, pb), i
+        assert (a.last_step_kernel, b.last_step_kernel) in TWIN_PAIRS
         finished += int(pb[:, 34].sum())
     assert finished >= 3 * n
     st = a.resident_status()
@@ -381,6 +386,8 @@ def _other_model_numbers(n, with_ring):
                 pg[k].copy_(mail_p[0])
         _sync()
         assert torch.equal(ps, pr) and (not with_ring or torch.equal(pg, pr)), rnd
+        assert (seq.last_step_kernel, ref.last_step_kernel) in TWIN_PAIRS
+        assert not with_ring or (ring.last_step_kernel, ref.last_step_kernel) in TWIN_PAIRS
         finished += int(pr[:, :, -1].sum())
     assert finished >= 2 * n
     _same_state(seq, ref)
@@ -390,3 +397,85 @@ def _other_model_numbers(n, with_ring):
         ring.resident_stop()
     for s in sims:
         s.close()
+
+
+def test_sequence_launch_in_the_explicit_pair_mapping():
+    """An explicit two-legs-per-lane request on a small grid runs the one-wave-workgroup one-launch form
+    (qg_step_kernel_pair_multi<1>), which AUTO never picks: the rows and state of per-step launches, through auto-resets."""
+    import torch
+    from quadruped_gym_amd.sim import BatchedSim
+    n, K = 1000, 12
+    task = _task()
+    a, b = BatchedSim(n, task=task), BatchedSim(n, task=task)
+    for s in (a, b):
+        s.set_mapping(_abi.MAP_PAIR)
+        s.reset(seed=7, flags=task.reset_flags)
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev); gen.manual_seed(8)
+    finished = 0
+    for rnd in range(3):
+        acts = torch.rand((K, n, 12), generator=gen, device=dev) * 3 - 1.5
+        pa, pb = torch.empty((K, n, 35), device=dev), torch.empty((K, n, 35), device=dev)
+        a.step_device_seq(acts, pa)
+        for k in range(K):
+            b.step_device_packed(acts[k], pb[k])
+        torch.cuda.synchronize()
+        assert torch.equal(pa, pb), rnd
+        finished += int(pa[:, :, -1].sum())
+    assert (a.last_step_kernel, b.last_step_kernel) == ("qg_step_kernel_pair_multi<1>", "qg_step_kernel_pair<1,0,0>")
+    assert finished >= n
+    _same_state(a, b)
+    a.close(); b.close()
+
+
+def test_set_task_under_the_resident_mode():
+    """qg_set_task while the resident mode is on: a task the resident kernel cannot run (unlagged sensors, hinge jitter at auto-reset)
+    is refused and the handle keeps its task, so the next rings still equal per-step launches; any other change is taken, and the
+    rings then equal a handle created with the new task."""
+    import torch
+    from quadruped_gym_amd.sim import BatchedSim
+    n = 1000
+    task = _task()
+    a, b = _twin(n, task)
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev); gen.manual_seed(9)
+    mail_a = torch.zeros((1, n, 12), device=dev)
+    mail_p = torch.zeros((1, n, 35), device=dev)
+    pb = torch.empty((n, 35), device=dev)
+    a.resident_start(mail_a, mail_p)
+
+    def ring_against(twin, steps):
+        for _ in range(steps):
+            act = torch.rand((n, 12), generator=gen, device=dev) * 2 - 1
+            mail_a[0].copy_(act)
+            a.resident_step(1)
+            got = mail_p[0].clone()
+            twin.step_device_packed(act, pb)
+            _sync()
+            assert torch.equal(got, pb)
+
+    ring_against(b, 3)
+    unlagged = _abi.QgTask.from_buffer_copy(task)
+    unlagged.sensor_lag = 0
+    jitter = _abi.QgTask.from_buffer_copy(task)
+    jitter.reset_flags |= _abi.RESET_JOINT_JITTER
+    for bad in (unlagged, jitter):
+        with pytest.raises(_abi.QuadGymError, match="qg_resident_stop first"):
+            a.set_task(bad)
+        assert bytes(a.get_task()) == bytes(task)
+        ring_against(b, 3)
+        assert a.last_step_kernel == "qg_step_kernel_link_multi<1,1>"
+    assert a.resident_status()["not_executed"] == 0
+    new = _abi.QgTask.from_buffer_copy(task)
+    new.frame_skip = 5
+    new.w_forward, new.w_ctrl, new.alive_bonus = 2.0, -0.2, 0.5
+    a.set_task(new)
+    assert bytes(a.get_task()) == bytes(new)
+    c = BatchedSim(n, task=new)
+    c.set_state(*b.get_state())
+    c.set_reset_streams(*b.get_reset_streams())
+    ring_against(c, 30)                               # (episodes of 20 env-steps: auto-resets under the new task)
+    st = a.resident_status()
+    assert st["not_executed"] == 0 and st["rung"] == 39
+    _same_state(a, c)
+    a.resident_stop(); a.close(); b.close(); c.close()
