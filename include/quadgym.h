@@ -446,8 +446,56 @@ int qg_set_dynamics_range(qg_sim *sim, const qg_dynamics_range *range);
 int qg_set_dynamics(qg_sim *sim, const uint8_t *mask, const float *rows);
 /* The current rows into a host [n_envs][QG_NDYN] array; identity rows while the mode is off. */
 int qg_get_dynamics(qg_sim *sim, float *rows);
-/* Back to the shared model (the range is dropped too); the compiled-in robot's baked kernels run again. */
+/* Back to the shared model (the range is dropped too); the compiled-in robot's baked kernels run again (unless wrench mode, below,
+ * is on: it keeps the per-env kernels, with identity rows). */
 int qg_clear_dynamics(qg_sim *sim);
+
+/* ---- external body wrenches (MuJoCo's data.xfrc_applied) and random pushes -----------------------------------------------------
+ * Each env has a row of QG_NBODY x QG_NXFRC f32: for body b (the numbering above: 0 = FRAME, 1+3k+i = link i of leg k) a force xyz and a
+ * torque xyz, both in the WORLD frame; the force acts at body b's centre of mass (body_ipos[b] of the handle's model -- a
+ * QG_DYN_PAYLOAD_* row does not move that point, as a welded payload body would not move MuJoCo's xipos).  The row is held constant
+ * over the frame_skip substeps of an env-step and rotated into the FRAME's axes at every substep with that substep's orientation; it
+ * adds no term to the implicit matrix (a constant force has no velocity derivative).  Rows persist across qg_reset and auto-resets, as
+ * dynamics rows do (QuadrupedEnv.reset() zeroes its Python mirror, as mj_resetData does).
+ * Push schedule (qg_set_push): random horizontal forces on the FRAME, drawn per env with no per-env state.  For env-step
+ * s = nstep / frame_skip of an episode, window w = s / interval, offset j = s % interval: the window holds a push if
+ * u_gate < probability; the push starts at o = (k_off (interval - duration + 1)) >> 24 (k_off: the 24-bit integer behind the uniform)
+ * and is active while o <= j < o + duration; its force (F cos th, F sin th, 0), F = force_min + (force_max - force_min) u_mag,
+ * th = 2 pi u_head, acts at the FRAME's centre of mass, added to the FRAME's row for that env-step.  Uniforms: streams
+ * 32 + 4 w + {0: gate, 1: offset, 2: magnitude, 3: heading} of the (seed, env_index_base + i, episode) key (disjoint from the reset
+ * streams 0..15 and the dynamics streams 16..26; the stream number wraps after 2^30 windows).
+ * Either qg_set_xfrc* or qg_set_push switches the handle into wrench mode: the per-env forms of the table-driven step kernels run (as
+ * with per-env dynamics, identity dynamics rows while that mode is off; qg_uses_baked_model returns 0); qg_step_device_seq, the
+ * resident form and the PAIR and LANE mappings are refused, as they are with per-env dynamics.  With every row zero and no schedule an
+ * env computes the bits it computes with the mode off on the same per-env kernel. */
+#define QG_NXFRC 6
+#define QG_XFRC_FX 0
+#define QG_XFRC_FY 1
+#define QG_XFRC_FZ 2
+#define QG_XFRC_TX 3
+#define QG_XFRC_TY 4
+#define QG_XFRC_TZ 5
+typedef struct {
+    int32_t interval;    /* env-steps per window, >= 1 */
+    int32_t duration;    /* env-steps a push lasts, 1 .. interval */
+    float probability;   /* of a push in a window, [0, 1] */
+    float force_min;     /* N, 0 <= force_min <= force_max */
+    float force_max;
+} qg_push_params;
+/* Sets rows from a host [n_envs][QG_NBODY][QG_NXFRC] array; mask == NULL sets every env, else only mask[i] != 0.  Non-finite values
+ * are refused (QG_ERR_ARG, nothing changes).  Waits for device work, as the other entry points that touch per-env state do. */
+int qg_set_xfrc(qg_sim *sim, const uint8_t *mask, const float *rows);
+/* The same from a device array of that layout, enqueued on `stream` (a copy; no validation): the ordering contract of the other
+ * *_device entry points.  The call that switches the mode on waits for the device first and must not be made while a stream is
+ * being captured. */
+int qg_set_xfrc_device(qg_sim *sim, const float *d_rows, void *stream);
+/* The rows as set (without the push) into a host [n_envs][QG_NBODY][QG_NXFRC] array; zeros while the mode is off. */
+int qg_get_xfrc(qg_sim *sim, float *rows);
+/* Validates and sets the push schedule (QG_ERR_ARG, nothing changes: interval < 1, duration outside 1 .. interval, probability
+ * outside [0, 1], force_min < 0 or > force_max); NULL turns the schedule off. */
+int qg_set_push(qg_sim *sim, const qg_push_params *push);
+/* Zero rows, schedule off, wrench mode off (the baked kernels run again unless per-env dynamics are on). */
+int qg_clear_xfrc(qg_sim *sim);
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,17 @@ class QgDynamicsRange(C.Structure):
     _fields_ = [("lo", C.c_float * NDYN), ("hi", C.c_float * NDYN)]
 
 
+# external wrenches (QG_NXFRC / QG_XFRC_* of include/quadgym.h): [n, NBODY, NXFRC] f32, world-frame force xyz and torque xyz per body
+NXFRC = 6
+XFRC_COLUMNS = ("fx", "fy", "fz", "tx", "ty", "tz")
+
+
+class QgPushParams(C.Structure):
+    """``qg_push_params``: the push schedule of wrench mode (env-steps, N)."""
+    _fields_ = [("interval", C.c_int32), ("duration", C.c_int32), ("probability", C.c_float), ("force_min", C.c_float),
+                ("force_max", C.c_float)]
+
+
 class QgCommandSampler(C.Structure):
     """``qg_command_sampler``: the options of ``VelocityHeadingControls.sample`` (``control_inputs.py:74-115``)."""
     _fields_ = [
@@ -236,6 +247,11 @@ def load_library():
     lib.qg_set_dynamics.argtypes = [vp, vp, vp]
     lib.qg_get_dynamics.argtypes = [vp, vp]
     lib.qg_clear_dynamics.argtypes = [vp]
+    lib.qg_set_xfrc.argtypes = [vp, vp, vp]
+    lib.qg_set_xfrc_device.argtypes = [vp, vp, vp]
+    lib.qg_get_xfrc.argtypes = [vp, vp]
+    lib.qg_set_push.argtypes = [vp, C.POINTER(QgPushParams)]
+    lib.qg_clear_xfrc.argtypes = [vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("qg_version", "qg_build_id", "qg_last_error", "qg_time_limit_substeps", "qg_walk_state_bytes", "qg_po_state_bytes",
@@ -260,6 +276,7 @@ EXPORTS = (
     "qg_step_device_seq", "qg_resident_start", "qg_resident_stop", "qg_resident_buffers", "qg_resident_step_device",
     "qg_resident_ensure", "qg_resident_status",
     "qg_set_dynamics_range", "qg_set_dynamics", "qg_get_dynamics", "qg_clear_dynamics",
+    "qg_set_xfrc", "qg_set_xfrc_device", "qg_get_xfrc", "qg_set_push", "qg_clear_xfrc",
 )
 
 
@@ -277,6 +294,31 @@ def recommended_batch(n_envs: int, device: int = -1) -> int:
     """The batch size at the top of the step-time stair ``n_envs`` stands on (``qg_recommended_batch``): 4096, 16 384, then multiples
     of 32 768 on an MI355X.  ``device=-1`` assumes an MI355X (no GPU needed)."""
     return int(load_library().qg_recommended_batch(int(n_envs), int(device)))
+
+
+def push_params(spec: dict | None) -> QgPushParams | None:
+    """``qg_push_params`` from ``{"interval": env-steps, "duration": env-steps, "probability": p, "force": (lo, hi) N}``; None: no
+    schedule."""
+    if spec is None:
+        return None
+    unknown = set(spec) - {"interval", "duration", "probability", "force"}
+    if unknown:
+        raise ValueError(f"push schedule keys {sorted(unknown)}: one of interval, duration, probability, force")
+    lo, hi = spec["force"]
+    return QgPushParams(int(spec["interval"]), int(spec["duration"]), float(spec["probability"]), float(lo), float(hi))
+
+
+def push_schedule_steps(spec: dict, step_seconds: float) -> dict:
+    """The VecEnvs' ``push_randomization={"interval_s", "duration_s", "probability", "force": (lo, hi)}`` as the env-step schedule of
+    ``BatchedSim.set_push_schedule``: seconds / (timestep x frame_skip), rounded to nearest, at least 1 env-step."""
+    unknown = set(spec) - {"interval_s", "duration_s", "probability", "force"}
+    if unknown:
+        raise ValueError(f"push_randomization keys {sorted(unknown)}: one of interval_s, duration_s, probability, force")
+
+    def steps(seconds):
+        return max(1, int(round(float(seconds) / float(step_seconds))))
+    return {"interval": steps(spec["interval_s"]), "duration": steps(spec["duration_s"]), "probability": float(spec["probability"]),
+            "force": tuple(float(f) for f in spec["force"])}
 
 
 def identity_dynamics_row(model: QgModel):

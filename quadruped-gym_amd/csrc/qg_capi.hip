@@ -9,6 +9,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -55,7 +56,12 @@ struct qg_sim {
     KDynRange dyn_range;
     float *d_dyn;             // [QG_NDYN][n]
     KModelDyn *d_model_dyn;   // the model tables and d_dyn: the per-env kernels' model pointer
-    int32_t mapping;          // QG_MAP_AUTO / QG_MAP_LANE / QG_MAP_QUAD (request)
+    // external wrenches (qg_set_xfrc / qg_set_push): wrench mode runs the same per-env kernels (identity dynamics rows while the
+    // dynamics mode is off)
+    int32_t xfrc;             // wrench mode is on
+    float *d_xfrc;            // [n][QG_NBODY][QG_NXFRC]
+    KPush push;               // the push schedule (interval 0: off)
+    int32_t mapping;         // QG_MAP_AUTO / QG_MAP_LANE / QG_MAP_QUAD (request)
     int32_t creating;
     int32_t walk_bound;       // qg_walk layers bound to this handle (qg_set_task refuses while > 0)
     int32_t po_unfused;       // env QG_PO_UNFUSED=1: keep the observation pack of qg_po_step a launch of its own (A/B, parity test)
@@ -170,7 +176,7 @@ extern "C" int qg_destroy(qg_sim *s) {
     (void)hipDeviceSynchronize();                  // steps may still be in flight on a caller's stream (the header's ordering contract)
     resident_free(s);
     void *ptrs[] = {s->d_model, s->d_task, s->st.qpos, s->st.qvel, s->st.act, s->st.ctrl, s->st.nstep, s->st.episode, s->d_actions,
-                    s->d_obs,   s->d_reward, s->d_comps, s->d_stage, s->d_done, s->d_mask, s->d_dyn, s->d_model_dyn};
+                    s->d_obs,   s->d_reward, s->d_comps, s->d_stage, s->d_done, s->d_mask, s->d_dyn, s->d_model_dyn, s->d_xfrc};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (s->h_pin) (void)hipHostFree(s->h_pin);
@@ -506,7 +512,8 @@ static int launch_step(qg_sim *s, const float *d_actions, float *d_obs, float *d
     P.packed = d_packed;
     P.seed = s->seed;
     P.env_index_base = s->env_index_base;
-    const StepLaunch L = {s, s->dyn ? &s->d_model_dyn->m : s->d_model, P, stream, walk, po};
+    const bool per_env = s->dyn || s->xfrc;
+    const StepLaunch L = {s, per_env ? &s->d_model_dyn->m : s->d_model, P, stream, walk, po};
     const int emap = effective_mapping(s);
     if (s->res.launched) {            // a per-launch step while the resident kernel holds the state in registers: it has to hand it back first
         int rr = resident_retire(s);
@@ -518,10 +525,10 @@ static int launch_step(qg_sim *s, const float *d_actions, float *d_obs, float *d
     const bool dyn_draw = s->task.auto_reset && (s->task.reset_flags & QG_RESET_DYNAMICS);
     if (dyn_draw && !s->dyn_range_set) return fail(QG_ERR_ARG, "step: task.reset_flags has QG_RESET_DYNAMICS and no range is set (qg_set_dynamics_range)");
     // per-env dynamics: the table-driven kernels' per-env forms, one link per lane up to 4096 envs (lagged sensors), one leg per lane
-    // above (qg_set_mapping refuses the other mappings while the mode is on)
-    if (s->dyn && emap != QG_MAP_LINK && emap != QG_MAP_QUAD)
+    // above (qg_set_mapping refuses the other mappings while the mode is on); wrench mode runs the same forms
+    if (per_env && emap != QG_MAP_LINK && emap != QG_MAP_QUAD)
         return fail(QG_ERR_ARG, "step: per-env dynamics run in the LINK and QUAD mappings only (mapping %d)", emap);
-    if (s->dyn) select_step<true>(L, emap);
+    if (per_env) select_step<true>(L, emap);
     else select_step<false>(L, emap);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "qg_step_kernel launch: %s", hipGetErrorString(e));
@@ -739,6 +746,8 @@ extern "C" int qg_set_mapping(qg_sim *s, int32_t mapping) {
     if (!s) return fail(QG_ERR_ARG, "null handle");
     if (s->dyn && (mapping == QG_MAP_PAIR || mapping == QG_MAP_LANE))
         return fail(QG_ERR_ARG, "qg_set_mapping: per-env dynamics run in the LINK and QUAD mappings only (qg_clear_dynamics first)");
+    if (s->xfrc && (mapping == QG_MAP_PAIR || mapping == QG_MAP_LANE))
+        return fail(QG_ERR_ARG, "qg_set_mapping: external wrenches run in the LINK and QUAD mappings only (qg_clear_xfrc first)");
     if (mapping == QG_MAP_PAIR && !s->baked)
         return fail(QG_ERR_ARG, "qg_set_mapping: the two-legs-per-lane kernel serves the compiled-in robot only");
     if (mapping != QG_MAP_AUTO && mapping != QG_MAP_LANE && mapping != QG_MAP_QUAD && mapping != QG_MAP_PAIR && mapping != QG_MAP_LINK)
@@ -844,6 +853,7 @@ static KStepArgs multi_step_args(const qg_sim *s) {
 extern "C" int qg_step_device_seq(qg_sim *s, const float *actions, float *packed, int32_t count, void *stream) {
     if (!s || !actions || !packed || count < 1) return fail(QG_ERR_ARG, "qg_step_device_seq: bad argument");
     if (s->dyn) return fail(QG_ERR_ARG, "qg_step_device_seq: not available with per-env dynamics (qg_clear_dynamics first)");
+    if (s->xfrc) return fail(QG_ERR_ARG, "qg_step_device_seq: not available with external wrenches (qg_clear_xfrc first)");
     if (s->walk_bound) return fail(QG_ERR_ARG, "qg_step_device_seq: a walking task layer is bound to this handle");
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     int rc;
@@ -935,6 +945,7 @@ extern "C" int qg_resident_start(qg_sim *s, int32_t slots, int32_t idle_timeout_
     if ((actions == nullptr) != (packed == nullptr)) return fail(QG_ERR_ARG, "qg_resident_start: pass both slot buffers or neither");
     if (s->res.active) return fail(QG_ERR_ARG, "qg_resident_start: already on");
     if (s->dyn) return fail(QG_ERR_ARG, "qg_resident_start: not available with per-env dynamics (qg_clear_dynamics first)");
+    if (s->xfrc) return fail(QG_ERR_ARG, "qg_resident_start: not available with external wrenches (qg_clear_xfrc first)");
     if (slots < 1 || slots > 4096) return fail(QG_ERR_ARG, "qg_resident_start: slots must be 1..4096");
     if (idle_timeout_us == 0) idle_timeout_us = 2000;
     if (idle_timeout_us < 50 || idle_timeout_us > 100000) return fail(QG_ERR_ARG, "qg_resident_start: idle_timeout_us must be 50..100000 (0 = 2000)");
@@ -1775,19 +1786,9 @@ static int dyn_check_row(const qg_sim *s, const float *row, const char *who, con
                     who, what, dm, p[0], p[1], p[2]);
     return QG_OK;
 }
-// switch the mode on: the row buffer (identity rows) and the per-env kernels' model pointer, the table-driven kernels
-static int dyn_enable(qg_sim *s, const char *who) {
-    if (s->dyn) return QG_OK;
-    if (s->mapping == QG_MAP_LANE || s->mapping == QG_MAP_PAIR)
-        return fail(QG_ERR_ARG, "%s: per-env dynamics run in the LINK and QUAD mappings only (qg_set_mapping AUTO, LINK or QUAD first)", who);
-    if (s->res.active) return fail(QG_ERR_ARG, "%s: the resident step mode is on (qg_resident_stop first)", who);
-    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }   // steps of the shared model may be in flight on a caller's stream
+// identity rows into the dynamics buffer (with them the per-env kernels compute the shared model's bits)
+static int dyn_fill_identity(qg_sim *s, const char *who) {
     const size_t n = (size_t)s->n;
-    if (!s->d_dyn) HIP_TRY(hipMalloc((void **)&s->d_dyn, n * QG_NDYN * sizeof(float)), QG_ERR_ALLOC);
-    if (!s->d_model_dyn) HIP_TRY(hipMalloc((void **)&s->d_model_dyn, sizeof(KModelDyn)), QG_ERR_ALLOC);
-    HIP_TRY(hipMemcpy(&s->d_model_dyn->m, s->d_model, sizeof(KModel), hipMemcpyDeviceToDevice), QG_ERR_DEVICE);
-    const float *rows = s->d_dyn;
-    HIP_TRY(hipMemcpy(&s->d_model_dyn->rows, &rows, sizeof rows, hipMemcpyHostToDevice), QG_ERR_DEVICE);
     float id[QG_NDYN];
     dyn_identity_row(s, id);
     float *h = (float *)malloc(n * QG_NDYN * sizeof(float));
@@ -1797,8 +1798,46 @@ static int dyn_enable(qg_sim *s, const char *who) {
     hipError_t e = hipMemcpy(s->d_dyn, h, n * QG_NDYN * sizeof(float), hipMemcpyHostToDevice);
     free(h);
     if (e != hipSuccess) return fail(QG_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
-    s->dyn = 1;
+    return QG_OK;
+}
+// what the per-env kernels read behind the model tables: the dynamics rows' address, the wrench rows' address (NULL while wrench mode
+// is off: the kernels' wave-uniform branch), the FRAME's centre of mass and the push schedule.  Callers have waited for the device.
+static int model_dyn_upload(qg_sim *s) {
+    KModelDyn h;
+    h.rows = s->d_dyn;
+    h.xfrc = s->xfrc ? s->d_xfrc : nullptr;
+    for (int i = 0; i < 3; i++) h.com0[i] = (float)s->model.body_ipos[0][i];
+    h.push = s->xfrc ? s->push : KPush{};
+    const size_t off = offsetof(KModelDyn, rows);
+    HIP_TRY(hipMemcpy((char *)s->d_model_dyn + off, (const char *)&h + off, sizeof(KModelDyn) - off, hipMemcpyHostToDevice), QG_ERR_DEVICE);
+    return QG_OK;
+}
+// The per-env forms of the table-driven kernels, for per-env dynamics and for wrench mode alike: the dynamics rows (identity) and the
+// kernels' model pointer.  Called when neither mode is on yet; `what` names the mode in the refusals.
+static int per_env_enable(qg_sim *s, const char *who, const char *what) {
+    if (s->mapping == QG_MAP_LANE || s->mapping == QG_MAP_PAIR)
+        return fail(QG_ERR_ARG, "%s: %s run in the LINK and QUAD mappings only (qg_set_mapping AUTO, LINK or QUAD first)", who, what);
+    if (s->res.active) return fail(QG_ERR_ARG, "%s: the resident step mode is on (qg_resident_stop first)", who);
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }   // steps of the shared model may be in flight on a caller's stream
+    const size_t n = (size_t)s->n;
+    if (!s->d_dyn) HIP_TRY(hipMalloc((void **)&s->d_dyn, n * QG_NDYN * sizeof(float)), QG_ERR_ALLOC);
+    if (!s->d_model_dyn) HIP_TRY(hipMalloc((void **)&s->d_model_dyn, sizeof(KModelDyn)), QG_ERR_ALLOC);
+    HIP_TRY(hipMemcpy(&s->d_model_dyn->m, s->d_model, sizeof(KModel), hipMemcpyDeviceToDevice), QG_ERR_DEVICE);
+    int rc = dyn_fill_identity(s, who);
+    if (rc != QG_OK) return rc;
+    rc = model_dyn_upload(s);
+    if (rc != QG_OK) return rc;
     s->baked = 0;
+    return QG_OK;
+}
+// switch the mode on: the row buffer (identity rows) and the per-env kernels' model pointer, the table-driven kernels
+static int dyn_enable(qg_sim *s, const char *who) {
+    if (s->dyn) return QG_OK;
+    if (!s->xfrc) {                 // (wrench mode runs the per-env kernels already, with identity rows)
+        int rc = per_env_enable(s, who, "per-env dynamics");
+        if (rc != QG_OK) return rc;
+    }
+    s->dyn = 1;
     return QG_OK;
 }
 
@@ -1885,8 +1924,142 @@ extern "C" int qg_clear_dynamics(qg_sim *s) {
     if (!s->dyn) return QG_OK;
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);        // per-env steps may be in flight on a caller's stream
+    if (s->xfrc) {                  // wrench mode keeps the per-env kernels: identity rows
+        int rc = dyn_fill_identity(s, "qg_clear_dynamics");
+        if (rc != QG_OK) return rc;
+    }
     s->dyn = 0;
     s->dyn_range_set = 0;
-    s->baked = s->model_baked;
+    if (!s->xfrc) s->baked = s->model_baked;
+    return QG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// external wrenches and the push schedule (include/quadgym.h, QG_NXFRC columns per body)
+// ------------------------------------------------------------------------------------------------------
+static size_t xfrc_bytes(const qg_sim *s) { return (size_t)s->n * QG_NBODY * QG_NXFRC * sizeof(float); }
+// switch wrench mode on: zero rows, no schedule, the per-env kernels (with identity dynamics rows unless that mode is on)
+static int xfrc_enable(qg_sim *s, const char *who) {
+    if (s->xfrc) return QG_OK;
+    if (!s->dyn) {
+        int rc = per_env_enable(s, who, "external wrenches");
+        if (rc != QG_OK) return rc;
+    } else {
+        int rr = retire_and_sync(s);        // per-env steps may be in flight on a caller's stream
+        if (rr != QG_OK) return rr;
+    }
+    if (!s->d_xfrc) HIP_TRY(hipMalloc((void **)&s->d_xfrc, xfrc_bytes(s)), QG_ERR_ALLOC);
+    HIP_TRY(hipMemset(s->d_xfrc, 0, xfrc_bytes(s)), QG_ERR_DEVICE);
+    s->push = KPush{};
+    s->xfrc = 1;
+    int rc = model_dyn_upload(s);
+    if (rc != QG_OK) { s->xfrc = 0; return rc; }
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    return QG_OK;
+}
+
+extern "C" int qg_set_xfrc(qg_sim *s, const uint8_t *mask, const float *rows) {
+    if (!s || !rows) return fail(QG_ERR_ARG, "qg_set_xfrc: null argument");
+    const size_t n = (size_t)s->n, w = QG_NBODY * QG_NXFRC;
+    for (size_t i = 0; i < n; i++) {
+        if (mask && !mask[i]) continue;
+        for (size_t c = 0; c < w; c++) {     // (exponent bits: the device pass, which parses this too, assumes finite math)
+            uint32_t bits;
+            memcpy(&bits, rows + i * w + c, 4);
+            if (((bits >> 23) & 0xFFu) == 0xFFu)
+                return fail(QG_ERR_ARG, "qg_set_xfrc: env %zu, body %zu, column %zu is not finite", i, c / QG_NXFRC, c % QG_NXFRC);
+        }
+    }
+    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
+    int rc = xfrc_enable(s, "qg_set_xfrc");
+    if (rc != QG_OK) return rc;
+    // steps may be in flight on a caller's stream even when the mode was already on -- the header's ordering contract
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }
+    if (!mask) {
+        HIP_TRY(hipMemcpy(s->d_xfrc, rows, xfrc_bytes(s), hipMemcpyHostToDevice), QG_ERR_DEVICE);
+        return QG_OK;
+    }
+    float *h = (float *)malloc(xfrc_bytes(s));
+    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
+    hipError_t e = hipMemcpy(h, s->d_xfrc, xfrc_bytes(s), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) {
+        for (size_t i = 0; i < n; i++)
+            if (mask[i]) memcpy(h + i * w, rows + i * w, w * sizeof(float));
+        e = hipMemcpy(s->d_xfrc, h, xfrc_bytes(s), hipMemcpyHostToDevice);
+    }
+    free(h);
+    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_set_xfrc: %s", hipGetErrorString(e));
+    return QG_OK;
+}
+
+extern "C" int qg_set_xfrc_device(qg_sim *s, const float *d_rows, void *stream) {
+    if (!s || !d_rows) return fail(QG_ERR_ARG, "qg_set_xfrc_device: null argument");
+    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
+    if (!s->xfrc) {                 // the first call switches the mode on, which waits for the device (not while a stream is captured)
+        int rc = xfrc_enable(s, "qg_set_xfrc_device");
+        if (rc != QG_OK) return rc;
+    }
+    if (s->res.launched) {          // (the resident kernel cannot run in wrench mode; a stale launch is retired as launch_step does)
+        int rr = resident_retire(s);
+        if (rr != QG_OK) return rr;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    note_caller_stream(s, st);
+    HIP_TRY(hipMemcpyAsync(s->d_xfrc, d_rows, xfrc_bytes(s), hipMemcpyDeviceToDevice, st), QG_ERR_LAUNCH);
+    return QG_OK;
+}
+
+extern "C" int qg_get_xfrc(qg_sim *s, float *rows) {
+    if (!s || !rows) return fail(QG_ERR_ARG, "qg_get_xfrc: null argument");
+    if (!s->xfrc) {
+        memset(rows, 0, xfrc_bytes(s));
+        return QG_OK;
+    }
+    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }
+    HIP_TRY(hipMemcpy(rows, s->d_xfrc, xfrc_bytes(s), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    return QG_OK;
+}
+
+extern "C" int qg_set_push(qg_sim *s, const qg_push_params *p) {
+    if (!s) return fail(QG_ERR_ARG, "null handle");
+    if (!p) {                       // the schedule off; the rows (and the mode) stay
+        if (!s->xfrc) return QG_OK;
+        HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
+        { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }
+        s->push = KPush{};
+        return model_dyn_upload(s);
+    }
+    if (p->interval < 1) return fail(QG_ERR_ARG, "qg_set_push: interval %d < 1 env-step", p->interval);
+    if (p->duration < 1 || p->duration > p->interval)
+        return fail(QG_ERR_ARG, "qg_set_push: duration %d outside 1 .. interval (%d)", p->duration, p->interval);
+    if (!(p->probability >= 0.f && p->probability <= 1.f)) return fail(QG_ERR_ARG, "qg_set_push: probability %g outside [0, 1]", (double)p->probability);
+    uint32_t fmax_bits;
+    memcpy(&fmax_bits, &p->force_max, 4);     // (exponent bits, as for the rows: the device pass assumes finite math)
+    if (!(p->force_min >= 0.f && p->force_min <= p->force_max) || ((fmax_bits >> 23) & 0xFFu) == 0xFFu)
+        return fail(QG_ERR_ARG, "qg_set_push: force range [%g, %g] (need 0 <= force_min <= force_max, finite)", (double)p->force_min, (double)p->force_max);
+    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
+    int rc = xfrc_enable(s, "qg_set_push");
+    if (rc != QG_OK) return rc;
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }
+    s->push.interval = p->interval;
+    s->push.duration = p->duration;
+    s->push.probability = p->probability;
+    s->push.force_min = p->force_min;
+    s->push.force_max = p->force_max;
+    return model_dyn_upload(s);
+}
+
+extern "C" int qg_clear_xfrc(qg_sim *s) {
+    if (!s) return fail(QG_ERR_ARG, "null handle");
+    if (!s->xfrc) return QG_OK;
+    HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
+    { int rr = retire_and_sync(s); if (rr != QG_OK) return rr; }      // steps in wrench mode may be in flight on a caller's stream
+    HIP_TRY(hipMemset(s->d_xfrc, 0, xfrc_bytes(s)), QG_ERR_DEVICE);
+    s->xfrc = 0;
+    s->push = KPush{};
+    int rc = model_dyn_upload(s);
+    if (rc != QG_OK) return rc;
+    if (!s->dyn) s->baked = s->model_baked;
     return QG_OK;
 }

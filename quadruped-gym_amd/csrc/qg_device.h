@@ -41,9 +41,21 @@ struct KModel {
 // the state's layout).  The per-env-dynamics variants of the generic step kernels get a KModelDyn as their model pointer: the shared
 // tables followed by the rows' address -- the kernel arguments (and so the existing variants' code) stay as they are.
 #define QGK_NDYN 11
+// External wrenches (qg_set_xfrc / qg_set_push): QG_NBODY x 6 f32 per env, env-major ([n][13][6], the ABI's layout: the device form
+// is a plain copy on the caller's stream, and the six numbers a lane reads are contiguous -- three 8-byte loads, a wave's loads one
+// contiguous range).  The push schedule draws a horizontal force on the FRAME per (env, episode, window) with no per-env state.
+#define QGK_NXFRC 6
+#define QGK_NBODY 13
+struct KPush {
+    int32_t interval, duration;       // env-steps per window, env-steps a push lasts (interval 0: no schedule)
+    float probability, force_min, force_max;
+};
 struct KModelDyn {
     KModel m;
     const float *rows;        // [QGK_NDYN][n]
+    const float *xfrc;        // [n][13][6] world-frame force and torque at each body's centre of mass, or NULL: wrench mode off
+    float com0[3];            // the FRAME's centre of mass, body frame (the shared model's body_ipos[0]: a payload does not move it)
+    KPush push;
 };
 // what one lane holds of its env's row: the replaced contact constants, the servo / hinge scales, the FRAME's rigid inertia about its
 // origin with the payload added

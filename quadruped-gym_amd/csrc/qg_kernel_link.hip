@@ -115,6 +115,9 @@ struct LinkRegs {
 };
 // this lane's hinge: lane r < 3 of leg k owns hinge 3k + r; the spare lane shadows hinge 3k + 2 (its copy is never stored)
 struct HingeLane { float q, qd, act, u, sn, cs; };
+// wrench mode: a link lane's own row; the spare lane of leg 0 holds the FRAME's (push included), the other spare lanes zeros; c0 is the
+// FRAME's centre of mass (where the spare lane's row acts)
+struct KXfrcLink { KWrench w; V3 c0; };
 
 DEV float sel3(int r, float a, float b, float c) { return r == 0 ? a : (r == 1 ? b : c); }
 DEV V3 sel3(int r, V3 a, V3 b, V3 c) { return v3(sel3(r, a.x, b.x, c.x), sel3(r, a.y, b.y, c.y), sel3(r, a.z, b.z, c.z)); }
@@ -133,10 +136,11 @@ DEV V3 sel3(int r, V3 a, V3 b, V3 c) { return v3(sel3(r, a.x, b.x, c.x), sel3(r,
 //     two fused DPP adds per value instead of every lane walking the chain;
 //   * the FRAME's twelve contact sample points are shared out one per link lane (the spare lane alone used to evaluate three).
 // DYN: per-env dynamics -- contact constants and the FRAME's rigid inertia of this lane's env from D (the servo / hinge scales are
-// already in K)
+// already in K); with `xon` (wave-uniform) the external wrench X of this lane (KXfrcLink)
 template <bool BAKED, bool DYN = false>
 DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env, BaseState &B, HingeLane &J, const LinkRegs &K,
-                      bool want_sensors, float *__restrict__ row, int kleg, float &zaxis_z, const KDyn &D = KDyn{}) {
+                      bool want_sensors, float *__restrict__ row, int kleg, float &zaxis_z, const KDyn &D = KDyn{}, bool xon = false,
+                      const KXfrcLink &X = KXfrcLink{}) {
     using namespace pk3;
     const float h = C.h;
     const BaseCtx bc = pk3::base_prelude_unit(C, B); // the quaternion is of unit length here (normalised at load, then by base_integrate)
@@ -199,9 +203,11 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
     // ---- this lane's link: rigid inertia about the FRAME origin (FRAME axes), bias force, ground contact -------------------------
     Rigid Bi;
     Bi.m = K.mass;
+    V3 cl;                                           // the link's centre of mass (where its external wrench acts)
     {
         const Fr &E = Ep;
         V3 c = pp + rot(E, v3(K.ipos[0], K.ipos[1], K.ipos[2]));
+        cl = c;
         Bi.h = Bi.m * c;
         V3 ux = fma3(K.inertia[0], E.ex, fma3(K.inertia[3], E.ey, K.inertia[4] * E.ez));
         V3 uy = fma3(K.inertia[3], E.ex, fma3(K.inertia[1], E.ey, K.inertia[5] * E.ez));
@@ -253,6 +259,16 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
         f.a = f.a - fe.a;
         f.l = f.l - fe.l;
         pk3::add_contact_damping(A, cd.mc, cd.w, cd.P, nb);
+    }
+    // external wrench (wrench mode, wave-uniform): a link lane's row acts on its link, next to the contact force (-1 x xw: exact); the
+    // spare lanes add nothing here (0 x xw) -- the one of leg 0 holds the FRAME's row, which joins the base right-hand side below
+    SV xw = {};
+    if constexpr (DYN) {
+        if (xon) {
+            xw = xfrc_spatial(bc, X.w, r < 3 ? cl : X.c0);
+            f.a = fma3(-K.ml, xw.a, f.a);
+            f.l = fma3(-K.ml, xw.l, f.l);
+        }
     }
     // FRAME contact: every link lane evaluates one of the FRAME's twelve sample points
     float wsumF = 0.f;
@@ -354,6 +370,12 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
         Cn.LL.xy = fmaf(-WL.x, L.y, A.LL.xy); Cn.LL.zz = fmaf(-WZ.y, Z.y, A.LL.zz);
     }
     // right-hand side share: -(f_own + z_r y_r / d_r)
+    if constexpr (DYN) {
+        if (xon) {          // the spare lane of leg 0: the FRAME's external wrench (x 0 in the link lanes, whose rows are in f already)
+            f.a = fma3(K.ml - 1.f, xw.a, f.a);
+            f.l = fma3(K.ml - 1.f, xw.l, f.l);
+        }
+    }
     const f2 nyr = {-yr, -yr};
     const f2 rh0 = __builtin_elementwise_fma(nyr, WP, f2{-f.a.x, -f.a.y}), rh1 = __builtin_elementwise_fma(nyr, WL, f2{-f.l.x, -f.l.y}),
              rh2 = __builtin_elementwise_fma(nyr, WZ, f2{-f.a.z, -f.l.z});
@@ -438,7 +460,7 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
 // come back through LDS behind one workgroup barrier after the loop.  Same lane mapping in both waves (lane r < 3 of leg k = channel
 // 3k + r of env el of wave w).
 // DYN (generic tables only): per-env dynamics -- `Mp` is a KModelDyn; each lane takes its env's row into registers once per launch
-// (dyn_load) and scales its servo / hinge constants in K with it.
+// (dyn_load) and scales its servo / hinge constants in K with it; in wrench mode it also holds its external wrench row (KXfrcLink).
 template <bool WALK = false, bool PO = false, bool BAKED = true, bool HELP = false, bool DYN = false>
 __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void qg_step_kernel_link(const KModel *__restrict__ Mp, const KTask *__restrict__ T, KStepArgs P,
                                                                                   const typename WalkArgT<WALK>::type WK,
@@ -572,6 +594,19 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
         D = dyn_load(Mp, C, n, env);
         K.kp *= D.kp; K.kv *= D.kv; K.force_lo *= D.force; K.force_hi *= D.force; K.damping *= D.damping;
     }
+    // external wrenches (wrench mode: KModelDyn::xfrc != NULL, wave-uniform): a link lane's row, the FRAME's (with this launch's push)
+    // in the spare lane of leg 0, zeros in the other spare lanes -- once per launch; nothing is loaded with the mode off
+    bool xon = false;
+    KXfrcLink X = {};
+    if constexpr (DYN) {
+        const KModelDyn *Md = reinterpret_cast<const KModelDyn *>(Mp);
+        xon = Md->xfrc != nullptr;
+        if (xon) {
+            if (r < 3) X.w = xfrc_row(Md->xfrc, env, 1 + 3 * k + r);
+            else if (k == 0) X.w = xfrc_frame(Md, P, env, Tk.frame_skip);
+            X.c0 = v3(Md->com0[0], Md->com0[1], Md->com0[2]);
+        }
+    }
 
     BaseState B;
     const unsigned n4 = 4u * (unsigned)n, e4 = 4u * (unsigned)env;        // byte strides of the [field][n] state arrays
@@ -656,7 +691,7 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
     QG_MARK(1);                                      // state in registers, prologue stores issued
     asm volatile(".p2align 6");
 #pragma unroll 1
-    for (int s = 0; s < fs; ++s) substep_link<BAKED, DYN>(C, cm, sm, r, lead_env, B, J, K, s == fs - 1, srow, k, zaxis_z, D);
+    for (int s = 0; s < fs; ++s) substep_link<BAKED, DYN>(C, cm, sm, r, lead_env, B, J, K, s == fs - 1, srow, k, zaxis_z, D, xon, X);
     int nstep = nstep0 + fs;
     QG_MARK(2);                                      // physics done
 

@@ -584,6 +584,67 @@ DEV KDyn dyn_load(const KModel *Mp, const KModel &C, int n, int env) {
 // a servo / hinge constant of the shared table, times this env's scale in the per-env-dynamics variants
 #define QG_DYN_SCALE(x, s) (DYN ? (x) * D.s : (x))
 
+// ---- external wrenches (qg_set_xfrc / qg_set_push, include/quadgym.h) ---------------------------------------------------------------
+// They ride on the per-env-dynamics variants: KModelDyn::xfrc is NULL with the mode off, and every use below sits behind a wave-uniform
+// branch on it, so those variants load and compute nothing more then.
+// the 24 random bits behind uniform24s (the push offset needs them as an integer: (bits * m) >> 24 is exact on host and device)
+DEV uint32_t bits24s(uint64_t seed, uint64_t env_index, uint64_t counter, uint32_t stream) {
+    const uint64_t sd = seed + 0xA0761D6478BD642Full * (uint64_t)stream;
+    const uint64_t x = sd + 0x9E3779B97F4A7C15ull * (env_index + 1) + 0xD1B54A32D192ED03ull * (counter + 1);
+    return (uint32_t)(mix64(mix64(x)) >> 40);
+}
+// The push schedule: env-step s = nstep / frame_skip of the episode lies in window w = s / interval at offset j = s % interval.  The
+// window holds a push if u_gate < probability; it starts at o = (k_off (interval - duration + 1)) >> 24 and lasts `duration` env-steps;
+// its force is F (cos th, sin th, 0) on the FRAME, F = f_min + (f_max - f_min) u_mag, th = 2 pi u_head.  Streams 32 + 4 w + {0 gate,
+// 1 offset, 2 magnitude, 3 heading} of the (seed, env, episode) key.  Once per launch and env: the force is held over the substeps.
+#define QG_STREAM_PUSH 32u
+DEV V3 push_force(const KPush &p, uint64_t seed, uint64_t env_index, int32_t episode, int32_t nstep, int32_t fs) {
+    V3 f = v3(0.f, 0.f, 0.f);
+    if (p.interval <= 0) return f;
+    const int32_t s = nstep / fs, w = s / p.interval, j = s - w * p.interval;
+    const uint32_t st = QG_STREAM_PUSH + 4u * (uint32_t)w;
+    const uint64_t key = (uint64_t)episode;
+    const float inv24 = 1.0f / 16777216.0f;
+    if (!((float)bits24s(seed, env_index, key, st) * inv24 < p.probability)) return f;
+    const int32_t o = (int32_t)(((uint64_t)bits24s(seed, env_index, key, st + 1u) * (uint64_t)(p.interval - p.duration + 1)) >> 24);
+    if (j < o || j >= o + p.duration) return f;
+    const float F = fmaf(p.force_max - p.force_min, (float)bits24s(seed, env_index, key, st + 2u) * inv24, p.force_min);
+    float sn, cs;
+    sincos_f(6.283185307179586f * ((float)bits24s(seed, env_index, key, st + 3u) * inv24), sn, cs);
+    return v3(F * cs, F * sn, 0.f);
+}
+// one body's row (world force, world torque at its centre of mass): three 8-byte loads (rows are 24-byte aligned)
+struct KWrench { V3 F, T; };
+DEV KWrench xfrc_row(const float *xf, int env, int body) {
+    const float2 *p = reinterpret_cast<const float2 *>(xf + ((size_t)env * QGK_NBODY + body) * QGK_NXFRC);
+    const float2 a = p[0], b = p[1], c = p[2];
+    return {v3(a.x, a.y, b.x), v3(b.y, c.x, c.y)};
+}
+// the FRAME's row of env `env` plus the push of this launch
+DEV KWrench xfrc_frame(const KModelDyn *Md, const KStepArgs &P, int env, int fs) {
+    KWrench w = xfrc_row(Md->xfrc, env, 0);
+    if (Md->push.interval > 0) {
+        const V3 pf = push_force(Md->push, P.seed, P.env_index_base + (uint64_t)env, P.st.episode[env], P.st.nstep[env], fs);
+        w.F = w.F + pf;
+    }
+    return w;
+}
+// a world-frame force F and torque T acting at point c (FRAME coordinates) as a spatial force in FRAME axes about the FRAME origin,
+// (R^T T + c x R^T F, R^T F): the form the contact forces take.  A zero row gives exact zeros, and the callers subtract / add it as a
+// whole (no product of it feeds their sum), so zero rows leave the bits of the mode-off path.
+DEV SV xfrc_spatial(const BaseCtx &bc, const KWrench &w, V3 c) {
+    const V3 Fb = v3(dot(bc.cx, w.F), dot(bc.cy, w.F), dot(bc.cz, w.F));
+    const V3 Tb = v3(dot(bc.cx, w.T), dot(bc.cy, w.T), dot(bc.cz, w.T));
+    return {v3(fmaf(c.y, Fb.z, fmaf(-c.z, Fb.y, Tb.x)), fmaf(c.z, Fb.x, fmaf(-c.x, Fb.z, Tb.y)), fmaf(c.x, Fb.y, fmaf(-c.y, Fb.x, Tb.z))), Fb};
+}
+// what a lane of the one-leg-per-lane kernel holds for a launch: its leg's three links and the FRAME (identical in the env's lanes), and
+// the FRAME's centre of mass; an empty struct in the variants without per-env dynamics (their code stays as it was)
+struct KXfrcQuad { KWrench link[3], frame; V3 com0; };
+template <bool DYN> struct XfrcQuadT { struct type {}; };
+template <> struct XfrcQuadT<true> { using type = KXfrcQuad; };
+DEV const KXfrcQuad *xfrc_quad_ptr(const KXfrcQuad &x) { return &x; }
+template <class E> DEV const KXfrcQuad *xfrc_quad_ptr(const E &) { return nullptr; }
+
 // ------------------------------------------------------------------------------------------
 // one leg: kinematics of fema / shin / foot, recursive Newton-Euler bias forces, ground contact,
 // composite (augmented) inertias = mass-matrix columns, servo / limit / damping terms.
@@ -598,11 +659,12 @@ DEV KDyn dyn_load(const KModel *Mp, const KModel &C, int n, int env) {
 // register-capped (3 and 4 waves per SIMD) instantiations of the one-leg-per-lane kernel.
 // sc: sin / cos of the three hinge rotations carried by the caller (advanced by each substep's small rotation, see hinge_advance),
 // or NULL: evaluate the polynomials here.
-// DYN: contact constants and servo / hinge scales of this lane's env from D (per-env dynamics)
+// DYN: contact constants and servo / hinge scales of this lane's env from D (per-env dynamics); with `xon` (wave-uniform) the external
+// wrenches X[0..2] of the leg's three links, subtracted from their forces next to the contact force
 template <class T, bool BAKED, bool QUAD, bool CULL_FEMUR = false, bool COMPACT = false, bool DYN = false>
 DEV void leg_pass(const KModel &C, int k, FrT<T> Ep, const T q[3], const T qd[3], const T act[3], const BaseCtx &bc, float zbase_f,
                   float h, Sym6T<T> &Ic, SVT<T> &fc, SVT<T> F[3], T Hd[3], T &H01, T &H02, T &H12, T bj[3], const T *sc = nullptr,
-                  const KDyn &D = KDyn{}) {
+                  const KDyn &D = KDyn{}, bool xon = false, const KWrench *X = nullptr) {
     const T zero = T(0.f);
     V3T<T> pp = v3<T>(zero, zero, zero);
     const V3T<T> nb = splat3<T>(bc.n);
@@ -682,6 +744,13 @@ DEV void leg_pass(const KModel &C, int k, FrT<T> Ep, const T q[3], const T qd[3]
                                              C.contact_margin, C.contact_mu, h, fe, Ag[i]);
             f[i].a = f[i].a - fe.a;
             f[i].l = f[i].l - fe.l;
+        }
+        if constexpr (DYN) {
+            if (xon) {          // external wrench on this link (wave-uniform: off in the mode-off launches)
+                const SV xw = xfrc_spatial(bc, X[i], c);
+                f[i].a = f[i].a - xw.a;
+                f[i].l = f[i].l - xw.l;
+            }
         }
         Ep = E; pp = p; vp = v; ap = a;
     }
@@ -1323,9 +1392,10 @@ template <bool PKQ> DEV void quad_integrate(const BaseCtx &c, float h, V3 wdot, 
 // share a SIMD (register cap 256), costs ~2 % when a wave has the register file to itself.
 // BAKED: the compiled-in robot, constants are literals and the lane works in its leg's quarter-turn frame.  Otherwise `C`
 // is the model table staged in LDS and every lane reads the constants of its own leg (k) from it -- any model numbers.
+// DYN: per-env dynamics (D) and, with `xon` (wave-uniform), the external wrenches X of this lane's leg and of the FRAME
 template <bool BAKED, bool LOWREG, bool DYN = false>
 DEV void substep_quad(const KModel &C, float cm, float sm, BaseState &B, LegState &L, bool want_sensors, float *__restrict__ row, int k, float &zaxis_z,
-                      const KDyn &D = KDyn{}) {
+                      const KDyn &D = KDyn{}, bool xon = false, const KXfrcQuad *X = nullptr) {
     const float h = C.h;
     const BaseCtx bc0 = quad_prelude<BAKED && !LOWREG>(C, B);
     V3 gb_keep;
@@ -1356,7 +1426,11 @@ DEV void substep_quad(const KModel &C, float cm, float sm, BaseState &B, LegStat
             leg_pass<float, true, true, LOWREG, false>(C, 0, Ek, L.q, L.qd, L.act, bc, B.pw.z, h, Ic, fc, F, Hd, H01, H02, H12, bj, L.sc);
         } else {
             Fr E0 = {v3(1.f, 0.f, 0.f), v3(0.f, 1.f, 0.f), v3(0.f, 0.f, 1.f)};
-            leg_pass<float, false, false, LOWREG, false, DYN>(C, k, E0, L.q, L.qd, L.act, bc, B.pw.z, h, Ic, fc, F, Hd, H01, H02, H12, bj, L.sc, D);
+            if constexpr (DYN)
+                leg_pass<float, false, false, LOWREG, false, DYN>(C, k, E0, L.q, L.qd, L.act, bc, B.pw.z, h, Ic, fc, F, Hd, H01, H02, H12, bj, L.sc, D,
+                                                                  xon, X->link);
+            else
+                leg_pass<float, false, false, LOWREG, false, DYN>(C, k, E0, L.q, L.qd, L.act, bc, B.pw.z, h, Ic, fc, F, Hd, H01, H02, H12, bj, L.sc, D);
         }
         leg_eliminate(F, Hd, H01, H02, H12, bj, Y0, Y1, Y2, u, YFt, Fu);
         sub(Ic, YFt);                       // this leg's Schur complement
@@ -1404,6 +1478,13 @@ DEV void substep_quad(const KModel &C, float cm, float sm, BaseState &B, LegStat
                 else contact_finish(wsum, s, E0, v3(0.f, 0.f, 0.f), bc.n, bc.V0, C.contact_k, C.contact_c, C.contact_inv_ramp, C.contact_mu, h, fe, Ic0);
                 b.a = b.a + fe.a;
                 b.l = b.l + fe.l;
+            }
+            if constexpr (DYN) {
+                if (xon) {      // the FRAME's external wrench (and push): every lane of the env, as the rest of the base block
+                    const SV xw = xfrc_spatial(bc, X->frame, X->com0);
+                    b.a = b.a + xw.a;
+                    b.l = b.l + xw.l;
+                }
             }
         }
         if constexpr (BAKED) pk3::base_solve(Ic0, b, x6);      // packed row pairs: fewer instructions for a wave alone on its SIMD, as many
@@ -1489,7 +1570,8 @@ DEV void po_wave_epilogue(const KPoLaunch &PK, const KWalkLaunch &WK, const KSte
 // copies the history rows ring -> out (po_copy_history_now), so that nothing of the copy rides on the physics wave's substep loop: the
 // first version, which kept the in-loop copy with the physics wave, lost to the one-role kernel (48.6 against 46.9 us per step at
 // 16 384 envs, frame_skip 10: at this register budget the copy cannot park in AGPRs across a substep); this one measures 45.4.
-// DYN (generic tables only): per-env dynamics -- `Mp` is a KModelDyn and each lane takes its env's row into registers (dyn_load)
+// DYN (generic tables only): per-env dynamics -- `Mp` is a KModelDyn and each lane takes its env's row into registers (dyn_load);
+// in wrench mode also its leg's and the FRAME's external wrench rows
 template <int WPE, bool BAKED, bool WALK = false, int WAVES = 1, bool PO = false, bool HELP = false, bool DYN = false>
 __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_step_kernel_quad(const KModel *__restrict__ Mp, const KTask *__restrict__ T, KStepArgs P,
                                                                              const typename WalkArgT<WALK>::type WK,
@@ -1529,6 +1611,20 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
     const float sm = (k == 1) ? 1.f : (k == 3) ? -1.f : 0.f;
     KDyn D = {};
     if constexpr (DYN) D = dyn_load(Mp, C, n, env);     // this env's dynamics row, once per launch
+    // external wrenches (wrench mode: KModelDyn::xfrc != NULL, wave-uniform): the rows of this lane's three links and the FRAME's with
+    // this launch's push, once per launch; nothing is loaded with the mode off
+    bool xon = false;
+    typename XfrcQuadT<DYN>::type XQ = {};
+    if constexpr (DYN) {
+        const KModelDyn *Md = reinterpret_cast<const KModelDyn *>(Mp);
+        xon = Md->xfrc != nullptr;
+        if (xon) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) XQ.link[i] = xfrc_row(Md->xfrc, env, 1 + 3 * k + i);
+            XQ.frame = xfrc_frame(Md, P, env, T->frame_skip);
+            XQ.com0 = v3(Md->com0[0], Md->com0[1], Md->com0[2]);
+        }
+    }
 
     if constexpr (HELP) {
         if (helper) {
@@ -1702,7 +1798,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
             PoCopyRegs<PO ? QG_PO_COPY_K : 1> pcr;
             if constexpr (PO_COPY) po_row_copy_load<QG_PO_COPY_K, 4>(PK.P, po_ring, k, s == 0, pcs, pcr);
             if constexpr (PO_COPY && !PO_DEFER) po_row_copy_store<QG_PO_COPY_K, 4>(PK.P, po_out, live, k, s == 0, pcs, pcr);
-            substep_quad<BAKED, (WPE > 1), DYN>(C, cm, sm, B, L, lag && (s == fs - 1), srow, k, zaxis_z, D);
+            substep_quad<BAKED, (WPE > 1), DYN>(C, cm, sm, B, L, lag && (s == fs - 1), srow, k, zaxis_z, D, xon, xfrc_quad_ptr(XQ));
             if constexpr (PO_DEFER) po_row_copy_store<QG_PO_COPY_K, 4>(PK.P, po_out, live, k, s == 0, pcs, pcr);
         }
         if constexpr (PO_COPY) po_row_copy_rest<QG_PO_COPY_K, 4>(PK.P, po_ring, po_out, live, k, pcs);
@@ -1713,7 +1809,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
         if (!lag) {   // un-lagged sensors (task.sensor_lag = 0): one extra forward pass on a scratch copy of the state
             BaseState B2 = B;
             LegState L2 = L;
-            substep_quad<BAKED, (WPE > 1), DYN>(C, cm, sm, B2, L2, true, srow, k, zaxis_z, D);
+            substep_quad<BAKED, (WPE > 1), DYN>(C, cm, sm, B2, L2, true, srow, k, zaxis_z, D, xon, xfrc_quad_ptr(XQ));
         }
         nstep = nstep0 + fs;
 #pragma unroll

@@ -45,7 +45,7 @@ class ModelView:
 
 
 class DataView:
-    """Host mirror of ``mujoco.MjData``: ``qpos, qvel, act, ctrl, time, sensordata`` as float64 arrays."""
+    """Host mirror of ``mujoco.MjData``: ``qpos, qvel, act, ctrl, time, sensordata, xfrc_applied`` as float64 arrays."""
 
     def __init__(self):
         self.qpos = np.zeros(19)
@@ -54,6 +54,7 @@ class DataView:
         self.ctrl = np.zeros(12)
         self.sensordata = np.zeros(33)
         self.time = 0.0
+        self.xfrc_applied = np.zeros((13, 6))   # world-frame force, torque at each body's centre of mass (MjData.xfrc_applied)
 
 
 class QuadrupedEnv(EnvBase):
@@ -102,6 +103,7 @@ class QuadrupedEnv(EnvBase):
             self.termination_fns["default"] = self._default_termination
         self.save_video, self.video_path = save_video, video_path
         self._synced = None
+        self._xfrc_synced = None            # what the device holds of data.xfrc_applied (None: never set, wrench mode off)
         self.seed()
 
     # -- reference API --------------------------------------------------------------------------
@@ -112,6 +114,7 @@ class QuadrupedEnv(EnvBase):
     def reset(self, seed=None, options=None):
         self._sim.reset()
         self._pull()
+        self.data.xfrc_applied[:] = 0.0                     # mj_resetData; the device rows follow at the next step
         self.data.time = 0.0
         self.data.ctrl[:] = np.array([0, 0, -0.5] * 4)     # quadruped.py:124
         self.data.sensordata[:] = 0.0                       # no mj_forward after mj_resetData: first obs is zeros
@@ -132,6 +135,7 @@ class QuadrupedEnv(EnvBase):
         lo, hi = self.action_space.low, self.action_space.high
         applied = np.minimum(np.maximum(np.asarray(action, dtype=np.float64), lo), hi)
         self._push_if_edited()
+        self._push_xfrc_if_edited()
         (sensed, _, _, _), state = self._sim.step_mirror(applied.astype(np.float32)[None])    # one launch, one synchronisation
         self._pull(state)
         h = self.model.opt.timestep
@@ -173,3 +177,12 @@ class QuadrupedEnv(EnvBase):
         if s is None or not (np.array_equal(s[0], self.data.qpos) and np.array_equal(s[1], self.data.qvel)
                              and np.array_equal(s[2], self.data.act)):
             self._sim.set_state(self.data.qpos[None], self.data.qvel[None], self.data.act[None])
+
+    def _push_xfrc_if_edited(self):
+        """``data.xfrc_applied`` goes to the device when it is non-zero or differs from what the device holds; an env that never
+        touches it stays on the kernel it runs."""
+        x = np.asarray(self.data.xfrc_applied, np.float64).reshape(13, 6)
+        if (not x.any()) if self._xfrc_synced is None else np.array_equal(x, self._xfrc_synced):
+            return
+        self._sim.set_external_wrench(x.astype(np.float32)[None])
+        self._xfrc_synced = x.copy()

@@ -146,7 +146,8 @@ class QuadrupedVecEnv(_VecEnvBase):
     def __init__(self, num_envs: int, model_path: str | None = "builtin", max_time: float = 10.0, frame_skip: int = 4,
                  reward_fns: dict | None = None, termination_fns: dict | None = None, use_default_termination: bool = True,
                  obs_mode: int = _abi.OBS_FULL, random_init: bool = False, device: int = 0, env_index_base: int = 0,
-                 seed: int = 0, callable_mode: str = "per_env", infos_mode: str = "lazy", dynamics_randomization: dict | None = None):
+                 seed: int = 0, callable_mode: str = "per_env", infos_mode: str = "lazy", dynamics_randomization: dict | None = None,
+                 push_randomization: dict | None = None):
         if callable_mode not in ("per_env", "batched"):
             raise ValueError("callable_mode must be 'per_env' or 'batched'")
         if infos_mode not in ("lazy", "finished"):
@@ -171,6 +172,8 @@ class QuadrupedVecEnv(_VecEnvBase):
         self._sim = BatchedSim(self.num_envs, device=device, model=qg_model, task=task, env_index_base=env_index_base)
         if dynamics_randomization is not None:
             self._sim.set_dynamics_range(dynamics_randomization)
+        if push_randomization is not None:          # random pushes on the base (seconds -> env-steps of timestep x frame_skip)
+            self._sim.set_push_schedule(_abi.push_schedule_steps(push_randomization, qg_model.timestep * self.frame_skip))
         self._task_key = self._key(task)
         self._seed = int(seed)
         self.obs_dim = self._sim.obs_dim
@@ -261,6 +264,14 @@ class QuadrupedVecEnv(_VecEnvBase):
     def dynamics(self):
         """``[num_envs, 11]`` f32: each env's dynamics row (columns ``_abi.DYN_COLUMNS``; identity rows without randomisation)."""
         return self._sim.get_dynamics()
+
+    def set_external_wrench(self, rows, indices=None):
+        """MuJoCo's ``data.xfrc_applied`` for the envs ``indices`` (all: None): ``[len, 13, 6]`` world-frame force and torque per body."""
+        self._sim.set_external_wrench_of(rows, indices)
+
+    def external_wrench(self):
+        """``[num_envs, 13, 6]`` f32: the external wrench rows (without the pushes of ``push_randomization``)."""
+        return self._sim.get_external_wrench()
 
     def _eval_callables(self, obs, state=None):
         """Host evaluation of the Python callables over ``self.data``; returns (components {name: [N]}, done [N])."""

@@ -69,7 +69,7 @@ class WalkingQuadrupedVecEnv(_VecEnvBase):      # SB3's VecEnv where that packag
     def __init__(self, num_envs, settling_time=0, random_controls=False, random_init=False, reset_options=None,
                  model_path="builtin", max_time=10.0, frame_skip=4, device=0, env_index_base=0, seed=0, walk_params=None,
                  device_commands=False, auto_reset=True, use_default_termination=True, infos_mode="lazy", nan_direction=True,
-                 dynamics_randomization=None):
+                 dynamics_randomization=None, push_randomization=None):
         if infos_mode not in ("lazy", "finished"):
             raise ValueError("infos_mode must be 'lazy' (every env's component dict, built when touched) or 'finished' (content "
                              "for the envs that finished only; `last_components` holds every env's components as one array)")
@@ -95,6 +95,8 @@ class WalkingQuadrupedVecEnv(_VecEnvBase):      # SB3's VecEnv where that packag
         self._sim = BatchedSim(self.num_envs, device=device, model=qg_model, task=task, env_index_base=env_index_base)
         if dynamics_randomization is not None:
             self._sim.set_dynamics_range(dynamics_randomization)
+        if push_randomization is not None:          # random pushes on the base (seconds -> env-steps of timestep x frame_skip)
+            self._sim.set_push_schedule(_abi.push_schedule_steps(push_randomization, qg_model.timestep * self.frame_skip))
         self._lib = _abi.load_library()
         self.params = walk_params if walk_params is not None else default_walk_params()
         self.params.settling_time = float(settling_time)
@@ -139,6 +141,14 @@ class WalkingQuadrupedVecEnv(_VecEnvBase):      # SB3's VecEnv where that packag
     def dynamics(self):
         """``[num_envs, 11]`` f32: each env's dynamics row (columns ``_abi.DYN_COLUMNS``; identity rows without randomisation)."""
         return self._sim.get_dynamics()
+
+    def set_external_wrench(self, rows, indices=None):
+        """MuJoCo's ``data.xfrc_applied`` for the envs ``indices`` (all: None): ``[len, 13, 6]`` world-frame force and torque per body."""
+        self._sim.set_external_wrench_of(rows, indices)
+
+    def external_wrench(self):
+        """``[num_envs, 13, 6]`` f32: the external wrench rows (without the pushes of ``push_randomization``)."""
+        return self._sim.get_external_wrench()
 
     # -- checkpoint / resume (SURVEY section 5; the reference resumes the policy only, train_quadruped.py:114-141) -------------------
     def snapshot(self):

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import NDYN, NQ, NV, NU, NREWARD, QgModel, QgTask, check
+from ._abi import NBODY, NDYN, NQ, NV, NU, NREWARD, NXFRC, QgModel, QgTask, check
 
 
 class BatchedSim:
@@ -276,16 +276,26 @@ class BatchedSim:
             snap["dynamics"] = self.get_dynamics()
             if self._dyn_range is not None:         # what later draws take their rows from
                 snap["dynamics_range"] = np.array([self._dyn_range.lo[:], self._dyn_range.hi[:]], np.float32)
+        if self.wrench_on:                          # wrench mode: the rows and the push schedule (None: no schedule)
+            snap["xfrc"] = self.get_external_wrench()
+            snap["push"] = dict(self._push) if self._push is not None else None
         return snap
 
     def restore(self, snap):
-        """All-or-nothing as far as the checks go: shapes and the dynamics mode are checked, and the per-env dynamics (which the
-        library may still refuse, e.g. on the LANE mapping) are applied, before the state is written."""
+        """All-or-nothing as far as the checks go: shapes, the dynamics and wrench modes are checked, and the per-env dynamics and
+        external wrenches (which the library may still refuse, e.g. on the LANE mapping) are applied, before the state is written."""
         shapes = {"qpos": (self.n, NQ), "qvel": (self.n, NV), "act": (self.n, NU), "ctrl": (self.n, NU), "nstep": (self.n,),
                   "episode": (self.n,)}
         for key, shape in shapes.items():
             if np.asarray(snap[key]).shape != shape:
                 raise ValueError(f"the snapshot's {key} has shape {np.asarray(snap[key]).shape}, expected {shape}")
+        if "xfrc" in snap:                  # checked before anything is written
+            if np.asarray(snap["xfrc"]).shape != (self.n, NBODY, NXFRC):
+                raise ValueError(f"the snapshot's external wrench rows have shape {np.asarray(snap['xfrc']).shape}, expected "
+                                 f"({self.n}, {NBODY}, {NXFRC})")
+            _abi.push_params(snap.get("push"))
+        elif self.wrench_on:
+            raise ValueError("the snapshot was taken without external wrenches, this handle has them on (clear_external_wrench() first)")
         if "dynamics" in snap:
             if np.asarray(snap["dynamics"]).shape != (self.n, NDYN):
                 raise ValueError(f"the snapshot's dynamics rows have shape {np.asarray(snap['dynamics']).shape}, expected ({self.n}, {NDYN})")
@@ -302,6 +312,9 @@ class BatchedSim:
             self.set_dynamics(snap["dynamics"])
         elif self.dynamics_on:
             raise ValueError("the snapshot was taken with the shared model, this handle has per-env dynamics on (clear_dynamics() first)")
+        if "xfrc" in snap:
+            self.set_external_wrench(np.asarray(snap["xfrc"], np.float32))
+            self.set_push_schedule(snap.get("push"))
         self.set_state(snap["qpos"], snap["qvel"], snap["act"], snap["ctrl"], snap["nstep"])
         self.set_reset_streams(snap["episode"], snap["seed"])
 
@@ -346,6 +359,70 @@ class BatchedSim:
 
     def _dynamics_mode(self, on: bool):
         self.dynamics_on = on
+        self.baked = bool(self._lib.qg_uses_baked_model(self._h))
+
+    # -- external wrenches and pushes (qg_set_xfrc / qg_set_push, include/quadgym.h) -------------------------------------------------
+    wrench_on = False
+    _push = None
+
+    def set_external_wrench(self, rows, mask=None, stream=None):
+        """MuJoCo's ``data.xfrc_applied`` per env: ``rows [n, 13, 6]`` f32 (world-frame force xyz, torque xyz at each body's centre of
+        mass; bodies as in ``include/quadgym.h``).  NumPy input (optionally for the envs where ``mask`` is true) is checked and written
+        before the call returns; a torch tensor on the handle's device is copied on ``stream`` (the current stream by default) with
+        no check and no wait, as the other ``*_device`` calls.  Switches wrench mode on; the rows persist across resets."""
+        if hasattr(rows, "data_ptr"):
+            import torch
+            if mask is not None:
+                raise ValueError("mask: only with host (NumPy) rows")
+            self._check_tensor(rows, (self.n, NBODY, NXFRC), torch.float32)
+            check(self._lib.qg_set_xfrc_device(self._h, rows.data_ptr(), self._stream_ptr(stream)), "qg_set_xfrc_device")
+        else:
+            r = np.ascontiguousarray(rows, dtype=np.float32)
+            if r.shape != (self.n, NBODY, NXFRC):
+                raise ValueError(f"expected shape ({self.n}, {NBODY}, {NXFRC}), got {r.shape}")
+            mp = None
+            if mask is not None:
+                mask = np.ascontiguousarray(mask, dtype=np.uint8)
+                if mask.shape != (self.n,):
+                    raise ValueError(f"mask: expected shape ({self.n},), got {mask.shape}")
+                mp = mask.ctypes.data
+            check(self._lib.qg_set_xfrc(self._h, mp, r.ctypes.data), "qg_set_xfrc")
+        self._wrench_mode(True)
+
+    def set_external_wrench_of(self, rows, indices=None):
+        """``rows [len(indices), 13, 6]`` (or ``[n, 13, 6]`` for every env) for the envs ``indices``; the others keep theirs."""
+        if indices is None:
+            return self.set_external_wrench(rows)
+        idx = np.asarray(indices, np.int64).reshape(-1)
+        full = np.zeros((self.n, NBODY, NXFRC), np.float32)
+        full[idx] = np.asarray(rows, np.float32).reshape(len(idx), NBODY, NXFRC)
+        mask = np.zeros(self.n, np.uint8)
+        mask[idx] = 1
+        self.set_external_wrench(full, mask=mask)
+
+    def get_external_wrench(self):
+        """``[n, 13, 6]`` f32: the rows as set (the push schedule's forces are not in them; zeros while the mode is off)."""
+        out = np.empty((self.n, NBODY, NXFRC), np.float32)
+        check(self._lib.qg_get_xfrc(self._h, out.ctypes.data), "qg_get_xfrc")
+        return out
+
+    def set_push_schedule(self, spec: dict | None):
+        """Random horizontal pushes on the FRAME: ``{"interval": env-steps, "duration": env-steps, "probability": p, "force": (lo, hi)}``
+        (include/quadgym.h); None turns the schedule off.  Switches wrench mode on."""
+        pp = _abi.push_params(spec)
+        check(self._lib.qg_set_push(self._h, C.byref(pp) if pp is not None else None), "qg_set_push")
+        self._push = dict(spec) if spec is not None else None
+        if spec is not None:
+            self._wrench_mode(True)
+
+    def clear_external_wrench(self):
+        """Zero rows, no schedule, wrench mode off: the kernel the handle ran before runs again."""
+        check(self._lib.qg_clear_xfrc(self._h), "qg_clear_xfrc")
+        self._push = None
+        self._wrench_mode(False)
+
+    def _wrench_mode(self, on: bool):
+        self.wrench_on = on
         self.baked = bool(self._lib.qg_uses_baked_model(self._h))
 
     def set_state(self, qpos=None, qvel=None, act=None, ctrl=None, nstep=None):

@@ -1,0 +1,153 @@
+"""The checker that tests/test_external_wrench_gpu.py builds its expected results with, pinned without a GPU.
+
+``generalized_force`` turns world-frame body wrenches (a force at each body's centre of mass, a torque) into the generalized force
+tau = sum_b J_com,b^T F_b + J_w,b^T T_b in MuJoCo's coordinates -- free joint: linear in the world frame, angular in the FRAME's axes;
+then the twelve hinges -- from what the oracle exports: kinematics() (xpos, xmat, xcom; a joint's anchor is its child body's origin)
+and jnt_axis (child-body axes).  With F_b = m_b dg it must be what a change of gravity does to the oracle's own inverse dynamics; its
+force and torque columns must match finite differences of kinematics().  Also: the header, the binding and qg_push_params agree."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from quadruped_gym_amd import _abi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+NV, NBODY = 18, 13
+
+
+def _leg_bodies(j):
+    """Bodies hinge j moves: its child body j + 1 and the links below it on the same leg."""
+    leg = j // 3
+    return range(j + 1, 3 * leg + 4)
+
+
+def generalized_force(oracle, model, qpos, F, T):
+    """tau [18] of world-frame forces F [13, 3] (at each body's centre of mass) and torques T [13, 3]."""
+    xpos, xmat, xcom = oracle.kinematics(model, qpos)
+    F, T = np.asarray(F, np.float64), np.asarray(T, np.float64)
+    tau = np.zeros(NV)
+    p0, R0 = xpos[0], xmat[0]
+    for b in range(NBODY):
+        tau[0:3] += F[b]
+        tau[3:6] += R0.T @ (T[b] + np.cross(xcom[b] - p0, F[b]))
+    for j in range(12):
+        axis = xmat[j + 1] @ np.array(model.jnt_axis[j][:])
+        anchor = xpos[j + 1]
+        for b in _leg_bodies(j):
+            tau[6 + j] += axis @ (T[b] + np.cross(xcom[b] - anchor, F[b]))
+    return tau
+
+
+def _quat_mul(a, b):
+    w1, x1, y1, z1 = a
+    w2, x2, y2, z2 = b
+    return np.array([w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2,
+                     w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
+
+
+def perturb(qpos, d, eps):
+    """qpos moved by eps along velocity coordinate d (free linear: world; free angular: FRAME axes, q <- q exp(eps e / 2))."""
+    q = np.array(qpos, np.float64)
+    if d < 3:
+        q[d] += eps
+    elif d < 6:
+        e = np.zeros(3)
+        e[d - 3] = np.sin(0.5 * eps)
+        q[3:7] = _quat_mul(q[3:7], np.concatenate([[np.cos(0.5 * eps)], e]))
+    else:
+        q[7 + d - 6] += eps
+    return q
+
+
+def gravity_model(oracle, base, dg):
+    m = oracle.default_model()
+    C.memmove(C.byref(m), C.byref(base), C.sizeof(m))
+    for c in range(3):
+        m.gravity[c] = base.gravity[c] + dg[c]
+    return m
+
+
+@pytest.fixture(scope="module")
+def seeded(oracle):
+    from make_golden import sample_states
+    q, v, _, _ = sample_states(oracle.default_model(), oracle.default_task(), 12, seed=23)
+    return q, v
+
+
+def test_body_force_equals_a_gravity_change(oracle, seeded):
+    model = oracle.default_model()
+    masses = np.array(model.body_mass[:])
+    rng = np.random.default_rng(5)
+    for q, v in zip(*seeded):
+        dg = rng.uniform(-3, 3, 3)
+        tau = generalized_force(oracle, model, q, masses[:, None] * dg[None, :], np.zeros((NBODY, 3)))
+        ref = oracle.rne(model, q, v, np.zeros(NV)) - oracle.rne(gravity_model(oracle, model, dg), q, v, np.zeros(NV))
+        np.testing.assert_allclose(tau, ref, rtol=1e-9, atol=1e-12)
+
+
+def test_force_and_torque_columns_match_finite_differences(oracle, seeded):
+    model = oracle.default_model()
+    rng = np.random.default_rng(6)
+    eps = 1e-6
+    for q in seeded[0][:6]:
+        Jw = np.zeros((NBODY, 3, NV))
+        Jc = np.zeros((NBODY, 3, NV))
+        for d in range(NV):
+            qp, qm = perturb(q, d, eps), perturb(q, d, -eps)
+            _, Rp, cp = oracle.kinematics(model, qp)
+            _, Rm, cm = oracle.kinematics(model, qm)
+            for b in range(NBODY):
+                dR = Rp[b] @ Rm[b].T                      # rotation by 2 eps omega (world)
+                Jw[b, :, d] = 0.5 * np.array([dR[2, 1] - dR[1, 2], dR[0, 2] - dR[2, 0], dR[1, 0] - dR[0, 1]]) / (2 * eps)
+                Jc[b, :, d] = (cp[b] - cm[b]) / (2 * eps)
+        for b in range(NBODY):
+            f, t = rng.normal(size=3), rng.normal(size=3)
+            F, T = np.zeros((NBODY, 3)), np.zeros((NBODY, 3))
+            F[b] = f
+            np.testing.assert_allclose(generalized_force(oracle, model, q, F, T), Jc[b].T @ f, atol=1e-7)
+            F[b] = 0
+            T[b] = t
+            np.testing.assert_allclose(generalized_force(oracle, model, q, F, T), Jw[b].T @ t, atol=1e-7)
+
+
+def test_header_binding_and_push_params_agree(tmp_path):
+    text = open(os.path.join(ROOT, "include", "quadgym.h")).read()
+    assert int(re.search(r"#define QG_NXFRC (\d+)", text).group(1)) == _abi.NXFRC == len(_abi.XFRC_COLUMNS)
+    for i, name in enumerate(_abi.XFRC_COLUMNS):
+        assert int(re.search(r"#define QG_XFRC_%s (\d+)" % name.upper(), text).group(1)) == i
+    new = {"qg_set_xfrc", "qg_set_xfrc_device", "qg_get_xfrc", "qg_set_push", "qg_clear_xfrc"}
+    assert new <= set(_abi.EXPORTS)
+    assert new <= set(re.findall(r"\b(qg_[a-z_]+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S)))
+    cc = shutil.which("gcc") or shutil.which("cc")
+    if cc is None:
+        pytest.fail("no C compiler to compile the header with")
+    fields = [f for f, _ in _abi.QgPushParams._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "quadgym.h"\nint main(void) {\n'
+                   '    printf("%zu", sizeof(qg_push_params));\n'
+                   + "".join(f'    printf(" %zu", offsetof(qg_push_params, {f}));\n' for f in fields)
+                   + '    printf(" %d\\n", QG_NBODY * QG_NXFRC);\n    return 0;\n}\n')
+    exe = tmp_path / "layout"
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    out = list(map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()))
+    assert out[0] == C.sizeof(_abi.QgPushParams)
+    assert out[1:-1] == [getattr(_abi.QgPushParams, f).offset for f in fields]
+    assert out[-1] == _abi.NBODY * _abi.NXFRC
+
+
+def test_push_schedule_conversion():
+    steps = _abi.push_schedule_steps({"interval_s": 1.0, "duration_s": 0.011, "probability": 0.5, "force": (1, 2)}, 0.008)
+    assert steps == {"interval": 125, "duration": 1, "probability": 0.5, "force": (1.0, 2.0)}
+    assert _abi.push_schedule_steps({"interval_s": 0.03, "duration_s": 0.0, "probability": 1, "force": (0, 0)}, 0.008)["interval"] == 4
+    with pytest.raises(ValueError):
+        _abi.push_schedule_steps({"interval": 3}, 0.008)
+    p = _abi.push_params({"interval": 7, "duration": 2, "probability": 0.25, "force": (3.0, 4.5)})
+    assert (p.interval, p.duration, p.probability, p.force_min, p.force_max) == (7, 2, 0.25, 3.0, 4.5)
+    assert _abi.push_params(None) is None
