@@ -685,6 +685,15 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
     float *srow = tile + el * 35;
     float zaxis_z = 1.f;
     const int fs = Tk.frame_skip;
+    // frame_skip >= 1: the host refuses anything else (build_tables, qg_tables.h).  Saying so takes the guard off the substep loop.
+    // Behind that guard the compiler sank everything only the loop reads (LinkRegs K, the sample-point pairs: ~140 instructions that
+    // depend on the lane number alone) into the loop's preheader, a block of its own behind the one that waits for the state.  In one
+    // block with the rest of the prologue the scheduler forms most of them in front of the FIRST s_waitcnt lgkmcnt(0), i.e. while the
+    // kernel arguments are still on their way, and the rest while the state loads are in flight (10.07 -> 9.67 us per launch at 4096
+    // envs, outputs bit for bit: tests/test_rollout_bits_gpu.py).  Only where it measured: the table-driven forms, which live at
+    // 256 VGPRs + AGPRs, pay for the longer live ranges with more AGPR copies (11.50 -> 12.18 us) and keep the guard, as do the
+    // instantiations no benchmark configuration runs.
+    if constexpr (BAKED && !PO && HELP == WALK) __builtin_assume(fs >= 1);
 #ifdef QG_PHASE_TIMES
     asm volatile("" :: "v"(B.pw.x), "v"(B.qw), "v"(B.vw.x), "v"(B.wb.x), "v"(J.q), "v"(J.qd), "v"(J.act), "v"(J.sn), "v"(J.cs));
 #endif
