@@ -497,6 +497,60 @@ int qg_set_push(qg_sim *sim, const qg_push_params *push);
 /* Zero rows, schedule off, wrench mode off (the baked kernels run again unless per-env dynamics are on). */
 int qg_clear_xfrc(qg_sim *sim);
 
+/* ---- fused MLP policy: actor, critic and the Gaussian log-probability in one launch -------------------------------------------------
+ * A qg_policy evaluates, for n rows of observations that are already on the device (the rows a step wrote, read in place), a tanh
+ * MLP policy of the kind SB3's MlpPolicy builds: action mean, optionally a sampled action and its log-probability under a diagonal
+ * Gaussian with a state-independent log_std, optionally the value of a second (critic) tower.  One kernel launch per call, exact
+ * f32 arithmetic (the f32-input matrix instruction: every output is a k-ordered fmaf chain), no intermediate result in global
+ * memory.  The handle is independent of qg_sim: one policy can serve several simulators or both halves of a pipelined rollout.
+ *
+ * Network: obs_dim -> hidden[0] -> .. -> hidden[n_hidden - 1] -> act_dim, tanh after every hidden layer (the only activation), the
+ * output layer linear (out_tanh = 0, SB3's action_net) or tanh (out_tanh = 1).  has_value = 1 adds a critic tower with the same hidden
+ * sizes and one linear output (SB3's default, non-shared net_arch).
+ *
+ * Canonical flat parameter vector (f32; qg_policy_param_count floats): the actor's layers in order, each W[out][in] row-major then
+ * b[out]; then log_std[act_dim]; then, with has_value, the critic's layers in the same way (its last layer is W[1][h], b[1]).
+ *
+ * Forward pass, per row i (it depends on row i of obs and eps and on the parameters only -- not on n, on the row's position or on
+ * the other rows: results are bit-identical however a batch is cut):
+ *   mean     = net(obs[i * obs_stride .. + obs_dim))
+ *   actions  = mean                              (eps == NULL: predict(deterministic=True))
+ *            = mean + exp(log_std) * eps[i]      (eps: caller-supplied standard-normal draws [n][act_dim]; NOT clipped)
+ *   log_prob = sum_a(-eps_a^2 / 2 - log_std_a - log(2 pi) / 2)    (eps == NULL: eps = 0, the log-density at the mean)
+ *   value    = critic(obs[i])
+ * obs_stride is counted in floats and >= obs_dim: the first 33 columns of a packed [n][35] row, or a row of an observation stack, are
+ * read where the step left them.  Outputs for non-finite observations or parameters are unspecified (the device code is compiled
+ * with finite-math assumptions).
+ *
+ * Ordering: qg_policy_forward_device and qg_policy_set_params_device follow the contract of the other *_device entry points (they
+ * enqueue on the caller's stream, return at once and may be captured into a hipGraph).  qg_policy_create, qg_policy_destroy,
+ * qg_policy_set_params and qg_policy_get_params wait for the device and must not be called while a stream is being captured. */
+typedef struct qg_policy qg_policy;
+typedef struct qg_policy_desc {
+    int32_t struct_size;       /* sizeof(qg_policy_desc): checked */
+    int32_t obs_dim;           /* 1 .. 512 */
+    int32_t act_dim;           /* 1 .. 16 */
+    int32_t n_hidden;          /* 1 .. 3 */
+    int32_t hidden[3];         /* the first n_hidden: each a multiple of 16, 16 .. 256 */
+    int32_t out_tanh;          /* 0 or 1 */
+    int32_t has_value;         /* 0 or 1 */
+} qg_policy_desc;
+/* Validation (QG_ERR_ARG) comes before the device check (QG_ERR_DEVICE: there is no CPU backend). */
+int qg_policy_create(int32_t device_id, const qg_policy_desc *desc, qg_policy **out);
+int qg_policy_destroy(qg_policy *policy);
+/* Length of the canonical flat vector, or QG_ERR_ARG for an invalid description.  Host only. */
+int qg_policy_param_count(const qg_policy_desc *desc);
+/* Parameters from / to a host array in the canonical order (a new handle holds zeros).  The round trip is exact. */
+int qg_policy_set_params(qg_policy *policy, const float *host_params);
+int qg_policy_get_params(qg_policy *policy, float *host_params);
+/* The same from a device array, enqueued on `stream` (a copy and one small repacking launch): a forward pass enqueued later on that
+ * stream uses the new parameters.  The training loop's path after each update. */
+int qg_policy_set_params_device(qg_policy *policy, const float *d_params, void *stream);
+/* One launch.  Device pointers: obs [n] rows of obs_stride floats; eps nullable [n][act_dim]; actions [n][act_dim]; log_prob nullable
+ * [n]; value nullable [n] (QG_ERR_ARG when given and has_value == 0; NULL: the critic tower is not evaluated). */
+int qg_policy_forward_device(qg_policy *policy, int32_t n, const float *obs, int32_t obs_stride, const float *eps, float *actions,
+                             float *log_prob, float *value, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

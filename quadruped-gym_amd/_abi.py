@@ -139,6 +139,23 @@ class QgWalkParams(C.Structure):
 NWALKREWARD = 11
 
 
+class QgPolicyDesc(C.Structure):
+    """``qg_policy_desc``: the shape of a fused MLP policy (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("n_hidden", C.c_int32),
+                ("hidden", C.c_int32 * 3), ("out_tanh", C.c_int32), ("has_value", C.c_int32)]
+
+    @classmethod
+    def make(cls, obs_dim, hidden, act_dim, out_tanh=False, value=True):
+        hidden = [int(h) for h in hidden]
+        d = cls()
+        d.struct_size = C.sizeof(cls)
+        d.obs_dim, d.act_dim, d.n_hidden = int(obs_dim), int(act_dim), len(hidden)
+        for i, h in enumerate(hidden[:3]):
+            d.hidden[i] = h
+        d.out_tanh, d.has_value = int(bool(out_tanh)), int(bool(value))
+        return d
+
+
 def package_dir() -> str:
     return os.path.dirname(os.path.abspath(__file__))
 
@@ -252,6 +269,13 @@ def load_library():
     lib.qg_get_xfrc.argtypes = [vp, vp]
     lib.qg_set_push.argtypes = [vp, C.POINTER(QgPushParams)]
     lib.qg_clear_xfrc.argtypes = [vp]
+    lib.qg_policy_create.argtypes = [C.c_int32, C.POINTER(QgPolicyDesc), C.POINTER(vp)]
+    lib.qg_policy_destroy.argtypes = [vp]
+    lib.qg_policy_param_count.argtypes = [C.POINTER(QgPolicyDesc)]
+    lib.qg_policy_set_params.argtypes = [vp, vp]
+    lib.qg_policy_get_params.argtypes = [vp, vp]
+    lib.qg_policy_set_params_device.argtypes = [vp, vp, vp]
+    lib.qg_policy_forward_device.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("qg_version", "qg_build_id", "qg_last_error", "qg_time_limit_substeps", "qg_walk_state_bytes", "qg_po_state_bytes",
@@ -277,6 +301,8 @@ EXPORTS = (
     "qg_resident_ensure", "qg_resident_status",
     "qg_set_dynamics_range", "qg_set_dynamics", "qg_get_dynamics", "qg_clear_dynamics",
     "qg_set_xfrc", "qg_set_xfrc_device", "qg_get_xfrc", "qg_set_push", "qg_clear_xfrc",
+    "qg_policy_create", "qg_policy_destroy", "qg_policy_param_count", "qg_policy_set_params", "qg_policy_get_params",
+    "qg_policy_set_params_device", "qg_policy_forward_device",
 )
 
 

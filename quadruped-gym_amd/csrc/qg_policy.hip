@@ -1,0 +1,235 @@
+// qg_policy.hip -- the fused MLP policy forward pass (include/quadgym.h: qg_policy_*): actor tower, optional critic tower and the
+// diagonal-Gaussian epilogue in ONE launch, exact f32 on the f32-input matrix instruction (v_mfma_f32_16x16x4_f32).
+//
+// Layout.  A workgroup owns a tile of 16 envs and one tower (blockIdx.y).  Every layer computes H^T = W . X^T: the 16
+// envs sit on the matrix instruction's column (lane & 15), output features on its rows, so lane (g = lane >> 4, e = lane & 15) holds
+// features 16m + 4g + {0..3} of env e in the four accumulator registers of output block m.  Those four registers are, unchanged, the
+// B operands of the next layer's k-steps 4m .. 4m + 3 when k-step s of a 16-feature block takes feature 4g + s from lane group g:
+// the A operand of that k-step is then W[row][16q + 4g + s], four consecutive floats of a row of W per lane and block of 16 inputs.
+// Activations pass from layer to layer through LDS in that very register image ([16-feature block][lane] float4: one ds_write_b128 per
+// accumulator, one conflict-free ds_read_b128 per four k-steps), so the output blocks of a layer can be shared out over the waves
+// of the workgroup; nothing between the observation row and the outputs touches global memory.
+//
+// Weights are read from the packed image qg_policy_pack_kernel writes ([layer][output block][block of 16 inputs][lane] float4, zero
+// padded: a wave's load is 1 KiB contiguous), two chunks of 16 float4 per lane in flight ahead of the matrix instructions.
+//
+// Numerics: every output is a k-ordered fmaf chain that starts from the bias, in a fixed order that depends on nothing but the
+// layer sizes -- a row's results do not depend on n, on its place in the tile or on the other rows.
+
+#define QGP_MAX_LAYERS 4          // n_hidden <= 3 hidden layers + the output layer
+#define QGP_TILE 16               // envs per workgroup
+
+struct KPolLayer {
+    int32_t nq;                   // blocks of 16 input features (the input width, zero padded)
+    int32_t nb;                   // blocks of 16 output features
+    int32_t in_dim, out_dim;      // the real sizes (pack kernel)
+    int32_t w_off, b_off;         // offsets (floats) into the packed image: W' [nb][nq][64][4], b' [nb][16]
+    int32_t src_w, src_b;         // offsets (floats) into the canonical flat vector: W [out][in], b [out]
+};
+
+struct KPolicy {
+    int32_t obs_dim, act_dim, n_layers, out_tanh, n_towers;
+    int32_t std_off;              // packed: std[16] = exp(log_std), then log_std[16]
+    int32_t src_log_std;          // canonical: log_std[act_dim]
+    int32_t packed_floats;
+    int32_t lds0_floats, lds1_floats;   // the two activation buffers (layer l reads buffer l & 1, writes the other)
+    KPolLayer layer[2][QGP_MAX_LAYERS];
+};
+
+typedef float qgp_f32x4 __attribute__((ext_vector_type(4)));
+
+// canonical flat parameters -> the packed image (one thread per packed float; runs on the caller's stream after every update)
+__global__ void qg_policy_pack_kernel(KPolicy P, const float *__restrict__ src, float *__restrict__ packed) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P.packed_floats) return;
+    if (i >= P.std_off) {
+        const int a = (i - P.std_off) & 15;
+        const bool is_std = i - P.std_off < 16;
+        float v = 0.f;
+        if (a < P.act_dim) {
+            const float ls = src[P.src_log_std + a];
+            v = is_std ? (float)exp((double)ls) : ls;      // exp in f64, rounded once: the correctly rounded f32 standard deviation
+        }
+        packed[i] = v;
+        return;
+    }
+    for (int t = 0; t < P.n_towers; t++)
+        for (int l = 0; l < P.n_layers; l++) {
+            const KPolLayer L = P.layer[t][l];
+            const int wn = L.nb * L.nq * 256;
+            if (i >= L.w_off && i < L.w_off + wn) {
+                const int j = i - L.w_off;
+                const int s = j & 3, lane = (j >> 2) & 63, rest = j >> 8;
+                const int q = rest % L.nq, m = rest / L.nq;
+                const int row = 16 * m + (lane & 15), col = 16 * q + 4 * (lane >> 4) + s;
+                packed[i] = (row < L.out_dim && col < L.in_dim) ? src[L.src_w + row * L.in_dim + col] : 0.f;
+                return;
+            }
+            if (i >= L.b_off && i < L.b_off + 16 * L.nb) {
+                const int row = i - L.b_off;
+                packed[i] = row < L.out_dim ? src[L.src_b + row] : 0.f;
+                return;
+            }
+        }
+}
+
+// one chunk of A operands: KQ blocks of 16 inputs for each of the wave's MB output blocks (m = wave + WAVES * i).  Indices past the
+// layer's end are clamped, not branched around (a branch per load would serialise them); the matrix instructions are what is guarded,
+// per block of 16 inputs.
+template <int WAVES, int MB, int KQ>
+__device__ __forceinline__ void qgp_load_chunk(qgp_f32x4 (&w)[MB][KQ], const float *__restrict__ packed, const KPolLayer &L, int q0, int wave,
+                                               int lane) {
+    const qgp_f32x4 *wp = (const qgp_f32x4 *)(packed + L.w_off);
+#pragma unroll
+    for (int i = 0; i < MB; i++) {
+        const int m = min(wave + WAVES * i, L.nb - 1);
+#pragma unroll
+        for (int kq = 0; kq < KQ; kq++) {
+            const int q = min(q0 + kq, L.nq - 1);
+            w[i][kq] = wp[(m * L.nq + q) * 64 + lane];
+        }
+    }
+}
+
+// the matrix instructions of one chunk on the first NB accumulators (s outer, block inner: consecutive instructions are independent;
+// each accumulator still takes its products in ascending k)
+template <int MB, int KQ, int NB>
+__device__ __forceinline__ void qgp_mfma_chunk(qgp_f32x4 (&acc)[MB], const qgp_f32x4 (&w)[MB][KQ], const qgp_f32x4 *xin, int nq, int q0, int lane) {
+#pragma unroll
+    for (int kq = 0; kq < KQ; kq++) {
+        const int q = q0 + kq;
+        if (q < nq) {
+            const qgp_f32x4 b = xin[q * 64 + lane];
+#pragma unroll
+            for (int s = 0; s < 4; s++)
+#pragma unroll
+                for (int i = 0; i < NB; i++) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i][kq][s], b[s], acc[i], 0, 0, 0);
+        }
+    }
+}
+
+// A wave with one output block in this layer (the output layer; the last blocks of a layer that does not fill every wave) runs one
+// accumulator; with more it runs all MB -- accumulators past the wave's last block chew on clamped weights and are never stored.
+template <int MB, int KQ>
+__device__ __forceinline__ void qgp_mfma_blocks(qgp_f32x4 (&acc)[MB], const qgp_f32x4 (&w)[MB][KQ], const qgp_f32x4 *xin, int nq, int nbw, int q0,
+                                                int lane) {
+    if (nbw > 1) qgp_mfma_chunk<MB, KQ, MB>(acc, w, xin, nq, q0, lane);
+    else if (nbw == 1) qgp_mfma_chunk<MB, KQ, 1>(acc, w, xin, nq, q0, lane);
+}
+
+// mean + std * eps with the product rounded before the sum (no contraction into an fma): the two roundings the formula reads with
+__device__ __forceinline__ float qgp_sample(float mean, float std, float eps) {
+#pragma clang fp contract(off)
+    const float prod = std * eps;
+    return mean + prod;
+}
+
+template <int WAVES, int MB>
+__global__ __launch_bounds__(64 * WAVES) void qg_policy_forward_kernel(KPolicy P, const float *__restrict__ packed, int n,
+                                                                       const float *__restrict__ obs, int obs_stride,
+                                                                       const float *__restrict__ eps, float *__restrict__ actions,
+                                                                       float *__restrict__ log_prob, float *__restrict__ value) {
+    constexpr int KQ = 16 / MB;
+    extern __shared__ qgp_f32x4 qgp_lds[];
+    const int tower = blockIdx.y, env0 = blockIdx.x * QGP_TILE;
+    const int lane = threadIdx.x & 63, e = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform, and known to be: what depends on it branches, not masks
+    float *x0 = (float *)qgp_lds;
+    float *x1 = x0 + P.lds0_floats;
+
+    qgp_f32x4 wa[MB][KQ], wb[MB][KQ];
+    qgp_load_chunk<WAVES, MB, KQ>(wa, packed, P.layer[tower][0], 0, wave, lane);
+
+    // the observation tile into buffer 0 in the operand image: feature c of env ee at float ((c >> 2) * 16 + ee) * 4 + (c & 3).  A wave
+    // takes rows wave, wave + WAVES, ..; a lane the columns lane, lane + 64, ..  Every load of a batch (16 per lane) is issued before
+    // the first LDS write, so the tile costs a few global-memory latencies, not one per row; addresses past the row or the batch are
+    // clamped and the value dropped.
+    {
+        constexpr int R = QGP_TILE / WAVES;
+        constexpr int JU = WAVES == 1 ? 1 : 4;
+        const int width = 16 * P.layer[tower][0].nq;
+        for (int c0 = lane; c0 < width + lane; c0 += 64 * JU) {
+            float v[JU][R];
+#pragma unroll
+            for (int ju = 0; ju < JU; ju++)
+#pragma unroll
+                for (int r = 0; r < R; r++) {
+                    const int env = env0 + wave + WAVES * r;
+                    v[ju][r] = obs[(size_t)min(env, n - 1) * obs_stride + min(c0 + 64 * ju, P.obs_dim - 1)];
+                }
+#pragma unroll
+            for (int ju = 0; ju < JU; ju++)
+#pragma unroll
+                for (int r = 0; r < R; r++) {
+                    const int c = c0 + 64 * ju, ee = wave + WAVES * r;
+                    if (c < width) x0[((c >> 2) * 16 + ee) * 4 + (c & 3)] = (c < P.obs_dim && env0 + ee < n) ? v[ju][r] : 0.f;
+                }
+        }
+    }
+
+    for (int l = 0; l < P.n_layers; l++) {
+        const KPolLayer L = P.layer[tower][l];
+        const bool last = l == P.n_layers - 1;
+        const KPolLayer LN = P.layer[tower][last ? l : l + 1];
+        const qgp_f32x4 *xin = (const qgp_f32x4 *)((l & 1) ? x1 : x0);
+        qgp_f32x4 *xout = (qgp_f32x4 *)((l & 1) ? x0 : x1);
+        const int nbw = L.nb > wave ? (L.nb - wave + WAVES - 1) / WAVES : 0;      // output blocks of this wave
+
+        qgp_f32x4 acc[MB];
+#pragma unroll
+        for (int i = 0; i < MB; i++) {
+            const int m = min(wave + WAVES * i, L.nb - 1);
+            acc[i] = *(const qgp_f32x4 *)(packed + L.b_off + 16 * m + 4 * g);
+        }
+        __syncthreads();          // the layer's input is complete (and the buffer it overwrites has been read by every wave)
+
+        for (int q0 = 0; q0 < L.nq; q0 += 2 * KQ) {
+            qgp_load_chunk<WAVES, MB, KQ>(wb, packed, L, q0 + KQ, wave, lane);
+            qgp_mfma_blocks<MB, KQ>(acc, wa, xin, L.nq, nbw, q0, lane);
+            // the chunk after next: this layer's, or the first of the next layer (its latency hides behind the epilogue and the barrier)
+            const bool more = q0 + 2 * KQ < L.nq;
+            qgp_load_chunk<WAVES, MB, KQ>(wa, packed, more ? L : LN, more ? q0 + 2 * KQ : 0, wave, lane);
+            qgp_mfma_blocks<MB, KQ>(acc, wb, xin, L.nq, nbw, q0 + KQ, lane);
+        }
+
+        if (!last) {
+#pragma unroll
+            for (int i = 0; i < MB; i++)
+                if (i < nbw) {
+                    qgp_f32x4 h;
+#pragma unroll
+                    for (int r = 0; r < 4; r++) h[r] = tanhf(acc[i][r]);
+                    xout[(wave + WAVES * i) * 64 + lane] = h;
+                }
+        } else if (wave == 0) {
+            const int env = env0 + e;
+            const bool live = env < n;
+            if (tower == 1) {
+                if (value && g == 0 && live) value[env] = acc[0][0];
+            } else {
+                const float *sd = packed + P.std_off;
+                double lp = 0.0;
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int a = 4 * g + r;
+                    if (a < P.act_dim) {
+                        float mean = acc[0][r];
+                        if (P.out_tanh) mean = tanhf(mean);
+                        float act = mean, ev = 0.f;
+                        if (eps) {
+                            ev = live ? eps[(size_t)env * P.act_dim + a] : 0.f;
+                            act = qgp_sample(mean, sd[a], ev);
+                        }
+                        if (live) actions[(size_t)env * P.act_dim + a] = act;
+                        lp += -0.5 * (double)ev * (double)ev - (double)sd[16 + a] - 0.91893853320467274178;
+                    }
+                }
+                if (log_prob) {   // the sum over the action components runs over the four lane groups (f64: rounded to f32 once)
+                    lp += __shfl_xor(lp, 16);
+                    lp += __shfl_xor(lp, 32);
+                    if (g == 0 && live) log_prob[env] = (float)lp;
+                }
+            }
+        }
+    }
+}

@@ -1,0 +1,205 @@
+"""``FusedMlpPolicy`` -- a tanh MLP policy (actor, optional critic, diagonal-Gaussian log-probability) evaluated in ONE launch of
+hand-written gfx950 code (``qg_policy_*`` of ``include/quadgym.h``, ``csrc/qg_policy.hip``).
+
+It reads the rows a step left on the device in place (a row stride is allowed) and writes what a PPO rollout collects: action,
+log-probability, value.  A closed-loop step is then two launches: the policy and the env step.  PyTorch is plumbing
+only: it owns the tensors and the stream.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from ._abi import QgPolicyDesc, check
+
+
+def _np32(a):
+    """A torch tensor or array-like as a float32 NumPy array (host copy)."""
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    return np.asarray(a, dtype=np.float32)
+
+
+def flatten_layers(actor, log_std, critic=None):
+    """The canonical flat parameter vector of ``include/quadgym.h``: the actor's layers in order, each ``W[out][in]`` row-major then
+    ``b[out]``; ``log_std``; then the critic's layers in the same way."""
+    parts = []
+    for W, b in actor:
+        parts += [_np32(W).ravel(), _np32(b).ravel()]
+    parts.append(_np32(log_std).ravel())
+    for W, b in (critic or []):
+        parts += [_np32(W).ravel(), _np32(b).ravel()]
+    return np.concatenate(parts).astype(np.float32)
+
+
+def _sequential_layers(seq):
+    """``[(W, b), ...]`` of a ``torch.nn.Sequential`` of ``Linear`` / ``Tanh``; the second value says whether it ends in ``Tanh``."""
+    import torch
+    layers, mods = [], list(seq)
+    for i, m in enumerate(mods):
+        if isinstance(m, torch.nn.Linear):
+            if m.bias is None:
+                raise ValueError("Linear layers need a bias")
+            if i + 1 < len(mods) and not isinstance(mods[i + 1], torch.nn.Tanh):
+                raise ValueError("every Linear but the last must be followed by Tanh (the only activation)")
+            layers.append((m.weight, m.bias))
+        elif not isinstance(m, torch.nn.Tanh):
+            raise ValueError(f"unsupported module {type(m).__name__}: Linear and Tanh only")
+        elif i == 0 or not isinstance(mods[i - 1], torch.nn.Linear):
+            raise ValueError("Tanh must follow a Linear")
+    return layers, bool(mods) and isinstance(mods[-1], torch.nn.Tanh)
+
+
+class FusedMlpPolicy:
+    """``obs_dim -> hidden[0] -> .. -> act_dim`` with tanh after every hidden layer; ``out_tanh`` puts a tanh on the action mean too
+    (``False``: SB3's linear ``action_net``); ``value=True`` adds a critic tower with the same hidden sizes and one output.
+
+    Hidden widths are multiples of 16 up to 256, at most three of them; ``obs_dim <= 512``, ``act_dim <= 16``.  A new policy holds
+    zeros; load parameters with ``load_layers`` / ``load_module`` / ``load_sb3_state_dict`` (host) or ``update_from`` (device,
+    stream-ordered).  Outputs for non-finite observations are unspecified."""
+
+    def __init__(self, obs_dim: int, hidden, act_dim: int, out_tanh: bool = False, value: bool = True, device: int = 0):
+        self._lib = _abi.load_library()
+        self.obs_dim, self.act_dim, self.hidden = int(obs_dim), int(act_dim), tuple(int(h) for h in hidden)
+        self.out_tanh, self.has_value, self.device = bool(out_tanh), bool(value), int(device)
+        if len(self.hidden) > 3:
+            raise ValueError("at most three hidden layers")
+        self.desc = QgPolicyDesc.make(self.obs_dim, self.hidden, self.act_dim, self.out_tanh, self.has_value)
+        h = C.c_void_p()
+        check(self._lib.qg_policy_create(self.device, C.byref(self.desc), C.byref(h)), "qg_policy_create")
+        self._h = h
+        self.n_params = int(self._lib.qg_policy_param_count(C.byref(self.desc)))
+
+    # -- lifetime ---------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.qg_policy_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- parameters -------------------------------------------------------------------------
+    def layer_shapes(self):
+        """``(actor, critic)``: the ``(out, in)`` shapes of the weight matrices, in order."""
+        dims = (self.obs_dim,) + self.hidden
+        body = [(dims[i + 1], dims[i]) for i in range(len(self.hidden))]
+        return body + [(self.act_dim, dims[-1])], (body + [(1, dims[-1])] if self.has_value else [])
+
+    def set_params(self, flat):
+        """The canonical flat vector from the host (synchronous)."""
+        flat = np.ascontiguousarray(_np32(flat))
+        if flat.shape != (self.n_params,):
+            raise ValueError(f"expected {self.n_params} parameters, got shape {flat.shape}")
+        check(self._lib.qg_policy_set_params(self._h, flat.ctypes.data), "qg_policy_set_params")
+
+    def params(self):
+        """The canonical flat vector as set (NumPy float32; waits for the device)."""
+        out = np.empty(self.n_params, np.float32)
+        check(self._lib.qg_policy_get_params(self._h, out.ctypes.data), "qg_policy_get_params")
+        return out
+
+    def load_layers(self, actor, log_std=None, critic=None):
+        """``actor=[(W, b), ...]`` with ``W`` of shape ``(out, in)`` (torch's ``Linear.weight``), torch tensors or NumPy arrays;
+        ``log_std`` defaults to zeros; ``critic`` likewise, required exactly when the policy has a value tower."""
+        want_a, want_c = self.layer_shapes()
+        critic = list(critic) if critic is not None else []
+        if bool(critic) != self.has_value:
+            raise ValueError("critic layers are required exactly when the policy was built with value=True")
+        for name, layers, want in (("actor", list(actor), want_a), ("critic", critic, want_c)):
+            if len(layers) != len(want):
+                raise ValueError(f"{name}: expected {len(want)} layers, got {len(layers)}")
+            for i, ((W, b), shape) in enumerate(zip(layers, want)):
+                if tuple(_np32(W).shape) != shape or tuple(_np32(b).shape) != (shape[0],):
+                    raise ValueError(f"{name} layer {i}: expected W {shape} and b ({shape[0]},), got {tuple(_np32(W).shape)}, {tuple(_np32(b).shape)}")
+        if log_std is None:
+            log_std = np.zeros(self.act_dim, np.float32)
+        if _np32(log_std).shape != (self.act_dim,):
+            raise ValueError(f"log_std must have shape ({self.act_dim},)")
+        self.set_params(flatten_layers(actor, log_std, critic))
+
+    def load_module(self, actor_seq, critic_seq=None, log_std=None):
+        """From ``torch.nn.Sequential`` modules of ``Linear`` / ``Tanh``.  Whether the actor ends in ``Tanh`` must agree with
+        ``out_tanh``; the critic ends in its ``Linear``."""
+        actor, a_tanh = _sequential_layers(actor_seq)
+        if a_tanh != self.out_tanh:
+            raise ValueError(f"the actor module {'ends' if a_tanh else 'does not end'} in Tanh but out_tanh is {self.out_tanh}")
+        critic = None
+        if critic_seq is not None:
+            critic, c_tanh = _sequential_layers(critic_seq)
+            if c_tanh:
+                raise ValueError("the critic's output layer is linear")
+        self.load_layers(actor, log_std, critic)
+
+    def load_sb3_state_dict(self, sd):
+        """From a plain dict with the key names of Stable-Baselines3's ``ActorCriticPolicy.state_dict()`` as of its 2.x releases, for
+        the default non-shared ``net_arch``: ``mlp_extractor.policy_net.{0,2,4}.{weight,bias}``, ``mlp_extractor.value_net.*``,
+        ``action_net.{weight,bias}``, ``value_net.{weight,bias}``, ``log_std``.  The key names are taken from SB3's source; this
+        has NOT been run against a real checkpoint (the package is not a dependency).  SB3's ``action_net`` is linear: ``out_tanh``
+        must be False."""
+        if self.out_tanh:
+            raise ValueError("SB3's action_net is linear: build the policy with out_tanh=False")
+
+        def tower(prefix, head):
+            return [(sd[f"{prefix}.{2 * i}.weight"], sd[f"{prefix}.{2 * i}.bias"]) for i in range(len(self.hidden))] + \
+                [(sd[f"{head}.weight"], sd[f"{head}.bias"])]
+        actor = tower("mlp_extractor.policy_net", "action_net")
+        critic = tower("mlp_extractor.value_net", "value_net") if self.has_value else None
+        self.load_layers(actor, sd["log_std"], critic)
+
+    # -- device path ------------------------------------------------------------------------
+    def _stream_ptr(self, stream):
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        return C.c_void_p(stream.cuda_stream)
+
+    def _check_tensor(self, t, shape, dtype):
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"tensor must live on cuda:{self.device}")
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"expected contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+    def _check_obs(self, obs):
+        """``[n, obs_dim]`` float32 whose rows are contiguous; the row stride is free (a column slice of a wider buffer).  Returns
+        ``(n, row stride in floats)``."""
+        import torch
+        if not obs.is_cuda or obs.device.index != self.device:
+            raise ValueError(f"tensor must live on cuda:{self.device}")
+        if obs.dim() != 2 or obs.shape[1] != self.obs_dim or obs.dtype != torch.float32 or obs.shape[0] < 1:
+            raise ValueError(f"expected a float32 tensor of shape (n, {self.obs_dim}), got {obs.dtype} {tuple(obs.shape)}")
+        if obs.stride(1) != 1 or (obs.shape[0] > 1 and obs.stride(0) < self.obs_dim):
+            raise ValueError(f"observation rows must be contiguous, at a row stride >= {self.obs_dim}; got strides {tuple(obs.stride())}")
+        return int(obs.shape[0]), int(obs.stride(0)) if obs.shape[0] > 1 else max(int(obs.stride(0)), self.obs_dim)
+
+    def update_from(self, params_tensor, stream=None):
+        """The canonical flat vector from a device tensor, enqueued on ``stream`` (default: torch's current stream): forward passes
+        enqueued later on that stream use it.  No host synchronisation."""
+        import torch
+        self._check_tensor(params_tensor, (self.n_params,), torch.float32)
+        check(self._lib.qg_policy_set_params_device(self._h, params_tensor.data_ptr(), self._stream_ptr(stream)),
+              "qg_policy_set_params_device")
+
+    def forward(self, obs, actions, eps=None, log_prob=None, value=None, stream=None):
+        """One launch: ``actions[n, act_dim]`` (the mean, or ``mean + exp(log_std) * eps`` with standard-normal ``eps[n, act_dim]`` from
+        the caller, not clipped), optionally ``log_prob[n]`` and ``value[n]``."""
+        import torch
+        n, stride = self._check_obs(obs)
+        self._check_tensor(actions, (n, self.act_dim), torch.float32)
+        if eps is not None:
+            self._check_tensor(eps, (n, self.act_dim), torch.float32)
+        if log_prob is not None:
+            self._check_tensor(log_prob, (n,), torch.float32)
+        if value is not None:
+            if not self.has_value:
+                raise ValueError("the policy was built with value=False")
+            self._check_tensor(value, (n,), torch.float32)
+        check(self._lib.qg_policy_forward_device(self._h, n, obs.data_ptr(), stride, eps.data_ptr() if eps is not None else None,
+                                                 actions.data_ptr(), log_prob.data_ptr() if log_prob is not None else None,
+                                                 value.data_ptr() if value is not None else None, self._stream_ptr(stream)),
+              "qg_policy_forward_device")
