@@ -471,18 +471,9 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
     static_assert(QGK_LINK_ENVS * QGK_LINK_WAVES == QG_PO_ENVS && QGK_WAVE * QGK_LINK_WAVES == QG_PO_THREADS, "workgroup layout of qg_po_dev.h");
     __shared__ float tile_all[QGK_LINK_WAVES][QGK_LINK_ENVS * 35];
     __shared__ KModel smodel;
-    if constexpr (!BAKED) {                         // any other robot: the model tables staged in LDS, read with per-lane (leg) addresses
-        const float *src = reinterpret_cast<const float *>(Mp);
-        float *dst = reinterpret_cast<float *>(&smodel);
-        for (int i = threadIdx.x; i < (int)(sizeof(KModel) / sizeof(float)); i += QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1)) dst[i] = src[i];
-        __syncthreads();
-    }
-    const KModel &C = BAKED ? QG_BAKED_MODEL : smodel;
-    // the task constants into scalar registers up front: read where they are used, every read in the epilogue was its own
-    // scalar-load round trip in front of a wave that has nothing else to do
-    struct { int32_t frame_skip, limit_substeps, use_fall, use_flip, obs_mode, auto_reset; uint32_t reset_flags; float fall_height, w_forward, w_ctrl, alive_bonus;
-             const float *default_ctrl; } Tk = {T->frame_skip, T->limit_substeps, T->use_fall, T->use_flip, T->obs_mode, T->auto_reset, T->reset_flags,
-                                               T->fall_height, T->w_forward, T->w_ctrl, T->alive_bonus, T->default_ctrl};
+    // any other robot (!BAKED): the model tables staged in LDS, read with per-lane (leg) addresses
+    QG_STAGE_MODEL(C, BAKED, smodel, Mp, QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1));
+    QG_TASK_REGS(Tk, T);
     QG_MARK(0);
     const int lane = threadIdx.x & (QGK_WAVE - 1);
     const int wave = (threadIdx.x >> 6) & (QGK_LINK_WAVES - 1);      // HELP: waves 4 .. 7 shadow waves 0 .. 3
@@ -610,10 +601,7 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
 
     BaseState B;
     const unsigned n4 = 4u * (unsigned)n, e4 = 4u * (unsigned)env;        // byte strides of the [field][n] state arrays
-    B.pw = v3(lk_ld(P.st.qpos, e4), lk_ld(P.st.qpos, n4 + e4), lk_ld(P.st.qpos, 2 * n4 + e4));
-    B.qw = lk_ld(P.st.qpos, 3 * n4 + e4); B.qx = lk_ld(P.st.qpos, 4 * n4 + e4); B.qy = lk_ld(P.st.qpos, 5 * n4 + e4); B.qz = lk_ld(P.st.qpos, 6 * n4 + e4);
-    B.vw = v3(lk_ld(P.st.qvel, e4), lk_ld(P.st.qvel, n4 + e4), lk_ld(P.st.qvel, 2 * n4 + e4));
-    B.wb = v3(lk_ld(P.st.qvel, 3 * n4 + e4), lk_ld(P.st.qvel, 4 * n4 + e4), lk_ld(P.st.qvel, 5 * n4 + e4));
+    QG_BASE_LOAD(B, P.st, QG_AT_LK, n4, e4);
     quat_unit(B);   // unit quaternion once per launch (qg_set_state may hand in any length); the substeps keep it normalised
     const int nstep0 = lk_ld(P.st.nstep, e4);
     // this lane's hinge (the spare lane shadows hinge 2 of its leg: same loads, nothing of it is ever stored)
@@ -662,6 +650,7 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
         const float ref = BAKED ? sel3(rk, C.link[0].ref, C.link[1].ref, C.link[2].ref) : Lj.ref;
         J.u = fminf(fmaxf(aclip, clo), chi);
         const unsigned j4 = (unsigned)jch * n4 + e4;                        // hinge jch of this env within a [12][n] block
+        // (not QG_HINGE_LOAD / _STORE: (7 + jch) * n4 + e4 is the same offset, but with it the one-link-per-lane kernels' listings change)
         J.q = lk_ld(P.st.qpos, 7 * n4 + j4);
         J.qd = lk_ld(P.st.qvel, 6 * n4 + j4);
         J.act = lk_ld(P.st.act, j4);
@@ -705,36 +694,15 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
     QG_MARK(2);                                      // physics done
 
     const float ssq = env_sum(r < 3 ? aclip * aclip : 0.f);
-    float c_fwd = Tk.w_forward * B.vw.x;
-    float c_ctl = Tk.w_ctrl * ssq;
-    float c_alive = Tk.alive_bonus;
-    float reward = reward_total(c_fwd, c_ctl, c_alive);
-    bool done = nstep >= Tk.limit_substeps;
-    if (Tk.use_fall) done = done || (B.pw.z < Tk.fall_height);
-    {
-        float probe = J.q + J.qd;
-        probe = env_sum(r < 3 ? probe : 0.f) + B.pw.x + B.pw.y + B.pw.z + B.qw + B.vw.x + B.vw.y + B.vw.z + B.wb.x + B.wb.y + B.wb.z;
-        done = done || state_is_bad(probe);
-    }
+    QG_REWARD_TERMS(Tk., B, ssq, nstep);
+    QG_DONE_IF_BAD_STATE(B, env_sum(r < 3 ? J.q + J.qd : 0.f));
     const int od = Tk.obs_mode == 1 ? 21 : 33;
     const int row = P.packed ? od + 2 : od;
-    if (Tk.use_flip) done = done || (zaxis_z < 0.f);              // walking_quad.py:156-160, on the step's sensordata
+    QG_DONE_IF_FLIPPED(Tk., zaxis_z);
     // The state goes out FIRST (two dozen of the launch's ~30 store instructions): it drains while the rest of the epilogue computes.
     const bool lead = live && lead_env;
     const bool rst = done && Tk.auto_reset;
-    if (rst) {
-        B.pw = v3(C.qpos0[0], C.qpos0[1], C.qpos0[2]);
-        B.qw = C.qpos0[3]; B.qx = C.qpos0[4]; B.qy = C.qpos0[5]; B.qz = C.qpos0[6];
-        if (Tk.reset_flags & 1u) {
-            float a = 6.283185307179586f * uniform24(P.seed, P.env_index_base + (uint64_t)env, (uint64_t)P.st.episode[env]);
-            float sn, cs;
-            sincos_f(0.5f * a, sn, cs);
-            B.qw = cs; B.qx = 0.f; B.qy = 0.f; B.qz = sn;
-        }
-        B.vw = v3(0.f, 0.f, 0.f);
-        B.wb = v3(0.f, 0.f, 0.f);
-        nstep = 0;
-    }
+    if (rst) QG_BASE_RESET(B, nstep, C.qpos0, Tk., P, env, P.st.episode[env]);
     if constexpr (HELP) {
         if constexpr (PO) {
             const int le = 4 * wave + el;
@@ -760,11 +728,7 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
         }
     }
     if (lead) {
-        lk_st(P.st.qpos, e4, B.pw.x); lk_st(P.st.qpos, n4 + e4, B.pw.y); lk_st(P.st.qpos, 2 * n4 + e4, B.pw.z);
-        lk_st(P.st.qpos, 3 * n4 + e4, B.qw); lk_st(P.st.qpos, 4 * n4 + e4, B.qx); lk_st(P.st.qpos, 5 * n4 + e4, B.qy); lk_st(P.st.qpos, 6 * n4 + e4, B.qz);
-        lk_st(P.st.qvel, e4, B.vw.x); lk_st(P.st.qvel, n4 + e4, B.vw.y); lk_st(P.st.qvel, 2 * n4 + e4, B.vw.z);
-        lk_st(P.st.qvel, 3 * n4 + e4, B.wb.x); lk_st(P.st.qvel, 4 * n4 + e4, B.wb.y); lk_st(P.st.qvel, 5 * n4 + e4, B.wb.z);
-        lk_st(P.st.nstep, e4, nstep);
+        QG_BASE_STORE(B, nstep, P.st, QG_PUT_LK, n4, e4);
         if (rst) P.st.episode[env] += 1;
     }
     if (wch) {                                      // every link lane stores its own hinge
@@ -816,11 +780,7 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
         if (lead) walk_reward_env(WK.P, WK.S, n, env, tile + el * 35, sum, win, done, P.reward, WK.comps, WK.sample, P.seed, P.env_index_base);
         QG_MARK(5);                                  // reward
     }
-    if (lead && P.comps) {
-        P.comps[(size_t)env * 3 + 0] = c_fwd;
-        P.comps[(size_t)env * 3 + 1] = c_ctl;
-        P.comps[(size_t)env * 3 + 2] = c_alive;
-    }
+    QG_COMPS_STORE(lead, P, env);
     QG_MARK(6);
     if constexpr (PO && HELP) {
         // the frame and the rows are the helper wave's; the new episode's command is drawn here (the helper shows the old one)

@@ -10,7 +10,9 @@
 //                 the ring kernel waits on -- so that a policy on the caller's stream stays in the loop (qg_resident_*).
 // Both run the SAME arithmetic per env-step as the per-launch kernel, in the same order (the quaternion is re-normalised and the
 // hinges' sines / cosines are re-evaluated at the head of every env-step, exactly what a fresh launch does with the state it loads),
-// so their results are bit-identical to it (tests/test_resident_gpu.py).
+// so their results are bit-identical to it (tests/test_resident_gpu.py).  The substeps are the per-launch kernels' functions and the
+// shell around them -- state load and store, reward, terminations, auto-reset, tile copy-out -- is the per-launch kernels' TEXT: both
+// expand the statement macros of qg_step_shell.h, so the two cannot drift apart.
 //
 // Safety of the resident form -- no unbounded wait anywhere:
 //   * a wave waits for the door with s_sleep polling against the 100 MHz clock (s_memrealtime); when `idle_ticks` pass without a
@@ -61,16 +63,8 @@ template <bool BAKED, bool DOOR>
 __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES, 1) void qg_step_kernel_link_multi(const KModel *__restrict__ Mp, const KTask *__restrict__ T, KStepArgs P, KResident R) {
     __shared__ __attribute__((aligned(16))) float tile_all[QGK_LINK_WAVES][QGK_LINK_ENVS * 35];
     __shared__ KModel smodel;
-    if constexpr (!BAKED) {
-        const float *src = reinterpret_cast<const float *>(Mp);
-        float *dst = reinterpret_cast<float *>(&smodel);
-        for (int i = threadIdx.x; i < (int)(sizeof(KModel) / sizeof(float)); i += QGK_WAVE * QGK_LINK_WAVES) dst[i] = src[i];
-        __syncthreads();                // before the loop: every wave reaches it exactly once
-    }
-    const KModel &C = BAKED ? QG_BAKED_MODEL : smodel;
-    struct { int32_t frame_skip, limit_substeps, use_fall, use_flip, obs_mode, auto_reset; uint32_t reset_flags; float fall_height, w_forward, w_ctrl, alive_bonus;
-             const float *default_ctrl; } Tk = {T->frame_skip, T->limit_substeps, T->use_fall, T->use_flip, T->obs_mode, T->auto_reset, T->reset_flags,
-                                               T->fall_height, T->w_forward, T->w_ctrl, T->alive_bonus, T->default_ctrl};
+    QG_STAGE_MODEL(C, BAKED, smodel, Mp, QGK_WAVE * QGK_LINK_WAVES);     // (its barrier: before the loop, every wave reaches it exactly once)
+    QG_TASK_REGS(Tk, T);
     const int lane = threadIdx.x & (QGK_WAVE - 1);
     const int wave = threadIdx.x >> 6;
     float *tile = tile_all[wave];
@@ -87,17 +81,14 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES, 1) void qg_step_kernel_l
     // ---- the state: loaded ONCE per launch ------------------------------------------------------------------------------------------
     BaseState B;
     const unsigned n4 = 4u * (unsigned)n, e4 = 4u * (unsigned)env;
-    B.pw = v3(lk_ld(P.st.qpos, e4), lk_ld(P.st.qpos, n4 + e4), lk_ld(P.st.qpos, 2 * n4 + e4));
-    B.qw = lk_ld(P.st.qpos, 3 * n4 + e4); B.qx = lk_ld(P.st.qpos, 4 * n4 + e4); B.qy = lk_ld(P.st.qpos, 5 * n4 + e4); B.qz = lk_ld(P.st.qpos, 6 * n4 + e4);
-    B.vw = v3(lk_ld(P.st.qvel, e4), lk_ld(P.st.qvel, n4 + e4), lk_ld(P.st.qvel, 2 * n4 + e4));
-    B.wb = v3(lk_ld(P.st.qvel, 3 * n4 + e4), lk_ld(P.st.qvel, 4 * n4 + e4), lk_ld(P.st.qvel, 5 * n4 + e4));
+    QG_BASE_LOAD(B, P.st, QG_AT_LK, n4, e4);
     int nstep = lk_ld(P.st.nstep, e4);
     int episode = lk_ld(P.st.episode, e4);
     const int rk = r < 3 ? r : 2;
     const int jch = 3 * k + rk;
     const unsigned j4 = (unsigned)jch * n4 + e4;
     HingeLane J;
-    J.q = lk_ld(P.st.qpos, 7 * n4 + j4);
+    J.q = lk_ld(P.st.qpos, 7 * n4 + j4);          // (as in qg_step_kernel_link: its own text, for the listing's sake)
     J.qd = lk_ld(P.st.qvel, 6 * n4 + j4);
     J.act = lk_ld(P.st.act, j4);
     J.u = 0.f; J.sn = 0.f; J.cs = 1.f;
@@ -205,32 +196,13 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES, 1) void qg_step_kernel_l
         QG_MARK(3);                                                 // physics done
 
         const float ssq = env_sum(r < 3 ? aclip * aclip : 0.f);
-        const float c_fwd = Tk.w_forward * B.vw.x;
-        const float c_ctl = Tk.w_ctrl * ssq;
-        const float c_alive = Tk.alive_bonus;
-        const float reward = reward_total(c_fwd, c_ctl, c_alive);
-        bool done = nstep >= Tk.limit_substeps;
-        if (Tk.use_fall) done = done || (B.pw.z < Tk.fall_height);
-        {
-            float probe = J.q + J.qd;
-            probe = env_sum(r < 3 ? probe : 0.f) + B.pw.x + B.pw.y + B.pw.z + B.qw + B.vw.x + B.vw.y + B.vw.z + B.wb.x + B.wb.y + B.wb.z;
-            done = done || state_is_bad(probe);
-        }
-        if (Tk.use_flip) done = done || (zaxis_z < 0.f);
+        QG_REWARD_TERMS(Tk., B, ssq, nstep);
+        QG_DONE_IF_BAD_STATE(B, env_sum(r < 3 ? J.q + J.qd : 0.f));
+        QG_DONE_IF_FLIPPED(Tk., zaxis_z);
         const bool rst = done && Tk.auto_reset;
         ctrl_reg = aclip;
         if (rst) {                                                  // the auto-reset of the per-launch kernel, on the registers
-            B.pw = v3(C.qpos0[0], C.qpos0[1], C.qpos0[2]);
-            B.qw = C.qpos0[3]; B.qx = C.qpos0[4]; B.qy = C.qpos0[5]; B.qz = C.qpos0[6];
-            if (Tk.reset_flags & 1u) {
-                float a = 6.283185307179586f * uniform24(P.seed, P.env_index_base + (uint64_t)env, (uint64_t)episode);
-                float sn, cs;
-                sincos_f(0.5f * a, sn, cs);
-                B.qw = cs; B.qx = 0.f; B.qy = 0.f; B.qz = sn;
-            }
-            B.vw = v3(0.f, 0.f, 0.f);
-            B.wb = v3(0.f, 0.f, 0.f);
-            nstep = 0;
+            QG_BASE_RESET(B, nstep, C.qpos0, Tk., P, env, episode);
             episode += 1;
             J.q = q0; J.qd = 0.f; J.act = 0.f;
             ctrl_reg = Tk.default_ctrl[jch];
@@ -282,11 +254,7 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES, 1) void qg_step_kernel_l
         }
     }
     if (lead) {
-        lk_st(P.st.qpos, e4, B.pw.x); lk_st(P.st.qpos, n4 + e4, B.pw.y); lk_st(P.st.qpos, 2 * n4 + e4, B.pw.z);
-        lk_st(P.st.qpos, 3 * n4 + e4, B.qw); lk_st(P.st.qpos, 4 * n4 + e4, B.qx); lk_st(P.st.qpos, 5 * n4 + e4, B.qy); lk_st(P.st.qpos, 6 * n4 + e4, B.qz);
-        lk_st(P.st.qvel, e4, B.vw.x); lk_st(P.st.qvel, n4 + e4, B.vw.y); lk_st(P.st.qvel, 2 * n4 + e4, B.vw.z);
-        lk_st(P.st.qvel, 3 * n4 + e4, B.wb.x); lk_st(P.st.qvel, 4 * n4 + e4, B.wb.y); lk_st(P.st.qvel, 5 * n4 + e4, B.wb.z);
-        lk_st(P.st.nstep, e4, nstep);
+        QG_BASE_STORE(B, nstep, P.st, QG_PUT_LK, n4, e4);
         lk_st(P.st.episode, e4, episode);
     }
     if (wch && stepped) {
@@ -387,15 +355,10 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair_multi
     f2 cm, sm;
     cm.x = half ? -1.f : 1.f; cm.y = 0.f;
     sm.x = 0.f; sm.y = half ? -1.f : 1.f;
-    struct { int32_t frame_skip, limit_substeps, use_fall, use_flip, obs_mode, auto_reset; uint32_t reset_flags; float fall_height, w_forward, w_ctrl, alive_bonus;
-             const float *default_ctrl; } Tk = {T->frame_skip, T->limit_substeps, T->use_fall, T->use_flip, T->obs_mode, T->auto_reset, T->reset_flags,
-                                               T->fall_height, T->w_forward, T->w_ctrl, T->alive_bonus, T->default_ctrl};
+    QG_TASK_REGS(Tk, T);
 
     BaseState B;
-    B.pw = v3<float>(P.st.qpos[0 * n + env], P.st.qpos[1 * n + env], P.st.qpos[2 * n + env]);
-    B.qw = P.st.qpos[3 * n + env]; B.qx = P.st.qpos[4 * n + env]; B.qy = P.st.qpos[5 * n + env]; B.qz = P.st.qpos[6 * n + env];
-    B.vw = v3<float>(P.st.qvel[0 * n + env], P.st.qvel[1 * n + env], P.st.qvel[2 * n + env]);
-    B.wb = v3<float>(P.st.qvel[3 * n + env], P.st.qvel[4 * n + env], P.st.qvel[5 * n + env]);
+    QG_BASE_LOAD(B, P.st, QG_AT, n, env);
     int nstep = P.st.nstep[env];
     int episode = P.st.episode[env];
     LegPair L;
@@ -404,7 +367,8 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair_multi
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int j = 3 * (2 * half + c) + i;
-            const float qq = P.st.qpos[(7 + j) * n + env], qv = P.st.qvel[(6 + j) * n + env], aa = P.st.act[j * n + env];
+            float qq, qv, aa;
+            QG_HINGE_LOAD(qq, qv, aa, P.st, QG_AT, n, env, j);
             if (c == 0) { L.q[i].x = qq; L.qd[i].x = qv; L.act[i].x = aa; L.u[i].x = 0.f; }
             else { L.q[i].y = qq; L.qd[i].y = qv; L.act[i].y = aa; L.u[i].y = 0.f; }
         }
@@ -454,18 +418,9 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair_multi
         nstep += fs;
         asm volatile("" : "+v"(env));
 
-        const float c_fwd = Tk.w_forward * B.vw.x;
-        const float c_ctl = Tk.w_ctrl * ssq;
-        const float c_alive = Tk.alive_bonus;
-        const float reward = reward_total(c_fwd, c_ctl, c_alive);
-        bool done = nstep >= Tk.limit_substeps;
-        if (Tk.use_fall) done = done || (B.pw.z < Tk.fall_height);
-        {
-            float probe = hsum(L.q[0]) + hsum(L.q[1]) + hsum(L.q[2]) + hsum(L.qd[0]) + hsum(L.qd[1]) + hsum(L.qd[2]);
-            probe = pair_sum(probe) + B.pw.x + B.pw.y + B.pw.z + B.qw + B.vw.x + B.vw.y + B.vw.z + B.wb.x + B.wb.y + B.wb.z;
-            done = done || state_is_bad(probe);
-        }
-        if (Tk.use_flip) done = done || (zaxis_z < 0.f);
+        QG_REWARD_TERMS(Tk., B, ssq, nstep);
+        QG_DONE_IF_BAD_STATE(B, pair_sum(hsum(L.q[0]) + hsum(L.q[1]) + hsum(L.q[2]) + hsum(L.qd[0]) + hsum(L.qd[1]) + hsum(L.qd[2])));
+        QG_DONE_IF_FLIPPED(Tk., zaxis_z);
         if (half == 0) {
             if (od == 21) { srow[18] = srow[30]; srow[19] = srow[31]; srow[20] = srow[32]; }
             srow[od] = reward; srow[od + 1] = done ? 1.f : 0.f;
@@ -473,32 +428,14 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair_multi
         wave_sync();
         {
             float *dst = R.packed + (size_t)kstep * slot_out + (size_t)env0 * row;
-            if (row == 35) {
-                for (int e = lane; e < total; e += QGK_WAVE) dst[e] = tile[e];
-            } else {
-                const unsigned magic = row == 23 ? 2850u : (65536u + row - 1) / row;
-                for (int e = lane; e < total; e += QGK_WAVE) {
-                    const int er = (int)(((unsigned)e * magic) >> 16), ec = e - er * row;
-                    dst[e] = tile[er * 35 + ec];
-                }
-            }
+            QG_TILE_COPY_OUT(dst, tile, lane, total, row);
         }
         wave_sync();
         const bool rst = done && Tk.auto_reset;
 #pragma unroll
         for (int c6 = 0; c6 < 6; ++c6) ctrl_reg[c6] = aclip[c6];
         if (rst) {
-            B.pw = v3<float>(C.qpos0[0], C.qpos0[1], C.qpos0[2]);
-            B.qw = C.qpos0[3]; B.qx = C.qpos0[4]; B.qy = C.qpos0[5]; B.qz = C.qpos0[6];
-            if (Tk.reset_flags & 1u) {
-                float a = 6.283185307179586f * uniform24(P.seed, P.env_index_base + (uint64_t)env, (uint64_t)episode);
-                float sn, cs;
-                sincos_f(0.5f * a, sn, cs);
-                B.qw = cs; B.qx = 0.f; B.qy = 0.f; B.qz = sn;
-            }
-            B.vw = v3<float>(0.f, 0.f, 0.f);
-            B.wb = v3<float>(0.f, 0.f, 0.f);
-            nstep = 0;
+            QG_BASE_RESET(B, nstep, C.qpos0, Tk., P, env, episode);
             episode += 1;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
@@ -510,11 +447,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair_multi
     }
 
     if (lead) {
-        P.st.qpos[0 * n + env] = B.pw.x; P.st.qpos[1 * n + env] = B.pw.y; P.st.qpos[2 * n + env] = B.pw.z;
-        P.st.qpos[3 * n + env] = B.qw; P.st.qpos[4 * n + env] = B.qx; P.st.qpos[5 * n + env] = B.qy; P.st.qpos[6 * n + env] = B.qz;
-        P.st.qvel[0 * n + env] = B.vw.x; P.st.qvel[1 * n + env] = B.vw.y; P.st.qvel[2 * n + env] = B.vw.z;
-        P.st.qvel[3 * n + env] = B.wb.x; P.st.qvel[4 * n + env] = B.wb.y; P.st.qvel[5 * n + env] = B.wb.z;
-        P.st.nstep[env] = nstep;
+        QG_BASE_STORE(B, nstep, P.st, QG_PUT, n, env);
         P.st.episode[env] = episode;
     }
     if (live && R.count > 0) {
@@ -523,9 +456,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair_multi
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const int j = 3 * (2 * half + c) + i;
-                P.st.qpos[(7 + j) * n + env] = c == 0 ? L.q[i].x : L.q[i].y;
-                P.st.qvel[(6 + j) * n + env] = c == 0 ? L.qd[i].x : L.qd[i].y;
-                P.st.act[j * n + env] = c == 0 ? L.act[i].x : L.act[i].y;
+                QG_HINGE_STORE(c == 0 ? L.q[i].x : L.q[i].y, c == 0 ? L.qd[i].x : L.qd[i].y, c == 0 ? L.act[i].x : L.act[i].y, P.st, QG_PUT, n, env, j);
                 if (P.track_ctrl) P.st.ctrl[j * n + env] = ctrl_reg[3 * c + i];
             }
         }
@@ -543,13 +474,7 @@ __global__ __launch_bounds__(QGK_WAVE * 4, WPE) void qg_step_kernel_quad_multi(c
     const int lane = threadIdx.x & (QGK_WAVE - 1);
     const int wave = threadIdx.x >> 6;
     float *tile = tile_all[wave];
-    if constexpr (!BAKED) {
-        const float *src = reinterpret_cast<const float *>(Mp);
-        float *dst = reinterpret_cast<float *>(&smodel);
-        for (int i = threadIdx.x; i < (int)(sizeof(KModel) / sizeof(float)); i += QGK_WAVE * WAVES) dst[i] = src[i];
-        __syncthreads();
-    }
-    const KModel &C = BAKED ? QG_BAKED_MODEL : smodel;
+    QG_STAGE_MODEL(C, BAKED, smodel, Mp, QGK_WAVE * WAVES);
     const int k = lane & 3;
     const int el = lane >> 2;
     const int env0 = (blockIdx.x * WAVES + wave) * QGK_QUAD_ENVS;
@@ -558,24 +483,17 @@ __global__ __launch_bounds__(QGK_WAVE * 4, WPE) void qg_step_kernel_quad_multi(c
     const int env = live ? env0 + el : n - 1;
     const float cm = (k == 0) ? 1.f : (k == 2) ? -1.f : 0.f;
     const float sm = (k == 1) ? 1.f : (k == 3) ? -1.f : 0.f;
-    struct { int32_t frame_skip, limit_substeps, use_fall, use_flip, obs_mode, auto_reset; uint32_t reset_flags; float fall_height, w_forward, w_ctrl, alive_bonus;
-             const float *default_ctrl; } Tk = {T->frame_skip, T->limit_substeps, T->use_fall, T->use_flip, T->obs_mode, T->auto_reset, T->reset_flags,
-                                               T->fall_height, T->w_forward, T->w_ctrl, T->alive_bonus, T->default_ctrl};
+    QG_TASK_REGS(Tk, T);
 
     BaseState B;
-    B.pw = v3(P.st.qpos[0 * n + env], P.st.qpos[1 * n + env], P.st.qpos[2 * n + env]);
-    B.qw = P.st.qpos[3 * n + env]; B.qx = P.st.qpos[4 * n + env]; B.qy = P.st.qpos[5 * n + env]; B.qz = P.st.qpos[6 * n + env];
-    B.vw = v3(P.st.qvel[0 * n + env], P.st.qvel[1 * n + env], P.st.qvel[2 * n + env]);
-    B.wb = v3(P.st.qvel[3 * n + env], P.st.qvel[4 * n + env], P.st.qvel[5 * n + env]);
+    QG_BASE_LOAD(B, P.st, QG_AT, n, env);
     int nstep = P.st.nstep[env];
     int episode = P.st.episode[env];
     LegState L;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int j = 3 * k + i;
-        L.q[i] = P.st.qpos[(7 + j) * n + env];
-        L.qd[i] = P.st.qvel[(6 + j) * n + env];
-        L.act[i] = P.st.act[j * n + env];
+        QG_HINGE_LOAD(L.q[i], L.qd[i], L.act[i], P.st, QG_AT, n, env, j);
         L.u[i] = 0.f; L.sc[2 * i] = 0.f; L.sc[2 * i + 1] = 1.f;
     }
     const int od = Tk.obs_mode == 1 ? 21 : 33;
@@ -616,18 +534,9 @@ __global__ __launch_bounds__(QGK_WAVE * 4, WPE) void qg_step_kernel_quad_multi(c
 #pragma unroll
         for (int i = 0; i < 3; ++i) ssq = fmaf(aclip[i], aclip[i], ssq);
         ssq = quad_sum(ssq);
-        const float c_fwd = Tk.w_forward * B.vw.x;
-        const float c_ctl = Tk.w_ctrl * ssq;
-        const float c_alive = Tk.alive_bonus;
-        const float reward = reward_total(c_fwd, c_ctl, c_alive);
-        bool done = nstep >= Tk.limit_substeps;
-        if (Tk.use_fall) done = done || (B.pw.z < Tk.fall_height);
-        {
-            float probe = L.q[0] + L.q[1] + L.q[2] + L.qd[0] + L.qd[1] + L.qd[2];
-            probe = quad_sum(probe) + B.pw.x + B.pw.y + B.pw.z + B.qw + B.vw.x + B.vw.y + B.vw.z + B.wb.x + B.wb.y + B.wb.z;
-            done = done || state_is_bad(probe);
-        }
-        if (Tk.use_flip) done = done || (zaxis_z < 0.f);
+        QG_REWARD_TERMS(Tk., B, ssq, nstep);
+        QG_DONE_IF_BAD_STATE(B, quad_sum(L.q[0] + L.q[1] + L.q[2] + L.qd[0] + L.qd[1] + L.qd[2]));
+        QG_DONE_IF_FLIPPED(Tk., zaxis_z);
         if (k == 0) {
             if (od == 21) { srow[18] = srow[30]; srow[19] = srow[31]; srow[20] = srow[32]; }
             srow[od] = reward; srow[od + 1] = done ? 1.f : 0.f;
@@ -635,15 +544,7 @@ __global__ __launch_bounds__(QGK_WAVE * 4, WPE) void qg_step_kernel_quad_multi(c
         wave_sync();
         {
             float *dst = R.packed + (size_t)kstep * slot_out + (size_t)env0 * row;
-            if (row == 35) {
-                for (int e = lane; e < total; e += QGK_WAVE) dst[e] = tile[e];
-            } else {
-                const unsigned magic = row == 23 ? 2850u : (65536u + row - 1) / row;
-                for (int e = lane; e < total; e += QGK_WAVE) {
-                    const int er = (int)(((unsigned)e * magic) >> 16), ec = e - er * row;
-                    dst[e] = tile[er * 35 + ec];
-                }
-            }
+            QG_TILE_COPY_OUT(dst, tile, lane, total, row);
         }
         wave_sync();
         const bool rst = done && Tk.auto_reset;
@@ -655,17 +556,7 @@ __global__ __launch_bounds__(QGK_WAVE * 4, WPE) void qg_step_kernel_quad_multi(c
             for (int i = 0; i < 3; ++i) P.st.ctrl[(3 * k + i) * n + env] = rst ? Tk.default_ctrl[3 * k + i] : aclip[i];
         }
         if (rst) {
-            B.pw = v3(C.qpos0[0], C.qpos0[1], C.qpos0[2]);
-            B.qw = C.qpos0[3]; B.qx = C.qpos0[4]; B.qy = C.qpos0[5]; B.qz = C.qpos0[6];
-            if (Tk.reset_flags & 1u) {
-                float a = 6.283185307179586f * uniform24(P.seed, P.env_index_base + (uint64_t)env, (uint64_t)episode);
-                float sn, cs;
-                sincos_f(0.5f * a, sn, cs);
-                B.qw = cs; B.qx = 0.f; B.qy = 0.f; B.qz = sn;
-            }
-            B.vw = v3(0.f, 0.f, 0.f);
-            B.wb = v3(0.f, 0.f, 0.f);
-            nstep = 0;
+            QG_BASE_RESET(B, nstep, C.qpos0, Tk., P, env, episode);
             episode += 1;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
@@ -680,20 +571,14 @@ __global__ __launch_bounds__(QGK_WAVE * 4, WPE) void qg_step_kernel_quad_multi(c
     int env_e = env, k_e = k;
     asm volatile("" : "+v"(env_e), "+v"(k_e));
     if (live && k_e == 0) {
-        P.st.qpos[0 * n + env_e] = B.pw.x; P.st.qpos[1 * n + env_e] = B.pw.y; P.st.qpos[2 * n + env_e] = B.pw.z;
-        P.st.qpos[3 * n + env_e] = B.qw; P.st.qpos[4 * n + env_e] = B.qx; P.st.qpos[5 * n + env_e] = B.qy; P.st.qpos[6 * n + env_e] = B.qz;
-        P.st.qvel[0 * n + env_e] = B.vw.x; P.st.qvel[1 * n + env_e] = B.vw.y; P.st.qvel[2 * n + env_e] = B.vw.z;
-        P.st.qvel[3 * n + env_e] = B.wb.x; P.st.qvel[4 * n + env_e] = B.wb.y; P.st.qvel[5 * n + env_e] = B.wb.z;
-        P.st.nstep[env_e] = nstep;
+        QG_BASE_STORE(B, nstep, P.st, QG_PUT, n, env_e);
         P.st.episode[env_e] = episode;
     }
     if (live && R.count > 0) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int j = 3 * k_e + i;
-            P.st.qpos[(7 + j) * n + env_e] = L.q[i];
-            P.st.qvel[(6 + j) * n + env_e] = L.qd[i];
-            P.st.act[j * n + env_e] = L.act[i];
+            QG_HINGE_STORE(L.q[i], L.qd[i], L.act[i], P.st, QG_PUT, n, env_e, j);
             if (WPE == 1 && P.track_ctrl) P.st.ctrl[j * n + env_e] = ctrl_reg[i];
         }
     }

@@ -34,6 +34,7 @@
 
 #include "qg_device.h"
 #include "qg_model_baked.h"
+#include "qg_step_shell.h"    // the env-step shell around the substeps, shared by every step kernel as statement macros
 
 #define DEV __device__ __forceinline__
 #define QG_STR2(x) #x
@@ -1225,10 +1226,7 @@ __global__ __launch_bounds__(QGK_WAVE) void qg_step_kernel(const KModel *__restr
 
     // ---- load state (coalesced: lane i reads base + i*4 of every field) -------------------
     BaseState B;
-    B.pw = v3(P.st.qpos[0 * n + env], P.st.qpos[1 * n + env], P.st.qpos[2 * n + env]);
-    B.qw = P.st.qpos[3 * n + env]; B.qx = P.st.qpos[4 * n + env]; B.qy = P.st.qpos[5 * n + env]; B.qz = P.st.qpos[6 * n + env];
-    B.vw = v3(P.st.qvel[0 * n + env], P.st.qvel[1 * n + env], P.st.qvel[2 * n + env]);
-    B.wb = v3(P.st.qvel[3 * n + env], P.st.qvel[4 * n + env], P.st.qvel[5 * n + env]);
+    QG_BASE_LOAD(B, P.st, QG_AT, n, env);
     int nstep = P.st.nstep[env];
     // action: clip to the action space [-1, 1] (quadruped.py:160), then to the servo's ctrlrange
     float ssq = 0.f;
@@ -1243,9 +1241,7 @@ __global__ __launch_bounds__(QGK_WAVE) void qg_step_kernel(const KModel *__restr
             aclip[j] = a;
             ssq = fmaf(a, a, ssq);
             lds[LU(j) * 64 + lane] = fminf(fmaxf(a, M->link[BAKED ? j % 3 : j].ctrl_lo), M->link[BAKED ? j % 3 : j].ctrl_hi);
-            lds[LQ(j) * 64 + lane] = P.st.qpos[(7 + j) * n + env];
-            lds[LQD(j) * 64 + lane] = P.st.qvel[(6 + j) * n + env];
-            lds[LACT(j) * 64 + lane] = P.st.act[j * n + env];
+            QG_HINGE_LOAD(lds[LQ(j) * 64 + lane], lds[LQD(j) * 64 + lane], lds[LACT(j) * 64 + lane], P.st, QG_AT, n, env, j);
         }
     }
 
@@ -1268,14 +1264,9 @@ __global__ __launch_bounds__(QGK_WAVE) void qg_step_kernel(const KModel *__restr
     }
 
     // ---- rewards and terminations on the post-step state (README.md:64-90) ----------------
-    float c_fwd = T->w_forward * B.vw.x;
-    float c_ctl = T->w_ctrl * ssq;
-    float c_alive = T->alive_bonus;
-    float reward = reward_total(c_fwd, c_ctl, c_alive);
-    bool done = nstep >= T->limit_substeps;
-    if (T->use_fall) done = done || (B.pw.z < T->fall_height);
-    if (T->use_flip) done = done || (so.zaxis.z < 0.f);          // walking_quad.py:156-160, on the step's sensordata
-    {
+    QG_REWARD_TERMS(T->, B, ssq, nstep);
+    QG_DONE_IF_FLIPPED(T->, so.zaxis.z);
+    {   // (base first, hinges second: not the rounding of QG_DONE_IF_BAD_STATE)
         float probe = B.pw.x + B.pw.y + B.pw.z + B.qw + B.vw.x + B.vw.y + B.vw.z + B.wb.x + B.wb.y + B.wb.z;
 #pragma unroll
         for (int j = 0; j < 12; ++j) probe += lds[LQ(j) * 64 + lane] + lds[LQD(j) * 64 + lane];
@@ -1301,39 +1292,17 @@ __global__ __launch_bounds__(QGK_WAVE) void qg_step_kernel(const KModel *__restr
         P.reward[env] = reward;
         P.done[env] = done ? 1 : 0;
     }
-    if (live && P.comps) {
-        P.comps[(size_t)env * 3 + 0] = c_fwd;
-        P.comps[(size_t)env * 3 + 1] = c_ctl;
-        P.comps[(size_t)env * 3 + 2] = c_alive;
-    }
+    QG_COMPS_STORE(live, P, env);
 
     // ---- auto-reset (VecEnv semantics) and state write-back ---------------------------------
     const bool rst = done && T->auto_reset;
-    if (rst) {
-        B.pw = v3(M->qpos0[0], M->qpos0[1], M->qpos0[2]);
-        B.qw = M->qpos0[3]; B.qx = M->qpos0[4]; B.qy = M->qpos0[5]; B.qz = M->qpos0[6];
-        if (T->reset_flags & 1u) {   // random heading (walking_quad.py:68-75)
-            float a = 6.283185307179586f * uniform24(P.seed, P.env_index_base + (uint64_t)env, (uint64_t)P.st.episode[env]);
-            float sn, cs;
-            sincos_f(0.5f * a, sn, cs);
-            B.qw = cs; B.qx = 0.f; B.qy = 0.f; B.qz = sn;
-        }
-        B.vw = v3(0.f, 0.f, 0.f);
-        B.wb = v3(0.f, 0.f, 0.f);
-        nstep = 0;
-    }
+    if (rst) QG_BASE_RESET(B, nstep, M->qpos0, T->, P, env, P.st.episode[env]);
     if (live) {
-        P.st.qpos[0 * n + env] = B.pw.x; P.st.qpos[1 * n + env] = B.pw.y; P.st.qpos[2 * n + env] = B.pw.z;
-        P.st.qpos[3 * n + env] = B.qw; P.st.qpos[4 * n + env] = B.qx; P.st.qpos[5 * n + env] = B.qy; P.st.qpos[6 * n + env] = B.qz;
-        P.st.qvel[0 * n + env] = B.vw.x; P.st.qvel[1 * n + env] = B.vw.y; P.st.qvel[2 * n + env] = B.vw.z;
-        P.st.qvel[3 * n + env] = B.wb.x; P.st.qvel[4 * n + env] = B.wb.y; P.st.qvel[5 * n + env] = B.wb.z;
-        P.st.nstep[env] = nstep;
+        QG_BASE_STORE(B, nstep, P.st, QG_PUT, n, env);
         if (rst) P.st.episode[env] += 1;
 #pragma unroll
         for (int j = 0; j < 12; ++j) {
-            P.st.qpos[(7 + j) * n + env] = rst ? M->qpos0[7 + j] : lds[LQ(j) * 64 + lane];
-            P.st.qvel[(6 + j) * n + env] = rst ? 0.f : lds[LQD(j) * 64 + lane];
-            P.st.act[j * n + env] = rst ? 0.f : lds[LACT(j) * 64 + lane];
+            QG_HINGE_STORE(rst ? M->qpos0[7 + j] : lds[LQ(j) * 64 + lane], rst ? 0.f : lds[LQD(j) * 64 + lane], rst ? 0.f : lds[LACT(j) * 64 + lane], P.st, QG_PUT, n, env, j);
         }
         if (P.track_ctrl) {
 #pragma unroll
@@ -1593,13 +1562,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
     const bool helper = HELP && (int)(threadIdx.x >> 6) >= WAVES;
     float *tile = tile_all[wave];
     QG_MARK(0);
-    if constexpr (!BAKED) {
-        const float *src = reinterpret_cast<const float *>(Mp);
-        float *dst = reinterpret_cast<float *>(&smodel);
-        for (int i = threadIdx.x; i < (int)(sizeof(KModel) / sizeof(float)); i += QGK_WAVE * WAVES * (HELP ? 2 : 1)) dst[i] = src[i];
-        __syncthreads();
-    }
-    const KModel &C = BAKED ? QG_BAKED_MODEL : smodel;
+    QG_STAGE_MODEL(C, BAKED, smodel, Mp, QGK_WAVE * WAVES * (HELP ? 2 : 1));
     const int k = lane & 3;                         // leg of this lane
     const int el = lane >> 2;                       // env within the wave
     const int env0 = (blockIdx.x * WAVES + wave) * QGK_QUAD_ENVS;
@@ -1693,10 +1656,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
         }
     }
     BaseState B;
-    B.pw = v3(P.st.qpos[0 * n + env], P.st.qpos[1 * n + env], P.st.qpos[2 * n + env]);
-    B.qw = P.st.qpos[3 * n + env]; B.qx = P.st.qpos[4 * n + env]; B.qy = P.st.qpos[5 * n + env]; B.qz = P.st.qpos[6 * n + env];
-    B.vw = v3(P.st.qvel[0 * n + env], P.st.qvel[1 * n + env], P.st.qvel[2 * n + env]);
-    B.wb = v3(P.st.qvel[3 * n + env], P.st.qvel[4 * n + env], P.st.qvel[5 * n + env]);
+    QG_BASE_LOAD(B, P.st, QG_AT, n, env);
     quat_unit(B);   // unit quaternion once per launch (qg_set_state may hand in any length); the substeps keep it normalised (base_prelude<UNIT>)
     LegState L;
     const int nstep0 = P.st.nstep[env];
@@ -1739,9 +1699,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
         float a = fminf(fmaxf(a_in, -1.f), 1.f);    // quadruped.py:160
         aclip0[i] = a;
         L.u[i] = fminf(fmaxf(a, link_of<BAKED>(C, k, i).ctrl_lo), link_of<BAKED>(C, k, i).ctrl_hi);
-        L.q[i] = P.st.qpos[(7 + j) * n + env];
-        L.qd[i] = P.st.qvel[(6 + j) * n + env];
-        L.act[i] = P.st.act[j * n + env];
+        QG_HINGE_LOAD(L.q[i], L.qd[i], L.act[i], P.st, QG_AT, n, env, j);
         sincos_f(L.q[i] - link_of<BAKED>(C, k, i).ref, L.sc[2 * i], L.sc[2 * i + 1]);
     }
     // PO: the env's filter state (lead lane) and ring position, this lane's share of its env's row copy ring -> out -- its loads go
@@ -1820,21 +1778,12 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
     for (int i = 0; i < 3; ++i) ssq = fmaf(aclip[i], aclip[i], ssq);
     ssq = quad_sum(ssq);
 
-    float c_fwd = T->w_forward * B.vw.x;
-    float c_ctl = T->w_ctrl * ssq;
-    float c_alive = T->alive_bonus;
-    float reward = reward_total(c_fwd, c_ctl, c_alive);
-    bool done = nstep >= T->limit_substeps;
-    if (T->use_fall) done = done || (B.pw.z < T->fall_height);
-    {
-        float probe = L.q[0] + L.q[1] + L.q[2] + L.qd[0] + L.qd[1] + L.qd[2];
-        probe = quad_sum(probe) + B.pw.x + B.pw.y + B.pw.z + B.qw + B.vw.x + B.vw.y + B.vw.z + B.wb.x + B.wb.y + B.wb.z;
-        done = done || state_is_bad(probe);
-    }
+    QG_REWARD_TERMS(T->, B, ssq, nstep);
+    QG_DONE_IF_BAD_STATE(B, quad_sum(L.q[0] + L.q[1] + L.q[2] + L.qd[0] + L.qd[1] + L.qd[2]));
 
     const int od = T->obs_mode == 1 ? 21 : 33;
     const int row = P.packed ? od + 2 : od;
-    if (T->use_flip) done = done || (zaxis_z < 0.f);              // walking_quad.py:156-160, on the step's sensordata
+    QG_DONE_IF_FLIPPED(T->, zaxis_z);
     if (k == 0) {                                                  // lane 0 of the quad wrote these entries itself
         if (od == 21) { srow[18] = srow[30]; srow[19] = srow[31]; srow[20] = srow[32]; }   // IMU pack: velocimeter follows the gyro
         if (P.packed) { srow[od] = reward; srow[od + 1] = done ? 1.f : 0.f; }
@@ -1843,16 +1792,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
     if constexpr (!PO) {
         const int total = live_envs * row;                               // (a whole wave may lie past the last env: live_envs = 0)
         float *dst = (P.packed ? P.packed : P.obs) + (size_t)env0 * row;
-        if (row == 35) {                       // rows were staged with a stride of 35 floats: the packed full layout is a straight copy
-            for (int e = lane; e < total; e += QGK_WAVE) dst[e] = tile[e];
-        } else {
-            // e / row without a division per element: row is 21, 23 or 33 here and e < 2^11, where (e * ceil(2^16 / row)) >> 16 is exact
-            const unsigned magic = row == 33 ? 1986u : row == 21 ? 3121u : row == 23 ? 2850u : (65536u + row - 1) / row;
-            for (int e = lane; e < total; e += QGK_WAVE) {
-                const int er = (int)(((unsigned)e * magic) >> 16), ec = e - er * row;
-                dst[e] = tile[er * 35 + ec];
-            }
-        }
+        QG_TILE_COPY_OUT(dst, tile, lane, total, row);
     }
     QG_MARK(3);                                      // obs tile written out
     const bool lead = live && k_e == 0;
@@ -1864,19 +1804,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
     if constexpr (POH) {
         // the auto-reset of the base FIRST (the reward below does not look at B): the helper wave's frame shows data.qpos[3:7] as the step
         // leaves it
-        if (done && T->auto_reset) {
-            B.pw = v3(C.qpos0[0], C.qpos0[1], C.qpos0[2]);
-            B.qw = C.qpos0[3]; B.qx = C.qpos0[4]; B.qy = C.qpos0[5]; B.qz = C.qpos0[6];
-            if (T->reset_flags & 1u) {
-                float a = 6.283185307179586f * uniform24(P.seed, P.env_index_base + (uint64_t)env_e, (uint64_t)P.st.episode[env_e]);
-                float sn, cs;
-                sincos_f(0.5f * a, sn, cs);
-                B.qw = cs; B.qx = 0.f; B.qy = 0.f; B.qz = sn;
-            }
-            B.vw = v3(0.f, 0.f, 0.f);
-            B.wb = v3(0.f, 0.f, 0.f);
-            nstep = 0;
-        }
+        if (done && T->auto_reset) QG_BASE_RESET(B, nstep, C.qpos0, T->, P, env_e, P.st.episode[env_e]);
         rst_done = true;
         if (k_e == 0) {
             s_done[wave][lane >> 2] = done ? 1.f : 0.f;
@@ -1918,41 +1846,19 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_ste
         QG_MARK(4);                                  // channel terms + sums
         if (!RWDH && lead) walk_reward_env(WK.P, WK.S, n, env_e, tile + (lane >> 2) * 35, sum, win, done, P.reward, WK.comps, WK.sample, P.seed, P.env_index_base);
     }
-    if (lead && P.comps) {
-        P.comps[(size_t)env_e * 3 + 0] = c_fwd;
-        P.comps[(size_t)env_e * 3 + 1] = c_ctl;
-        P.comps[(size_t)env_e * 3 + 2] = c_alive;
-    }
+    QG_COMPS_STORE(lead, P, env_e);
 
     const bool rst = done && T->auto_reset;
-    if (rst && !rst_done) {
-        B.pw = v3(C.qpos0[0], C.qpos0[1], C.qpos0[2]);
-        B.qw = C.qpos0[3]; B.qx = C.qpos0[4]; B.qy = C.qpos0[5]; B.qz = C.qpos0[6];
-        if (T->reset_flags & 1u) {
-            float a = 6.283185307179586f * uniform24(P.seed, P.env_index_base + (uint64_t)env_e, (uint64_t)P.st.episode[env_e]);
-            float sn, cs;
-            sincos_f(0.5f * a, sn, cs);
-            B.qw = cs; B.qx = 0.f; B.qy = 0.f; B.qz = sn;
-        }
-        B.vw = v3(0.f, 0.f, 0.f);
-        B.wb = v3(0.f, 0.f, 0.f);
-        nstep = 0;
-    }
+    if (rst && !rst_done) QG_BASE_RESET(B, nstep, C.qpos0, T->, P, env_e, P.st.episode[env_e]);
     if (lead) {
-        P.st.qpos[0 * n + env_e] = B.pw.x; P.st.qpos[1 * n + env_e] = B.pw.y; P.st.qpos[2 * n + env_e] = B.pw.z;
-        P.st.qpos[3 * n + env_e] = B.qw; P.st.qpos[4 * n + env_e] = B.qx; P.st.qpos[5 * n + env_e] = B.qy; P.st.qpos[6 * n + env_e] = B.qz;
-        P.st.qvel[0 * n + env_e] = B.vw.x; P.st.qvel[1 * n + env_e] = B.vw.y; P.st.qvel[2 * n + env_e] = B.vw.z;
-        P.st.qvel[3 * n + env_e] = B.wb.x; P.st.qvel[4 * n + env_e] = B.wb.y; P.st.qvel[5 * n + env_e] = B.wb.z;
-        P.st.nstep[env_e] = nstep;
+        QG_BASE_STORE(B, nstep, P.st, QG_PUT, n, env_e);
         if (rst) P.st.episode[env_e] += 1;
     }
     if (live) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int j = 3 * k_e + i;
-            P.st.qpos[(7 + j) * n + env_e] = rst ? C.qpos0[7 + (BAKED ? i : j)] : L.q[i];
-            P.st.qvel[(6 + j) * n + env_e] = rst ? 0.f : L.qd[i];
-            P.st.act[j * n + env_e] = rst ? 0.f : L.act[i];
+            QG_HINGE_STORE(rst ? C.qpos0[7 + (BAKED ? i : j)] : L.q[i], rst ? 0.f : L.qd[i], rst ? 0.f : L.act[i], P.st, QG_PUT, n, env_e, j);
             if (P.track_ctrl) P.st.ctrl[j * n + env_e] = rst ? T->default_ctrl[j] : aclip[i];
         }
     }
@@ -2129,10 +2035,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair(const
     sm.x = 0.f; sm.y = half ? -1.f : 1.f;
 
     BaseState B;
-    B.pw = v3<float>(P.st.qpos[0 * n + env], P.st.qpos[1 * n + env], P.st.qpos[2 * n + env]);
-    B.qw = P.st.qpos[3 * n + env]; B.qx = P.st.qpos[4 * n + env]; B.qy = P.st.qpos[5 * n + env]; B.qz = P.st.qpos[6 * n + env];
-    B.vw = v3<float>(P.st.qvel[0 * n + env], P.st.qvel[1 * n + env], P.st.qvel[2 * n + env]);
-    B.wb = v3<float>(P.st.qvel[3 * n + env], P.st.qvel[4 * n + env], P.st.qvel[5 * n + env]);
+    QG_BASE_LOAD(B, P.st, QG_AT, n, env);
     quat_unit(B);   // unit quaternion once per launch (qg_set_state may hand in any length); the substeps keep it normalised (base_prelude<UNIT>)
     int nstep = P.st.nstep[env];
     LegPair L;
@@ -2184,7 +2087,8 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair(const
             aclip[3 * c + i] = a;
             ssq = fmaf(a, a, ssq);
             float uu = fminf(fmaxf(a, C.link[i].ctrl_lo), C.link[i].ctrl_hi);
-            float qq = P.st.qpos[(7 + j) * n + env], qv = P.st.qvel[(6 + j) * n + env], aa = P.st.act[j * n + env];
+            float qq, qv, aa;
+            QG_HINGE_LOAD(qq, qv, aa, P.st, QG_AT, n, env, j);
             if (c == 0) { L.u[i].x = uu; L.q[i].x = qq; L.qd[i].x = qv; L.act[i].x = aa; }
             else { L.u[i].y = uu; L.q[i].y = qq; L.qd[i].y = qv; L.act[i].y = aa; }
         }
@@ -2252,20 +2156,11 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair(const
         substep_pair(C, cm, sm, B2, L2, true, srow, half, zaxis_z);
     }
 
-    float c_fwd = T->w_forward * B.vw.x;
-    float c_ctl = T->w_ctrl * ssq;
-    float c_alive = T->alive_bonus;
-    float reward = reward_total(c_fwd, c_ctl, c_alive);
-    bool done = nstep >= T->limit_substeps;
-    if (T->use_fall) done = done || (B.pw.z < T->fall_height);
-    {
-        float probe = hsum(L.q[0]) + hsum(L.q[1]) + hsum(L.q[2]) + hsum(L.qd[0]) + hsum(L.qd[1]) + hsum(L.qd[2]);
-        probe = pair_sum(probe) + B.pw.x + B.pw.y + B.pw.z + B.qw + B.vw.x + B.vw.y + B.vw.z + B.wb.x + B.wb.y + B.wb.z;
-        done = done || state_is_bad(probe);
-    }
+    QG_REWARD_TERMS(T->, B, ssq, nstep);
+    QG_DONE_IF_BAD_STATE(B, pair_sum(hsum(L.q[0]) + hsum(L.q[1]) + hsum(L.q[2]) + hsum(L.qd[0]) + hsum(L.qd[1]) + hsum(L.qd[2])));
     const int od = T->obs_mode == 1 ? 21 : 33;
     const int row = P.packed ? od + 2 : od;
-    if (T->use_flip) done = done || (zaxis_z < 0.f);
+    QG_DONE_IF_FLIPPED(T->, zaxis_z);
     if (half == 0) {
         if (od == 21) { srow[18] = srow[30]; srow[19] = srow[31]; srow[20] = srow[32]; }
         if (P.packed) { srow[od] = reward; srow[od + 1] = done ? 1.f : 0.f; }
@@ -2274,16 +2169,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair(const
     if constexpr (!PO) {
         const int total = live_envs * row;                               // (a whole wave may lie past the last env: live_envs = 0)
         float *dst = (P.packed ? P.packed : P.obs) + (size_t)env0 * row;
-        if (row == 35) {
-            for (int e = lane; e < total; e += QGK_WAVE) dst[e] = tile[e];
-        } else {
-            // e / row without a division per element: row is 21, 23 or 33 here and e < 2^11, where (e * ceil(2^16 / row)) >> 16 is exact
-            const unsigned magic = row == 33 ? 1986u : row == 21 ? 3121u : row == 23 ? 2850u : (65536u + row - 1) / row;
-            for (int e = lane; e < total; e += QGK_WAVE) {
-                const int er = (int)(((unsigned)e * magic) >> 16), ec = e - er * row;
-                dst[e] = tile[er * 35 + ec];
-            }
-        }
+        QG_TILE_COPY_OUT(dst, tile, lane, total, row);
     }
     QG_MARK(3);                                      // obs tile written out
     const bool lead = live && half == 0;
@@ -2303,32 +2189,12 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair(const
         if (lead) walk_reward_env(WK.P, WK.S, n, env, tile + el * 35, sum, win, done, P.reward, WK.comps, WK.sample, P.seed, P.env_index_base);
         QG_MARK(5);                                  // reward
     }
-    if (lead && P.comps) {
-        P.comps[(size_t)env * 3 + 0] = c_fwd;
-        P.comps[(size_t)env * 3 + 1] = c_ctl;
-        P.comps[(size_t)env * 3 + 2] = c_alive;
-    }
+    QG_COMPS_STORE(lead, P, env);
 
     const bool rst = done && T->auto_reset;
-    if (rst) {
-        B.pw = v3<float>(C.qpos0[0], C.qpos0[1], C.qpos0[2]);
-        B.qw = C.qpos0[3]; B.qx = C.qpos0[4]; B.qy = C.qpos0[5]; B.qz = C.qpos0[6];
-        if (T->reset_flags & 1u) {
-            float a = 6.283185307179586f * uniform24(P.seed, P.env_index_base + (uint64_t)env, (uint64_t)P.st.episode[env]);
-            float sn, cs;
-            sincos_f(0.5f * a, sn, cs);
-            B.qw = cs; B.qx = 0.f; B.qy = 0.f; B.qz = sn;
-        }
-        B.vw = v3<float>(0.f, 0.f, 0.f);
-        B.wb = v3<float>(0.f, 0.f, 0.f);
-        nstep = 0;
-    }
+    if (rst) QG_BASE_RESET(B, nstep, C.qpos0, T->, P, env, P.st.episode[env]);
     if (lead) {
-        P.st.qpos[0 * n + env] = B.pw.x; P.st.qpos[1 * n + env] = B.pw.y; P.st.qpos[2 * n + env] = B.pw.z;
-        P.st.qpos[3 * n + env] = B.qw; P.st.qpos[4 * n + env] = B.qx; P.st.qpos[5 * n + env] = B.qy; P.st.qpos[6 * n + env] = B.qz;
-        P.st.qvel[0 * n + env] = B.vw.x; P.st.qvel[1 * n + env] = B.vw.y; P.st.qvel[2 * n + env] = B.vw.z;
-        P.st.qvel[3 * n + env] = B.wb.x; P.st.qvel[4 * n + env] = B.wb.y; P.st.qvel[5 * n + env] = B.wb.z;
-        P.st.nstep[env] = nstep;
+        QG_BASE_STORE(B, nstep, P.st, QG_PUT, n, env);
         if (rst) P.st.episode[env] += 1;
     }
     if (live) {
@@ -2337,9 +2203,7 @@ __global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair(const
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const int j = 3 * (2 * half + c) + i;
-                P.st.qpos[(7 + j) * n + env] = rst ? C.qpos0[7 + i] : (c == 0 ? L.q[i].x : L.q[i].y);
-                P.st.qvel[(6 + j) * n + env] = rst ? 0.f : (c == 0 ? L.qd[i].x : L.qd[i].y);
-                P.st.act[j * n + env] = rst ? 0.f : (c == 0 ? L.act[i].x : L.act[i].y);
+                QG_HINGE_STORE(rst ? C.qpos0[7 + i] : (c == 0 ? L.q[i].x : L.q[i].y), rst ? 0.f : (c == 0 ? L.qd[i].x : L.qd[i].y), rst ? 0.f : (c == 0 ? L.act[i].x : L.act[i].y), P.st, QG_PUT, n, env, j);
                 if (P.track_ctrl && rst) P.st.ctrl[j * n + env] = T->default_ctrl[j];          // (the step's data.ctrl went out in the prologue)
             }
         }
@@ -2365,12 +2229,8 @@ __global__ void qg_reset_kernel(const KModel *__restrict__ M, const KTask *__res
             st.qpos[(7 + j) * n + env] = jittered_hinge(M->qpos0[7 + j], M->link[j].lo, M->link[j].hi, T->reset_joint_jitter, seed,
                                                         env_index_base + (uint64_t)env, ep, j);
     }
-    if (flags & 1u) {
-        float a = 6.283185307179586f * uniform24(seed, env_index_base + (uint64_t)env, (uint64_t)ep);
-        float sn, cs;
-        sincos_f(0.5f * a, sn, cs);
-        st.qpos[3 * n + env] = cs; st.qpos[4 * n + env] = 0.f; st.qpos[5 * n + env] = 0.f; st.qpos[6 * n + env] = sn;
-    }
+    if (flags & 1u)
+        QG_RESET_HEADING(seed, env_index_base + (uint64_t)env, ep, st.qpos[3 * n + env], st.qpos[4 * n + env], st.qpos[5 * n + env], st.qpos[6 * n + env]);
     for (int j = 0; j < 18; ++j) st.qvel[j * n + env] = 0.f;
     for (int j = 0; j < 12; ++j) { st.act[j * n + env] = 0.f; st.ctrl[j * n + env] = T->default_ctrl[j]; }
     st.nstep[env] = 0;

@@ -50,3 +50,41 @@ def test_twin_cases_exist():
 def test_last_step_kernel_is_declared():
     header = open(os.path.join(K.ROOT, "include", "quadgym.h")).read()
     assert re.search(r"int32_t qg_debug_last_step_kernel\(const qg_sim \*sim, char \*buf, int32_t len\);", header)
+
+
+def test_step_shell_exists_once():
+    """The shell of an env-step (state load / store, reward, terminations, auto-reset, tile copy-out) is text of qg_step_shell.h that the
+    step kernels expand, not a copy per kernel: each fragment occurs once in the .hip / .h / .inc files of csrc/.  A copy that stays
+    for the listing's sake (tools/asm_diff.py) is named here with its reason, and the count is what the tree has."""
+    csrc = os.path.dirname(K.CAPI)
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".inc"))}
+    assert "qg_step_shell.h" in text
+
+    def sites(needle):
+        return [(f, ln) for f, t in text.items() for ln in t.split("\n") if needle in ln]
+
+    def files(needle):
+        return [f for f, _ in sites(needle)]
+
+    shell = ["qg_step_shell.h"]
+    # the random heading draw of the auto-reset and of qg_reset_kernel
+    assert files("6.283185307179586f * uniform24(") == shell
+    # the plain reward: one call site besides the definition
+    assert [f for f, ln in sites("reward_total(") if "DEV float reward_total(" not in ln] == shell
+    # the store of the base quaternion: once, through the access pair handed to QG_BASE_STORE (plain or byte-offset form) ...
+    assert files("PUT(ST.qpos, 3, n, e, B.qw)") == shell
+    assert files("lk_st(P.st.qpos, 3 * n4") == []
+    # ... and the one place that spells the plain index out is not a copy of it: qg_reset_kernel has no BaseState and hands
+    # st.qpos[3 * n + env] .. [6 * n + env] to QG_RESET_HEADING as the heading's destination
+    assert files(".qpos[3 * n") == ["qg_kernels.hip"]
+    assert all("QG_RESET_HEADING(" in ln for _, ln in sites(".qpos[3 * n"))
+    # the bad-state termination: the shell's, and the one-env-per-lane kernel's own (it adds the base first and its 24 hinge values
+    # one by one from LDS -- another order of the additions, so another rounding: not the shell's probe)
+    assert files("state_is_bad(probe)") == ["qg_kernels.hip", "qg_step_shell.h"]
+    # tile copy-out multipliers, model staging, task snapshot, reward components
+    for needle in ("const unsigned magic =", "reinterpret_cast<float *>(&smodel)", "Tk = {T->frame_skip", "P.comps[(size_t)env * 3 + 0]"):
+        assert files(needle) == shell, needle
+    # hinge state: through QG_HINGE_LOAD / QG_HINGE_STORE, except in the one-link-per-lane kernels -- per-launch and many-steps form,
+    # a load and a store each -- whose listings change with the macros' (7 + j) * n4 + e4 for their 7 * n4 + (j * n4 + e4)
+    assert files("P.st.qpos[(7 + j) * n") == []
+    assert files("7 * n4 + j4") == ["qg_kernel_link.hip"] * 2 + ["qg_kernel_resident.hip"] * 2
