@@ -91,6 +91,8 @@ DEV float leg_suffix(float x) {
     x += dpp_any<0xFE>(x);    // quad_perm [2,3,3,3] of the partial sums: lane 0 adds (x2 + x3), lane 1 adds x3 = 0
     return x;
 }
+// z += z[lane 1 of the leg] * c in one instruction: the DPP operand is the destination's own old value (substep_link, z = L^-1 F)
+#define QG_Z_FM(i) "v_fmac_f32_dpp %[z" i "], %[z" i "], %[c] quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf\n\t"
 DEV float leg_bcast0(float x) { return dpp_any<0x00>(x); }
 DEV float leg_bcast1(float x) { return dpp_any<0x55>(x); }
 DEV float leg_bcast2(float x) { return dpp_any<0xAA>(x); }
@@ -143,7 +145,7 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
                       const KXfrcLink &X = KXfrcLink{}) {
     using namespace pk3;
     const float h = C.h;
-    const BaseCtx bc = pk3::base_prelude_unit(C, B); // the quaternion is of unit length here (normalised at load, then by base_integrate)
+    const BaseCtx bc = pk3::base_prelude_unit<BAKED>(C, B); // the quaternion is of unit length here (normalised at load, then by base_integrate)
     const V3 nb = bc.n;
     if (want_sensors) {              // the step's sensordata describes the state at the start of its last substep
         zaxis_z = bc.cz.z;
@@ -246,7 +248,9 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
 #pragma unroll
             for (int i = 0; i < QGK_CP_LINK / 2; ++i) contact_point(v3<f2>(K.cp2[i][0], K.cp2[i][1], K.cp2[i][2]), nl2, zb2, w2, s2);
             wsum = w2.x + w2.y;
-            s = v3(s2.x.x + s2.x.y, s2.y.x + s2.y.y, s2.z.x + s2.z.y);
+            // (x and y behind `opaque`: seen as a pair of sums, the two adds become ONE packed add of the transposed pairs -- three
+            // copies to form those and the add, for the two adds)
+            s = v3(opaque(s2.x.x + s2.x.y), opaque(s2.y.x + s2.y.y), s2.z.x + s2.z.y);
         } else {
 #pragma unroll
             for (int i = 0; i < QGK_CP_LINK; ++i) contact_point(v3(K.cp[i][0], K.cp[i][1], K.cp[i][2]), nl, zb, wsum, s);
@@ -258,7 +262,8 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
         else pk3::contact_eval(wsum, s, Ep, pp, nb, vp, C.contact_k, C.contact_c, C.contact_inv_ramp, C.contact_mu, h, fe, cd);
         f.a = f.a - fe.a;
         f.l = f.l - fe.l;
-        pk3::add_contact_damping(A, cd.mc, cd.w, cd.P, nb);
+        if constexpr (BAKED) pk3::add_contact_damping<true>(A, cd.mc, cd.w, cd.P, nb, Bi.h);
+        else pk3::add_contact_damping(A, cd.mc, cd.w, cd.P, nb);
     }
     // external wrench (wrench mode, wave-uniform): a link lane's row acts on its link, next to the contact force (-1 x xw: exact); the
     // spare lanes add nothing here (0 x xw) -- the one of leg 0 holds the FRAME's row, which joins the base right-hand side below
@@ -337,8 +342,20 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
         const float nc0 = r == 1 ? -l10 : (r == 2 ? -l20 : 0.f), nc1 = r == 2 ? -l21 : 0.f;
 #pragma unroll
         for (int i = 0; i < 6; ++i) z[i] = fmaf(leg_bcast0(z[i]), nc0, z[i]);
+        if constexpr (BAKED) {
+            // The second pass updates z in place, so the broadcast can be the DPP operand of the multiply-add itself, read from the
+            // register the instruction then writes: six v_fmac_f32_dpp behind one s_nop 1 for six moves and six multiply-adds (the
+            // compiler's DPP combiner leaves a move whose source its consumer overwrites; same operands, fused as before).  The
+            // first pass cannot follow: F stays live for the hinge accelerations below, so its multiply-add is three-address, which
+            // has no DPP form here.  Hazard (see env_sum_banked16): the s_nop 1 covers a z written by the instruction in front; z is
+            // read by no DPP instruction behind the block.
+            asm("s_nop 1\n\t" QG_Z_FM("0") QG_Z_FM("1") QG_Z_FM("2") QG_Z_FM("3") QG_Z_FM("4") QG_Z_FM("5")
+                : [z0] "+v"(z[0]), [z1] "+v"(z[1]), [z2] "+v"(z[2]), [z3] "+v"(z[3]), [z4] "+v"(z[4]), [z5] "+v"(z[5])
+                : [c] "v"(nc1));
+        } else {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) z[i] = fmaf(leg_bcast1(z[i]), nc1, z[i]);
+            for (int i = 0; i < 6; ++i) z[i] = fmaf(leg_bcast1(z[i]), nc1, z[i]);
+        }
     }
     // ---- this lane's share of the base block: its own link's inertia and force (summed over the env's lanes they are the legs' composite
     // inertias and forces) minus z z^T / d_r;  F u = sum_r z_r y_r / d_r ----
@@ -378,7 +395,8 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
     }
     const f2 nyr = {-yr, -yr};
     const f2 rh0 = __builtin_elementwise_fma(nyr, WP, f2{-f.a.x, -f.a.y}), rh1 = __builtin_elementwise_fma(nyr, WL, f2{-f.l.x, -f.l.y}),
-             rh2 = __builtin_elementwise_fma(nyr, WZ, f2{-f.a.z, -f.l.z});
+             rh2 = BAKED ? __builtin_elementwise_fma(nyr, WZ, -f2{f.a.z, f.l.z})      // (the sign on the pair, not on its halves: two v_xor)
+                         : __builtin_elementwise_fma(nyr, WZ, f2{-f.a.z, -f.l.z});
     SV rhn = {v3(rh0.x, rh0.y, rh2.x), v3(rh1.x, rh1.y, rh2.y)};
     // ---- base block: FRAME body, the sums over the env's 16 lanes, the FRAME's contact (a wave-uniform branch that updates the block
     // in place: on the usual path, no contact, nothing has to be moved), the 6x6 solve -- all redundant in the 16 lanes.  Every DPP
@@ -439,7 +457,7 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
         hinge_advance(h * J.qd, J.sn, J.cs);
         J.act = fmaf(J.u - J.act, K.act_decay, J.act);
     }
-    pk3::base_integrate_unit(bc, h, wdot, acl, B);
+    pk3::base_integrate_unit<BAKED>(bc, h, wdot, acl, B);
 }
 
 // Workgroups of four waves (one per SIMD of a CU): a grid of 1024 one-wave workgroups measured 1.65 us more fixed time per launch
@@ -702,7 +720,14 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
     // The state goes out FIRST (two dozen of the launch's ~30 store instructions): it drains while the rest of the epilogue computes.
     const bool lead = live && lead_env;
     const bool rst = done && Tk.auto_reset;
-    if (rst) QG_BASE_RESET(B, nstep, C.qpos0, Tk., P, env, P.st.episode[env]);
+    // An env that auto-resets costs the wave ONE load round trip at most, and none behind its own stores: the data.ctrl an env restarts
+    // with is fetched here, next to the episode load of the random heading (the only value of the reset path the wave has to wait
+    // for) and ahead of the two dozen state stores -- behind them its s_waitcnt would also sit out their acknowledgements.
+    float ctrl0 = 0.f;
+    if (rst) {
+        ctrl0 = Tk.default_ctrl[jch];       // (whether data.ctrl is tracked or not: asking first costs the walking forms scalar registers)
+        QG_BASE_RESET(B, nstep, C.qpos0, Tk., P, env, P.st.episode[env]);
+    }
     if constexpr (HELP) {
         if constexpr (PO) {
             const int le = 4 * wave + el;
@@ -729,7 +754,8 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
     }
     if (lead) {
         QG_BASE_STORE(B, nstep, P.st, QG_PUT_LK, n4, e4);
-        if (rst) P.st.episode[env] += 1;
+        // the episode counter advances in memory (an atomic add that returns nothing): the wave does not wait for the old value
+        if (rst) __hip_atomic_fetch_add(P.st.episode + env, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (wch) {                                      // every link lane stores its own hinge
         const float q0 = BAKED ? sel3(rk, C.qpos0[7], C.qpos0[8], C.qpos0[9]) : C.qpos0[7 + jch];
@@ -737,7 +763,7 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
         lk_st(P.st.qpos, 7 * n4 + j4, rst ? q0 : J.q);
         lk_st(P.st.qvel, 6 * n4 + j4, rst ? 0.f : J.qd);
         lk_st(P.st.act, j4, rst ? 0.f : J.act);
-        if (P.track_ctrl) lk_st(P.st.ctrl, j4, rst ? Tk.default_ctrl[jch] : aclip);
+        if (P.track_ctrl) lk_st(P.st.ctrl, j4, rst ? ctrl0 : aclip);
     }
     if (lead_env) {
         if (!RWDH && od == 21) { srow[18] = srow[30]; srow[19] = srow[31]; srow[20] = srow[32]; }   // IMU pack: velocimeter follows the gyro

@@ -138,6 +138,15 @@ DEV V3 cross_add(V3 a, V3 b, V3 acc) {
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_hi:[1,0,0]" : "=v"(r) : "v"(A), "v"(bz), "v"(m));
     return v3<float>(r.x, r.y, fmaf(a.x, b.y, fmaf(-a.y, b.x, acc.z)));
 }
+// a x b - acc: cross_add with the sign of the addend as an operand modifier (a negated addend is formed with two v_xor first)
+DEV V3 cross_sub(V3 a, V3 b, V3 acc) {
+    if (has_literal(a) || has_literal(b)) return cross_add(a, b, v3<float>(-acc.x, -acc.y, -acc.z));
+    f2 A = {a.x, a.y}, Bv = {b.x, b.y}, C2 = {acc.x, acc.y}, az, bz, m, r;
+    az.x = a.z; bz.x = b.z;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,0,1] neg_lo:[1,0,1] neg_hi:[0,0,1]" : "=v"(m) : "v"(az), "v"(Bv), "v"(C2));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_hi:[1,0,0]" : "=v"(r) : "v"(A), "v"(bz), "v"(m));
+    return v3<float>(r.x, r.y, fmaf(a.x, b.y, fmaf(-a.y, b.x, -acc.z)));
+}
 }  // namespace pk3
 DEV V3 ld3(const float *p) { return v3<float>(p[0], p[1], p[2]); }
 template <class T> DEV V3T<T> ld3t(const float *p) { return v3<T>(T(p[0]), T(p[1]), T(p[2])); }     // a model constant, same for every component
@@ -389,7 +398,11 @@ typedef float T;
 #undef QG_CROSS_ADD
 #undef QG_TEMPLATE_T
 // add_contact_damping on the pairs the packed code keeps a symmetric block in: (xx, yy), (xz, yz) and the (x, y) halves of AL's rows
-DEV void add_contact_damping(Sym6 &A, float m, float w, V3 r, V3 n) {
+// RIGID (the compiled-in robot's one-link-per-lane substep): A is sym6_of() of a body with first moment bh on entry, i.e. AL is
+// [bh]x and its pairs (0, -z), (z, 0), (-y, x) are halves of pairs that exist anyway, swapped and negated -- as written they are each
+// formed first (v_xor / v_mov: four per substep); here the swaps and signs are operand modifiers of the instructions that consume them
+template <bool RIGID = false>
+DEV void add_contact_damping(Sym6 &A, float m, float w, V3 r, V3 n, V3 bh = V3{}) {
     const float rr = dot(r, r);
     const V3 h = m * r;
     const f2 hxy = {h.x, h.y}, rxy = {r.x, r.y}, nxy = {n.x, n.y};
@@ -399,9 +412,15 @@ DEV void add_contact_damping(Sym6 &A, float m, float w, V3 r, V3 n) {
     const f2 aao = __builtin_elementwise_fma(-hxy, f2{r.z, r.z}, f2{A.AA.xz, A.AA.yz});
     A.AA.zz += fmaf(-h.z, r.z, mrr);
     A.AA.xy = fmaf(-h.x, r.y, A.AA.xy);
-    A.AL.r0.y -= h.z; A.AL.r0.z += h.y;
+    A.AL.r0.z += h.y;
     A.AL.r1.x += h.z; A.AL.r1.z -= h.x;
-    const f2 r2xy = f2{A.AL.r2.x, A.AL.r2.y} + f2{-h.y, h.x};
+    f2 r2xy;
+    if constexpr (RIGID) {      // (-bh.y, bh.x) + (-h.y, h.x) on the pairs bh and h
+        asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,0] neg_lo:[1,1]" : "=v"(r2xy) : "v"(f2{bh.x, bh.y}), "v"(hxy));
+    } else {
+        A.AL.r0.y -= h.z;
+        r2xy = f2{A.AL.r2.x, A.AL.r2.y} + f2{-h.y, h.x};
+    }
     const f2 lld = f2{A.LL.xx, A.LL.yy} + f2{m, m};
     A.LL.zz += m;
     // w a a^T, a = [r x n; n]
@@ -411,7 +430,14 @@ DEV void add_contact_damping(Sym6 &A, float m, float w, V3 r, V3 n) {
     const f2 aao2 = __builtin_elementwise_fma(wraxy, f2{ra.z, ra.z}, aao);
     A.AA.xx = aad2.x; A.AA.yy = aad2.y; A.AA.xz = aao2.x; A.AA.yz = aao2.y;
     A.AA.xy = fmaf(wra.x, ra.y, A.AA.xy); A.AA.zz = fmaf(wra.z, ra.z, A.AA.zz);
-    A.AL.r0 = fma3(wra.x, n, A.AL.r0);
+    if constexpr (RIGID) {      // row 0's addend (0, -(bh.z + h.z)) is row 1's (bh.z + h.z, 0), halves swapped, the high one negated
+        const f2 r1xy = {A.AL.r1.x, A.AL.r1.y};
+        f2 r0xy;
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[0,1,0] neg_hi:[0,0,1]" : "=v"(r0xy) : "v"(wraxy), "v"(nxy), "v"(r1xy));
+        A.AL.r0 = v3<float>(r0xy.x, r0xy.y, fmaf(wra.x, n.z, A.AL.r0.z));
+    } else {
+        A.AL.r0 = fma3(wra.x, n, A.AL.r0);
+    }
     A.AL.r1 = fma3(wra.y, n, A.AL.r1);
     A.AL.r2 = fma3(wra.z, n, v3<float>(r2xy.x, r2xy.y, A.AL.r2.z));
     const f2 lld2 = __builtin_elementwise_fma(wnxy, nxy, lld);
@@ -1026,9 +1052,14 @@ namespace pk3 {
 // into one vector load -- here that load would straddle the (qw, qx) pair other code writes as a vector, the struct could no longer
 // be split into registers and landed in LDS (.amdhsa_group_segment_fixed_size 2 240 -> 5 312)
 DEV float opaque(float v) { asm("" : "+v"(v)); return v; }
+// CARRY (the one-link-per-lane substep): the pair X goes to the integration in c.x, c.y instead of being read from B a second time --
+// `opaque` writes the register it reads, so with B.qx, B.qy still live behind it each call was a copy of the pair (two v_mov at the
+// head of the substep); and gravity enters the base's bias acceleration through cross_sub instead of as a negated vector (two v_xor)
+template <bool CARRY = false>
 DEV BaseCtx base_prelude_unit(const KModel &C, const BaseState &B) {
     BaseCtx c;                                           // (c.w .. c.z stay unset: base_integrate_unit reads the quaternion from B)
     const f2 W = {B.qw, B.qz}, X = {opaque(B.qx), opaque(B.qy)};
+    if constexpr (CARRY) { c.x = X.x; c.y = X.y; }
     const f2 W2 = W + W, X2 = X + X;
     const f2 m10 = {-1.f, 0.f};
     f2 A, cxp, cyp, T, czp, np;
@@ -1047,13 +1078,15 @@ DEV BaseCtx base_prelude_unit(const KModel &C, const BaseState &B) {
     c.vb = v3(dot(c.cx, B.vw), dot(c.cy, B.vw), dot(c.cz, B.vw));
     c.V0.a = B.wb; c.V0.l = c.vb;
     c.A0.a = v3(0.f, 0.f, 0.f);
-    c.A0.l = cross_add(c.vb, B.wb, v3(-c.gb.x, -c.gb.y, -c.gb.z));        // -(w x v) - g
+    if constexpr (CARRY) c.A0.l = cross_sub(c.vb, B.wb, c.gb);
+    else c.A0.l = cross_add(c.vb, B.wb, v3(-c.gb.x, -c.gb.y, -c.gb.z));        // -(w x v) - g
     return c;
 }
 // base_integrate<true> with the 3-vector updates and the quaternion product q * (cw, dv) as eight packed multiply-adds on
 // DW = (cw, dv.z), DX = (dv.x, dv.y) -- dv's own (x, y) pair; cw and dv.z are plain producers that write into their halves:
 //   (nw, nz) = w (cw, dz) + x (-dx, dy) + y (-dy, -dx) + z (-dz, cw);   (nx, ny) = w (dx, dy) + x (cw, -dz) + y (dz, cw) + z (-dy, dx)
 // (each component sums its four products in the order z, y, x, w)
+template <bool CARRY = false>
 DEV void base_integrate_unit(const BaseCtx &c, float h, V3 wdot, V3 acl, BaseState &B) {
     V3 aw = fma3(acl.x, c.cx, fma3(acl.y, c.cy, acl.z * c.cz));
     B.vw = fma3(h, aw, B.vw);
@@ -1064,7 +1097,10 @@ DEV void base_integrate_unit(const BaseCtx &c, float h, V3 wdot, V3 acl, BaseSta
     const float sc = hh * fmaf(x2, fmaf(x2, 1.f / 120.f, -1.f / 6.f), 1.f);
     const float cw = fmaf(x2, fmaf(x2, 1.f / 24.f, -0.5f), 1.f);
     const V3 dv = sc * B.wb;
-    const f2 W = {B.qw, B.qz}, X = {opaque(B.qx), opaque(B.qy)};
+    f2 X;
+    if constexpr (CARRY) X = f2{c.x, c.y};
+    else X = f2{opaque(B.qx), opaque(B.qy)};
+    const f2 W = {B.qw, B.qz};
     const f2 DW = {cw, dv.z}, DX = {dv.x, dv.y};
     f2 a, b;
     QG_PKMUL(a, W, DW, "op_sel:[1,1] op_sel_hi:[1,0] neg_lo:[0,1]");                                  // z (-dz, cw)
