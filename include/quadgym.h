@@ -550,6 +550,10 @@ int qg_policy_set_params_device(qg_policy *policy, const float *d_params, void *
  * [n]; value nullable [n] (QG_ERR_ARG when given and has_value == 0; NULL: the critic tower is not evaluated). */
 int qg_policy_forward_device(qg_policy *policy, int32_t n, const float *obs, int32_t obs_stride, const float *eps, float *actions,
                              float *log_prob, float *value, void *stream);
+/* The launch shape qg_policy_forward_device picks for n rows (with_value: a value buffer is given, so the critic tower is launched):
+ * waves per 16-env tile (1 or 4) and output blocks per wave (1, 4 or 16).  Results do not depend on it, only the time does; tests
+ * and A/B timing read it to know which instantiation ran.  Host only, launches nothing. */
+int qg_policy_launch_shape(const qg_policy *policy, int32_t n, int32_t with_value, int32_t *waves, int32_t *blocks);
 
 #ifdef __cplusplus
 }

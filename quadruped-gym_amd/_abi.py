@@ -276,6 +276,7 @@ def load_library():
     lib.qg_policy_get_params.argtypes = [vp, vp]
     lib.qg_policy_set_params_device.argtypes = [vp, vp, vp]
     lib.qg_policy_forward_device.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
+    lib.qg_policy_launch_shape.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("qg_version", "qg_build_id", "qg_last_error", "qg_time_limit_substeps", "qg_walk_state_bytes", "qg_po_state_bytes",
@@ -302,7 +303,7 @@ EXPORTS = (
     "qg_set_dynamics_range", "qg_set_dynamics", "qg_get_dynamics", "qg_clear_dynamics",
     "qg_set_xfrc", "qg_set_xfrc_device", "qg_get_xfrc", "qg_set_push", "qg_clear_xfrc",
     "qg_policy_create", "qg_policy_destroy", "qg_policy_param_count", "qg_policy_set_params", "qg_policy_get_params",
-    "qg_policy_set_params_device", "qg_policy_forward_device",
+    "qg_policy_set_params_device", "qg_policy_forward_device", "qg_policy_launch_shape",
 )
 
 

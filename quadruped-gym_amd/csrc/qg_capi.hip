@@ -2229,6 +2229,26 @@ static void launch_policy(const qg_policy *p, int32_t n, const float *obs, int32
     qg_policy_forward_kernel<WAVES, MB><<<grid, 64 * WAVES, lds, st>>>(p->k, p->d_packed, n, obs, obs_stride, eps, actions, log_prob, value);
 }
 
+// Waves per 16-env tile and output blocks per wave: four waves -- the output blocks of a layer shared out, one barrier per
+// layer -- for nets wider than 64 at every size, and for the narrow ones while one wave per tile would leave SIMDs without a wave; one
+// from there on.  A wave holds the blocks of a 64-wide layer (1 on four waves, 4 on one) or of a 256-wide one (4, 16).
+static void policy_launch_shape(const qg_policy *p, int32_t n, bool with_value, int32_t *waves, int32_t *blocks) {
+    int widest = 0;
+    for (int i = 0; i < p->desc.n_hidden; i++) widest = p->desc.hidden[i] > widest ? p->desc.hidden[i] : widest;
+    const int towers = with_value ? p->k.n_towers : 1;     // no value buffer: the critic tower is not launched
+    const int64_t tiles = ((int64_t)(n + QGP_TILE - 1) / QGP_TILE) * towers;
+    *waves = p->force_waves ? p->force_waves : ((widest > 64 || tiles < (int64_t)p->simds) ? 4 : 1);
+    *blocks = *waves == 4 ? (widest <= 64 ? 1 : 4) : (widest <= 64 ? 4 : 16);
+}
+
+extern "C" int qg_policy_launch_shape(const qg_policy *p, int32_t n, int32_t with_value, int32_t *waves, int32_t *blocks) {
+    if (!p || !waves || !blocks) return fail(QG_ERR_ARG, "qg_policy_launch_shape: null argument");
+    if (n < 1) return fail(QG_ERR_ARG, "qg_policy_launch_shape: n must be >= 1");
+    if (with_value && !p->desc.has_value) return fail(QG_ERR_ARG, "qg_policy_launch_shape: with_value, but the policy has no critic tower");
+    policy_launch_shape(p, n, with_value != 0, waves, blocks);
+    return QG_OK;
+}
+
 extern "C" int qg_policy_forward_device(qg_policy *p, int32_t n, const float *obs, int32_t obs_stride, const float *eps, float *actions,
                                         float *log_prob, float *value, void *stream) {
     if (!p || !obs || !actions) return fail(QG_ERR_ARG, "qg_policy_forward_device: null argument");
@@ -2237,20 +2257,14 @@ extern "C" int qg_policy_forward_device(qg_policy *p, int32_t n, const float *ob
     if (value && !p->desc.has_value) return fail(QG_ERR_ARG, "qg_policy_forward_device: a value buffer, but the policy has no critic tower");
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     const hipStream_t st = (hipStream_t)stream;
-    int widest = 0;
-    for (int i = 0; i < p->desc.n_hidden; i++) widest = p->desc.hidden[i] > widest ? p->desc.hidden[i] : widest;
-    // Waves per 16-env tile: four -- the output blocks of a layer shared out, one barrier per layer -- for nets wider than
-    // 64 at every size, and for the narrow ones while one wave per tile would leave SIMDs without a wave; one from there on.
-    const int towers = value ? p->k.n_towers : 1;          // no value buffer: the critic tower is not launched
-    const int64_t tiles = ((int64_t)(n + QGP_TILE - 1) / QGP_TILE) * towers;
-    const int waves = p->force_waves ? p->force_waves : ((widest > 64 || tiles < (int64_t)p->simds) ? 4 : 1);
-    if (waves == 4) {
-        if (widest <= 64) launch_policy<4, 1>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
-        else launch_policy<4, 4>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
-    } else {
-        if (widest <= 64) launch_policy<1, 4>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
-        else launch_policy<1, 16>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
-    }
+    int32_t waves, blocks;
+    policy_launch_shape(p, n, value != nullptr, &waves, &blocks);
+    if (waves == 4 && blocks == 1) launch_policy<4, 1>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
+    else if (waves == 4 && blocks == 4) launch_policy<4, 4>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
+    else if (waves == 1 && blocks == 4) launch_policy<1, 4>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
+    else if (waves == 1 && blocks == 16) launch_policy<1, 16>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
+    // only if policy_launch_shape and the launch sites above drift apart (tests/test_policy_api.py compares them on the host)
+    else return fail(QG_ERR_LAUNCH, "qg_policy_forward_device: no kernel for %d waves x %d blocks", waves, blocks);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
     return QG_OK;
 }

@@ -185,6 +185,14 @@ class FusedMlpPolicy:
         check(self._lib.qg_policy_set_params_device(self._h, params_tensor.data_ptr(), self._stream_ptr(stream)),
               "qg_policy_set_params_device")
 
+    def launch_shape(self, n: int, value: bool = False):
+        """``(waves per 16-env tile, output blocks per wave)`` of the kernel ``forward`` launches for ``n`` rows, with or without a
+        value buffer.  Results do not depend on it; it tells a test or a timing which instantiation ran."""
+        waves, blocks = C.c_int32(), C.c_int32()
+        check(self._lib.qg_policy_launch_shape(self._h, int(n), int(bool(value)), C.byref(waves), C.byref(blocks)),
+              "qg_policy_launch_shape")
+        return waves.value, blocks.value
+
     def forward(self, obs, actions, eps=None, log_prob=None, value=None, stream=None):
         """One launch: ``actions[n, act_dim]`` (the mean, or ``mean + exp(log_std) * eps`` with standard-normal ``eps[n, act_dim]`` from
         the caller, not clipped), optionally ``log_prob[n]`` and ``value[n]``."""

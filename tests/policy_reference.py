@@ -12,6 +12,96 @@ SHAPES = {
 }
 
 
+# Descriptions chosen against the forward kernel's branches: every launch shape meets an idle wave, a one-block wave, a
+# partly filled and a full wave where it can have them, every class of its chunk loop, and the obs_dim / act_dim / LDS edges.
+# tests/test_policy_api.py holds the census that pins this; tests/test_policy_shapes_gpu.py runs every row at one and four waves.
+SHAPE_TABLE = (
+    # widest layer <= 64: <4,1> and <1,4>
+    (1, (16,), 1), (3, (32,), 3), (16, (48,), 4), (17, (64,), 5), (33, (16, 64), 12), (63, (64, 16), 13),
+    (64, (48, 32, 16), 16), (65, (16, 16, 16), 2), (512, (64, 64, 64), 12), (260, (32, 48), 7),
+    (40, (16, 48, 64), 8),        # third hidden layer wider than the first: it sizes LDS buffer 1
+    # wider: <4,4> and <1,16>
+    (1, (80,), 1), (15, (128,), 16), (33, (144,), 12), (100, (192,), 6), (260, (208,), 12), (511, (256,), 9),
+    (5, (16, 256), 12), (260, (256, 16), 3), (48, (80, 256, 48), 12), (129, (240, 96, 176), 15),
+    (512, (256, 256, 256), 16), (20, (16, 32, 240), 4), (257, (112, 224), 1),
+)
+
+TILE = 16                        # envs per workgroup
+
+
+def launch_shape(hidden, n, towers, simds, force_waves=0):
+    """``(waves per env tile, output blocks per wave)`` by the rule of DESIGN 4.8: four waves for nets wider than 64 at every size and
+    for the narrow ones while tiles x towers is below the SIMD count, one from there on (``force_waves``: QG_POLICY_WAVES); a wave
+    holds 1 / 4 blocks on four waves and 4 / 16 on one, by whether the widest layer fits 64."""
+    widest = max(hidden)
+    tiles = -(-n // TILE)
+    waves = force_waves if force_waves in (1, 4) else (4 if widest > 64 or tiles * towers < simds else 1)
+    narrow = widest <= 64
+    return waves, {4: 1 if narrow else 4, 1: 4 if narrow else 16}[waves]
+
+
+def conditions(desc, waves):
+    """The branch conditions of the forward pass that ``desc = (obs_dim, hidden, act_dim)`` exercises when launched with ``waves``
+    waves per tile: a set of ``(waves, blocks, name)``.
+
+    Per hidden layer (a wave ``w`` of ``W`` owns the output blocks ``w, w + W, ..`` of the layer's ``nb``; it runs ``blocks``
+    accumulators): ``hidden:idle`` a wave with no block, ``hidden:single`` one block on a wave that has several accumulators (the
+    one-accumulator path), ``hidden:partial`` more than one block but not all accumulators (the rest run on clamped weights and are
+    not stored), ``hidden:full``, and ``hidden:uneven`` when the busy waves of one layer hold different counts.
+    Per layer, the output layer included, with ``nq`` input blocks of 16 and a chunk loop that advances by two half-chunks of
+    ``kq = 16 / blocks`` input blocks: ``chunk:nq<kq``, ``chunk:second-half-off`` (the last round's second half-chunk entirely guarded
+    off), ``chunk:multiple`` (``nq`` a multiple of ``2 kq``), ``chunk:second-half-partial`` (``nq % 2 kq > kq``) and ``chunk:rounds>1``.
+    And the edges of the description itself: ``obs:no-padding``, ``obs<4``, ``obs=512``, ``act:partial-group``, ``act<4``,
+    ``lds1:hidden2`` (buffer 1 sized by the third hidden layer), ``lds0:hidden1`` (buffer 0 by the second, not by the observation)."""
+    obs_dim, hidden, act_dim = desc
+    _, blocks = launch_shape(hidden, 1, 1, 1, force_waves=waves)
+    kq = 16 // blocks
+    names = set()
+    for h in hidden:
+        nb = h // 16
+        counts = [len(range(w, nb, waves)) for w in range(waves)]
+        for c in counts:
+            if c == 0:
+                names.add("hidden:idle")
+            elif c == 1 and blocks > 1:
+                names.add("hidden:single")
+            elif c < blocks:
+                names.add("hidden:partial")
+            else:
+                assert c == blocks
+                names.add("hidden:full")
+        if len({c for c in counts if c}) > 1:
+            names.add("hidden:uneven")
+    for width in (obs_dim,) + tuple(hidden):
+        nq = -(-width // 16)
+        rest = nq % (2 * kq)
+        if nq < kq:
+            names.add("chunk:nq<kq")
+        if rest == 0:
+            names.add("chunk:multiple")
+        elif rest <= kq:
+            names.add("chunk:second-half-off")
+        else:
+            names.add("chunk:second-half-partial")
+        if nq > 2 * kq:
+            names.add("chunk:rounds>1")
+    if obs_dim % 16 == 0:
+        names.add("obs:no-padding")
+    if obs_dim < 4:
+        names.add("obs<4")
+    if obs_dim == 512:
+        names.add("obs=512")
+    if act_dim % 4:
+        names.add("act:partial-group")
+    if act_dim < 4:
+        names.add("act<4")
+    if len(hidden) > 2 and hidden[2] > hidden[0]:
+        names.add("lds1:hidden2")
+    if len(hidden) > 1 and hidden[1] > 16 * -(-obs_dim // 16):
+        names.add("lds0:hidden1")
+    return {(waves, blocks, name) for name in names}
+
+
 def tower_shapes(obs_dim, hidden, out_dim):
     dims = (obs_dim,) + tuple(hidden)
     return [(dims[i + 1], dims[i]) for i in range(len(hidden))] + [(out_dim, dims[-1])]

@@ -1,8 +1,10 @@
 """The fused MLP policy without a GPU: the float64 checker of tests/policy_reference.py against torch, the host-only part of the C
-ABI (qg_policy_param_count, argument validation before the device check, no CPU backend) and the parameter loaders' flat order."""
+ABI (qg_policy_param_count, argument validation before the device check, no CPU backend), the parameter loaders' flat order, and
+the two censuses of tests/policy_reference.py's SHAPE_TABLE: the branch conditions it reaches, and the kernel instantiations."""
 import ctypes as C
 import math
 import os
+import re
 import sys
 
 import numpy as np
@@ -177,3 +179,118 @@ def test_loaders_refuse_what_the_kernel_cannot_run():
     with pytest.raises(ValueError):
         p.load_layers([(np.zeros((64, 33)), np.zeros(64))])      # too few layers
     assert math.isclose(0.5 * math.log(2 * math.pi), 0.91893853320467274178)
+
+
+# ---- the shape table of tests/test_policy_shapes_gpu.py ----------------------------------------------------------------------------
+def _ids(desc):
+    return "%d-%s-%d" % (desc[0], "-".join(str(h) for h in desc[1]), desc[2])
+
+
+# Every branch condition of the forward pass (policy_reference.conditions) in every launch shape <waves, blocks> where it can occur.
+# It cannot occur: <4,1> holds one block per wave (no single / partial / uneven) and its 32-block round covers obs_dim <= 512 in one;
+# on one wave no wave is idle and none differs from another; <1,16> advances by single input blocks (nq >= kq = 1, no partly live
+# half-chunk).  Written out, so that a row deleted from the table fails here.
+_EDGES = {"obs:no-padding", "obs<4", "obs=512", "act:partial-group", "act<4", "lds1:hidden2", "lds0:hidden1"}
+REQUIRED = {
+    (4, 1): _EDGES | {"hidden:idle", "hidden:full",
+                      "chunk:nq<kq", "chunk:second-half-off", "chunk:multiple", "chunk:second-half-partial"},
+    (4, 4): _EDGES | {"hidden:idle", "hidden:single", "hidden:partial", "hidden:full", "hidden:uneven",
+                      "chunk:nq<kq", "chunk:second-half-off", "chunk:multiple", "chunk:second-half-partial", "chunk:rounds>1"},
+    (1, 4): _EDGES | {"hidden:single", "hidden:partial", "hidden:full",
+                      "chunk:nq<kq", "chunk:second-half-off", "chunk:multiple", "chunk:second-half-partial", "chunk:rounds>1"},
+    (1, 16): _EDGES | {"hidden:single", "hidden:partial", "hidden:full",
+                       "chunk:second-half-off", "chunk:multiple", "chunk:rounds>1"},
+}
+
+
+def _census(table):
+    return set().union(*(R.conditions(desc, waves) for desc in table for waves in (1, 4)))
+
+
+def test_shape_table_reaches_every_branch_condition():
+    required = {(w, b, name) for (w, b), names in REQUIRED.items() for name in names}
+    reached = _census(R.SHAPE_TABLE)
+    assert required - reached == set(), "branch conditions no row of SHAPE_TABLE reaches"
+    assert reached - required == set(), "conditions() names something the census does not require"
+
+
+def test_conditions_of_known_layers():
+    """conditions() against block counts worked out by hand: 80 / 144 / 208 / 240 wide on four waves are 2/1/1/1, 3/2/2/2, 4/3/3/3 and
+    4/4/4/3 blocks per wave."""
+    def hidden(desc, waves):
+        return {name for _, _, name in R.conditions(desc, waves) if name.startswith("hidden:")}
+    assert hidden((1, (80,), 1), 4) == {"hidden:single", "hidden:partial", "hidden:uneven"}
+    assert hidden((33, (144,), 12), 4) == {"hidden:partial", "hidden:uneven"}
+    assert hidden((260, (208,), 12), 4) == {"hidden:partial", "hidden:full", "hidden:uneven"}
+    assert hidden((129, (240, 96, 176), 15), 4) == {"hidden:partial", "hidden:full", "hidden:uneven", "hidden:single"}
+    assert hidden((512, (256, 256, 256), 16), 4) == {"hidden:full"} == hidden((512, (256, 256, 256), 16), 1)
+    assert hidden((65, (16, 16, 16), 2), 4) == {"hidden:idle", "hidden:full"} and hidden((65, (16, 16, 16), 2), 1) == {"hidden:single"}
+    assert hidden((20, (16, 32, 240), 4), 1) == {"hidden:single", "hidden:partial"}
+    assert {b for _, b, _ in R.conditions((1, (80,), 1), 1)} == {16} and {b for _, b, _ in R.conditions((1, (16,), 1), 4)} == {1}
+    # 65 inputs are five blocks: on <1,4> (rounds of 8) the second half-chunk is partly live; on <4,1> (rounds of 32) it is off
+    assert (1, 4, "chunk:second-half-partial") in R.conditions((65, (16, 16, 16), 2), 1)
+    assert (4, 1, "chunk:second-half-off") in R.conditions((65, (16, 16, 16), 2), 4)
+
+
+def test_launch_sites_equal_what_the_table_launches():
+    """Every instantiation of qg_policy_forward_kernel the library can launch is one the table reaches (each row runs at one and at
+    four waves in tests/test_policy_shapes_gpu.py), and the other way round: a fifth launch site fails here until a row reaches it."""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "quadruped-gym_amd", "csrc", "qg_capi.hip")).read()
+    sites = {(int(w), int(b)) for w, b in re.findall(r"launch_policy<\s*(\d+)\s*,\s*(\d+)\s*>\s*\(", src)}
+    assert sites == {(4, 1), (4, 4), (1, 4), (1, 16)}
+    kernels = {(int(w), int(b)) for w, b in re.findall(r"qg_policy_forward_kernel<\s*(\w+)\s*,\s*(\w+)\s*>", src) if w.isdigit()}
+    assert kernels == set()                            # the kernel is launched through launch_policy alone
+    reached = {R.launch_shape(hidden, n, towers, 1024, force) for _, hidden, _ in R.SHAPE_TABLE for n in (83, 16 * 1024)
+               for towers in (1, 2) for force in (1, 4)}
+    assert reached == sites == set(REQUIRED)
+    # the rule itself (DESIGN 4.8), on the numbers of an MI355X: 1024 SIMDs
+    assert R.launch_shape((64, 64), 4096, 1, 1024) == (4, 1) and R.launch_shape((64, 64), 16384, 1, 1024) == (1, 4)
+    assert R.launch_shape((64, 64), 16369, 1, 1024) == (1, 4) and R.launch_shape((64, 64), 16368, 1, 1024) == (4, 1)
+    assert R.launch_shape((64, 64), 8192, 2, 1024) == (1, 4) and R.launch_shape((64, 64), 8176, 2, 1024) == (4, 1)
+    assert R.launch_shape((64, 80), 1 << 20, 2, 1024) == (4, 4) and R.launch_shape((256,), 1, 1, 1024, force_waves=1) == (1, 16)
+
+
+@pytest.mark.parametrize("value", [False, True])
+@pytest.mark.parametrize("desc", R.SHAPE_TABLE, ids=_ids)
+def test_param_count_over_the_table(desc, value):
+    obs_dim, hidden, act_dim = desc
+    d = _abi.QgPolicyDesc.make(obs_dim, hidden, act_dim, False, value)
+    want = act_dim                                     # log_std; then (in + 1) x out per layer of each tower
+    for out_dim in (act_dim, 1)[:2 if value else 1]:
+        dims = (obs_dim,) + hidden + (out_dim,)
+        want += sum((dims[k] + 1) * dims[k + 1] for k in range(len(dims) - 1))
+    assert _abi.load_library().qg_policy_param_count(C.byref(d)) == R.param_count(obs_dim, hidden, act_dim, value) == want
+
+
+@pytest.mark.parametrize("desc", R.SHAPE_TABLE, ids=_ids)
+def test_checker_equals_torch_float64_over_the_table(desc):
+    obs_dim, hidden, act_dim = desc
+    rng = np.random.default_rng(1)
+    out_tanh = bool(R.SHAPE_TABLE.index(desc) % 2)
+    actor = R.random_layers(rng, R.tower_shapes(obs_dim, hidden, act_dim), "linear")
+    critic = R.random_layers(rng, R.tower_shapes(obs_dim, hidden, 1), "sb3", head_gain=1.0)
+    obs = (rng.standard_normal((37, obs_dim)) * np.logspace(-2, 1, obs_dim)).astype(np.float32)
+    mean, _, _, value = R.forward(actor, np.zeros(act_dim), obs, critic=critic, out_tanh=out_tanh)
+    with torch.no_grad():
+        x = torch.from_numpy(obs).double()
+        t_mean = _sequential(actor, out_tanh, torch.float64)(x).numpy()
+        t_value = _sequential(critic, False, torch.float64)(x).numpy()[:, 0]
+    assert mean.shape == (37, act_dim) and value.shape == (37,)
+    assert np.abs(mean - t_mean).max() <= 1e-12
+    assert np.abs(value - t_value).max() <= 1e-12 * max(1.0, np.abs(t_value).max())
+
+
+@pytest.mark.parametrize("desc", [(512, (256, 256, 256), 16), (1, (16,), 1)], ids=_ids)
+def test_descriptions_at_the_limits_are_accepted(desc):
+    obs_dim, hidden, act_dim = desc
+    lib = _abi.load_library()
+    for value in (False, True):
+        d = _abi.QgPolicyDesc.make(obs_dim, hidden, act_dim, True, value)
+        assert lib.qg_policy_param_count(C.byref(d)) == R.param_count(obs_dim, hidden, act_dim, value) > 0
+
+
+def test_launch_shape_needs_a_handle():
+    lib = _abi.load_library()
+    waves, blocks = C.c_int32(-7), C.c_int32(-7)
+    assert lib.qg_policy_launch_shape(None, 83, 0, C.byref(waves), C.byref(blocks)) == QG_ERR_ARG
+    assert (waves.value, blocks.value) == (-7, -7)
