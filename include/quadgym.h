@@ -555,6 +555,75 @@ int qg_policy_forward_device(qg_policy *policy, int32_t n, const float *obs, int
  * and A/B timing read it to know which instantiation ran.  Host only, launches nothing. */
 int qg_policy_launch_shape(const qg_policy *policy, int32_t n, int32_t with_value, int32_t *waves, int32_t *blocks);
 
+/* ---- running observation and reward normalisation (SB3's VecNormalize) on the device ---------------------------------------------------
+ * A qg_norm keeps, in f64 on the device, a running mean and variance per observation column, a discounted return per env and the
+ * running variance of those returns, and normalises the rows a step left on the device: the semantics of Stable-Baselines3 2.x
+ * VecNormalize / RunningMeanStd.  Like qg_policy it is independent of qg_sim and touches no step kernel.
+ *
+ * A running statistic holds mean (initially 0), var (1) and count (1e-4).  update(batch of n rows), with bm the column means and bv
+ * the population variances (divisor n) of the batch:
+ *   delta = bm - mean;  tot = count + n
+ *   mean' = mean + delta * n / tot
+ *   M2    = var * count + bv * n + delta^2 * count * n / tot
+ *   var'  = M2 / tot;   count' = tot
+ * One training step over the n envs, in this order:
+ *   1. norm_obs:     obs_rms.update(obs)
+ *   2. obs_out     = f32(clip((obs - mean) / sqrt(var + epsilon), -clip_obs, clip_obs))          with the updated statistics
+ *   3. returns     = returns * gamma + reward  (f64, one per env);  ret_rms.update(returns), a one-column statistic
+ *   4. norm_reward: reward_out = f32(clip(reward / sqrt(ret_var + epsilon), -clip_reward, clip_reward))   with the updated ret_var
+ *   5. returns[done] = 0
+ * With training == 0 steps 1, 3 and 5 are skipped (no word of the state changes); 2 and 4 use the statistics as they stand.  A flag
+ * that is switched off copies the value through unchanged.  The quotient is rounded to f32 once and then clipped, so a clipped
+ * element is exactly +-f32(clip).
+ *
+ * Batch moments are accumulated in f64 (shifted sums within a tile of rows, Chan's merge above that) and combined in an order that
+ * depends on (n, obs_dim) alone: no floating-point atomics, results are bit-identical from run to run and under graph replay.  A
+ * row's output depends on the statistics and on that row alone.  Outputs for non-finite inputs are unspecified (the device code is
+ * compiled with finite-math assumptions): a NaN reward would also poison the return statistic for good.
+ *
+ * Ordering: the *_device calls follow the contract of the other *_device entry points (they enqueue on the caller's stream, return
+ * at once and may be captured into a hipGraph; everything that changes from call to call lives in device memory, so a captured step
+ * replays correctly any number of times).  A training step is three kernel launches, an apply one, an update two.  qg_norm_create,
+ * qg_norm_destroy, qg_norm_get_state and qg_norm_set_state wait for the device and must not be called during a capture. */
+typedef struct qg_norm qg_norm;
+typedef struct qg_norm_desc {
+    int32_t struct_size;       /* sizeof(qg_norm_desc): checked */
+    int32_t obs_dim;           /* 1 .. 512 */
+    int32_t n_envs;            /* >= 1 */
+    double gamma;              /* finite, >= 0 (SB3: 0.99) */
+    double epsilon;            /* finite, >= 0 (1e-8) */
+    double clip_obs;           /* > 0 (10) */
+    double clip_reward;        /* > 0 (10) */
+    int32_t norm_obs;          /* 0 or 1 */
+    int32_t norm_reward;       /* 0 or 1 */
+} qg_norm_desc;
+#define QG_NORM_DONE_U8 0      /* done is uint8 (the walking and partially observable envs' buffer) */
+#define QG_NORM_DONE_F32 1     /* done is f32 (the last column of the plain env's packed row) */
+/* Validation (QG_ERR_ARG) comes before the device check (QG_ERR_DEVICE: there is no CPU backend). */
+int qg_norm_create(int32_t device_id, const qg_norm_desc *desc, qg_norm **out);
+int qg_norm_destroy(qg_norm *norm);
+/* One step as above; n must equal n_envs.  Device pointers; strides in elements.  obs rows of obs_dim floats at in_stride /
+ * out_stride >= obs_dim; obs_out == obs_in (in place) is allowed, and so is reward_out == reward_in.  reward_in nullable: NULL is an
+ * observation-only step (steps 1 and 2).  done nullable (no return is ever cleared), of the type done_kind names.  With the strides
+ * one call normalises a packed [n][obs_dim + 2] row in place: obs at column 0, reward at column obs_dim, done at obs_dim + 1, every
+ * stride obs_dim + 2.  Loads and stores are 16 bytes per lane where obs_dim and both strides are multiples of 4 and both bases are
+ * 16-byte aligned, 4 bytes otherwise (the packed stride of 35). */
+int qg_norm_step_device(qg_norm *norm, int32_t n, const float *obs_in, int32_t in_stride, float *obs_out, int32_t out_stride,
+                        const float *reward_in, int32_t reward_in_stride, float *reward_out, int32_t reward_out_stride, const void *done,
+                        int32_t done_kind, int32_t done_stride, int32_t training, void *stream);
+/* Step 1 alone, whatever norm_obs says, for any n >= 1: what SB3 does with the observations reset() returns. */
+int qg_norm_update_obs_device(qg_norm *norm, int32_t n, const float *obs, int32_t stride, void *stream);
+/* Step 2 alone with the statistics as they stand, for any n >= 1: terminal observations, evaluation, a second consumer. */
+int qg_norm_apply_obs_device(qg_norm *norm, int32_t n, const float *obs_in, int32_t in_stride, float *obs_out, int32_t out_stride,
+                             void *stream);
+/* returns = 0 for every env (SB3's reset()). */
+int qg_norm_reset_returns_device(qg_norm *norm, void *stream);
+/* The whole state from / to host f64 arrays: mean[obs_dim], var[obs_dim], returns[n_envs] and the scalars.  The round trip is exact. */
+int qg_norm_get_state(qg_norm *norm, double *mean, double *var, double *count, double *ret_mean, double *ret_var, double *ret_count,
+                      double *returns);
+int qg_norm_set_state(qg_norm *norm, const double *mean, const double *var, double count, double ret_mean, double ret_var,
+                      double ret_count, const double *returns);
+
 #ifdef __cplusplus
 }
 #endif

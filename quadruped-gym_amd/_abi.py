@@ -156,6 +156,25 @@ class QgPolicyDesc(C.Structure):
         return d
 
 
+class QgNormDesc(C.Structure):
+    """``qg_norm_desc``: a running normaliser's shape and constants (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("obs_dim", C.c_int32), ("n_envs", C.c_int32), ("gamma", C.c_double),
+                ("epsilon", C.c_double), ("clip_obs", C.c_double), ("clip_reward", C.c_double), ("norm_obs", C.c_int32),
+                ("norm_reward", C.c_int32)]
+
+    @classmethod
+    def make(cls, obs_dim, n_envs, gamma=0.99, epsilon=1e-8, clip_obs=10.0, clip_reward=10.0, norm_obs=True, norm_reward=True):
+        d = cls()
+        d.struct_size = C.sizeof(cls)
+        d.obs_dim, d.n_envs = int(obs_dim), int(n_envs)
+        d.gamma, d.epsilon, d.clip_obs, d.clip_reward = float(gamma), float(epsilon), float(clip_obs), float(clip_reward)
+        d.norm_obs, d.norm_reward = int(bool(norm_obs)), int(bool(norm_reward))
+        return d
+
+
+NORM_DONE_U8, NORM_DONE_F32 = 0, 1
+
+
 def package_dir() -> str:
     return os.path.dirname(os.path.abspath(__file__))
 
@@ -277,6 +296,15 @@ def load_library():
     lib.qg_policy_set_params_device.argtypes = [vp, vp, vp]
     lib.qg_policy_forward_device.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
     lib.qg_policy_launch_shape.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    i32, f64 = C.c_int32, C.c_double
+    lib.qg_norm_create.argtypes = [i32, C.POINTER(QgNormDesc), C.POINTER(vp)]
+    lib.qg_norm_destroy.argtypes = [vp]
+    lib.qg_norm_step_device.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp]
+    lib.qg_norm_update_obs_device.argtypes = [vp, i32, vp, i32, vp]
+    lib.qg_norm_apply_obs_device.argtypes = [vp, i32, vp, i32, vp, i32, vp]
+    lib.qg_norm_reset_returns_device.argtypes = [vp, vp]
+    lib.qg_norm_get_state.argtypes = [vp] * 8
+    lib.qg_norm_set_state.argtypes = [vp, vp, vp, f64, f64, f64, f64, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("qg_version", "qg_build_id", "qg_last_error", "qg_time_limit_substeps", "qg_walk_state_bytes", "qg_po_state_bytes",
@@ -304,6 +332,8 @@ EXPORTS = (
     "qg_set_xfrc", "qg_set_xfrc_device", "qg_get_xfrc", "qg_set_push", "qg_clear_xfrc",
     "qg_policy_create", "qg_policy_destroy", "qg_policy_param_count", "qg_policy_set_params", "qg_policy_get_params",
     "qg_policy_set_params_device", "qg_policy_forward_device", "qg_policy_launch_shape",
+    "qg_norm_create", "qg_norm_destroy", "qg_norm_step_device", "qg_norm_update_obs_device", "qg_norm_apply_obs_device",
+    "qg_norm_reset_returns_device", "qg_norm_get_state", "qg_norm_set_state",
 )
 
 

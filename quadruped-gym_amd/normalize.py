@@ -1,0 +1,277 @@
+"""``RunningNormalizer`` and ``DeviceVecNormalize`` -- running observation and reward normalisation (SB3's ``VecNormalize``) on rows
+that stay on the GPU (``qg_norm_*`` of ``include/quadgym.h``, ``csrc/qg_norm.hip``).
+
+A training step is three small launches of hand-written gfx950 code on the caller's stream: f64 column moments of the batch, a
+fixed-order combine with the running merge, and the normalise pass.  PyTorch is plumbing only: it owns the tensors and the stream.
+There is no CPU path.  Outputs for non-finite inputs are unspecified (train the walking envs with ``nan_direction=False``).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from ._abi import QgNormDesc, check
+
+
+class RunningNormalizer:
+    """Per-column running mean / variance of the observations, rewards divided by the running standard deviation of the discounted
+    return, both clipped: the semantics of Stable-Baselines3 2.x ``VecNormalize`` (restated in ``include/quadgym.h``), with the
+    statistics in float64 on the device.  ``training = False`` freezes every word of the state.
+
+    ``state_dict()`` uses the attribute names of SB3's ``VecNormalize`` (``obs_rms.mean`` ...); the names are taken from SB3's
+    source and this has NOT been run against an SB3 pickle (the package is not a dependency)."""
+
+    def __init__(self, num_envs: int, obs_dim: int, gamma: float = 0.99, epsilon: float = 1e-8, clip_obs: float = 10.0,
+                 clip_reward: float = 10.0, norm_obs: bool = True, norm_reward: bool = True, device: int = 0):
+        self._lib = _abi.load_library()
+        self.num_envs, self.obs_dim, self.device = int(num_envs), int(obs_dim), int(device)
+        self.gamma, self.epsilon, self.clip_obs, self.clip_reward = float(gamma), float(epsilon), float(clip_obs), float(clip_reward)
+        self.norm_obs, self.norm_reward = bool(norm_obs), bool(norm_reward)
+        self.training = True
+        self.desc = QgNormDesc.make(self.obs_dim, self.num_envs, gamma, epsilon, clip_obs, clip_reward, norm_obs, norm_reward)
+        h = C.c_void_p()
+        check(self._lib.qg_norm_create(self.device, C.byref(self.desc), C.byref(h)), "qg_norm_create")
+        self._h = h
+
+    # -- lifetime ---------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.qg_norm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- tensor checks ----------------------------------------------------------------------
+    def _stream_ptr(self, stream):
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        return C.c_void_p(stream.cuda_stream)
+
+    def _check_obs(self, obs, n=None, what="obs"):
+        """``[n, obs_dim]`` float32 whose rows are contiguous; the row stride is free.  Returns ``(n, row stride in floats)``."""
+        import torch
+        if not obs.is_cuda or obs.device.index != self.device:
+            raise ValueError(f"{what} must live on cuda:{self.device}")
+        if obs.dim() != 2 or obs.shape[1] != self.obs_dim or obs.dtype != torch.float32 or obs.shape[0] < 1 or \
+                (n is not None and obs.shape[0] != n):
+            rows = "n" if n is None else n
+            raise ValueError(f"{what}: expected a float32 tensor of shape ({rows}, {self.obs_dim}), got {obs.dtype} {tuple(obs.shape)}")
+        if obs.stride(1) != 1 or (obs.shape[0] > 1 and obs.stride(0) < self.obs_dim):
+            raise ValueError(f"{what}: rows must be contiguous, at a row stride >= {self.obs_dim}; got strides {tuple(obs.stride())}")
+        return int(obs.shape[0]), int(obs.stride(0)) if obs.shape[0] > 1 else max(int(obs.stride(0)), self.obs_dim)
+
+    def _check_vec(self, t, dtypes, what):
+        """``[num_envs]`` of one of ``dtypes`` at any positive element stride.  Returns the stride."""
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{what} must live on cuda:{self.device}")
+        if t.dim() != 1 or t.shape[0] != self.num_envs or t.dtype not in dtypes:
+            raise ValueError(f"{what}: expected a tensor of shape ({self.num_envs},) and dtype in {dtypes}, got {t.dtype} {tuple(t.shape)}")
+        if self.num_envs > 1 and t.stride(0) < 1:
+            raise ValueError(f"{what}: the element stride must be >= 1, got {t.stride(0)}")
+        return max(int(t.stride(0)), 1)
+
+    # -- device path ------------------------------------------------------------------------
+    def step(self, obs, reward=None, done=None, obs_out=None, reward_out=None, stream=None):
+        """One step over the ``num_envs`` rows: ``obs`` float32 ``[N, obs_dim]`` (strided rows allowed), ``reward`` float32 ``[N]``
+        or None (an observation-only step), ``done`` uint8 / bool / float32 ``[N]`` or None.  ``obs_out`` / ``reward_out`` default to
+        in place.  Returns ``(obs_out, reward_out)``."""
+        import torch
+        _, in_stride = self._check_obs(obs, self.num_envs)
+        obs_out = obs if obs_out is None else obs_out
+        _, out_stride = self._check_obs(obs_out, self.num_envs, "obs_out")
+        r_ptr = ro_ptr = d_ptr = None
+        r_stride = ro_stride = d_stride = 1
+        kind = _abi.NORM_DONE_U8
+        if reward is not None:
+            r_stride = self._check_vec(reward, (torch.float32,), "reward")
+            reward_out = reward if reward_out is None else reward_out
+            ro_stride = self._check_vec(reward_out, (torch.float32,), "reward_out")
+            r_ptr, ro_ptr = reward.data_ptr(), reward_out.data_ptr()
+            if done is not None:
+                d_stride = self._check_vec(done, (torch.uint8, torch.bool, torch.float32), "done")
+                kind = _abi.NORM_DONE_F32 if done.dtype == torch.float32 else _abi.NORM_DONE_U8
+                d_ptr = done.data_ptr()
+        elif done is not None or reward_out is not None:
+            raise ValueError("done and reward_out need a reward")
+        check(self._lib.qg_norm_step_device(self._h, self.num_envs, obs.data_ptr(), in_stride, obs_out.data_ptr(), out_stride, r_ptr,
+                                            r_stride, ro_ptr, ro_stride, d_ptr, kind, d_stride, int(bool(self.training)),
+                                            self._stream_ptr(stream)), "qg_norm_step_device")
+        return obs_out, reward_out
+
+    def step_packed(self, packed, out=None, stream=None):
+        """The plain env's packed rows ``[N, obs_dim + 2]`` (obs, reward, done as float32) in one call, in place unless ``out`` is
+        given (its done column is then copied over).  Returns the normalised packed tensor."""
+        import torch
+        D = self.obs_dim
+        for t, what in ((packed, "packed"),) + (((out, "out"),) if out is not None else ()):
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError(f"{what} must live on cuda:{self.device}")
+            if tuple(t.shape) != (self.num_envs, D + 2) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{what}: expected a contiguous float32 tensor of shape ({self.num_envs}, {D + 2}), got {t.dtype} {tuple(t.shape)}")
+        dst = packed if out is None else out
+        self.step(packed[:, :D], packed[:, D], packed[:, D + 1], obs_out=dst[:, :D], reward_out=dst[:, D], stream=stream)
+        if out is not None:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+                out[:, D + 1].copy_(packed[:, D + 1])
+        return dst
+
+    def update_obs(self, obs, stream=None):
+        """``obs_rms.update(obs)`` alone, for any number of rows (the observations of ``reset()``)."""
+        n, stride = self._check_obs(obs)
+        check(self._lib.qg_norm_update_obs_device(self._h, n, obs.data_ptr(), stride, self._stream_ptr(stream)), "qg_norm_update_obs_device")
+
+    def normalize_obs(self, obs, out=None, stream=None):
+        """Step 2 alone with the statistics as they stand, for any number of rows; in place unless ``out`` is given."""
+        n, in_stride = self._check_obs(obs)
+        out = obs if out is None else out
+        _, out_stride = self._check_obs(out, n, "out")
+        check(self._lib.qg_norm_apply_obs_device(self._h, n, obs.data_ptr(), in_stride, out.data_ptr(), out_stride, self._stream_ptr(stream)),
+              "qg_norm_apply_obs_device")
+        return out
+
+    def reset_returns(self, stream=None):
+        check(self._lib.qg_norm_reset_returns_device(self._h, self._stream_ptr(stream)), "qg_norm_reset_returns_device")
+
+    # -- state ------------------------------------------------------------------------------
+    def state_dict(self):
+        """NumPy float64 (waits for the device): ``obs_rms.mean``, ``obs_rms.var``, ``obs_rms.count``, ``ret_rms.mean``,
+        ``ret_rms.var``, ``ret_rms.count``, ``returns``."""
+        mean, var = np.empty(self.obs_dim), np.empty(self.obs_dim)
+        returns = np.empty(self.num_envs)
+        s = [C.c_double() for _ in range(4)]
+        check(self._lib.qg_norm_get_state(self._h, mean.ctypes.data, var.ctypes.data, *[C.addressof(x) for x in s], returns.ctypes.data),
+              "qg_norm_get_state")
+        return {"obs_rms.mean": mean, "obs_rms.var": var, "obs_rms.count": np.float64(s[0].value), "ret_rms.mean": np.float64(s[1].value),
+                "ret_rms.var": np.float64(s[2].value), "ret_rms.count": np.float64(s[3].value), "returns": returns}
+
+    def load_state_dict(self, sd):
+        mean = np.ascontiguousarray(sd["obs_rms.mean"], dtype=np.float64)
+        var = np.ascontiguousarray(sd["obs_rms.var"], dtype=np.float64)
+        returns = np.ascontiguousarray(sd["returns"], dtype=np.float64)
+        if mean.shape != (self.obs_dim,) or var.shape != (self.obs_dim,) or returns.shape != (self.num_envs,):
+            raise ValueError(f"the state was taken from a normaliser of another shape: mean {mean.shape}, var {var.shape}, returns {returns.shape}")
+        check(self._lib.qg_norm_set_state(self._h, mean.ctypes.data, var.ctypes.data, float(sd["obs_rms.count"]), float(sd["ret_rms.mean"]),
+                                          float(sd["ret_rms.var"]), float(sd["ret_rms.count"]), returns.ctypes.data), "qg_norm_set_state")
+
+
+class DeviceVecNormalize:
+    """``VecNormalize`` around ``QuadrupedVecEnv``, ``WalkingQuadrupedVecEnv`` or ``POWalkingQuadrupedVecEnv`` whose ``step_tensor``
+    stays on the device: the env's launch, then the normaliser's on the same stream.  Keyword options are ``RunningNormalizer``'s.
+    The NumPy ``reset()`` / ``step()`` are a cold path built for correctness only (they upload the rows and run the same device
+    calls).  Every other attribute passes through to the wrapped env."""
+
+    def __init__(self, venv, **options):
+        self.venv = venv
+        obs_dim = int(getattr(venv, "obs_dim", 0) or venv.observation_space.shape[0])
+        self._packed = not hasattr(venv, "_w")              # the plain env steps into packed [N, obs_dim + 2] rows
+        device = options.pop("device", venv._sim.device)
+        self.normalizer = RunningNormalizer(venv.num_envs, obs_dim, device=device, **options)
+        self._obs_dim = obs_dim
+        self.old_obs = self.old_reward = None
+
+    def __getattr__(self, name):                            # only reached for what this class does not define
+        if name == "venv":
+            raise AttributeError(name)
+        return getattr(self.venv, name)
+
+    @property
+    def training(self):
+        return self.normalizer.training
+
+    @training.setter
+    def training(self, on):
+        self.normalizer.training = bool(on)
+
+    # -- device path ------------------------------------------------------------------------
+    def step_tensor(self, actions, *args, **kwargs):
+        """The wrapped env's ``step_tensor`` with its signature; the buffers it fills come back normalised in place."""
+        stream = kwargs.get("stream")
+        if self._packed:
+            packed = self.venv.step_tensor(actions, *args, **kwargs)
+            return self.normalizer.step_packed(packed, stream=stream)
+        names = ("obs", "reward", "done", "components", "terminal_obs")
+        bound = dict(zip(names, args))
+        bound.update({k: v for k, v in kwargs.items() if k in names})
+        self.venv.step_tensor(actions, *args, **kwargs)
+        self.normalizer.step(bound["obs"], bound["reward"], bound["done"], stream=stream)
+        if bound.get("terminal_obs") is not None:
+            self.normalizer.normalize_obs(bound["terminal_obs"], stream=stream)
+        return None
+
+    # -- NumPy cold path --------------------------------------------------------------------
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.normalizer.device)
+
+    def _normalize_rows(self, rows):
+        import torch
+        t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float32)).to(self._dev())
+        return self.normalizer.normalize_obs(t).cpu().numpy()
+
+    def reset(self):
+        import torch
+        obs = np.ascontiguousarray(self.venv.reset(), dtype=np.float32)
+        self.old_obs = obs.copy()
+        t = torch.from_numpy(obs).to(self._dev())
+        self.normalizer.reset_returns()
+        if self.normalizer.training and self.normalizer.norm_obs:
+            self.normalizer.update_obs(t)
+        return self.normalizer.normalize_obs(t).cpu().numpy()
+
+    def step_async(self, actions):
+        self.venv.step_async(actions)
+
+    def step_wait(self):
+        import torch
+        obs, rew, done, infos = self.venv.step_wait()
+        obs, rew = np.ascontiguousarray(obs, dtype=np.float32), np.ascontiguousarray(rew, dtype=np.float32)
+        self.old_obs, self.old_reward = obs.copy(), rew.copy()
+        dev = self._dev()
+        t_obs, t_rew = torch.from_numpy(obs).to(dev), torch.from_numpy(rew).to(dev)
+        t_done = torch.from_numpy(np.ascontiguousarray(done, dtype=np.uint8)).to(dev)
+        self.normalizer.step(t_obs, t_rew, t_done)
+        finished = np.nonzero(done)[0]
+        rows = [(int(i), infos[int(i)]) for i in finished]
+        rows = [(i, info) for i, info in rows if isinstance(info, dict) and info.get("terminal_observation") is not None]
+        if rows:
+            term = self._normalize_rows(np.stack([info["terminal_observation"] for _, info in rows]))
+            for k, (i, info) in enumerate(rows):
+                info = dict(info)
+                info["terminal_observation"] = term[k]
+                infos[i] = info
+        return t_obs.cpu().numpy(), t_rew.cpu().numpy(), done, infos
+
+    def step(self, actions):
+        self.step_async(actions)
+        return self.step_wait()
+
+    def get_original_obs(self):
+        return None if self.old_obs is None else self.old_obs.copy()
+
+    def get_original_reward(self):
+        return None if self.old_reward is None else self.old_reward.copy()
+
+    # -- checkpoint / resume ----------------------------------------------------------------
+    def snapshot(self):
+        """The wrapped env's snapshot (its own, or the simulator's for the plain env) with the normaliser's state beside it."""
+        env = self.venv.snapshot() if hasattr(self.venv, "snapshot") else {"sim": self.venv._sim.snapshot()}
+        return {"env": env, "normalizer": self.normalizer.state_dict(), "training": self.normalizer.training}
+
+    def restore(self, snap):
+        if hasattr(self.venv, "restore"):
+            self.venv.restore(snap["env"])
+        else:
+            self.venv._sim.restore(snap["env"]["sim"])
+        self.normalizer.load_state_dict(snap["normalizer"])
+        self.normalizer.training = bool(snap.get("training", True))
+
+    def close(self):
+        self.normalizer.close()
+        self.venv.close()
