@@ -1,0 +1,58 @@
+"""``Handle`` -- what every Python class around a handle of the C ABI shares: the loaded library, the handle and its lifetime,
+the HIP stream of a call, and the checks of the torch tensors whose pointers are handed over."""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _abi
+
+
+class Handle:
+    """A subclass names the ABI's destroy function in ``_destroy``, sets ``device`` and stores what its create call returned in
+    ``_h``."""
+
+    _destroy: str = ""
+    _h = None
+
+    def __init__(self, device: int = 0):
+        self._lib = _abi.load_library()
+        self.device = int(device)
+
+    # -- lifetime ---------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- torch plumbing ---------------------------------------------------------------------
+    def _stream_ptr(self, stream):
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        return C.c_void_p(stream.cuda_stream)
+
+    def _check_tensor(self, t, shape, dtype):
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"tensor must live on cuda:{self.device}")
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError(f"expected contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+    def _check_obs(self, t, n=None, what="obs"):
+        """``[n, self.obs_dim]`` float32 whose rows are contiguous; the row stride is free (a column slice of a wider buffer).
+        Returns ``(n, row stride in floats)``."""
+        import torch
+        width = self.obs_dim
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{what} must live on cuda:{self.device}")
+        if t.dim() != 2 or t.shape[1] != width or t.dtype != torch.float32 or t.shape[0] < 1 or (n is not None and t.shape[0] != n):
+            rows = "n" if n is None else n
+            raise ValueError(f"{what}: expected a float32 tensor of shape ({rows}, {width}), got {t.dtype} {tuple(t.shape)}")
+        if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < width):
+            raise ValueError(f"{what}: rows must be contiguous, at a row stride >= {width}; got strides {tuple(t.stride())}")
+        return int(t.shape[0]), int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), width)

@@ -64,6 +64,8 @@ struct KDyn {
     float kp, kv, force, damping;             // scales of act_kp, act_kv, act_forcerange, jnt_damping
     float m0, h0[3], I0[6];
 };
+// the range QG_RESET_DYNAMICS draws an env's row from (qg_dyn_draw_kernel)
+struct KDynRange { float lo[QGK_NDYN], hi[QGK_NDYN]; };
 
 struct KTask {
     int32_t frame_skip;
@@ -104,3 +106,57 @@ struct KStepArgs {
     uint64_t seed;            // reset stream
     uint64_t env_index_base;
 };
+
+// The mailbox of the many-env-steps-per-launch forms of the one-link-per-lane kernel (qg_kernel_resident.hip) and the status words
+// its kernels report to the host.
+#define QG_RES_SHARDS 32            // arrival counters, one 128-byte line each; wave w of the grid arrives at shard w % 32
+#define QG_RES_RUNNING 1ull         // hstat[0]
+#define QG_RES_EXIT_STOP 2ull       // retired on request (qg_resident_stop, or any entry point that needs the state in memory)
+#define QG_RES_EXIT_IDLE 3ull       // retired itself: no ring within idle_ticks
+#define QG_RES_RETIRING 4ull        // no ring for idle_ticks / 2: the kernel still takes rings, and leaves at idle_ticks if none comes.  The
+                                    // host does not ring a kernel in this state (it retires it and launches again): a ring it enqueues
+                                    // after seeing RUNNING therefore has idle_ticks / 2 to reach the GPU before the door can shut
+
+struct KResident {
+    unsigned long long *door;       // device: env-steps rung so far | QG_DOOR_STOP
+    unsigned long long *done;       // device: [QG_RES_SHARDS] arrival counters (index 16 s), cumulative env-steps x waves
+    unsigned long long *completed;  // device: env-steps the previous launches have completed (where this launch starts)
+    unsigned long long *hstat;      // page-locked host memory: [0] QG_RES_*, [1] env-steps completed at exit, [2] env-steps of refused
+                                    // rings, [3] rings that gave up waiting
+    const float *actions;           // [slots][n][12]
+    float *packed;                  // [slots][n][D + 2]
+    int32_t slots;
+    int32_t count;                  // DOOR = false: env-steps of this launch
+    uint32_t idle_ticks;            // DOOR: give up waiting for a ring after this many ticks of the 100 MHz clock
+    uint32_t ring_ticks;            // ring kernel: give up after this long without an arrival
+};
+
+#ifdef __HIPCC__
+// counter-based uniform in [0,1) with 24 random bits (same stream as the oracle's qgo_uniform)
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+__device__ __forceinline__ float uniform24(uint64_t seed, uint64_t env_index, uint64_t counter) {
+    uint64_t x = seed + 0x9E3779B97F4A7C15ull * (env_index + 1) + 0xD1B54A32D192ED03ull * (counter + 1);
+    x = mix64(mix64(x));
+    return (float)(uint32_t)(x >> 40) * (1.0f / 16777216.0f);
+}
+// independent streams of the same (seed, env, episode) key: 0 = reset yaw, 1..12 = hinge jitter, 13..15 = walking command
+#define QG_STREAM_HINGE 1u
+#define QG_STREAM_COMMAND 13u
+__device__ __forceinline__ float uniform24s(uint64_t seed, uint64_t env_index, uint64_t counter, uint32_t stream) {
+    return uniform24(seed + 0xA0761D6478BD642Full * (uint64_t)stream, env_index, counter);
+}
+
+// Hand-off through LDS between the lanes of ONE wave (a tile no other wave touches): the wave's LDS operations execute in order, so
+// no s_barrier is needed -- in a four-wave workgroup that would also make every wave wait for the slowest of the four -- only the
+// compiler has to be told that other lanes read what this lane wrote.
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+#endif

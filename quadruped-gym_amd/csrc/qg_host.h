@@ -1,0 +1,63 @@
+// qg_host.h -- what every host translation unit of the library shares: the error record, opening a device, and the owner of a
+// handle's device allocations.  Internal: not installed, and nothing in here is exported (libquadgym.map).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/quadgym.h"
+
+int qg_fail(int code, const char *fmt, ...);   // records the message for qg_last_error() and returns `code` (qg_capi.hip)
+#define fail qg_fail
+
+#ifdef __HIPCC__   // (qg_tables.h, which the plain-C++ generator of the baked table includes, needs the line above only)
+#include <hip/hip_runtime.h>
+
+#define HIP_TRY(expr, code)                                                                         \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess) return fail(code, "%s: %s", #expr, hipGetErrorString(e_));            \
+    } while (0)
+
+// SIMDs of a GPU (hipDeviceProp: compute units x 4); 1024, an MI355X's, where the query fails
+static inline int qg_device_simds(int32_t device_id) {
+    hipDeviceProp_t prop;
+    if (device_id >= 0 && hipGetDeviceProperties(&prop, device_id) == hipSuccess && prop.multiProcessorCount > 0) return 4 * prop.multiProcessorCount;
+    (void)hipGetLastError();
+    return 1024;
+}
+
+// what every create does first: there is a device, `device_id` names one, it is the calling thread's current device
+static inline int qg_open_device(int32_t device_id, int *simds) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+        (void)hipGetLastError();
+        return fail(QG_ERR_DEVICE, "no HIP device is available; quadgym has no CPU backend");
+    }
+    if (device_id < 0 || device_id >= ndev) return fail(QG_ERR_DEVICE, "device_id %d out of range (0..%d)", device_id, ndev - 1);
+    HIP_TRY(hipSetDevice(device_id), QG_ERR_DEVICE);
+    if (simds) *simds = qg_device_simds(device_id);
+    return QG_OK;
+}
+
+// The device allocations of one handle: alloc() records what it hands out, free_all() in the handle's destroy releases all of it --
+// no list of pointers to keep in step with the allocations.  All zeros is the empty owner (the handles are zero-filled at create).
+struct QgDevMem {
+    void *ptr[40];
+    int count;
+
+    template <class T> int alloc(T *&p, size_t bytes, bool zero = false) {
+        if (count == (int)(sizeof ptr / sizeof ptr[0])) return fail(QG_ERR_ALLOC, "hipMalloc(%zu): the handle's allocation table is full", bytes);
+        hipError_t e = hipMalloc((void **)&p, bytes);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return fail(QG_ERR_ALLOC, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
+        }
+        ptr[count++] = (void *)p;
+        if (zero && (e = hipMemset((void *)p, 0, bytes)) != hipSuccess) return fail(QG_ERR_ALLOC, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
+        return QG_OK;
+    }
+    void free_all() {
+        while (count > 0) (void)hipFree(ptr[--count]);
+    }
+};
+#endif

@@ -27,27 +27,7 @@
 // outputs (packed rows only).  The sequence form also exists for the two-legs-per-lane and the one-leg-per-lane kernels (end of file).
 
 #define QG_DOOR_STOP (1ull << 63)
-#define QG_RES_SHARDS 32            // arrival counters, one 128-byte line each; wave w of the grid arrives at shard w % 32
-#define QG_RES_RUNNING 1ull         // hstat[0]
-#define QG_RES_EXIT_STOP 2ull       // retired on request (qg_resident_stop, or any entry point that needs the state in memory)
-#define QG_RES_EXIT_IDLE 3ull       // retired itself: no ring within idle_ticks
-#define QG_RES_RETIRING 4ull        // no ring for idle_ticks / 2: the kernel still takes rings, and leaves at idle_ticks if none comes.  The
-                                    // host does not ring a kernel in this state (it retires it and launches again): a ring it enqueues
-                                    // after seeing RUNNING therefore has idle_ticks / 2 to reach the GPU before the door can shut
-
-struct KResident {
-    unsigned long long *door;       // device: env-steps rung so far | QG_DOOR_STOP
-    unsigned long long *done;       // device: [QG_RES_SHARDS] arrival counters (index 16 s), cumulative env-steps x waves
-    unsigned long long *completed;  // device: env-steps the previous launches have completed (where this launch starts)
-    unsigned long long *hstat;      // page-locked host memory: [0] QG_RES_*, [1] env-steps completed at exit, [2] env-steps of refused
-                                    // rings, [3] rings that gave up waiting
-    const float *actions;           // [slots][n][12]
-    float *packed;                  // [slots][n][D + 2]
-    int32_t slots;
-    int32_t count;                  // DOOR = false: env-steps of this launch
-    uint32_t idle_ticks;            // DOOR: give up waiting for a ring after this many ticks of the 100 MHz clock
-    uint32_t ring_ticks;            // ring kernel: give up after this long without an arrival
-};
+// (the mailbox KResident and the QG_RES_* status words the host reads are in qg_device.h)
 
 DEV unsigned long long res_load_u64(const unsigned long long *p) {
     const unsigned long long v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // global_load_dwordx2 sc1

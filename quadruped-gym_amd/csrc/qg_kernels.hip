@@ -320,24 +320,7 @@ DEV bool state_is_bad(float probe) {
     return ((bits >> 23) & 0xFFu) >= 0x9Eu;          // NaN, Inf, or magnitude >= 2^31
 }
 
-// counter-based uniform in [0,1) with 24 random bits (same stream as the oracle's qgo_uniform)
-DEV uint64_t mix64(uint64_t x) {
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-DEV float uniform24(uint64_t seed, uint64_t env_index, uint64_t counter) {
-    uint64_t x = seed + 0x9E3779B97F4A7C15ull * (env_index + 1) + 0xD1B54A32D192ED03ull * (counter + 1);
-    x = mix64(mix64(x));
-    return (float)(uint32_t)(x >> 40) * (1.0f / 16777216.0f);
-}
-// independent streams of the same (seed, env, episode) key: 0 = reset yaw, 1..12 = hinge jitter, 13..15 = walking command
-#define QG_STREAM_HINGE 1u
-#define QG_STREAM_COMMAND 13u
-DEV float uniform24s(uint64_t seed, uint64_t env_index, uint64_t counter, uint32_t stream) {
-    return uniform24(seed + 0xA0761D6478BD642Full * (uint64_t)stream, env_index, counter);
-}
+// (the counter-based uniform draws of the resets -- uniform24 / uniform24s and their stream numbers -- are in qg_device.h)
 // In-kernel phase clock (development builds only: -DQG_PHASE_TIMES, tools/phase_times.sh).  Wave 0 of workgroup 0 stamps
 // s_memrealtime (100 MHz) at the marks below into qg_phase_times[]; qg_debug_phase_times() copies them out and tools/phase_times.py
 // prints the deltas.  Compiled out otherwise: the production kernels carry none of it.
@@ -348,15 +331,7 @@ __device__ unsigned long long qg_phase_times[16];
 #define QG_MARK(i) do { } while (0)
 #endif
 
-// Hand-off through LDS between the lanes of ONE wave (a tile no other wave touches): the wave's LDS operations execute in order, so
-// no s_barrier is needed -- in a four-wave workgroup that would also make every wave wait for the slowest of the four -- only the
-// compiler has to be told that other lanes read what this lane wrote.
-DEV void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
+// (wave_sync, the hand-off through LDS between the lanes of one wave, is in qg_device.h)
 #include "qg_walk_dev.h"     // walking task layer: per-env device functions used by the fused walking variant of the quad kernel
 #include "qg_po_dev.h"       // partially observable observation pack: per-env / per-wave device functions of the fused <WALK, PO> variants
 
@@ -2295,7 +2270,6 @@ __global__ void qg_jitter_kernel(const KModel *__restrict__ M, const KTask *__re
 // as qg_jitter_kernel and for its reason, as a launch of its own behind a step that auto-resets (`done` bytes or the packed rows' last
 // column: the envs that finished; their counter has advanced, key_offset -1).
 #define QG_STREAM_DYNAMICS 16u
-struct KDynRange { float lo[QGK_NDYN], hi[QGK_NDYN]; };
 __global__ void qg_dyn_draw_kernel(float *__restrict__ rows, KDynRange R, const int32_t *__restrict__ episode, int n, const uint8_t *__restrict__ mask,
                                    const uint8_t *__restrict__ done, const float *__restrict__ packed, int row, int key_offset, uint64_t seed,
                                    uint64_t env_index_base) {

@@ -19,6 +19,15 @@
 // Numerics.  Within a tile a thread accumulates sum(x - K) and sum((x - K)^2) in f64 with K its first element (x - K is exact in
 // f64 for f32 inputs; a constant column gives M2 = 0 exactly), never E[x^2] - E[x]^2; everything above is Chan's pairwise merge.
 
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+#include "qg_host.h"
+
 #define QGN_COLS 64               // columns per workgroup of the moments pass (one per lane)
 #define QGN_WAVES 4
 #define QGN_MAX_TILES 512         // slab entries per column; the rows per tile grow with n so that this holds
@@ -226,4 +235,230 @@ __global__ __launch_bounds__(256) void qg_norm_apply_kernel(KNormApply A, const 
             if (d) returns[i] = 0.0;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------------
+struct qg_norm {
+    int32_t device;
+    qg_norm_desc desc;
+    int32_t Dp;               // obs_dim + 1: the returns are the last column of every table
+    QgDevMem mem;
+    double *d_stats;          // [4][Dp]: mean | var | count | 1 / sqrt(var + epsilon)
+    double *d_returns;        // [n_envs]
+    double2 *d_part;          // [QGN_MAX_TILES][Dp]: the moments pass's (mean, M2) per tile and column
+};
+
+// by the bit pattern: the device pass of this file is compiled with finite-math assumptions and warns at isfinite()
+static bool norm_finite(double x) {
+    uint64_t u;
+    memcpy(&u, &x, sizeof u);
+    return ((u >> 52) & 0x7ff) != 0x7ff;
+}
+
+static int norm_validate(const qg_norm_desc *d) {
+    if (!d) return fail(QG_ERR_ARG, "qg_norm: null description");
+    if (d->struct_size != (int32_t)sizeof(qg_norm_desc))
+        return fail(QG_ERR_ARG, "qg_norm_desc.struct_size is %d, this library's is %d", d->struct_size, (int)sizeof(qg_norm_desc));
+    if (d->obs_dim < 1 || d->obs_dim > 512) return fail(QG_ERR_ARG, "qg_norm: obs_dim %d outside 1 .. 512", d->obs_dim);
+    if (d->n_envs < 1) return fail(QG_ERR_ARG, "qg_norm: n_envs %d must be >= 1", d->n_envs);
+    if (!norm_finite(d->gamma) || d->gamma < 0.0) return fail(QG_ERR_ARG, "qg_norm: gamma %g must be finite and >= 0", d->gamma);
+    if (!norm_finite(d->epsilon) || d->epsilon < 0.0) return fail(QG_ERR_ARG, "qg_norm: epsilon %g must be finite and >= 0", d->epsilon);
+    if (!norm_finite(d->clip_obs) || d->clip_obs <= 0.0) return fail(QG_ERR_ARG, "qg_norm: clip_obs %g must be finite and > 0", d->clip_obs);
+    if (!norm_finite(d->clip_reward) || d->clip_reward <= 0.0)
+        return fail(QG_ERR_ARG, "qg_norm: clip_reward %g must be finite and > 0", d->clip_reward);
+    if ((d->norm_obs != 0 && d->norm_obs != 1) || (d->norm_reward != 0 && d->norm_reward != 1))
+        return fail(QG_ERR_ARG, "qg_norm: norm_obs and norm_reward are 0 or 1");
+    return QG_OK;
+}
+
+extern "C" int qg_norm_destroy(qg_norm *p) {
+    if (!p) return QG_OK;
+    (void)hipSetDevice(p->device);
+    (void)hipDeviceSynchronize();                  // steps may still be in flight on a caller's stream
+    p->mem.free_all();
+    delete p;
+    return QG_OK;
+}
+
+// mean 0, var 1, count 1e-4 for the observations and the returns; returns 0
+static int norm_upload(qg_norm *p, const double *mean, const double *var, const double *count, double ret_mean, double ret_var,
+                       double ret_count, const double *returns) {
+    const int D = p->desc.obs_dim, Dp = p->Dp;
+    double *h = new (std::nothrow) double[(size_t)4 * Dp];
+    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
+    for (int c = 0; c < D; c++) h[c] = mean ? mean[c] : 0.0, h[Dp + c] = var ? var[c] : 1.0, h[2 * Dp + c] = count ? *count : 1e-4;
+    h[D] = ret_mean, h[Dp + D] = ret_var, h[2 * Dp + D] = ret_count;
+    for (int c = 0; c < Dp; c++) h[3 * Dp + c] = 0.0;
+    hipError_t e = hipMemcpy(p->d_stats, h, (size_t)4 * Dp * sizeof(double), hipMemcpyHostToDevice);
+    delete[] h;
+    if (e == hipSuccess)
+        e = returns ? hipMemcpy(p->d_returns, returns, (size_t)p->desc.n_envs * sizeof(double), hipMemcpyHostToDevice)
+                    : hipMemset(p->d_returns, 0, (size_t)p->desc.n_envs * sizeof(double));
+    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_norm: %s", hipGetErrorString(e));
+    qg_norm_inv_kernel<<<1, 64, 0, nullptr>>>(Dp, p->d_stats, p->desc.epsilon);
+    HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    return QG_OK;
+}
+
+extern "C" int qg_norm_create(int32_t device_id, const qg_norm_desc *desc, qg_norm **out) {
+    if (!out) return fail(QG_ERR_ARG, "qg_norm_create: null output");
+    *out = nullptr;
+    int rc = norm_validate(desc);
+    if (rc != QG_OK) return rc;
+    if ((rc = qg_open_device(device_id, nullptr)) != QG_OK) return rc;
+    qg_norm *p = new (std::nothrow) qg_norm();
+    if (!p) return fail(QG_ERR_ALLOC, "out of host memory");
+    memset(p, 0, sizeof *p);
+    p->device = device_id;
+    p->desc = *desc;
+    p->Dp = desc->obs_dim + 1;
+    if (p->mem.alloc(p->d_stats, (size_t)4 * p->Dp * sizeof(double)) || p->mem.alloc(p->d_returns, (size_t)desc->n_envs * sizeof(double)) ||
+        p->mem.alloc(p->d_part, (size_t)QGN_MAX_TILES * p->Dp * sizeof(double2))) {
+        qg_norm_destroy(p);
+        return QG_ERR_ALLOC;
+    }
+    rc = norm_upload(p, nullptr, nullptr, nullptr, 0.0, 1.0, 1e-4, nullptr);
+    if (rc != QG_OK) {
+        qg_norm_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return QG_OK;
+}
+
+// rows per tile of the moments pass: 16, or what keeps n rows within QGN_MAX_TILES tiles (a multiple of the four waves)
+static int norm_tile_rows(int32_t n) {
+    const int r = (int)(((int64_t)n + QGN_MAX_TILES - 1) / QGN_MAX_TILES);
+    return r <= 16 ? 16 : (r + QGN_WAVES - 1) / QGN_WAVES * QGN_WAVES;
+}
+
+// steps 1 and 3: the moments of obs (when given) and of the advanced returns (when reward is given), merged into the statistics
+static int norm_update(qg_norm *p, int32_t n, const float *obs, int32_t stride, const float *reward, int32_t rstride, hipStream_t st) {
+    if (!obs && !reward) return QG_OK;
+    const int D = p->desc.obs_dim, R = norm_tile_rows(n), G = (n + R - 1) / R;
+    const int nchunk = (D + QGN_COLS - 1) / QGN_COLS;
+    const dim3 grid((unsigned)G, (unsigned)((obs ? nchunk : 0) + (reward ? 1 : 0)));
+    qg_norm_moments_kernel<<<grid, 64 * QGN_WAVES, 0, st>>>(n, D, R, nchunk, obs ? 0 : nchunk, obs, stride, reward, rstride, p->d_returns,
+                                                           p->desc.gamma, p->d_part);
+    HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
+    const int c_lo = obs ? 0 : D, c_hi = reward ? D + 1 : D;
+    qg_norm_combine_kernel<<<(c_hi - c_lo + 15) / 16, 16 * QGN_SLICES, 0, st>>>(n, R, G, p->Dp, c_lo, c_hi, p->d_part, p->d_stats, p->desc.epsilon);
+    HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
+    return QG_OK;
+}
+
+// steps 2, 4 and 5
+static int norm_apply(qg_norm *p, int32_t n, const float *obs_in, int32_t in_stride, float *obs_out, int32_t out_stride, const float *reward_in,
+                      int32_t rin_stride, float *reward_out, int32_t rout_stride, const void *done, int32_t done_kind, int32_t done_stride,
+                      bool zero_returns, hipStream_t st) {
+    const int D = p->desc.obs_dim;
+    KNormApply A;
+    memset(&A, 0, sizeof A);
+    A.n = n, A.D = D, A.Dp = p->Dp;
+    A.in_stride = in_stride, A.out_stride = out_stride;
+    A.norm_obs = p->desc.norm_obs, A.norm_reward = p->desc.norm_reward;
+    A.rin_stride = rin_stride, A.rout_stride = rout_stride;
+    A.done_kind = done_kind, A.done_stride = done_stride;
+    A.zero_returns = zero_returns && done;
+    A.clip_obs = (float)p->desc.clip_obs, A.clip_reward = (float)p->desc.clip_reward;
+    const bool vec = D % 4 == 0 && in_stride % 4 == 0 && out_stride % 4 == 0 && ((uintptr_t)obs_in | (uintptr_t)obs_out) % 16 == 0;
+    const bool obs_work = obs_in && (A.norm_obs || obs_in != obs_out);          // switched off and in place: nothing to copy
+    const bool rew_work = reward_in && (A.norm_reward || reward_in != reward_out || A.zero_returns);
+    const int64_t obs_items = obs_work ? (int64_t)n * (D / (vec ? 4 : 1)) : 0;
+    const int64_t blocks = (obs_items + 255) / 256 + (rew_work ? ((int64_t)n + 255) / 256 : 0);
+    if (blocks == 0) return QG_OK;
+    if (blocks > INT32_MAX) return fail(QG_ERR_ARG, "qg_norm: %d rows of %d columns are more than one launch takes", n, D);
+    A.obs_blocks = (int32_t)((obs_items + 255) / 256);
+    if (vec) qg_norm_apply_kernel<true><<<(unsigned)blocks, 256, 0, st>>>(A, obs_in, obs_out, p->d_stats, reward_in, reward_out, done, p->d_returns);
+    else qg_norm_apply_kernel<false><<<(unsigned)blocks, 256, 0, st>>>(A, obs_in, obs_out, p->d_stats, reward_in, reward_out, done, p->d_returns);
+    HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
+    return QG_OK;
+}
+
+extern "C" int qg_norm_step_device(qg_norm *p, int32_t n, const float *obs_in, int32_t in_stride, float *obs_out, int32_t out_stride,
+                                   const float *reward_in, int32_t reward_in_stride, float *reward_out, int32_t reward_out_stride,
+                                   const void *done, int32_t done_kind, int32_t done_stride, int32_t training, void *stream) {
+    if (!p || !obs_in || !obs_out) return fail(QG_ERR_ARG, "qg_norm_step_device: null argument");
+    if (n != p->desc.n_envs) return fail(QG_ERR_ARG, "qg_norm_step_device: n is %d, the handle was built for %d envs", n, p->desc.n_envs);
+    if (in_stride < p->desc.obs_dim || out_stride < p->desc.obs_dim)
+        return fail(QG_ERR_ARG, "qg_norm_step_device: strides %d, %d < obs_dim %d", in_stride, out_stride, p->desc.obs_dim);
+    if (reward_in) {
+        if (!reward_out) return fail(QG_ERR_ARG, "qg_norm_step_device: reward_in without reward_out");
+        if (reward_in_stride < 1 || reward_out_stride < 1) return fail(QG_ERR_ARG, "qg_norm_step_device: reward strides must be >= 1");
+        if (done && (done_kind != QG_NORM_DONE_U8 && done_kind != QG_NORM_DONE_F32))
+            return fail(QG_ERR_ARG, "qg_norm_step_device: done_kind %d is neither QG_NORM_DONE_U8 nor QG_NORM_DONE_F32", done_kind);
+        if (done && done_stride < 1) return fail(QG_ERR_ARG, "qg_norm_step_device: done_stride must be >= 1");
+    }
+    HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
+    const hipStream_t st = (hipStream_t)stream;
+    if (training) {
+        int rc = norm_update(p, n, p->desc.norm_obs ? obs_in : nullptr, in_stride, reward_in, reward_in_stride, st);
+        if (rc != QG_OK) return rc;
+    }
+    return norm_apply(p, n, obs_in, in_stride, obs_out, out_stride, reward_in, reward_in_stride, reward_out, reward_out_stride,
+                      reward_in ? done : nullptr, done_kind, done_stride, training != 0, st);
+}
+
+extern "C" int qg_norm_update_obs_device(qg_norm *p, int32_t n, const float *obs, int32_t stride, void *stream) {
+    if (!p || !obs) return fail(QG_ERR_ARG, "qg_norm_update_obs_device: null argument");
+    if (n < 1) return fail(QG_ERR_ARG, "qg_norm_update_obs_device: n must be >= 1");
+    if (stride < p->desc.obs_dim) return fail(QG_ERR_ARG, "qg_norm_update_obs_device: stride %d < obs_dim %d", stride, p->desc.obs_dim);
+    HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
+    return norm_update(p, n, obs, stride, nullptr, 0, (hipStream_t)stream);
+}
+
+extern "C" int qg_norm_apply_obs_device(qg_norm *p, int32_t n, const float *obs_in, int32_t in_stride, float *obs_out, int32_t out_stride,
+                                        void *stream) {
+    if (!p || !obs_in || !obs_out) return fail(QG_ERR_ARG, "qg_norm_apply_obs_device: null argument");
+    if (n < 1) return fail(QG_ERR_ARG, "qg_norm_apply_obs_device: n must be >= 1");
+    if (in_stride < p->desc.obs_dim || out_stride < p->desc.obs_dim)
+        return fail(QG_ERR_ARG, "qg_norm_apply_obs_device: strides %d, %d < obs_dim %d", in_stride, out_stride, p->desc.obs_dim);
+    HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
+    return norm_apply(p, n, obs_in, in_stride, obs_out, out_stride, nullptr, 0, nullptr, 0, nullptr, 0, 0, false, (hipStream_t)stream);
+}
+
+extern "C" int qg_norm_reset_returns_device(qg_norm *p, void *stream) {
+    if (!p) return fail(QG_ERR_ARG, "qg_norm_reset_returns_device: null argument");
+    HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
+    HIP_TRY(hipMemsetAsync(p->d_returns, 0, (size_t)p->desc.n_envs * sizeof(double), (hipStream_t)stream), QG_ERR_LAUNCH);
+    return QG_OK;
+}
+
+extern "C" int qg_norm_get_state(qg_norm *p, double *mean, double *var, double *count, double *ret_mean, double *ret_var, double *ret_count,
+                                 double *returns) {
+    if (!p || !mean || !var || !count || !ret_mean || !ret_var || !ret_count || !returns)
+        return fail(QG_ERR_ARG, "qg_norm_get_state: null argument");
+    HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);         // a step may be in flight on a caller's stream
+    const int D = p->desc.obs_dim, Dp = p->Dp;
+    double *h = new (std::nothrow) double[(size_t)3 * Dp];
+    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
+    hipError_t e = hipMemcpy(h, p->d_stats, (size_t)3 * Dp * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(returns, p->d_returns, (size_t)p->desc.n_envs * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) {
+        memcpy(mean, h, (size_t)D * sizeof(double));
+        memcpy(var, h + Dp, (size_t)D * sizeof(double));
+        *count = h[2 * Dp];
+        *ret_mean = h[D], *ret_var = h[Dp + D], *ret_count = h[2 * Dp + D];
+    }
+    delete[] h;
+    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_norm_get_state: %s", hipGetErrorString(e));
+    return QG_OK;
+}
+
+extern "C" int qg_norm_set_state(qg_norm *p, const double *mean, const double *var, double count, double ret_mean, double ret_var,
+                                 double ret_count, const double *returns) {
+    if (!p || !mean || !var || !returns) return fail(QG_ERR_ARG, "qg_norm_set_state: null argument");
+    for (int c = 0; c < p->desc.obs_dim; c++)
+        if (!norm_finite(mean[c]) || !norm_finite(var[c]) || var[c] < 0.0)
+            return fail(QG_ERR_ARG, "qg_norm_set_state: column %d: mean %g, var %g (finite, var >= 0)", c, mean[c], var[c]);
+    if (!norm_finite(count) || count <= 0.0 || !norm_finite(ret_count) || ret_count <= 0.0 || !norm_finite(ret_mean) ||
+        !norm_finite(ret_var) || ret_var < 0.0)
+        return fail(QG_ERR_ARG, "qg_norm_set_state: counts must be > 0, the return statistic finite with var >= 0");
+    HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    return norm_upload(p, mean, var, &count, ret_mean, ret_var, ret_count, returns);
 }

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qg_device.h"       // wave_sync
+
 #define QG_PO_FRAME 26
 
 struct KPoParams {

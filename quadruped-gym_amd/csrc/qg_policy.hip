@@ -16,6 +16,15 @@
 // Numerics: every output is a k-ordered fmaf chain that starts from the bias, in a fixed order that depends on nothing but the
 // layer sizes -- a row's results do not depend on n, on its place in the tile or on the other rows.
 
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+#include "qg_host.h"
+
 #define QGP_MAX_LAYERS 4          // n_hidden <= 3 hidden layers + the output layer
 #define QGP_TILE 16               // envs per workgroup
 
@@ -232,4 +241,199 @@ __global__ __launch_bounds__(64 * WAVES) void qg_policy_forward_kernel(KPolicy P
             }
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------------
+struct qg_policy {
+    int32_t device;
+    qg_policy_desc desc;
+    KPolicy k;
+    int32_t n_params;
+    int32_t simds;
+    int32_t force_waves;      // env QG_POLICY_WAVES at qg_policy_create: 1 or 4 waves per env tile whatever the size (A/B; 0: by size)
+    QgDevMem mem;
+    float *d_params;          // canonical flat vector (what qg_policy_get_params returns)
+    float *d_packed;          // the operand image the forward kernel reads
+};
+
+// the description is valid: fills the kernel's layer table (offsets into both parameter images) and returns the canonical length
+static int policy_layout(const qg_policy_desc *d, KPolicy *k) {
+    if (!d) return fail(QG_ERR_ARG, "qg_policy: null description");
+    if (d->struct_size != (int32_t)sizeof(qg_policy_desc))
+        return fail(QG_ERR_ARG, "qg_policy_desc.struct_size is %d, this library's is %d", d->struct_size, (int)sizeof(qg_policy_desc));
+    if (d->obs_dim < 1 || d->obs_dim > 512) return fail(QG_ERR_ARG, "qg_policy: obs_dim %d outside 1 .. 512", d->obs_dim);
+    if (d->act_dim < 1 || d->act_dim > 16) return fail(QG_ERR_ARG, "qg_policy: act_dim %d outside 1 .. 16", d->act_dim);
+    if (d->n_hidden < 1 || d->n_hidden > 3) return fail(QG_ERR_ARG, "qg_policy: n_hidden %d outside 1 .. 3", d->n_hidden);
+    for (int i = 0; i < d->n_hidden; i++)
+        if (d->hidden[i] < 16 || d->hidden[i] > 256 || d->hidden[i] % 16)
+            return fail(QG_ERR_ARG, "qg_policy: hidden[%d] = %d (a multiple of 16, 16 .. 256; tanh layers only)", i, d->hidden[i]);
+    if ((d->out_tanh != 0 && d->out_tanh != 1) || (d->has_value != 0 && d->has_value != 1))
+        return fail(QG_ERR_ARG, "qg_policy: out_tanh and has_value are 0 or 1");
+    KPolicy p;
+    memset(&p, 0, sizeof p);
+    p.obs_dim = d->obs_dim;
+    p.act_dim = d->act_dim;
+    p.n_layers = d->n_hidden + 1;
+    p.out_tanh = d->out_tanh;
+    p.n_towers = d->has_value ? 2 : 1;
+    int src = 0, dst = 0;
+    for (int t = 0; t < p.n_towers; t++) {
+        int in = d->obs_dim;
+        for (int l = 0; l < p.n_layers; l++) {
+            const int out = l < d->n_hidden ? d->hidden[l] : (t == 0 ? d->act_dim : 1);
+            KPolLayer &L = p.layer[t][l];
+            L.in_dim = in;
+            L.out_dim = out;
+            L.nq = (in + 15) / 16;
+            L.nb = (out + 15) / 16;
+            L.src_w = src;
+            L.src_b = src + out * in;
+            src += out * in + out;
+            L.w_off = dst;
+            L.b_off = dst + L.nb * L.nq * 256;
+            dst = L.b_off + 16 * L.nb;
+            in = out;
+        }
+        if (t == 0) {
+            p.src_log_std = src;
+            src += d->act_dim;
+        }
+    }
+    p.std_off = dst;
+    p.packed_floats = dst + 32;
+    // activation buffers, floats (16 envs per feature): layer l reads buffer l & 1 and writes the other
+    int f0 = 16 * p.layer[0][0].nq, f1 = d->hidden[0];
+    if (d->n_hidden > 1 && d->hidden[1] > f0) f0 = d->hidden[1];
+    if (d->n_hidden > 2 && d->hidden[2] > f1) f1 = d->hidden[2];
+    p.lds0_floats = 16 * f0;
+    p.lds1_floats = 16 * f1;
+    if (k) *k = p;
+    return src;
+}
+
+extern "C" int qg_policy_param_count(const qg_policy_desc *desc) { return policy_layout(desc, nullptr); }
+
+extern "C" int qg_policy_destroy(qg_policy *p) {
+    if (!p) return QG_OK;
+    (void)hipSetDevice(p->device);
+    (void)hipDeviceSynchronize();                  // forward passes may still be in flight on a caller's stream
+    p->mem.free_all();
+    delete p;
+    return QG_OK;
+}
+
+static int policy_pack(qg_policy *p, hipStream_t st) {
+    const int threads = 256;
+    qg_policy_pack_kernel<<<(p->k.packed_floats + threads - 1) / threads, threads, 0, st>>>(p->k, p->d_params, p->d_packed);
+    HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
+    return QG_OK;
+}
+
+extern "C" int qg_policy_create(int32_t device_id, const qg_policy_desc *desc, qg_policy **out) {
+    if (!out) return fail(QG_ERR_ARG, "qg_policy_create: null output");
+    *out = nullptr;
+    KPolicy k;
+    const int count = policy_layout(desc, &k);
+    if (count < 0) return count;
+    int simds;
+    int rc = qg_open_device(device_id, &simds);
+    if (rc != QG_OK) return rc;
+    qg_policy *p = new (std::nothrow) qg_policy();
+    if (!p) return fail(QG_ERR_ALLOC, "out of host memory");
+    memset(p, 0, sizeof *p);
+    p->device = device_id;
+    p->desc = *desc;
+    p->k = k;
+    p->n_params = count;
+    p->simds = simds;
+    if (const char *e = getenv("QG_POLICY_WAVES")) p->force_waves = atoi(e) == 1 ? 1 : (atoi(e) == 4 ? 4 : 0);
+    if (p->mem.alloc(p->d_params, (size_t)count * sizeof(float), true) || p->mem.alloc(p->d_packed, (size_t)k.packed_floats * sizeof(float))) {
+        qg_policy_destroy(p);
+        return QG_ERR_ALLOC;
+    }
+    rc = policy_pack(p, nullptr);
+    if (rc == QG_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(QG_ERR_LAUNCH, "qg_policy_create: the packing launch failed");
+    if (rc != QG_OK) {
+        qg_policy_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return QG_OK;
+}
+
+extern "C" int qg_policy_set_params(qg_policy *p, const float *host_params) {
+    if (!p || !host_params) return fail(QG_ERR_ARG, "qg_policy_set_params: null argument");
+    HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);         // forward passes on a caller's stream read the image this rewrites
+    HIP_TRY(hipMemcpy(p->d_params, host_params, (size_t)p->n_params * sizeof(float), hipMemcpyHostToDevice), QG_ERR_DEVICE);
+    int rc = policy_pack(p, nullptr);
+    if (rc != QG_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
+    return QG_OK;
+}
+
+extern "C" int qg_policy_get_params(qg_policy *p, float *host_params) {
+    if (!p || !host_params) return fail(QG_ERR_ARG, "qg_policy_get_params: null argument");
+    HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
+    HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);         // an update may be in flight on a caller's stream
+    HIP_TRY(hipMemcpy(host_params, p->d_params, (size_t)p->n_params * sizeof(float), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    return QG_OK;
+}
+
+extern "C" int qg_policy_set_params_device(qg_policy *p, const float *d_params, void *stream) {
+    if (!p || !d_params) return fail(QG_ERR_ARG, "qg_policy_set_params_device: null argument");
+    HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
+    const hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(p->d_params, d_params, (size_t)p->n_params * sizeof(float), hipMemcpyDeviceToDevice, st), QG_ERR_LAUNCH);
+    return policy_pack(p, st);
+}
+
+template <int WAVES, int MB>
+static void launch_policy(const qg_policy *p, int32_t n, const float *obs, int32_t obs_stride, const float *eps, float *actions,
+                          float *log_prob, float *value, hipStream_t st) {
+    const dim3 grid((unsigned)((n + QGP_TILE - 1) / QGP_TILE), value ? (unsigned)p->k.n_towers : 1u);
+    const size_t lds = (size_t)(p->k.lds0_floats + p->k.lds1_floats) * sizeof(float);
+    qg_policy_forward_kernel<WAVES, MB><<<grid, 64 * WAVES, lds, st>>>(p->k, p->d_packed, n, obs, obs_stride, eps, actions, log_prob, value);
+}
+
+// Waves per 16-env tile and output blocks per wave: four waves -- the output blocks of a layer shared out, one barrier per
+// layer -- for nets wider than 64 at every size, and for the narrow ones while one wave per tile would leave SIMDs without a wave; one
+// from there on.  A wave holds the blocks of a 64-wide layer (1 on four waves, 4 on one) or of a 256-wide one (4, 16).
+static void policy_launch_shape(const qg_policy *p, int32_t n, bool with_value, int32_t *waves, int32_t *blocks) {
+    int widest = 0;
+    for (int i = 0; i < p->desc.n_hidden; i++) widest = p->desc.hidden[i] > widest ? p->desc.hidden[i] : widest;
+    const int towers = with_value ? p->k.n_towers : 1;     // no value buffer: the critic tower is not launched
+    const int64_t tiles = ((int64_t)(n + QGP_TILE - 1) / QGP_TILE) * towers;
+    *waves = p->force_waves ? p->force_waves : ((widest > 64 || tiles < (int64_t)p->simds) ? 4 : 1);
+    *blocks = *waves == 4 ? (widest <= 64 ? 1 : 4) : (widest <= 64 ? 4 : 16);
+}
+
+extern "C" int qg_policy_launch_shape(const qg_policy *p, int32_t n, int32_t with_value, int32_t *waves, int32_t *blocks) {
+    if (!p || !waves || !blocks) return fail(QG_ERR_ARG, "qg_policy_launch_shape: null argument");
+    if (n < 1) return fail(QG_ERR_ARG, "qg_policy_launch_shape: n must be >= 1");
+    if (with_value && !p->desc.has_value) return fail(QG_ERR_ARG, "qg_policy_launch_shape: with_value, but the policy has no critic tower");
+    policy_launch_shape(p, n, with_value != 0, waves, blocks);
+    return QG_OK;
+}
+
+extern "C" int qg_policy_forward_device(qg_policy *p, int32_t n, const float *obs, int32_t obs_stride, const float *eps, float *actions,
+                                        float *log_prob, float *value, void *stream) {
+    if (!p || !obs || !actions) return fail(QG_ERR_ARG, "qg_policy_forward_device: null argument");
+    if (n < 1) return fail(QG_ERR_ARG, "qg_policy_forward_device: n must be >= 1");
+    if (obs_stride < p->desc.obs_dim) return fail(QG_ERR_ARG, "qg_policy_forward_device: obs_stride %d < obs_dim %d", obs_stride, p->desc.obs_dim);
+    if (value && !p->desc.has_value) return fail(QG_ERR_ARG, "qg_policy_forward_device: a value buffer, but the policy has no critic tower");
+    HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
+    const hipStream_t st = (hipStream_t)stream;
+    int32_t waves, blocks;
+    policy_launch_shape(p, n, value != nullptr, &waves, &blocks);
+    if (waves == 4 && blocks == 1) launch_policy<4, 1>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
+    else if (waves == 4 && blocks == 4) launch_policy<4, 4>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
+    else if (waves == 1 && blocks == 4) launch_policy<1, 4>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
+    else if (waves == 1 && blocks == 16) launch_policy<1, 16>(p, n, obs, obs_stride, eps, actions, log_prob, value, st);
+    // only if policy_launch_shape and the launch sites above drift apart (tests/test_policy_api.py compares them on the host)
+    else return fail(QG_ERR_LAUNCH, "qg_policy_forward_device: no kernel for %d waves x %d blocks", waves, blocks);
+    HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
+    return QG_OK;
 }

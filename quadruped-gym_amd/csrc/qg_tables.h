@@ -10,9 +10,7 @@
 
 #include "../../include/quadgym.h"
 #include "qg_device.h"
-
-int qg_fail(int code, const char *fmt, ...);   // records the message for qg_last_error()
-#define fail qg_fail
+#include "qg_host.h"         // qg_fail / fail
 
 static inline int64_t qg_time_limit_substeps_impl(double timestep, double max_time) {
     if (!(timestep > 0)) return -1;
@@ -131,5 +129,3 @@ static inline int build_tables(const qg_model *m, const qg_task *t, KModel *km, 
     kt->reset_joint_jitter = (float)t->reset_joint_jitter;
     return QG_OK;
 }
-
-#undef fail

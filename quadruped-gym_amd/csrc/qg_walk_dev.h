@@ -2,10 +2,11 @@
 // and by the fused walking variant of the step kernel (qg_kernels.hip, qg_step_kernel_quad<.., WALK = true>): the control-signal
 // frequency / amplitude estimator (src/envs/math_utils.py:11-158), the command sampler (src/envs/control_inputs.py:74-115) and
 // the eleven reward terms of input_control_reward (src/envs/walking_quad.py:352-428).
-// Included from qg_kernels.hip after the counter-based random streams (uniform24s) it uses.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "qg_device.h"       // uniform24s: the reset streams the command draw reads
 
 #define QG_WALK_BLOCK 16      // samples per block summary of the estimator's ring buffer
 

@@ -13,9 +13,10 @@ import numpy as np
 
 from . import _abi
 from ._abi import QgNormDesc, check
+from ._handle import Handle
 
 
-class RunningNormalizer:
+class RunningNormalizer(Handle):
     """Per-column running mean / variance of the observations, rewards divided by the running standard deviation of the discounted
     return, both clipped: the semantics of Stable-Baselines3 2.x ``VecNormalize`` (restated in ``include/quadgym.h``), with the
     statistics in float64 on the device.  ``training = False`` freezes every word of the state.
@@ -23,10 +24,12 @@ class RunningNormalizer:
     ``state_dict()`` uses the attribute names of SB3's ``VecNormalize`` (``obs_rms.mean`` ...); the names are taken from SB3's
     source and this has NOT been run against an SB3 pickle (the package is not a dependency)."""
 
+    _destroy = "qg_norm_destroy"
+
     def __init__(self, num_envs: int, obs_dim: int, gamma: float = 0.99, epsilon: float = 1e-8, clip_obs: float = 10.0,
                  clip_reward: float = 10.0, norm_obs: bool = True, norm_reward: bool = True, device: int = 0):
-        self._lib = _abi.load_library()
-        self.num_envs, self.obs_dim, self.device = int(num_envs), int(obs_dim), int(device)
+        super().__init__(device)
+        self.num_envs, self.obs_dim = int(num_envs), int(obs_dim)
         self.gamma, self.epsilon, self.clip_obs, self.clip_reward = float(gamma), float(epsilon), float(clip_obs), float(clip_reward)
         self.norm_obs, self.norm_reward = bool(norm_obs), bool(norm_reward)
         self.training = True
@@ -35,38 +38,7 @@ class RunningNormalizer:
         check(self._lib.qg_norm_create(self.device, C.byref(self.desc), C.byref(h)), "qg_norm_create")
         self._h = h
 
-    # -- lifetime ---------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.qg_norm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # -- tensor checks ----------------------------------------------------------------------
-    def _stream_ptr(self, stream):
-        import torch
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
-        return C.c_void_p(stream.cuda_stream)
-
-    def _check_obs(self, obs, n=None, what="obs"):
-        """``[n, obs_dim]`` float32 whose rows are contiguous; the row stride is free.  Returns ``(n, row stride in floats)``."""
-        import torch
-        if not obs.is_cuda or obs.device.index != self.device:
-            raise ValueError(f"{what} must live on cuda:{self.device}")
-        if obs.dim() != 2 or obs.shape[1] != self.obs_dim or obs.dtype != torch.float32 or obs.shape[0] < 1 or \
-                (n is not None and obs.shape[0] != n):
-            rows = "n" if n is None else n
-            raise ValueError(f"{what}: expected a float32 tensor of shape ({rows}, {self.obs_dim}), got {obs.dtype} {tuple(obs.shape)}")
-        if obs.stride(1) != 1 or (obs.shape[0] > 1 and obs.stride(0) < self.obs_dim):
-            raise ValueError(f"{what}: rows must be contiguous, at a row stride >= {self.obs_dim}; got strides {tuple(obs.stride())}")
-        return int(obs.shape[0]), int(obs.stride(0)) if obs.shape[0] > 1 else max(int(obs.stride(0)), self.obs_dim)
-
     def _check_vec(self, t, dtypes, what):
         """``[num_envs]`` of one of ``dtypes`` at any positive element stride.  Returns the stride."""
         if not t.is_cuda or t.device.index != self.device:

@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import QgPolicyDesc, check
+from ._handle import Handle
 
 
 def _np32(a):
@@ -52,7 +53,7 @@ def _sequential_layers(seq):
     return layers, bool(mods) and isinstance(mods[-1], torch.nn.Tanh)
 
 
-class FusedMlpPolicy:
+class FusedMlpPolicy(Handle):
     """``obs_dim -> hidden[0] -> .. -> act_dim`` with tanh after every hidden layer; ``out_tanh`` puts a tanh on the action mean too
     (``False``: SB3's linear ``action_net``); ``value=True`` adds a critic tower with the same hidden sizes and one output.
 
@@ -60,10 +61,12 @@ class FusedMlpPolicy:
     zeros; load parameters with ``load_layers`` / ``load_module`` / ``load_sb3_state_dict`` (host) or ``update_from`` (device,
     stream-ordered).  Outputs for non-finite observations are unspecified."""
 
+    _destroy = "qg_policy_destroy"
+
     def __init__(self, obs_dim: int, hidden, act_dim: int, out_tanh: bool = False, value: bool = True, device: int = 0):
-        self._lib = _abi.load_library()
+        super().__init__(device)
         self.obs_dim, self.act_dim, self.hidden = int(obs_dim), int(act_dim), tuple(int(h) for h in hidden)
-        self.out_tanh, self.has_value, self.device = bool(out_tanh), bool(value), int(device)
+        self.out_tanh, self.has_value = bool(out_tanh), bool(value)
         if len(self.hidden) > 3:
             raise ValueError("at most three hidden layers")
         self.desc = QgPolicyDesc.make(self.obs_dim, self.hidden, self.act_dim, self.out_tanh, self.has_value)
@@ -71,18 +74,6 @@ class FusedMlpPolicy:
         check(self._lib.qg_policy_create(self.device, C.byref(self.desc), C.byref(h)), "qg_policy_create")
         self._h = h
         self.n_params = int(self._lib.qg_policy_param_count(C.byref(self.desc)))
-
-    # -- lifetime ---------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.qg_policy_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # -- parameters -------------------------------------------------------------------------
     def layer_shapes(self):
@@ -153,30 +144,6 @@ class FusedMlpPolicy:
         self.load_layers(actor, sd["log_std"], critic)
 
     # -- device path ------------------------------------------------------------------------
-    def _stream_ptr(self, stream):
-        import torch
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
-        return C.c_void_p(stream.cuda_stream)
-
-    def _check_tensor(self, t, shape, dtype):
-        if not t.is_cuda or t.device.index != self.device:
-            raise ValueError(f"tensor must live on cuda:{self.device}")
-        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError(f"expected contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-
-    def _check_obs(self, obs):
-        """``[n, obs_dim]`` float32 whose rows are contiguous; the row stride is free (a column slice of a wider buffer).  Returns
-        ``(n, row stride in floats)``."""
-        import torch
-        if not obs.is_cuda or obs.device.index != self.device:
-            raise ValueError(f"tensor must live on cuda:{self.device}")
-        if obs.dim() != 2 or obs.shape[1] != self.obs_dim or obs.dtype != torch.float32 or obs.shape[0] < 1:
-            raise ValueError(f"expected a float32 tensor of shape (n, {self.obs_dim}), got {obs.dtype} {tuple(obs.shape)}")
-        if obs.stride(1) != 1 or (obs.shape[0] > 1 and obs.stride(0) < self.obs_dim):
-            raise ValueError(f"observation rows must be contiguous, at a row stride >= {self.obs_dim}; got strides {tuple(obs.stride())}")
-        return int(obs.shape[0]), int(obs.stride(0)) if obs.shape[0] > 1 else max(int(obs.stride(0)), self.obs_dim)
-
     def update_from(self, params_tensor, stream=None):
         """The canonical flat vector from a device tensor, enqueued on ``stream`` (default: torch's current stream): forward passes
         enqueued later on that stream use it.  No host synchronisation."""

@@ -12,22 +12,24 @@ import numpy as np
 
 from . import _abi
 from ._abi import NBODY, NDYN, NQ, NV, NU, NREWARD, NXFRC, QgModel, QgTask, check
+from ._handle import Handle
 
 
-class BatchedSim:
+class BatchedSim(Handle):
     """n independent quadrupeds on one GPU.
 
     Replaces, for a whole batch, what ``QuadrupedEnv.__init__/reset/step`` do for
     one robot through ``mujoco`` (``src/envs/quadruped.py:59-60,115-139,153-182``).
     """
 
+    _destroy = "qg_destroy"
+
     def __init__(self, n_envs: int, device: int = 0, model: QgModel | None = None, task: QgTask | None = None,
                  env_index_base: int = 0):
-        self._lib = _abi.load_library()
+        super().__init__(device)
         self.model = model if model is not None else _abi.default_model()
         self.task = task if task is not None else _abi.default_task()
         self.n = int(n_envs)
-        self.device = int(device)
         self.env_index_base = int(env_index_base)
         h = C.c_void_p()
         check(self._lib.qg_create(self.n, self.device, C.byref(self.model), C.byref(self.task), self.env_index_base,
@@ -44,18 +46,6 @@ class BatchedSim:
         self.obs_dim = self._lib.qg_obs_dim(self._h)
         self.baked = bool(self._lib.qg_uses_baked_model(self._h))
         self.limit_substeps = int(self._lib.qg_time_limit_substeps(self.model.timestep, self.task.max_time))
-
-    # -- lifetime ---------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.qg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # -- reset / step through host (NumPy) buffers ------------------------------------------------
     def reset(self, mask=None, seed: int = 0, flags: int = 0):
@@ -98,18 +88,6 @@ class BatchedSim:
         return (obs, rew, done.astype(bool), comps), (qpos, qvel, act, ctrl, nstep)
 
     # -- zero-copy forms on torch (ROCm) tensors ---------------------------------------------------
-    def _stream_ptr(self, stream):
-        import torch
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
-        return C.c_void_p(stream.cuda_stream)
-
-    def _check_tensor(self, t, shape, dtype):
-        if not t.is_cuda or t.device.index != self.device:
-            raise ValueError(f"tensor must live on cuda:{self.device}")
-        if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError(f"expected contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-
     def step_device(self, actions, obs, reward, done, comps=None, stream=None):
         import torch
         self._check_tensor(actions, (self.n, NU), torch.float32)

@@ -3,6 +3,8 @@ include/quadgym.h declares, and refuses to compute without a GPU (there is no CP
 import ctypes as C
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -27,6 +29,18 @@ def test_library_exports_every_declared_symbol():
     for name in _declared_functions():
         assert hasattr(lib, name), f"libquadgym.so does not export {name}"
     assert b"gfx950" in lib.qg_version()
+
+
+@pytest.mark.skipif(shutil.which("nm") is None, reason="needs binutils' nm")
+def test_library_exports_nothing_but_the_declared_symbols():
+    """The library's translation units call each other through internal functions (csrc/qg_sim.h, csrc/qg_host.h): none of them is a
+    dynamic symbol.  The defined dynamic qg_* function symbols are exactly the entry points of include/quadgym.h."""
+    _abi.load_library()                                # raises if the library has not been built
+    out = subprocess.run(["nm", "-D", "--defined-only", _abi.library_path()], check=True, capture_output=True, text=True).stdout
+    symbols = [ln.split() for ln in out.splitlines() if len(ln.split()) == 3]
+    functions = sorted(name for _, kind, name in symbols if kind in "TtWw")
+    assert [name for name in functions if name.startswith("qg_")] == sorted(_abi.EXPORTS)
+    assert [name for name in functions if "qg_" in name and not name.startswith("qg_")] == []      # mangled internal names
 
 
 def test_struct_layouts_match_the_c_side(oracle):

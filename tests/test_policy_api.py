@@ -235,7 +235,7 @@ def test_conditions_of_known_layers():
 def test_launch_sites_equal_what_the_table_launches():
     """Every instantiation of qg_policy_forward_kernel the library can launch is one the table reaches (each row runs at one and at
     four waves in tests/test_policy_shapes_gpu.py), and the other way round: a fifth launch site fails here until a row reaches it."""
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "quadruped-gym_amd", "csrc", "qg_capi.hip")).read()
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "quadruped-gym_amd", "csrc", "qg_policy.hip")).read()
     sites = {(int(w), int(b)) for w, b in re.findall(r"launch_policy<\s*(\d+)\s*,\s*(\d+)\s*>\s*\(", src)}
     assert sites == {(4, 1), (4, 4), (1, 4), (1, 16)}
     kernels = {(int(w), int(b)) for w, b in re.findall(r"qg_policy_forward_kernel<\s*(\w+)\s*,\s*(\w+)\s*>", src) if w.isdigit()}

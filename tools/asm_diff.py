@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """Compare the kernels of two device listings (hipcc -save-temps .s files) instruction by instruction.
 
-usage: asm_diff.py <base.s> <new.s> [substring of the mangled names to look at]
-       asm_diff.py --loops <base.s> <new.s> [substring]     compare only each kernel's substep loop (the loop with the most multiply-adds)
+usage: asm_diff.py <base> <new> [substring of the mangled names to look at]
+       asm_diff.py --loops <base> <new> [substring]     compare only each kernel's substep loop (the loop with the most multiply-adds)
+Each side is one listing, several separated by commas, or a directory (its *-hip-amdgcn-*.s files: what `make asm` writes, one per
+translation unit).  Every file is parsed on its own and the kernels are merged by name.
 Labels are renumbered per kernel (.LBB<function index>_<n> changes when kernels are added or removed elsewhere in the code object);
 comments, .loc / .file / .cfi directives and blank lines are ignored.  Prints one line per kernel: identical / differs (first
 differing instruction) / only in one listing."""
+import glob
+import os
 import re
 import sys
 
@@ -54,11 +58,24 @@ def loops(path):
     return out
 
 
+def side(arg, parse):
+    """the kernels of every listing `arg` names; a name still open at the end of a file (a data label) is dropped with that file"""
+    out = {}
+    for item in arg.split(","):
+        for path in (sorted(glob.glob(os.path.join(item, "*-hip-amdgcn-*.s"))) if os.path.isdir(item) else [item]):
+            found = parse(path)
+            twice = set(found) & set(out)
+            if twice:
+                sys.exit(f"{path}: defined in an earlier listing as well: {sorted(twice)[0]}")
+            out.update(found)
+    return out
+
+
 def main():
     only_loops = len(sys.argv) > 1 and sys.argv[1] == "--loops"
     if only_loops:
         sys.argv.pop(1)
-    a, b = (loops if only_loops else kernels)(sys.argv[1]), (loops if only_loops else kernels)(sys.argv[2])
+    a, b = side(sys.argv[1], loops if only_loops else kernels), side(sys.argv[2], loops if only_loops else kernels)
     key = sys.argv[3] if len(sys.argv) > 3 else ""
     same = diff = 0
     for k in sorted(set(a) | set(b)):

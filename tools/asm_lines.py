@@ -5,11 +5,14 @@ usage: asm_lines.py <listing.s> <substring of the mangled kernel name> [file sub
 Counts the instructions of the largest floating-point loop per (file, line) of the innermost .loc and prints them in line order with
 the source text, plus totals per 'section' comment is left to the reader."""
 import collections
+import os
 import re
 import sys
 
 sys.path.insert(0, __file__.rsplit("/", 1)[0])
 from asm_hist import kernel_lines, largest_loop  # noqa: E402
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "quadruped-gym_amd", "csrc")
 
 
 def main():
@@ -36,7 +39,7 @@ def main():
         name = files.get(f, "?")
         if name not in src_cache:
             try:
-                src_cache[name] = open(name if name.startswith("/") else "/root/repo/quadruped-gym_amd/csrc/" + name).read().splitlines()
+                src_cache[name] = open(name if name.startswith("/") else os.path.join(CSRC, name)).read().splitlines()
             except OSError:
                 src_cache[name] = []
         text = src_cache[name][l - 1].strip()[:110] if 0 < l <= len(src_cache[name]) else ""

@@ -1,6 +1,6 @@
-import sys, time, ctypes as C
+import os, sys, time, ctypes as C
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from quadruped_gym_amd.sim import BatchedSim
 from quadruped_gym_amd import _abi
 for n in (1, 64, 4096):

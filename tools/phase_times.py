@@ -1,6 +1,6 @@
 """Where the time of ONE launch of the one-link-per-lane kernel goes, from inside the kernel: the first wave of the grid stamps the
 100 MHz clock at its phase marks (QG_MARK in qg_kernel_link.hip; development build only).
-usage (GPU box):  make -C quadruped-gym_amd/csrc clean && make -C quadruped-gym_amd/csrc CXXFLAGS+=-DQG_PHASE_TIMES  (see tools/phase_times.sh)
+usage (on an MI355X):  tools/phase_times.sh build  (the library with -DQG_PHASE_TIMES, as tools/lib_phase.so)
                   python tools/phase_times.py [plain|walking|po] [n_envs] [frame_skip]"""
 import ctypes as C
 import os
