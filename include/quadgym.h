@@ -624,6 +624,133 @@ int qg_norm_get_state(qg_norm *norm, double *mean, double *var, double *count, d
 int qg_norm_set_state(qg_norm *norm, const double *mean, const double *var, double count, double ret_mean, double ret_var,
                       double ret_count, const double *returns);
 
+/* ---- PPO rollout buffer on the device: step record, fused GAE, minibatch gather (SB3's RolloutBuffer) --------------------------------
+ * A qg_rollout turns the rows a collection loop leaves on the device into what PPO trains on.  The caller owns the storage (device
+ * arrays it allocates and keeps alive: qg_rollout_storage); the handle owns only the small state: the cursor `pos`, two integer error
+ * counters and the per-env episode accumulators, all in device memory, so that a captured call replays correctly any number of
+ * times.  Like qg_policy and qg_norm it is independent of qg_sim and touches no step kernel.  With n = n_envs, K = n_steps:
+ *
+ * begin(obs):  pos = 0; slot 0 of storage.obs takes obs.  obs == NULL: slot `pos` (as the launch finds it: the observation after the
+ *   last recorded step of the previous rollout) is copied to slot 0.  The episode accumulators are not touched.
+ *
+ * add(step), called after the env step; p = pos as the launch finds it.  p == K: nothing is stored, overflow += 1, pos stays.  Else
+ *   1. actions[p], log_prob[p], values[p] take the arguments; dones[p][i] = (done[i] != 0) as 0 / 1
+ *   2. rewards[p][i] = reward[i]                                         trunc_value == NULL
+ *                    = fma(f32(gamma), trunc_value[i], reward[i])        else: ONE rounding.  The caller passes V(terminal observation)
+ *      where the time limit truncated the episode and 0 elsewhere (SB3's time-limit bootstrap).
+ *   3. slot p + 1 of obs takes next_obs (slot t is the observation the policy saw at step t; slot pos the one after the last step:
+ *      the caller's critic turns it into last_values)
+ *   4. per env i, by one thread: cur_return += f64((episode_reward ? episode_reward : reward)[i]) in f64; cur_length += 1; where
+ *      done[i]: fin_return_sum += cur_return, fin_length_sum += cur_length, fin_count += 1, then cur_return = 0, cur_length = 0.
+ *      No cross-env reduction happens on the device.  episode_reward lets a caller who normalises rewards log the raw returns.
+ *   5. pos = p + 1
+ *
+ * compute(last_values): with F = pos read on the device, per env, for t = F - 1 .. 0 in this order, in f32:
+ *      nnt   = 1 - dones[t]                   (the done stored with step t ends the episode: nothing flows back across it)
+ *      nv    = t == F - 1 ? last_values : values[t + 1]
+ *      delta = rewards[t] + gamma * nv * nnt - values[t]
+ *      A[t]  = delta + gamma * gae_lambda * nnt * A[t + 1]              (A[F] = 0)
+ *      returns[t] = A[t] + values[t]
+ *   (RolloutBuffer.compute_returns_and_advantage of SB3 2.x with episode_starts[t + 1] written as dones[t]).  Slots >= F are not
+ *   written.  Rounding order: g = f32(gamma) and gl = f32(gamma * gae_lambda), the product formed in f64 on the host; g * nnt and
+ *   gl * nnt are exact (nnt is 0 or 1); then
+ *      delta = fl(fma(g * nnt, nv, rewards[t]) - values[t])     A[t] = fma(gl * nnt, A[t + 1], delta)     returns[t] = fl(A[t] + values[t])
+ *   -- two fused multiply-adds, one subtraction, one addition: four roundings per step.  One lane owns one env and walks time
+ *   serially (no scan over time), so the results do not depend on n or on the launch shape.
+ *
+ * gather(idx, B): flat sample f = t * n + i is valid for 0 <= f < F * n (F = pos read on the device).  Row b of every non-NULL output
+ *   takes sample idx[b]: obs slot t row i, actions, log_prob, values, advantages, returns -- copies, bit for bit.  An index outside
+ *   the valid range reads nothing: its row is written as zeros and bad_index += 1 (once per such row).  idx is int64, what
+ *   torch.randperm yields.
+ *
+ * Arithmetic: no floating-point atomics; integer atomics only for the cursor's ticket and the two counters.  Every stored float
+ * depends on its own env or sample alone: results are bit-identical between runs, between eager calls and graph replay and however
+ * a launch is shaped.  Outputs for non-finite inputs are unspecified (the device code is compiled with finite-math assumptions).
+ * Row copies are 16 bytes per lane where obs_dim and the row stride are multiples of 4 and both bases are 16-byte aligned, 4 bytes
+ * otherwise (the rule of qg_norm).
+ *
+ * Ordering: qg_rollout_begin_device, _add_device, _compute_device and _gather_device follow the contract of the other *_device entry
+ * points (they enqueue on the caller's stream, return at once and may be captured into a hipGraph); each is ONE kernel launch, the
+ * cursor's update included: every workgroup of a begin / add launch reads the cursor before it takes an integer ticket, and the
+ * workgroup that draws the last ticket writes the new cursor, so no workgroup observes the cursor its own launch writes.  Calls on
+ * one handle must be ordered by the caller (one stream, or events): two launches that move the cursor must not overlap.
+ * qg_rollout_create, _destroy, _get_info and _episode_stats wait for the device and must not be called during a capture. */
+typedef struct qg_rollout qg_rollout;
+typedef struct qg_rollout_desc {
+    int32_t struct_size;       /* sizeof(qg_rollout_desc): checked */
+    int32_t n_envs;            /* >= 1 */
+    int32_t n_steps;           /* K >= 1; (K + 1) * n_envs <= 2^31 - 1 */
+    int32_t obs_dim;           /* 1 .. 512 */
+    int32_t act_dim;           /* 1 .. 16 */
+    int32_t reserved;          /* 0 */
+    double gamma;              /* finite, in [0, 1] (SB3: 0.99) */
+    double gae_lambda;         /* finite, in [0, 1] (0.95) */
+} qg_rollout_desc;
+/* Device pointers the caller owns and keeps alive while the handle lives; none may be NULL, the f32 ones are 4-byte aligned. */
+typedef struct qg_rollout_storage {
+    int32_t struct_size;       /* sizeof(qg_rollout_storage): checked */
+    int32_t reserved;          /* 0 */
+    float *obs;                /* [K + 1][n][obs_dim] */
+    float *actions;            /* [K][n][act_dim] */
+    float *log_prob;           /* [K][n], as values, rewards, advantages, returns */
+    float *values;
+    float *rewards;
+    float *advantages;
+    float *returns;
+    uint8_t *dones;            /* [K][n] */
+} qg_rollout_storage;
+#define QG_ROLLOUT_DONE_U8 0   /* = QG_NORM_DONE_U8 */
+#define QG_ROLLOUT_DONE_F32 1  /* = QG_NORM_DONE_F32: the last column of the plain env's packed row */
+/* The rows of one env-step (device pointers; strides in elements). */
+typedef struct qg_rollout_step {
+    int32_t struct_size;       /* sizeof(qg_rollout_step): checked */
+    int32_t next_obs_stride;   /* >= obs_dim */
+    int32_t reward_stride;     /* >= 1 */
+    int32_t done_kind;         /* QG_ROLLOUT_DONE_U8 or _F32 */
+    int32_t done_stride;       /* >= 1 */
+    int32_t episode_reward_stride; /* >= 1 where episode_reward is given */
+    const float *next_obs;     /* [n] rows of obs_dim floats: the observation after the step */
+    const float *actions;      /* [n][act_dim] */
+    const float *log_prob;     /* [n] */
+    const float *value;        /* [n] */
+    const float *reward;       /* [n] at reward_stride */
+    const void *done;          /* [n] at done_stride, of the type done_kind names */
+    const float *trunc_value;  /* nullable [n] */
+    const float *episode_reward; /* nullable [n] at episode_reward_stride */
+} qg_rollout_step;
+/* The outputs of a gather (device pointers, each nullable: a NULL output is skipped). */
+typedef struct qg_rollout_batch {
+    int32_t struct_size;       /* sizeof(qg_rollout_batch): checked */
+    int32_t reserved;          /* 0 */
+    float *obs;                /* [B][obs_dim] */
+    float *actions;            /* [B][act_dim] */
+    float *old_log_prob;       /* [B], as old_values, advantages, returns */
+    float *old_values;
+    float *advantages;
+    float *returns;
+} qg_rollout_batch;
+typedef struct qg_rollout_info {
+    int32_t pos;               /* the cursor: slots [0, pos) are filled */
+    int32_t reserved;
+    int64_t overflow;          /* adds that found the buffer full (nothing stored) */
+    int64_t bad_index;         /* gather rows whose index was out of range (written as zeros) */
+} qg_rollout_info;
+/* Validation (QG_ERR_ARG: a field out of range, a NULL or misaligned storage pointer, a wrong struct_size) comes before the device
+ * check (QG_ERR_DEVICE: there is no CPU backend).  A new handle has pos = 0, both counters 0 and empty episode accumulators. */
+int qg_rollout_create(int32_t device_id, const qg_rollout_desc *desc, const qg_rollout_storage *storage, qg_rollout **out);
+int qg_rollout_destroy(qg_rollout *rollout);
+/* One launch each, as above.  obs: [n] rows at obs_stride >= obs_dim, or NULL. */
+int qg_rollout_begin_device(qg_rollout *rollout, const float *obs, int32_t obs_stride, void *stream);
+int qg_rollout_add_device(qg_rollout *rollout, const qg_rollout_step *step, void *stream);
+int qg_rollout_compute_device(qg_rollout *rollout, const float *last_values, void *stream);
+/* B >= 1 (QG_ERR_ARG otherwise); idx [B] int64 on the device. */
+int qg_rollout_gather_device(qg_rollout *rollout, const int64_t *idx, int32_t B, const qg_rollout_batch *out, void *stream);
+/* Host: waits for the device, then reads pos and the counters. */
+int qg_rollout_get_info(qg_rollout *rollout, qg_rollout_info *info);
+/* Host: waits for the device, copies the per-env finished-episode accumulators and sums them in env order (deterministic).  clear != 0
+ * zeroes them; running episodes (cur_return, cur_length) continue. */
+int qg_rollout_episode_stats(qg_rollout *rollout, double *return_sum, int64_t *length_sum, int64_t *count, int32_t clear);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,59 @@ class QgNormDesc(C.Structure):
 NORM_DONE_U8, NORM_DONE_F32 = 0, 1
 
 
+class QgRolloutDesc(C.Structure):
+    """``qg_rollout_desc``: a rollout buffer's shape and constants (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_envs", C.c_int32), ("n_steps", C.c_int32), ("obs_dim", C.c_int32),
+                ("act_dim", C.c_int32), ("reserved", C.c_int32), ("gamma", C.c_double), ("gae_lambda", C.c_double)]
+
+    @classmethod
+    def make(cls, n_envs, n_steps, obs_dim, act_dim, gamma=0.99, gae_lambda=0.95):
+        d = cls()
+        d.struct_size = C.sizeof(cls)
+        d.n_envs, d.n_steps, d.obs_dim, d.act_dim = int(n_envs), int(n_steps), int(obs_dim), int(act_dim)
+        d.gamma, d.gae_lambda = float(gamma), float(gae_lambda)
+        return d
+
+
+class _Sized(C.Structure):
+    """A struct whose first field is its own size: ``make(**fields)`` fills it in."""
+
+    @classmethod
+    def make(cls, **fields):
+        s = cls(**fields)
+        s.struct_size = C.sizeof(cls)
+        return s
+
+
+class QgRolloutStorage(_Sized):
+    """``qg_rollout_storage``: the device arrays the caller owns."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("obs", C.c_void_p), ("actions", C.c_void_p),
+                ("log_prob", C.c_void_p), ("values", C.c_void_p), ("rewards", C.c_void_p), ("advantages", C.c_void_p),
+                ("returns", C.c_void_p), ("dones", C.c_void_p)]
+
+
+class QgRolloutStep(_Sized):
+    """``qg_rollout_step``: the rows of one env-step."""
+    _fields_ = [("struct_size", C.c_int32), ("next_obs_stride", C.c_int32), ("reward_stride", C.c_int32), ("done_kind", C.c_int32),
+                ("done_stride", C.c_int32), ("episode_reward_stride", C.c_int32), ("next_obs", C.c_void_p), ("actions", C.c_void_p),
+                ("log_prob", C.c_void_p), ("value", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p),
+                ("trunc_value", C.c_void_p), ("episode_reward", C.c_void_p)]
+
+
+class QgRolloutBatch(_Sized):
+    """``qg_rollout_batch``: the outputs of a gather, each nullable."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("obs", C.c_void_p), ("actions", C.c_void_p),
+                ("old_log_prob", C.c_void_p), ("old_values", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p)]
+
+
+class QgRolloutInfo(C.Structure):
+    """``qg_rollout_info``: the cursor and the two error counters."""
+    _fields_ = [("pos", C.c_int32), ("reserved", C.c_int32), ("overflow", C.c_int64), ("bad_index", C.c_int64)]
+
+
+ROLLOUT_DONE_U8, ROLLOUT_DONE_F32 = NORM_DONE_U8, NORM_DONE_F32
+
+
 def package_dir() -> str:
     return os.path.dirname(os.path.abspath(__file__))
 
@@ -305,6 +358,14 @@ def load_library():
     lib.qg_norm_reset_returns_device.argtypes = [vp, vp]
     lib.qg_norm_get_state.argtypes = [vp] * 8
     lib.qg_norm_set_state.argtypes = [vp, vp, vp, f64, f64, f64, f64, vp]
+    lib.qg_rollout_create.argtypes = [i32, C.POINTER(QgRolloutDesc), C.POINTER(QgRolloutStorage), C.POINTER(vp)]
+    lib.qg_rollout_destroy.argtypes = [vp]
+    lib.qg_rollout_begin_device.argtypes = [vp, vp, i32, vp]
+    lib.qg_rollout_add_device.argtypes = [vp, C.POINTER(QgRolloutStep), vp]
+    lib.qg_rollout_compute_device.argtypes = [vp, vp, vp]
+    lib.qg_rollout_gather_device.argtypes = [vp, vp, i32, C.POINTER(QgRolloutBatch), vp]
+    lib.qg_rollout_get_info.argtypes = [vp, C.POINTER(QgRolloutInfo)]
+    lib.qg_rollout_episode_stats.argtypes = [vp, C.POINTER(f64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("qg_version", "qg_build_id", "qg_last_error", "qg_time_limit_substeps", "qg_walk_state_bytes", "qg_po_state_bytes",
@@ -334,6 +395,8 @@ EXPORTS = (
     "qg_policy_set_params_device", "qg_policy_forward_device", "qg_policy_launch_shape",
     "qg_norm_create", "qg_norm_destroy", "qg_norm_step_device", "qg_norm_update_obs_device", "qg_norm_apply_obs_device",
     "qg_norm_reset_returns_device", "qg_norm_get_state", "qg_norm_set_state",
+    "qg_rollout_create", "qg_rollout_destroy", "qg_rollout_begin_device", "qg_rollout_add_device", "qg_rollout_compute_device",
+    "qg_rollout_gather_device", "qg_rollout_get_info", "qg_rollout_episode_stats",
 )
 
 

@@ -37,11 +37,22 @@ class Handle:
             stream = torch.cuda.current_stream(self.device)
         return C.c_void_p(stream.cuda_stream)
 
-    def _check_tensor(self, t, shape, dtype):
+    def _check_tensor(self, t, shape, dtype, what=None):
         if not t.is_cuda or t.device.index != self.device:
-            raise ValueError(f"tensor must live on cuda:{self.device}")
+            raise ValueError(f"{what or 'tensor'} must live on cuda:{self.device}")
         if tuple(t.shape) != tuple(shape) or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError(f"expected contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+            raise ValueError((f"{what}: " if what else "") +
+                             f"expected contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+    def _check_vec(self, t, dtypes, what):
+        """``[self.num_envs]`` of one of ``dtypes`` at any positive element stride.  Returns the stride."""
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{what} must live on cuda:{self.device}")
+        if t.dim() != 1 or t.shape[0] != self.num_envs or t.dtype not in dtypes:
+            raise ValueError(f"{what}: expected a tensor of shape ({self.num_envs},) and dtype in {dtypes}, got {t.dtype} {tuple(t.shape)}")
+        if self.num_envs > 1 and t.stride(0) < 1:
+            raise ValueError(f"{what}: the element stride must be >= 1, got {t.stride(0)}")
+        return max(int(t.stride(0)), 1)
 
     def _check_obs(self, t, n=None, what="obs"):
         """``[n, self.obs_dim]`` float32 whose rows are contiguous; the row stride is free (a column slice of a wider buffer).

@@ -38,17 +38,6 @@ class RunningNormalizer(Handle):
         check(self._lib.qg_norm_create(self.device, C.byref(self.desc), C.byref(h)), "qg_norm_create")
         self._h = h
 
-    # -- tensor checks ----------------------------------------------------------------------
-    def _check_vec(self, t, dtypes, what):
-        """``[num_envs]`` of one of ``dtypes`` at any positive element stride.  Returns the stride."""
-        if not t.is_cuda or t.device.index != self.device:
-            raise ValueError(f"{what} must live on cuda:{self.device}")
-        if t.dim() != 1 or t.shape[0] != self.num_envs or t.dtype not in dtypes:
-            raise ValueError(f"{what}: expected a tensor of shape ({self.num_envs},) and dtype in {dtypes}, got {t.dtype} {tuple(t.shape)}")
-        if self.num_envs > 1 and t.stride(0) < 1:
-            raise ValueError(f"{what}: the element stride must be >= 1, got {t.stride(0)}")
-        return max(int(t.stride(0)), 1)
-
     # -- device path ------------------------------------------------------------------------
     def step(self, obs, reward=None, done=None, obs_out=None, reward_out=None, stream=None):
         """One step over the ``num_envs`` rows: ``obs`` float32 ``[N, obs_dim]`` (strided rows allowed), ``reward`` float32 ``[N]``
