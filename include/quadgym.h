@@ -555,6 +555,60 @@ int qg_policy_forward_device(qg_policy *policy, int32_t n, const float *obs, int
  * and A/B timing read it to know which instantiation ran.  Host only, launches nothing. */
 int qg_policy_launch_shape(const qg_policy *policy, int32_t n, int32_t with_value, int32_t *waves, int32_t *blocks);
 
+/* ---- the PPO loss and its gradient for a qg_policy (one minibatch of SB3 2.x PPO.train) ------------------------------------------------
+ * With c = clip_range, cv = clip_range_vf, sigma = exp(log_std), per row of the batch:
+ *   mean = actor(obs)  (tanh on it when out_tanh);  z_a = (action_a - mean_a) / sigma_a
+ *   logp = sum_a(-z_a^2 / 2 - log_std_a - log(2 pi) / 2);  lr = logp - old_log_prob;  r = exp(lr)
+ *   policy_loss  = -mean_rows( min(adv r, adv clamp(r, 1 - c, 1 + c)) )
+ *   v = critic(obs);  vp = cv > 0 ? old_values + clamp(v - old_values, -cv, cv) : v;  value_loss = mean_rows((returns - vp)^2)
+ *   entropy_loss = -sum_a(0.5 + log(2 pi) / 2 + log_std_a)          (state-independent)
+ *   loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss
+ * Without a critic (has_value == 0) value_loss = 0 and old_values / returns are not read.  Advantages are used as given (normalise
+ * them beforehand); the optimiser and gradient-norm clipping are the caller's: grad is ONE flat vector.
+ *
+ * grad [qg_policy_param_count] is d loss / d parameters in the canonical order, every element overwritten (the caller need not clear
+ * it).  The heads: d loss / d logp = -(adv r) / B, and 0 where (adv > 0 and r > 1 + c) or (adv < 0 and r < 1 - c);
+ * d logp / d mean_a = z_a / sigma_a; d loss / d log_std_a = sum_rows(d loss / d logp (z_a^2 - 1)) - ent_coef;
+ * d loss / d v = vf_coef 2 (vp - returns) / B, and 0 where cv > 0 and |v - old_values| >= cv; a factor 1 - mean^2 with out_tanh; then
+ * back through the tanh layers.  stats (nullable, [8]): loss, policy_loss, value_loss, entropy_loss, approx_kl = mean((r - 1) - lr),
+ * clip_fraction = mean(|r - 1| > c), 0, 0 -- summed in f64 and rounded once.
+ *
+ * THREE launches per call (rows: forward recomputed, heads, deltas; weights: partial sums of every dW and db; reduce), all matrix
+ * products on the exact-f32 matrix instruction, the heads in f64.  No floating-point atomics and no workgroup waits for another: sums
+ * over rows are taken per tile of 16 rows, over slots of 32 consecutive tiles (512 rows) in ascending order, then over the slots in
+ * ascending order -- a partition that depends on B alone.  The same inputs therefore give the same bits on every run, eagerly and under
+ * graph replay; bits may differ between different B.  A row with adv = 0 and no value term contributes exact zeros wherever it sits.
+ * Outputs for non-finite inputs are unspecified.  The policy's parameters and its forward pass are not touched.
+ *
+ * qg_policy_reserve_grad allocates the scratch of the pass for up to max_batch rows (activations and deltas of every layer per row,
+ * one partial gradient per 512 rows) and the transposed weight image, which every later parameter update then also repacks (a policy
+ * that never reserves enqueues exactly what it did before).  Host call: it waits for the device, must not be called during a stream
+ * capture, and may be called again to grow.  qg_policy_ppo_grad_device follows the *_device contract: it enqueues on the caller's
+ * stream, returns at once, can be captured into a hipGraph (params are taken by value at the call: a captured graph keeps them) and
+ * allocates nothing.  QG_ERR_ARG, before any device check: NULL policy / params / batch / grad, a wrong struct_size, reserved != 0,
+ * B < 1, B > the rows reserved (nothing reserved included), obs_stride < obs_dim, clip_range not finite or <= 0, another parameter
+ * not finite, a NULL obs / actions / old_log_prob / advantages, and with a critic a NULL returns, or a NULL old_values with cv > 0. */
+typedef struct qg_ppo_params {
+    int32_t struct_size;       /* sizeof(qg_ppo_params): checked */
+    int32_t reserved;          /* 0 */
+    float clip_range;          /* finite, > 0            (SB3: 0.2) */
+    float clip_range_vf;       /* finite; <= 0: value clipping off (SB3: None) */
+    float ent_coef, vf_coef;   /* finite                 (SB3: 0.0, 0.5) */
+} qg_ppo_params;
+typedef struct qg_ppo_batch {  /* device pointers: what qg_rollout_gather_device wrote */
+    int32_t struct_size;       /* sizeof(qg_ppo_batch): checked */
+    int32_t obs_stride;        /* floats, >= obs_dim */
+    const float *obs;          /* [B] rows */
+    const float *actions;      /* [B][act_dim] */
+    const float *old_log_prob; /* [B] */
+    const float *advantages;   /* [B] */
+    const float *old_values;   /* [B]; may be NULL without a critic or when clip_range_vf <= 0 */
+    const float *returns;      /* [B]; may be NULL without a critic */
+} qg_ppo_batch;
+int qg_policy_reserve_grad(qg_policy *policy, int32_t max_batch);
+int qg_policy_ppo_grad_device(qg_policy *policy, const qg_ppo_params *params, int32_t B, const qg_ppo_batch *batch, float *grad,
+                              float *stats, void *stream);
+
 /* ---- running observation and reward normalisation (SB3's VecNormalize) on the device ---------------------------------------------------
  * A qg_norm keeps, in f64 on the device, a running mean and variance per observation column, a discounted return per env and the
  * running variance of those returns, and normalises the rows a step left on the device: the semantics of Stable-Baselines3 2.x

@@ -156,6 +156,34 @@ class QgPolicyDesc(C.Structure):
         return d
 
 
+class QgPpoParams(C.Structure):
+    """``qg_ppo_params``: the coefficients of one PPO loss call (``struct_size`` is filled in); ``clip_range_vf=None`` is off."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("clip_range", C.c_float), ("clip_range_vf", C.c_float),
+                ("ent_coef", C.c_float), ("vf_coef", C.c_float)]
+
+    @classmethod
+    def make(cls, clip_range=0.2, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5):
+        d = cls()
+        d.struct_size = C.sizeof(cls)
+        d.clip_range, d.clip_range_vf = float(clip_range), 0.0 if clip_range_vf is None else float(clip_range_vf)
+        d.ent_coef, d.vf_coef = float(ent_coef), float(vf_coef)
+        return d
+
+
+class QgPpoBatch(C.Structure):
+    """``qg_ppo_batch``: device pointers of one minibatch (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("obs_stride", C.c_int32), ("obs", C.c_void_p), ("actions", C.c_void_p),
+                ("old_log_prob", C.c_void_p), ("advantages", C.c_void_p), ("old_values", C.c_void_p), ("returns", C.c_void_p)]
+
+    @classmethod
+    def make(cls, obs_stride, **ptrs):
+        d = cls()
+        d.struct_size, d.obs_stride = C.sizeof(cls), int(obs_stride)
+        for name, ptr in ptrs.items():
+            setattr(d, name, ptr)
+        return d
+
+
 class QgNormDesc(C.Structure):
     """``qg_norm_desc``: a running normaliser's shape and constants (``struct_size`` is filled in)."""
     _fields_ = [("struct_size", C.c_int32), ("obs_dim", C.c_int32), ("n_envs", C.c_int32), ("gamma", C.c_double),
@@ -349,6 +377,8 @@ def load_library():
     lib.qg_policy_set_params_device.argtypes = [vp, vp, vp]
     lib.qg_policy_forward_device.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
     lib.qg_policy_launch_shape.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.qg_policy_reserve_grad.argtypes = [vp, C.c_int32]
+    lib.qg_policy_ppo_grad_device.argtypes = [vp, C.POINTER(QgPpoParams), C.c_int32, C.POINTER(QgPpoBatch), vp, vp, vp]
     i32, f64 = C.c_int32, C.c_double
     lib.qg_norm_create.argtypes = [i32, C.POINTER(QgNormDesc), C.POINTER(vp)]
     lib.qg_norm_destroy.argtypes = [vp]
@@ -393,6 +423,7 @@ EXPORTS = (
     "qg_set_xfrc", "qg_set_xfrc_device", "qg_get_xfrc", "qg_set_push", "qg_clear_xfrc",
     "qg_policy_create", "qg_policy_destroy", "qg_policy_param_count", "qg_policy_set_params", "qg_policy_get_params",
     "qg_policy_set_params_device", "qg_policy_forward_device", "qg_policy_launch_shape",
+    "qg_policy_reserve_grad", "qg_policy_ppo_grad_device",
     "qg_norm_create", "qg_norm_destroy", "qg_norm_step_device", "qg_norm_update_obs_device", "qg_norm_apply_obs_device",
     "qg_norm_reset_returns_device", "qg_norm_get_state", "qg_norm_set_state",
     "qg_rollout_create", "qg_rollout_destroy", "qg_rollout_begin_device", "qg_rollout_add_device", "qg_rollout_compute_device",

@@ -23,29 +23,7 @@
 #include <cstring>
 #include <new>
 
-#include "qg_host.h"
-
-#define QGP_MAX_LAYERS 4          // n_hidden <= 3 hidden layers + the output layer
-#define QGP_TILE 16               // envs per workgroup
-
-struct KPolLayer {
-    int32_t nq;                   // blocks of 16 input features (the input width, zero padded)
-    int32_t nb;                   // blocks of 16 output features
-    int32_t in_dim, out_dim;      // the real sizes (pack kernel)
-    int32_t w_off, b_off;         // offsets (floats) into the packed image: W' [nb][nq][64][4], b' [nb][16]
-    int32_t src_w, src_b;         // offsets (floats) into the canonical flat vector: W [out][in], b [out]
-};
-
-struct KPolicy {
-    int32_t obs_dim, act_dim, n_layers, out_tanh, n_towers;
-    int32_t std_off;              // packed: std[16] = exp(log_std), then log_std[16]
-    int32_t src_log_std;          // canonical: log_std[act_dim]
-    int32_t packed_floats;
-    int32_t lds0_floats, lds1_floats;   // the two activation buffers (layer l reads buffer l & 1, writes the other)
-    KPolLayer layer[2][QGP_MAX_LAYERS];
-};
-
-typedef float qgp_f32x4 __attribute__((ext_vector_type(4)));
+#include "qg_policy.h"
 
 // canonical flat parameters -> the packed image (one thread per packed float; runs on the caller's stream after every update)
 __global__ void qg_policy_pack_kernel(KPolicy P, const float *__restrict__ src, float *__restrict__ packed) {
@@ -246,18 +224,6 @@ __global__ __launch_bounds__(64 * WAVES) void qg_policy_forward_kernel(KPolicy P
 // ------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------
-struct qg_policy {
-    int32_t device;
-    qg_policy_desc desc;
-    KPolicy k;
-    int32_t n_params;
-    int32_t simds;
-    int32_t force_waves;      // env QG_POLICY_WAVES at qg_policy_create: 1 or 4 waves per env tile whatever the size (A/B; 0: by size)
-    QgDevMem mem;
-    float *d_params;          // canonical flat vector (what qg_policy_get_params returns)
-    float *d_packed;          // the operand image the forward kernel reads
-};
-
 // the description is valid: fills the kernel's layer table (offsets into both parameter images) and returns the canonical length
 static int policy_layout(const qg_policy_desc *d, KPolicy *k) {
     if (!d) return fail(QG_ERR_ARG, "qg_policy: null description");
@@ -328,7 +294,7 @@ static int policy_pack(qg_policy *p, hipStream_t st) {
     const int threads = 256;
     qg_policy_pack_kernel<<<(p->k.packed_floats + threads - 1) / threads, threads, 0, st>>>(p->k, p->d_params, p->d_packed);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
-    return QG_OK;
+    return qg_policy_pack_transposed(p, st);       // the gradient pass's image, once qg_policy_reserve_grad has been called
 }
 
 extern "C" int qg_policy_create(int32_t device_id, const qg_policy_desc *desc, qg_policy **out) {

@@ -7,12 +7,13 @@ only: it owns the tensors and the stream.  There is no CPU path.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
 
 from . import _abi
-from ._abi import QgPolicyDesc, check
+from ._abi import QgPolicyDesc, QgPpoBatch, QgPpoParams, check
 from ._handle import Handle
 
 
@@ -62,6 +63,10 @@ class FusedMlpPolicy(Handle):
     stream-ordered).  Outputs for non-finite observations are unspecified."""
 
     _destroy = "qg_policy_destroy"
+    # rows per partial-sum slot of ``ppo_grad`` (32 tiles of 16 rows): a workgroup of its weight-gradient launch sums that many
+    # consecutive rows, the reduce launch adds the slots in ascending order (QGG_SLOT_TILES of csrc/qg_policy.h)
+    GRAD_TILE_ROWS = 16
+    GRAD_SLOT_ROWS = 512
 
     def __init__(self, obs_dim: int, hidden, act_dim: int, out_tanh: bool = False, value: bool = True, device: int = 0):
         super().__init__(device)
@@ -81,6 +86,28 @@ class FusedMlpPolicy(Handle):
         dims = (self.obs_dim,) + self.hidden
         body = [(dims[i + 1], dims[i]) for i in range(len(self.hidden))]
         return body + [(self.act_dim, dims[-1])], (body + [(1, dims[-1])] if self.has_value else [])
+
+    @staticmethod
+    def param_layout(obs_dim, hidden, act_dim, value=True):
+        """``name -> (offset, shape)`` over the canonical flat vector of a policy of this description, in order: ``actor.0.weight``,
+        ``actor.0.bias``, .., ``log_std``, ``critic.0.weight``, ..  (``k`` counts the Linear layers of a tower).  Host arithmetic
+        only."""
+        dims = (int(obs_dim),) + tuple(int(h) for h in hidden)
+        out, off = collections.OrderedDict(), 0
+        for tower, last in (("actor", int(act_dim)), ("critic", 1))[:2 if value else 1]:
+            for k, (i, o) in enumerate(zip(dims, dims[1:] + (last,))):
+                out[f"{tower}.{k}.weight"] = (off, (o, i))
+                out[f"{tower}.{k}.bias"] = (off + o * i, (o,))
+                off += o * i + o
+            if tower == "actor":
+                out["log_std"] = (off, (int(act_dim),))
+                off += int(act_dim)
+        return out
+
+    def param_slices(self):
+        """``param_layout`` of this policy: view ``params()``, a flat parameter tensor or the ``grad`` of ``ppo_grad`` per layer with
+        ``flat[off:off + math.prod(shape)].view(shape)``."""
+        return self.param_layout(self.obs_dim, self.hidden, self.act_dim, self.has_value)
 
     def set_params(self, flat):
         """The canonical flat vector from the host (synchronous)."""
@@ -178,3 +205,40 @@ class FusedMlpPolicy(Handle):
                                                  actions.data_ptr(), log_prob.data_ptr() if log_prob is not None else None,
                                                  value.data_ptr() if value is not None else None, self._stream_ptr(stream)),
               "qg_policy_forward_device")
+
+    # -- the PPO update ---------------------------------------------------------------------
+    def reserve_grad(self, max_batch: int):
+        """Allocate what ``ppo_grad`` needs for minibatches of up to ``max_batch`` rows (waits for the device; not during a graph
+        capture; call again to grow).  From here on every parameter update also repacks the transposed weights the pass reads."""
+        check(self._lib.qg_policy_reserve_grad(self._h, int(max_batch)), "qg_policy_reserve_grad")
+
+    def ppo_grad(self, batch, grad, stats=None, clip_range=0.2, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5, stream=None):
+        """The PPO loss of one minibatch (SB3 2.x ``PPO.train``; ``include/quadgym.h`` states it) and its gradient, three launches on
+        ``stream``: ``grad[n_params]`` in the canonical order, every element overwritten; ``stats[8]`` (optional) = loss, policy_loss,
+        value_loss, entropy_loss, approx_kl, clip_fraction, 0, 0.  ``batch`` is a ``RolloutBufferSamples`` or anything with its six
+        attributes (``old_values`` / ``returns`` may be None without a critic; ``old_values`` also without value clipping);
+        ``observations`` may be row-strided.  Advantages are used as given."""
+        import torch
+        n, stride = self._check_obs(batch.observations, what="observations")
+        f32 = torch.float32
+        self._check_tensor(batch.actions, (n, self.act_dim), f32, "actions")
+        self._check_tensor(batch.old_log_prob, (n,), f32, "old_log_prob")
+        self._check_tensor(batch.advantages, (n,), f32, "advantages")
+        ptrs = dict(obs=batch.observations.data_ptr(), actions=batch.actions.data_ptr(), old_log_prob=batch.old_log_prob.data_ptr(),
+                    advantages=batch.advantages.data_ptr())
+        if self.has_value:
+            if batch.returns is None or (batch.old_values is None and clip_range_vf is not None and clip_range_vf > 0):
+                raise ValueError("a policy with a critic needs returns, and old_values when clip_range_vf is set")
+            for name in ("old_values", "returns"):
+                t = getattr(batch, name)
+                if t is not None:
+                    self._check_tensor(t, (n,), f32, name)
+                    ptrs[name] = t.data_ptr()
+        self._check_tensor(grad, (self.n_params,), f32, "grad")
+        if stats is not None:
+            self._check_tensor(stats, (8,), f32, "stats")
+        params = QgPpoParams.make(clip_range, clip_range_vf, ent_coef, vf_coef)
+        desc = QgPpoBatch.make(stride, **ptrs)
+        check(self._lib.qg_policy_ppo_grad_device(self._h, C.byref(params), n, C.byref(desc), grad.data_ptr(),
+                                                  stats.data_ptr() if stats is not None else None, self._stream_ptr(stream)),
+              "qg_policy_ppo_grad_device")
