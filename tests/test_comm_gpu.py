@@ -51,6 +51,12 @@ def test_native_rollout_matches_plain_stepping():
     # a second call continues the double-buffer protocol where the first one stopped
     check(lib.qg_comm_rollout(comm, a_arr, 4, p_arr, g_arr, 2, 0), "qg_comm_rollout")
     check(lib.qg_comm_synchronize(comm), "qg_comm_synchronize")
-    assert (a_sim.get_state()[4] == b_sim.get_state()[4] + 8).all() or True   # (auto-reset may have restarted some envs)
+    for k in range(2):                                   # the call restarts at k = 0: pool[0], pool[1] into buffers 0, 1
+        b_sim.step_device_packed(pool[k], ref)
+    torch.cuda.synchronize()
+    want = ref.cpu().numpy().tobytes()                   # bit for bit
+    assert packed[1].cpu().numpy().tobytes() == want
+    assert gathered[1][0].cpu().numpy().tobytes() == want
+    assert a_sim.get_state()[0].tobytes() == b_sim.get_state()[0].tobytes()
     lib.qg_comm_destroy(comm)
     a_sim.close(); b_sim.close()
