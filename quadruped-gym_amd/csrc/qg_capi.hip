@@ -2,8 +2,10 @@
 //
 // Owns the per-env device state (struct-of-arrays in HBM), converts the double-precision
 // model/task descriptions into the kernarg-sized single-precision tables the kernels read,
-// and launches the step kernels, every instantiation of which is compiled in this translation unit.  The handles bound to a
-// simulator (qg_comm.hip, qg_walk.hip, qg_po.hip) reach it through qg_sim.h; qg_policy.hip and qg_norm.hip share qg_host.h only.
+// and decides which mapping a step runs.  The step kernels, their launchers and the leaves of each mapping are translation units of
+// their own, one per family (qg_kernel_link.hip, qg_kernel_quad.hip, qg_kernel_pair.hip; their entry points: qg_step_launch.h);
+// this one compiles only the five small kernels of reset and state transfer.  The handles bound to a simulator (qg_comm.hip,
+// qg_walk.hip, qg_po.hip) reach it through qg_sim.h; qg_policy.hip and qg_norm.hip share qg_host.h only.
 // There is no CPU code path: every compute entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
@@ -18,11 +20,8 @@
 
 #include "../../include/quadgym.h"
 #include "../../include/qg_model_data.h"
-// the step kernels are compiled in this translation unit (one code object per translation unit, no -fgpu-rdc)
-#include "qg_kernels.hip"
-#include "qg_kernel_link.hip"
-#include "qg_kernel_resident.hip"
-#include "qg_sim.h"
+#include "qg_step_dev.h"       // the shared device code: the reset kernels below draw and place the start pose as the step kernels do
+#include "qg_step_launch.h"
 #include "qg_tables.h"
 
 static int resident_retire(qg_sim *s);
@@ -189,6 +188,80 @@ extern "C" int qg_create(int32_t n_envs, int32_t device_id, const qg_model *mode
 extern "C" int qg_num_envs(const qg_sim *s) { return s ? s->n : fail(QG_ERR_ARG, "null handle"); }
 extern "C" int qg_obs_dim(const qg_sim *s) { return s ? s->obs_dim : fail(QG_ERR_ARG, "null handle"); }
 
+// ------------------------------------------------------------------------------------------
+// reset (quadruped.py:115-139): mj_resetData, time = 0, ctrl = default; optional random yaw and hinge jitter
+// ------------------------------------------------------------------------------------------
+__global__ void qg_reset_kernel(const KModel *__restrict__ M, const KTask *__restrict__ T, KState st, int n, const uint8_t *mask,
+                                uint64_t seed, uint64_t env_index_base, uint32_t flags, int count_episode) {
+    int env = blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= n) return;
+    if (mask && !mask[env]) return;
+    const int ep = st.episode[env];
+    for (int j = 0; j < 19; ++j) st.qpos[j * n + env] = M->qpos0[j];
+    if (flags & 2u) {
+        for (int j = 0; j < 12; ++j)
+            st.qpos[(7 + j) * n + env] = jittered_hinge(M->qpos0[7 + j], M->link[j].lo, M->link[j].hi, T->reset_joint_jitter, seed,
+                                                        env_index_base + (uint64_t)env, ep, j);
+    }
+    if (flags & 1u)
+        QG_RESET_HEADING(seed, env_index_base + (uint64_t)env, ep, st.qpos[3 * n + env], st.qpos[4 * n + env], st.qpos[5 * n + env], st.qpos[6 * n + env]);
+    for (int j = 0; j < 18; ++j) st.qvel[j * n + env] = 0.f;
+    for (int j = 0; j < 12; ++j) { st.act[j * n + env] = 0.f; st.ctrl[j * n + env] = T->default_ctrl[j]; }
+    st.nstep[env] = 0;
+    if (count_episode) st.episode[env] += 1;
+}
+
+// QG_RESET_JOINT_JITTER for the envs the step kernel has just auto-reset: their hinges stand at qpos0 and their episode counter
+// has advanced, so the key of the episode that begins is episode - 1 (the one its reset yaw used).  A separate launch, issued
+// only when the task asks for jitter: inside the step kernels even a never-taken branch of this size measured +0.9 % at 4096
+// envs and +2 % at 32 768 (same-box A/B).  One thread per (hinge, env); `done` is the step's done output, either as bytes
+// or as the last column of the packed rows.
+__global__ void qg_jitter_kernel(const KModel *__restrict__ M, const KTask *__restrict__ T, KState st, int n, const uint8_t *__restrict__ done,
+                                 const float *__restrict__ packed, int row, uint64_t seed, uint64_t env_index_base) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 12 * n) return;
+    const int j = t / n, env = t - j * n;
+    const bool was_reset = done ? (done[env] != 0) : (packed[(size_t)env * row + (row - 1)] > 0.5f);
+    if (!was_reset) return;
+    st.qpos[(7 + j) * n + env] = jittered_hinge(M->qpos0[7 + j], M->link[j].lo, M->link[j].hi, T->reset_joint_jitter, seed,
+                                                env_index_base + (uint64_t)env, st.episode[env] - 1, j);
+}
+
+// QG_RESET_DYNAMICS: column c of env i drawn for episode e as lo + (hi - lo) u, u = uniform24s(seed, base + i, e, 16 + c) -- streams of
+// their own, so the yaw (0), hinge (1..12) and command (13..15) draws are the same with the flag as without.  One thread per (column,
+// env).  Behind qg_reset (`mask`: the envs reset, NULL: all; key = the episode counter before the reset advances it, key_offset 0) and,
+// as qg_jitter_kernel and for its reason, as a launch of its own behind a step that auto-resets (`done` bytes or the packed rows' last
+// column: the envs that finished; their counter has advanced, key_offset -1).
+#define QG_STREAM_DYNAMICS 16u
+__global__ void qg_dyn_draw_kernel(float *__restrict__ rows, KDynRange R, const int32_t *__restrict__ episode, int n, const uint8_t *__restrict__ mask,
+                                   const uint8_t *__restrict__ done, const float *__restrict__ packed, int row, int key_offset, uint64_t seed,
+                                   uint64_t env_index_base) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= QGK_NDYN * n) return;
+    const int c = t / n, env = t - c * n;
+    if (mask && !mask[env]) return;
+    if (!mask && (done || packed)) {
+        const bool was_reset = done ? (done[env] != 0) : (packed[(size_t)env * row + (row - 1)] > 0.5f);
+        if (!was_reset) return;
+    }
+    const float u = uniform24s(seed, env_index_base + (uint64_t)env, (uint64_t)(episode[env] + key_offset), QG_STREAM_DYNAMICS + (uint32_t)c);
+    rows[(size_t)c * n + env] = fmaf(R.hi[c] - R.lo[c], u, R.lo[c]);
+}
+
+// env-major [n][w] <-> field-major [w][n] (state snapshot / restore at the ABI)
+__global__ void qg_transpose_in(const float *__restrict__ src, float *__restrict__ dst, int n, int w) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * w) return;
+    int f = i / n, e = i - f * n;
+    dst[i] = src[(size_t)e * w + f];
+}
+__global__ void qg_transpose_out(const float *__restrict__ src, float *__restrict__ dst, int n, int w) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * w) return;
+    int e = i / w, f = i - e * w;
+    dst[i] = src[(size_t)f * n + e];
+}
+
 extern "C" int qg_reset(qg_sim *s, const uint8_t *mask, uint64_t seed, uint32_t flags) {
     if (!s) return fail(QG_ERR_ARG, "null handle");
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
@@ -245,82 +318,6 @@ int qg_effective_mapping(const qg_sim *s) {
     return QG_MAP_QUAD;
 }
 
-// ---- step-kernel grids ------------------------------------------------------------------------------------------------------------
-// The size predicates every step-kernel choice reads (po_fusable, launch_step, qg_step_device_seq), and the launchers: one per kernel
-// family, each deriving grid and block from the instantiation it launches, as the kernel's __launch_bounds__ does.
-static int link_blocks(const qg_sim *s) { return (s->n + QGK_LINK_ENVS * QGK_LINK_WAVES - 1) / (QGK_LINK_ENVS * QGK_LINK_WAVES); }
-static int quad_blocks(const qg_sim *s) { return (s->n + QGK_QUAD_ENVS - 1) / QGK_QUAD_ENVS; }    // one wave each
-static int pair_blocks(const qg_sim *s) { return (s->n + QGK_PAIR_ENVS - 1) / QGK_PAIR_ENVS; }
-// four-wave workgroups for grids of more than one wave per compute unit
-static bool quad_wg4(const qg_sim *s) { return quad_blocks(s) > s->simds / 4; }
-static bool pair_wg4(const qg_sim *s) { return pair_blocks(s) > s->simds / 4; }
-// at most one wave per SIMD (256 CUs x 4 on an MI355X): give each wave the whole register file
-static bool quad_one_wave(const qg_sim *s) { return quad_blocks(s) <= s->simds; }
-static dim3 wave_grid(int waves, int per_group) { return dim3(per_group == 4 ? (waves + 3) / 4 : waves); }
-
-// what every per-launch step kernel takes, and where it goes
-struct StepLaunch {
-    const qg_sim *s;
-    const KModel *model;      // the model tables (per-env dynamics: the KModelDyn in front of the rows)
-    KStepArgs P;
-    hipStream_t stream;
-    const KWalkLaunch *walk;
-    const KPoLaunch *po;
-};
-template <bool WALK> static typename WalkArgT<WALK>::type walk_arg(const KWalkLaunch *w) {
-    if constexpr (WALK) return *w;
-    else return {};
-}
-template <bool PO> static typename PoArgT<PO>::type po_arg(const KPoLaunch *p) {
-    if constexpr (PO) return *p;
-    else return {};
-}
-
-// Which instantiation a launcher enqueued, for qg_debug_last_step_kernel: the family in the low nibble, then one nibble per template
-// argument in declaration order (every argument is 0 .. 4).  A store of a constant on the launch path; the name is formatted on request.
-enum StepFamily : uint32_t { KF_NONE, KF_LANE, KF_LINK, KF_QUAD, KF_PAIR, KF_LINK_MULTI, KF_QUAD_MULTI, KF_PAIR_MULTI };
-template <int... A> static constexpr uint32_t step_kernel_code(StepFamily fam) {
-    uint32_t code = fam, shift = 4;
-    ((code |= (uint32_t)A << shift, shift += 4), ...);
-    return code;
-}
-
-template <bool BAKED> static void launch_lane(const StepLaunch &L) {
-    L.s->last_step_kernel = step_kernel_code<BAKED>(KF_LANE);
-    hipLaunchKernelGGL(qg_step_kernel<BAKED>, dim3((L.s->n + QGK_WAVE - 1) / QGK_WAVE), dim3(QGK_WAVE), 0, L.stream, L.model, L.s->d_task, L.P);
-}
-template <bool WALK, bool PO, bool BAKED, bool HELP = false, bool DYN = false> static void launch_link(const StepLaunch &L) {
-    L.s->last_step_kernel = step_kernel_code<WALK, PO, BAKED, HELP, DYN>(KF_LINK);
-    hipLaunchKernelGGL((qg_step_kernel_link<WALK, PO, BAKED, HELP, DYN>), dim3(link_blocks(L.s)), dim3(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1)), 0,
-                       L.stream, L.model, L.s->d_task, L.P, walk_arg<WALK>(L.walk), po_arg<PO>(L.po));
-}
-template <int WPE, bool BAKED, bool WALK, int WAVES, bool PO = false, bool HELP = false, bool DYN = false> static void launch_quad(const StepLaunch &L) {
-    static_assert(WAVES == 1 || WAVES == 4, "one-wave or four-wave workgroups");
-    L.s->last_step_kernel = step_kernel_code<WPE, BAKED, WALK, WAVES, PO, HELP, DYN>(KF_QUAD);
-    hipLaunchKernelGGL((qg_step_kernel_quad<WPE, BAKED, WALK, WAVES, PO, HELP, DYN>), wave_grid(quad_blocks(L.s), WAVES),
-                       dim3(QGK_WAVE * WAVES * (HELP ? 2 : 1)), 0, L.stream, L.model, L.s->d_task, L.P, walk_arg<WALK>(L.walk), po_arg<PO>(L.po));
-}
-template <int WAVES, bool WALK, bool PO = false> static void launch_pair(const StepLaunch &L) {
-    static_assert(WAVES == 1 || WAVES == 4, "one-wave or four-wave workgroups");
-    L.s->last_step_kernel = step_kernel_code<WAVES, WALK, PO>(KF_PAIR);
-    hipLaunchKernelGGL((qg_step_kernel_pair<WAVES, WALK, PO>), wave_grid(pair_blocks(L.s), WAVES), dim3(QGK_WAVE * WAVES), 0, L.stream, L.s->d_task,
-                       L.P, walk_arg<WALK>(L.walk), po_arg<PO>(L.po));
-}
-// the many-env-steps-per-launch forms (qg_kernel_resident.hip)
-template <bool BAKED, bool DOOR> static void launch_link_multi(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
-    s->last_step_kernel = step_kernel_code<BAKED, DOOR>(KF_LINK_MULTI);
-    hipLaunchKernelGGL((qg_step_kernel_link_multi<BAKED, DOOR>), dim3(link_blocks(s)), dim3(QGK_WAVE * QGK_LINK_WAVES), 0, st, s->d_model, s->d_task, P, R);
-}
-template <int WPE, bool BAKED> static void launch_quad_multi(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
-    s->last_step_kernel = step_kernel_code<WPE, BAKED>(KF_QUAD_MULTI);
-    hipLaunchKernelGGL((qg_step_kernel_quad_multi<WPE, BAKED>), wave_grid(quad_blocks(s), 4), dim3(QGK_WAVE * 4), 0, st, s->d_model, s->d_task, P, R);
-}
-template <int WAVES> static void launch_pair_multi(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
-    static_assert(WAVES == 1 || WAVES == 4, "one-wave or four-wave workgroups");
-    s->last_step_kernel = step_kernel_code<WAVES>(KF_PAIR_MULTI);
-    hipLaunchKernelGGL((qg_step_kernel_pair_multi<WAVES>), wave_grid(pair_blocks(s), WAVES), dim3(QGK_WAVE * WAVES), 0, st, s->d_task, P, R);
-}
-
 // Which step kernels carry the fused observation pack (KPoLaunch): the one-link-per-lane kernel, and -- round 3 -- the four-wave-workgroup
 // forms of the two-legs-per-lane and one-leg-per-lane kernels that AUTO runs above 4096 envs (explicit mapping requests on small
 // grids, which launch the one-wave-workgroup forms, keep the observation pack a launch of its own).
@@ -345,62 +342,6 @@ static void note_caller_stream(qg_sim *s, hipStream_t stream) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); s->captured_once = 1; }
     else if (cs == hipStreamCaptureStatusActive) s->captured_once = 1;
-}
-
-// One decision per mapping; every leaf names the instantiation it launches.  DYN: per-env dynamics, which run the table-driven
-// (!baked) leaves of the LINK and QUAD mappings only.
-template <bool DYN> static void select_step(const StepLaunch &L, int emap) {
-    const qg_sim *s = L.s;
-    const bool walk = L.walk, po = L.po;
-    switch (emap) {
-    case QG_MAP_LINK:
-        if (!s->baked) {
-            if (po) launch_link<true, true, false, false, DYN>(L);
-            else if (walk) launch_link<true, false, false, false, DYN>(L);
-            else launch_link<false, false, false, false, DYN>(L);
-        } else if (walk && s->link_helpers) {
-            // helper waves (qg_step_kernel_link<.., HELP>): the compiled-in robot's walking forms; QG_LINK_HELPERS=0 at qg_create keeps the one-role kernels
-            if (po) launch_link<true, true, true, true>(L);
-            else launch_link<true, false, true, true>(L);
-        } else if (po) launch_link<true, true, true>(L);
-        else if (walk) launch_link<true, false, true>(L);
-        else launch_link<false, false, true>(L);
-        break;
-    case QG_MAP_QUAD:
-        if (!s->baked) {
-            // tables in LDS: the 256-register cap spills 888 B per lane and measured 2x slower at every grid size (363 vs 741 us
-            // at 262 144 envs), so any other robot runs the one-wave-per-SIMD form throughout
-            if (po) launch_quad<1, false, true, 4, true, false, DYN>(L);     // qg_po_fusable(): four-wave workgroups
-            else if (walk && quad_wg4(s)) launch_quad<1, false, true, 4, false, false, DYN>(L);
-            else if (walk) launch_quad<1, false, true, 1, false, false, DYN>(L);
-            else if (quad_wg4(s)) launch_quad<1, false, false, 4, false, false, DYN>(L);
-            else launch_quad<1, false, false, 1, false, false, DYN>(L);
-        } else if (po) {            // qg_po_fusable(): four-wave workgroups, register cap for one or two waves per SIMD
-            if (quad_one_wave(s) && s->link_helpers) launch_quad<2, true, true, 4, true, true>(L);
-            else if (quad_one_wave(s)) launch_quad<1, true, true, 4, true>(L);
-            else launch_quad<2, true, true, 4, true>(L);
-        } else if (walk) {
-            // at most one physics wave per SIMD: helper waves beside them (QG_LINK_HELPERS, as for the one-link-per-lane kernel)
-            if (quad_one_wave(s) && s->link_helpers) launch_quad<2, true, true, 4, false, true>(L);
-            else if (quad_one_wave(s) && quad_wg4(s)) launch_quad<1, true, true, 4>(L);
-            else if (quad_one_wave(s)) launch_quad<1, true, true, 1>(L);
-            else launch_quad<2, true, true, 4>(L);
-        } else if (quad_one_wave(s)) {
-            if (quad_wg4(s)) launch_quad<1, true, false, 4>(L);
-            else launch_quad<1, true, false, 1>(L);
-        } else launch_quad<2, true, false, 4>(L);       // (more than one wave per SIMD is more than one per compute unit: quad_wg4)
-        break;
-    case QG_MAP_PAIR:                       // (the compiled-in robot only)
-        if (po) launch_pair<4, true, true>(L);                             // qg_po_fusable(): four-wave workgroups
-        else if (walk && pair_wg4(s)) launch_pair<4, true>(L);
-        else if (walk) launch_pair<1, true>(L);
-        else if (pair_wg4(s)) launch_pair<4, false>(L);
-        else launch_pair<1, false>(L);
-        break;
-    default:                                // QG_MAP_LANE
-        if (s->baked) launch_lane<true>(L);
-        else launch_lane<false>(L);
-    }
 }
 
 // `walk` != NULL: the fused walking launch (one-leg-per-lane kernel with the task layer folded in); walk_comps / walk_sample go
@@ -436,8 +377,12 @@ int qg_launch_step(qg_sim *s, const float *d_actions, float *d_obs, float *d_rew
     // above (qg_set_mapping refuses the other mappings while the mode is on); wrench mode runs the same forms
     if (per_env && emap != QG_MAP_LINK && emap != QG_MAP_QUAD)
         return fail(QG_ERR_ARG, "step: per-env dynamics run in the LINK and QUAD mappings only (mapping %d)", emap);
-    if (per_env) select_step<true>(L, emap);
-    else select_step<false>(L, emap);
+    switch (emap) {                         // the leaves of a mapping are with its kernels (qg_step_launch.h)
+    case QG_MAP_LINK: qg_select_step_link(L, per_env); break;
+    case QG_MAP_QUAD: qg_select_step_quad(L, per_env); break;
+    case QG_MAP_PAIR: qg_select_step_pair(L); break;
+    default: qg_select_step_lane(L);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "qg_step_kernel launch: %s", hipGetErrorString(e));
     if (jitter_at_reset(s)) {         // start-pose randomisation of the envs just auto-reset
@@ -716,12 +661,18 @@ extern "C" int32_t qg_debug_last_step_kernel(const qg_sim *s, char *buf, int32_t
     return QG_OK;
 }
 
-/* development builds (-DQG_PHASE_TIMES): the s_memrealtime stamps (10 ns units) of the last launch's first wave; QG_ERR_ARG in production builds */
+/* development builds (-DQG_PHASE_TIMES): the s_memrealtime stamps (10 ns units) of the last launch's first wave, read from the kernel
+   unit that launched last (qg_step_launch.h); QG_ERR_ARG in production builds */
+#ifdef QG_PHASE_TIMES
+static QgPhaseReader g_phase_reader;
+void qg_phase_unit(QgPhaseReader reader) { g_phase_reader = reader; }
+#endif
 extern "C" int qg_debug_phase_times(uint64_t out[16]) {
 #ifdef QG_PHASE_TIMES
     if (!out) return fail(QG_ERR_ARG, "qg_debug_phase_times: null output");
+    if (!g_phase_reader) return fail(QG_ERR_ARG, "qg_debug_phase_times: no step kernel launched yet");
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(qg_phase_times), 16 * sizeof(uint64_t)), QG_ERR_DEVICE);
+    HIP_TRY(g_phase_reader(out), QG_ERR_DEVICE);
     return QG_OK;
 #else
     (void)out;
@@ -737,7 +688,7 @@ extern "C" int qg_set_track_ctrl(qg_sim *s, int32_t on) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-// many env-steps per launch: the sequence form and the resident form of the one-link-per-lane kernel (qg_kernel_resident.hip)
+// many env-steps per launch: the sequence forms, and the resident form of the one-link-per-lane kernel (qg_kernel_resident.hip)
 // ------------------------------------------------------------------------------------------------------
 static int multi_step_usable(const qg_sim *s, const char *who) {
     if (qg_effective_mapping(s) != QG_MAP_LINK)
@@ -786,15 +737,9 @@ extern "C" int qg_step_device_seq(qg_sim *s, const float *actions, float *packed
     R.count = count;
     R.slots = 1;
     const KStepArgs P = multi_step_args(s);
-    if (seq_pair) {
-        if (pair_wg4(s)) launch_pair_multi<4>(s, st, P, R);
-        else launch_pair_multi<1>(s, st, P, R);
-    } else if (seq_quad) {              // as launch_step: the whole register file while the grid is one wave per SIMD
-        if (!s->baked) launch_quad_multi<1, false>(s, st, P, R);       // (tables in LDS: always the one-wave form)
-        else if (quad_one_wave(s)) launch_quad_multi<1, true>(s, st, P, R);
-        else launch_quad_multi<2, true>(s, st, P, R);
-    } else if (s->baked) launch_link_multi<true, false>(s, st, P, R);
-    else launch_link_multi<false, false>(s, st, P, R);
+    if (seq_pair) qg_select_seq_pair(s, st, P, R);
+    else if (seq_quad) qg_select_seq_quad(s, st, P, R);
+    else qg_select_seq_link(s, st, P, R);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "qg_step_device_seq launch: %s", hipGetErrorString(e));
     return QG_OK;
@@ -821,7 +766,7 @@ static int resident_retire(qg_sim *s) {
         (void)hipStreamSynchronize(s->res.last_stream);      // (a stream the caller has destroyed since is no reason to fail)
         (void)hipGetLastError();
     }
-    hipLaunchKernelGGL(qg_resident_ctl_kernel, dim3(1), dim3(64), 0, s->res.ctl_stream, s->res.k.door, 0);
+    qg_launch_resident_ctl(s->res.ctl_stream, s->res.k.door, 0);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
     HIP_TRY(hipStreamSynchronize(s->res.ctl_stream), QG_ERR_LAUNCH);
     HIP_TRY(hipStreamSynchronize(s->stream), QG_ERR_LAUNCH);
@@ -834,11 +779,9 @@ static int resident_launch(qg_sim *s) {
     int rc = multi_step_usable(s, "resident kernel launch");
     if (rc != QG_OK) return rc;
     s->res.hstat[0] = QG_RES_RUNNING;
-    hipLaunchKernelGGL(qg_resident_ctl_kernel, dim3(1), dim3(64), 0, s->stream, s->res.k.door, 1);
+    qg_launch_resident_ctl(s->stream, s->res.k.door, 1);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
-    const KStepArgs P = multi_step_args(s);
-    if (s->baked) launch_link_multi<true, true>(s, s->stream, P, s->res.k);
-    else launch_link_multi<false, true>(s, s->stream, P, s->res.k);
+    qg_select_resident(s, multi_step_args(s));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "resident kernel launch: %s", hipGetErrorString(e));
     s->res.launched = 1;
@@ -956,8 +899,7 @@ extern "C" int qg_resident_step_device(qg_sim *s, int32_t count, void *stream) {
     if (rc != QG_OK) return rc;
     if ((rc = qg_resident_ensure(s)) != QG_OK) return rc;
     const unsigned nwaves = link_blocks(s) * QGK_LINK_WAVES;
-    hipLaunchKernelGGL(qg_resident_ring_kernel, dim3(1), dim3(QGK_WAVE), 0, (hipStream_t)stream, s->res.k, (unsigned)count, nwaves,
-                       (unsigned long long)s->res.rung);
+    qg_launch_resident_ring((hipStream_t)stream, s->res.k, (unsigned)count, nwaves, (unsigned long long)s->res.rung);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(QG_ERR_LAUNCH, "ring kernel launch: %s", hipGetErrorString(e));
     s->res.last_stream = (hipStream_t)stream;

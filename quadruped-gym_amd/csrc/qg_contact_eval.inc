@@ -1,4 +1,4 @@
-// qg_contact_eval.inc -- contact_eval() of qg_kernels.hip's contact section, textually included twice: at global scope as the template
+// qg_contact_eval.inc -- contact_eval() of qg_step_dev.h's contact section, textually included twice: at global scope as the template
 // every kernel uses (QG_TEMPLATE_T = `template <class T>`, T = float or f2), and inside namespace pk3 as a plain float function
 // (QG_TEMPLATE_T empty, T a typedef of float there), where the V3 operators are the packed (x, y) + z overloads -- the one-link-per-lane
 // kernel calls that one.  Same text, same arithmetic, same rounding.

@@ -7,6 +7,11 @@
 #define QGK_CP_FRAME 12    // contact sample points on the FRAME
 #define QGK_CP_LINK 8      // ... on every leg link
 #define QGK_WAVE 64
+// envs per wave of the step kernels' work mappings (the grid predicates of qg_step_launch.h and AUTO's boundaries are in these units)
+#define QGK_LINK_ENVS 4     // one link per lane (qg_kernel_link.hip), in workgroups of QGK_LINK_WAVES waves
+#define QGK_LINK_WAVES 4
+#define QGK_QUAD_ENVS 16    // one leg per lane (qg_kernel_quad.hip)
+#define QGK_PAIR_ENVS 32    // two legs per lane (qg_kernel_pair.hip)
 
 // One leg link and the hinge that drives it (quadruped.xml:71-141, joint defaults :9,24-37,
 // servo defaults :10-37).  All hinge axes are the link's local z (quadruped.xml:9), which the

@@ -22,8 +22,12 @@
 //     bit-identical sum); base prelude, 6x6 solve and base integration run redundantly in the 16 lanes.
 // Lagged sensors only (the reference's), at most one wave per SIMD: the launcher uses it for n <= 4096.  Two variants as for the
 // one-leg-per-lane kernel: the compiled-in robot with literal constants, any other robot with the model tables staged in LDS.
-#define QGK_LINK_ENVS 4     // envs per wave
-#include "qg_po_dev.h"      // partially observable observation pack: per-env device functions of the fused <WALK, PO> variant
+//
+// This file is a translation unit, and so a code object, of its own: the per-launch kernel below, its many-env-steps forms with the
+// resident mailbox's ring and door kernels (qg_kernel_resident.hip, included in front of the host side), their launchers and the
+// leaves of the QG_MAP_LINK mapping (entry points: qg_step_launch.h).
+#include "qg_step_dev.h"
+#include "qg_step_launch.h"
 
 // State accesses of this kernel: a scalar base plus a 32-bit BYTE offset per lane (global_load / store v, voff, s[base]) instead of a
 // 64-bit address computed per access -- two to three instructions fewer in front of every load, i.e. the prologue's loads go out
@@ -462,8 +466,7 @@ DEV void substep_link(const KModel &C, float cm, float sm, int r, bool lead_env,
 
 // Workgroups of four waves (one per SIMD of a CU): a grid of 1024 one-wave workgroups measured 1.65 us more fixed time per launch
 // than 256 (kernel time against frame_skip, tools/fs_sweep.sh: intercept 5.75 vs 4.1 us) -- the dispatch of the workgroups
-// themselves; the waves do not interact (own tile rows, own envs).
-#define QGK_LINK_WAVES 4
+// themselves; the waves do not interact (own tile rows, own envs): QGK_LINK_WAVES (qg_device.h).
 // WALK: the walking task layer fused in as in qg_step_kernel_quad<.., WALK>, one control channel per lane: lane r < 3 of leg k owns
 // channel 3k + r (estimator update in the prologue, its terms of the reward sums in the epilogue), the env's lead lane evaluates
 // the reward.
@@ -833,4 +836,57 @@ __global__ __launch_bounds__(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1), 1) void
     }
     QG_MARK(8);
     QG_MARK(9);                                      // every store issued
+}
+
+#include "qg_kernel_resident.hip"
+
+// ---- host side: the launchers, and every leaf of the mapping --------------------------------------------------------------------
+template <bool WALK, bool PO, bool BAKED, bool HELP = false, bool DYN = false> static void launch_link(const StepLaunch &L) {
+    L.s->last_step_kernel = step_kernel_code<WALK, PO, BAKED, HELP, DYN>(KF_LINK);
+    hipLaunchKernelGGL((qg_step_kernel_link<WALK, PO, BAKED, HELP, DYN>), dim3(link_blocks(L.s)), dim3(QGK_WAVE * QGK_LINK_WAVES * (HELP ? 2 : 1)), 0,
+                       L.stream, L.model, L.s->d_task, L.P, walk_arg<WALK>(L.walk), po_arg<PO>(L.po));
+}
+// the many-env-steps-per-launch forms (qg_kernel_resident.hip)
+template <bool BAKED, bool DOOR> static void launch_link_multi(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
+    s->last_step_kernel = step_kernel_code<BAKED, DOOR>(KF_LINK_MULTI);
+    hipLaunchKernelGGL((qg_step_kernel_link_multi<BAKED, DOOR>), dim3(link_blocks(s)), dim3(QGK_WAVE * QGK_LINK_WAVES), 0, st, s->d_model, s->d_task, P, R);
+}
+
+// Every leaf names the instantiation it launches.  DYN: per-env dynamics, which run the table-driven (!baked) leaves only.
+template <bool DYN> static void select_step_link(const StepLaunch &L) {
+    const qg_sim *s = L.s;
+    const bool walk = L.walk, po = L.po;
+    if (!s->baked) {
+        if (po) launch_link<true, true, false, false, DYN>(L);
+        else if (walk) launch_link<true, false, false, false, DYN>(L);
+        else launch_link<false, false, false, false, DYN>(L);
+    } else if (walk && s->link_helpers) {
+        // helper waves (qg_step_kernel_link<.., HELP>): the compiled-in robot's walking forms; QG_LINK_HELPERS=0 at qg_create keeps the one-role kernels
+        if (po) launch_link<true, true, true, true>(L);
+        else launch_link<true, false, true, true>(L);
+    } else if (po) launch_link<true, true, true>(L);
+    else if (walk) launch_link<true, false, true>(L);
+    else launch_link<false, false, true>(L);
+}
+void qg_select_step_link(const StepLaunch &L, bool dyn) {
+    QG_PHASE_UNIT();
+    if (dyn) select_step_link<true>(L);
+    else select_step_link<false>(L);
+}
+
+void qg_select_seq_link(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
+    QG_PHASE_UNIT();
+    if (s->baked) launch_link_multi<true, false>(s, st, P, R);
+    else launch_link_multi<false, false>(s, st, P, R);
+}
+void qg_select_resident(const qg_sim *s, const KStepArgs &P) {
+    QG_PHASE_UNIT();
+    if (s->baked) launch_link_multi<true, true>(s, s->stream, P, s->res.k);
+    else launch_link_multi<false, true>(s, s->stream, P, s->res.k);
+}
+void qg_launch_resident_ctl(hipStream_t st, unsigned long long *door, int op) {
+    hipLaunchKernelGGL(qg_resident_ctl_kernel, dim3(1), dim3(64), 0, st, door, op);
+}
+void qg_launch_resident_ring(hipStream_t st, const KResident &R, unsigned count, unsigned nwaves, unsigned long long hint) {
+    hipLaunchKernelGGL(qg_resident_ring_kernel, dim3(1), dim3(QGK_WAVE), 0, st, R, count, nwaves, hint);
 }

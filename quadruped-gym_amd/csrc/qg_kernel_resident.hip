@@ -24,7 +24,8 @@
 //   * the ring kernel's wait for the arrivals gives up after a period without progress and reports it.
 // Out of scope of these forms (the launcher refuses, or falls back to per-step launches): the walking / observation-pack layers,
 // un-lagged sensors, hinge jitter at auto-reset (a launch of its own behind every per-launch step), separate obs / reward / done
-// outputs (packed rows only).  The sequence form also exists for the two-legs-per-lane and the one-leg-per-lane kernels (end of file).
+// outputs (packed rows only).  The sequence form also exists for the two-legs-per-lane and the one-leg-per-lane kernels, with those kernels
+// (qg_step_kernel_pair_multi in qg_kernel_pair.hip, qg_step_kernel_quad_multi in qg_kernel_quad.hip).
 
 #define QG_DOOR_STOP (1ull << 63)
 // (the mailbox KResident and the QG_RES_* status words the host reads are in qg_device.h)
@@ -312,254 +313,5 @@ __global__ void qg_resident_ctl_kernel(unsigned long long *door, int op) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         if (op == 0) (void)__hip_atomic_fetch_or(door, QG_DOOR_STOP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else (void)__hip_atomic_fetch_and(door, ~QG_DOOR_STOP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// ---- the sequence form for the two-legs-per-lane kernel (16 385 .. 32 768 envs and >= 57 344: BASELINE configs 3 and 4's sizes) ----------
-// qg_step_kernel_pair with an outer loop over env-steps, exactly as qg_step_kernel_link_multi<.., DOOR = false> is to qg_step_kernel_link:
-// state loaded once and stored once, per env-step what a fresh launch does with the state it loads, bit-identical results.  Compiled-in
-// robot, lagged sensors, packed rows (the launcher falls back to per-step launches otherwise).
-template <int WAVES>
-__global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair_multi(const KTask *__restrict__ T, KStepArgs P, KResident R) {
-    __shared__ float tile_all[WAVES][QGK_PAIR_ENVS * 35];
-    const KModel &C = QG_BAKED_MODEL;
-    const int lane = threadIdx.x & (QGK_WAVE - 1);
-    const int wave = threadIdx.x >> 6;
-    float *tile = tile_all[wave];
-    const int half = lane & 1;
-    const int el = lane >> 1;
-    const int env0 = (blockIdx.x * WAVES + wave) * QGK_PAIR_ENVS;
-    const int n = P.n;
-    const bool live = env0 + el < n;
-    int env = live ? env0 + el : n - 1;
-    f2 cm, sm;
-    cm.x = half ? -1.f : 1.f; cm.y = 0.f;
-    sm.x = 0.f; sm.y = half ? -1.f : 1.f;
-    QG_TASK_REGS(Tk, T);
-
-    BaseState B;
-    QG_BASE_LOAD(B, P.st, QG_AT, n, env);
-    int nstep = P.st.nstep[env];
-    int episode = P.st.episode[env];
-    LegPair L;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int j = 3 * (2 * half + c) + i;
-            float qq, qv, aa;
-            QG_HINGE_LOAD(qq, qv, aa, P.st, QG_AT, n, env, j);
-            if (c == 0) { L.q[i].x = qq; L.qd[i].x = qv; L.act[i].x = aa; L.u[i].x = 0.f; }
-            else { L.q[i].y = qq; L.qd[i].y = qv; L.act[i].y = aa; L.u[i].y = 0.f; }
-        }
-    }
-    const int od = Tk.obs_mode == 1 ? 21 : 33;
-    const int row = od + 2;
-    const int fs = Tk.frame_skip;
-    const int live_envs = max(0, min(QGK_PAIR_ENVS, n - env0));
-    const int total = live_envs * row;
-    const bool lead = live && half == 0;
-    float *srow = tile + el * 35;
-    const size_t slot_act = (size_t)n * 12, slot_out = (size_t)n * row;
-    float ctrl_reg[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float a_next[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    bool have_next = false;
-
-    for (int kstep = 0; kstep < R.count; ++kstep) {
-        float a_in[6];
-        const float *ap = R.actions + (size_t)kstep * slot_act + (size_t)env * 12 + 6 * half;
-#pragma unroll
-        for (int c6 = 0; c6 < 6; ++c6) a_in[c6] = have_next ? a_next[c6] : ap[c6];
-        have_next = kstep + 1 < R.count;
-        if (have_next) {
-#pragma unroll
-            for (int c6 = 0; c6 < 6; ++c6) a_next[c6] = ap[slot_act + c6];
-        }
-        float aclip[6];
-        float ssq = 0.f;
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const float a = fminf(fmaxf(a_in[3 * c + i], -1.f), 1.f);    // quadruped.py:160
-                aclip[3 * c + i] = a;
-                ssq = fmaf(a, a, ssq);
-                const float uu = fminf(fmaxf(a, C.link[i].ctrl_lo), C.link[i].ctrl_hi);
-                if (c == 0) L.u[i].x = uu; else L.u[i].y = uu;
-            }
-        }
-        ssq = pair_sum(ssq);
-        quat_unit(B);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) sincos_f(L.q[i] - f2(C.link[i].ref), L.sc[2 * i], L.sc[2 * i + 1]);
-        float zaxis_z = 1.f;
-#pragma unroll 1
-        for (int s = 0; s < fs; ++s) substep_pair(C, cm, sm, B, L, s == fs - 1, srow, half, zaxis_z);
-        nstep += fs;
-        asm volatile("" : "+v"(env));
-
-        QG_REWARD_TERMS(Tk., B, ssq, nstep);
-        QG_DONE_IF_BAD_STATE(B, pair_sum(hsum(L.q[0]) + hsum(L.q[1]) + hsum(L.q[2]) + hsum(L.qd[0]) + hsum(L.qd[1]) + hsum(L.qd[2])));
-        QG_DONE_IF_FLIPPED(Tk., zaxis_z);
-        if (half == 0) {
-            if (od == 21) { srow[18] = srow[30]; srow[19] = srow[31]; srow[20] = srow[32]; }
-            srow[od] = reward; srow[od + 1] = done ? 1.f : 0.f;
-        }
-        wave_sync();
-        {
-            float *dst = R.packed + (size_t)kstep * slot_out + (size_t)env0 * row;
-            QG_TILE_COPY_OUT(dst, tile, lane, total, row);
-        }
-        wave_sync();
-        const bool rst = done && Tk.auto_reset;
-#pragma unroll
-        for (int c6 = 0; c6 < 6; ++c6) ctrl_reg[c6] = aclip[c6];
-        if (rst) {
-            QG_BASE_RESET(B, nstep, C.qpos0, Tk., P, env, episode);
-            episode += 1;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                L.q[i] = f2(C.qpos0[7 + i]); L.qd[i] = f2(0.f); L.act[i] = f2(0.f);
-            }
-#pragma unroll
-            for (int c6 = 0; c6 < 6; ++c6) ctrl_reg[c6] = Tk.default_ctrl[6 * half + c6];
-        }
-    }
-
-    if (lead) {
-        QG_BASE_STORE(B, nstep, P.st, QG_PUT, n, env);
-        P.st.episode[env] = episode;
-    }
-    if (live && R.count > 0) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int j = 3 * (2 * half + c) + i;
-                QG_HINGE_STORE(c == 0 ? L.q[i].x : L.q[i].y, c == 0 ? L.qd[i].x : L.qd[i].y, c == 0 ? L.act[i].x : L.act[i].y, P.st, QG_PUT, n, env, j);
-                if (P.track_ctrl) P.st.ctrl[j * n + env] = ctrl_reg[3 * c + i];
-            }
-        }
-    }
-}
-
-// ---- ... and for the one-leg-per-lane kernel (4 097 .. 16 384 envs at one wave per SIMD, 32 769 .. 57 343 at two; any model numbers) ------
-// qg_step_kernel_quad's plain path with an outer loop over env-steps; WPE / BAKED choose the same substep instantiation the per-launch
-// launcher picks for the grid, so the bits are the per-launch kernel's.  Four-wave workgroups (every grid AUTO gives this mapping).
-template <int WPE, bool BAKED>
-__global__ __launch_bounds__(QGK_WAVE * 4, WPE) void qg_step_kernel_quad_multi(const KModel *__restrict__ Mp, const KTask *__restrict__ T, KStepArgs P, KResident R) {
-    constexpr int WAVES = 4;
-    __shared__ float tile_all[WAVES][QGK_QUAD_ENVS * 35];
-    __shared__ KModel smodel;
-    const int lane = threadIdx.x & (QGK_WAVE - 1);
-    const int wave = threadIdx.x >> 6;
-    float *tile = tile_all[wave];
-    QG_STAGE_MODEL(C, BAKED, smodel, Mp, QGK_WAVE * WAVES);
-    const int k = lane & 3;
-    const int el = lane >> 2;
-    const int env0 = (blockIdx.x * WAVES + wave) * QGK_QUAD_ENVS;
-    const int n = P.n;
-    const bool live = env0 + el < n;
-    const int env = live ? env0 + el : n - 1;
-    const float cm = (k == 0) ? 1.f : (k == 2) ? -1.f : 0.f;
-    const float sm = (k == 1) ? 1.f : (k == 3) ? -1.f : 0.f;
-    QG_TASK_REGS(Tk, T);
-
-    BaseState B;
-    QG_BASE_LOAD(B, P.st, QG_AT, n, env);
-    int nstep = P.st.nstep[env];
-    int episode = P.st.episode[env];
-    LegState L;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int j = 3 * k + i;
-        QG_HINGE_LOAD(L.q[i], L.qd[i], L.act[i], P.st, QG_AT, n, env, j);
-        L.u[i] = 0.f; L.sc[2 * i] = 0.f; L.sc[2 * i + 1] = 1.f;
-    }
-    const int od = Tk.obs_mode == 1 ? 21 : 33;
-    const int row = od + 2;
-    const int fs = Tk.frame_skip;
-    const int live_envs = max(0, min(QGK_QUAD_ENVS, n - env0));
-    const int total = live_envs * row;
-    float *srow = tile + el * 35;
-    const size_t slot_act = (size_t)n * 12, slot_out = (size_t)n * row;
-    float ctrl_reg[3] = {0.f, 0.f, 0.f}, a_next[3] = {0.f, 0.f, 0.f};
-    bool have_next = false;
-
-    for (int kstep = 0; kstep < R.count; ++kstep) {
-        const float *ap = R.actions + (size_t)kstep * slot_act + (size_t)env * 12 + 3 * k;
-        float aclip[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float a_in = have_next ? a_next[i] : ap[i];
-            const float a = fminf(fmaxf(a_in, -1.f), 1.f);    // quadruped.py:160
-            aclip[i] = a;
-            L.u[i] = fminf(fmaxf(a, link_of<BAKED>(C, k, i).ctrl_lo), link_of<BAKED>(C, k, i).ctrl_hi);
-        }
-        have_next = WPE == 1 && kstep + 1 < R.count;     // (two waves per SIMD: no registers to park the next action in; the partner covers the load)
-        if (have_next) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) a_next[i] = ap[slot_act + i];
-        }
-        quat_unit(B);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) sincos_f(L.q[i] - link_of<BAKED>(C, k, i).ref, L.sc[2 * i], L.sc[2 * i + 1]);
-        float zaxis_z = 1.f;
-        asm volatile(".p2align 6");
-#pragma unroll 1
-        for (int s = 0; s < fs; ++s) substep_quad<BAKED, (WPE > 1)>(C, cm, sm, B, L, s == fs - 1, srow, k, zaxis_z);
-        nstep += fs;
-
-        float ssq = 0.f;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) ssq = fmaf(aclip[i], aclip[i], ssq);
-        ssq = quad_sum(ssq);
-        QG_REWARD_TERMS(Tk., B, ssq, nstep);
-        QG_DONE_IF_BAD_STATE(B, quad_sum(L.q[0] + L.q[1] + L.q[2] + L.qd[0] + L.qd[1] + L.qd[2]));
-        QG_DONE_IF_FLIPPED(Tk., zaxis_z);
-        if (k == 0) {
-            if (od == 21) { srow[18] = srow[30]; srow[19] = srow[31]; srow[20] = srow[32]; }
-            srow[od] = reward; srow[od + 1] = done ? 1.f : 0.f;
-        }
-        wave_sync();
-        {
-            float *dst = R.packed + (size_t)kstep * slot_out + (size_t)env0 * row;
-            QG_TILE_COPY_OUT(dst, tile, lane, total, row);
-        }
-        wave_sync();
-        const bool rst = done && Tk.auto_reset;
-        if constexpr (WPE == 1) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) ctrl_reg[i] = aclip[i];
-        } else if (live && P.track_ctrl) {      // two waves per SIMD: data.ctrl goes out every env-step (as the per-launch kernel writes it) rather
-#pragma unroll                                  // than riding through the substep loop in three more registers
-            for (int i = 0; i < 3; ++i) P.st.ctrl[(3 * k + i) * n + env] = rst ? Tk.default_ctrl[3 * k + i] : aclip[i];
-        }
-        if (rst) {
-            QG_BASE_RESET(B, nstep, C.qpos0, Tk., P, env, episode);
-            episode += 1;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                L.q[i] = C.qpos0[7 + (BAKED ? i : 3 * k + i)]; L.qd[i] = 0.f; L.act[i] = 0.f;
-                if constexpr (WPE == 1) ctrl_reg[i] = Tk.default_ctrl[3 * k + i];
-            }
-        }
-    }
-
-    // the addresses of the final stores are derived from (env, leg) AFTER the loops: visible to the optimiser they are computed ahead of
-    // them and carried through the substep loop (qg_step_kernel_quad does the same for its epilogue)
-    int env_e = env, k_e = k;
-    asm volatile("" : "+v"(env_e), "+v"(k_e));
-    if (live && k_e == 0) {
-        QG_BASE_STORE(B, nstep, P.st, QG_PUT, n, env_e);
-        P.st.episode[env_e] = episode;
-    }
-    if (live && R.count > 0) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int j = 3 * k_e + i;
-            QG_HINGE_STORE(L.q[i], L.qd[i], L.act[i], P.st, QG_PUT, n, env_e, j);
-            if (WPE == 1 && P.track_ctrl) P.st.ctrl[j * n + env_e] = ctrl_reg[i];
-        }
     }
 }

@@ -1,5 +1,6 @@
 // qg_sim.h -- the simulator handle and the few functions of the core (qg_capi.hip) and of the walking layer (qg_walk.hip) that the
-// layers bound to a simulator -- qg_comm.hip, qg_walk.hip, qg_po.hip -- call across translation units.  Internal: not installed, and
+// layers bound to a simulator -- qg_comm.hip, qg_walk.hip, qg_po.hip -- call across translation units (what the core and the
+// step-kernel units share on top of it is in qg_step_launch.h).  Internal: not installed, and
 // nothing in here is exported (libquadgym.map).
 #pragma once
 #include "qg_host.h"

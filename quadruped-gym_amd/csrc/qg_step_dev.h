@@ -1,4 +1,6 @@
-// qg_kernels.hip -- gfx950 kernels of the batched quadruped simulator.
+// qg_step_dev.h -- the device code every step-kernel unit shares (qg_kernel_link.hip, qg_kernel_quad.hip, qg_kernel_pair.hip, and
+// qg_capi.hip for its reset kernels): vector and spatial algebra, contact, the leg pass, the base solve, the substeps' pieces.  It
+// defines no kernel; each unit that includes it is a code object of its own (no -fgpu-rdc).
 //
 // Replaces the arithmetic behind QuadrupedEnv.step() (src/envs/quadruped.py:153-182 of
 // antopio26/quadruped-gym): frame_skip x mj_step (quadruped.py:163-165, integrator
@@ -1221,117 +1223,8 @@ DEV void write_obs_row(float *r, int od, const float *jpos, const SensorOut &so)
 }
 
 // ------------------------------------------------------------------------------------------
-// env-step kernel, ONE ENV PER LANE: one launch = frame_skip substeps + sensor pack + rewards +
-// terminations (+ auto-reset) for every env.  grid = ceil(n / 64) workgroups of one wave.
-// ------------------------------------------------------------------------------------------
-template <bool BAKED>
-__global__ __launch_bounds__(QGK_WAVE) void qg_step_kernel(const KModel *__restrict__ Mp, const KTask *__restrict__ T, KStepArgs P) {
-    const KModel *M = &table<BAKED>(Mp);
-    __shared__ float lds[QG_LDS_SLOTS * 64];
-    __shared__ float tile[QG_OBS_TILE_FLOATS];
-    const int lane = threadIdx.x;
-    const int env0 = blockIdx.x * QGK_WAVE;
-    const int n = P.n;
-    const bool live = env0 + lane < n;
-    const int env = live ? env0 + lane : n - 1;   // tail lanes shadow the last env; their stores are masked
-
-    // ---- load state (coalesced: lane i reads base + i*4 of every field) -------------------
-    BaseState B;
-    QG_BASE_LOAD(B, P.st, QG_AT, n, env);
-    int nstep = P.st.nstep[env];
-    // action: clip to the action space [-1, 1] (quadruped.py:160), then to the servo's ctrlrange
-    float ssq = 0.f;
-    float aclip[12];
-    {
-        const float4 *ap = reinterpret_cast<const float4 *>(P.actions + (size_t)env * 12);
-        float4 a0 = ap[0], a1 = ap[1], a2 = ap[2];
-        float av[12] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w};
-#pragma unroll
-        for (int j = 0; j < 12; ++j) {
-            float a = fminf(fmaxf(av[j], -1.f), 1.f);
-            aclip[j] = a;
-            ssq = fmaf(a, a, ssq);
-            lds[LU(j) * 64 + lane] = fminf(fmaxf(a, M->link[BAKED ? j % 3 : j].ctrl_lo), M->link[BAKED ? j % 3 : j].ctrl_hi);
-            QG_HINGE_LOAD(lds[LQ(j) * 64 + lane], lds[LQD(j) * 64 + lane], lds[LACT(j) * 64 + lane], P.st, QG_AT, n, env, j);
-        }
-    }
-
-    // ---- frame_skip physics substeps (quadruped.py:163-165) ----------------------------------
-    SensorOut so;
-    float jpos[12];
-    const int fs = T->frame_skip;
-    const bool lag = T->sensor_lag != 0;
-#pragma unroll 1
-    for (int s = 0; s < fs; ++s) substep<BAKED>(Mp, lds, lane, B, lag && (s == fs - 1), so, jpos);
-    nstep += fs;
-    if (!lag) {   // un-lagged sensors: one extra forward pass on a scratch copy of the state
-        BaseState B2 = B;
-        float keep[36];
-#pragma unroll
-        for (int j = 0; j < 36; ++j) keep[j] = lds[j * 64 + lane];
-        substep<BAKED>(Mp, lds, lane, B2, true, so, jpos);
-#pragma unroll
-        for (int j = 0; j < 36; ++j) lds[j * 64 + lane] = keep[j];
-    }
-
-    // ---- rewards and terminations on the post-step state (README.md:64-90) ----------------
-    QG_REWARD_TERMS(T->, B, ssq, nstep);
-    QG_DONE_IF_FLIPPED(T->, so.zaxis.z);
-    {   // (base first, hinges second: not the rounding of QG_DONE_IF_BAD_STATE)
-        float probe = B.pw.x + B.pw.y + B.pw.z + B.qw + B.vw.x + B.vw.y + B.vw.z + B.wb.x + B.wb.y + B.wb.z;
-#pragma unroll
-        for (int j = 0; j < 12; ++j) probe += lds[LQ(j) * 64 + lane] + lds[LQD(j) * 64 + lane];
-        done = done || state_is_bad(probe);
-    }
-
-    // ---- outputs: stage rows in LDS, then store the wave's contiguous chunk coalesced ------
-    const int od = T->obs_mode == 1 ? 21 : 33;
-    const int row = P.packed ? od + 2 : od;
-    {
-        float *r = tile + lane * row;
-        write_obs_row(r, od, jpos, so);
-        if (P.packed) { r[od] = reward; r[od + 1] = done ? 1.f : 0.f; }
-    }
-    __syncthreads();
-    {
-        const int live_envs = min(QGK_WAVE, n - env0);
-        const int total = live_envs * row;
-        float *dst = (P.packed ? P.packed : P.obs) + (size_t)env0 * row;
-        for (int e = lane; e < total; e += QGK_WAVE) dst[e] = tile[e];
-    }
-    if (live && !P.packed) {
-        P.reward[env] = reward;
-        P.done[env] = done ? 1 : 0;
-    }
-    QG_COMPS_STORE(live, P, env);
-
-    // ---- auto-reset (VecEnv semantics) and state write-back ---------------------------------
-    const bool rst = done && T->auto_reset;
-    if (rst) QG_BASE_RESET(B, nstep, M->qpos0, T->, P, env, P.st.episode[env]);
-    if (live) {
-        QG_BASE_STORE(B, nstep, P.st, QG_PUT, n, env);
-        if (rst) P.st.episode[env] += 1;
-#pragma unroll
-        for (int j = 0; j < 12; ++j) {
-            QG_HINGE_STORE(rst ? M->qpos0[7 + j] : lds[LQ(j) * 64 + lane], rst ? 0.f : lds[LQD(j) * 64 + lane], rst ? 0.f : lds[LACT(j) * 64 + lane], P.st, QG_PUT, n, env, j);
-        }
-        if (P.track_ctrl) {
-#pragma unroll
-            for (int j = 0; j < 12; ++j) P.st.ctrl[j * n + env] = rst ? T->default_ctrl[j] : aclip[j];
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// env-step kernel, ONE LEG PER LANE: the four lanes 4e..4e+3 of a quad share env e, lane k owns
-// leg k (and a quarter of the FRAME's contact points); the base prelude, the 6x6 base solve and
-// the base integration run redundantly in all four lanes; the leg contributions to the base
-// block (Schur complements, 33 numbers) are summed over the quad with DPP quad_perm moves --
-// no LDS, no run-time indexed arrays.  A wave carries 16 envs, so 4096 envs fill 256 waves
-// instead of 64: at batch sizes that cannot fill the chip with one env per lane this cuts the
-// instructions per wave (= the time, a lone wave issues one VALU instruction per ~4.5-5 cycles) ~3.5x.
-// BAKED variant: the compiled-in robot, whose legs are quarter-turn copies of one another (constants become literals).
-// Generic variant: any model numbers; the tables are staged in LDS and each lane reads its own leg's rows.
+// shared by the one-leg-per-lane and the two-legs-per-lane kernels: sums over the lanes of a quad, and the epilogue of the fused
+// observation pack
 // ------------------------------------------------------------------------------------------
 template <int CTRL> DEV float dpp_quad(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), CTRL, 0xF, 0xF, true));
@@ -1349,151 +1242,6 @@ DEV V3 quad_sum(V3 a) { return v3(quad_sum(a.x), quad_sum(a.y), quad_sum(a.z)); 
 DEV void quad_sum(Sym3 &a) { a.xx = quad_sum(a.xx); a.yy = quad_sum(a.yy); a.zz = quad_sum(a.zz); a.xy = quad_sum(a.xy); a.xz = quad_sum(a.xz); a.yz = quad_sum(a.yz); }
 DEV void quad_sum(Sym6 &a) { quad_sum(a.AA); quad_sum(a.LL); a.AL.r0 = quad_sum(a.AL.r0); a.AL.r1 = quad_sum(a.AL.r1); a.AL.r2 = quad_sum(a.AL.r2); }
 
-struct LegState {
-    float q[3], qd[3], act[3], u[3];
-    float sc[6];      // sin, cos of (q[i] - ref_i), advanced with the hinge
-};
-
-// Ordered for low register pressure: the leg pass (the widest live set) runs first with only the base context alive;
-// the FRAME terms are built afterwards; sensors go straight to the LDS tile; the rotation is rebuilt at integration.
-// The one-leg-per-lane kernel of the compiled-in robot at ONE wave per SIMD takes the packed prelude / integration of the
-// one-link-per-lane kernel (a lone wave pays per instruction: 2 109 -> 2 072 per substep, 17.74 -> 17.48 us at 8 192 envs, 18.3 -> 18.1
-// at 16 384, sequence form 15.4 -> 15.2); at two waves per SIMD they measured 1.2 % slower and with the generic robot's tables 7 %
-// slower (profiles/r04/quad_packed_prelude_ab.txt), so those keep the plain forms.
-template <bool PKQ> DEV BaseCtx quad_prelude(const KModel &C, const BaseState &B) {
-    if constexpr (PKQ) return pk3::base_prelude_unit(C, B);
-    else return base_prelude<true>(C, B);
-}
-template <bool PKQ> DEV void quad_integrate(const BaseCtx &c, float h, V3 wdot, V3 acl, BaseState &B) {
-    if constexpr (PKQ) pk3::base_integrate_unit(c, h, wdot, acl, B);
-    else base_integrate<true>(c, h, wdot, acl, B);
-}
-// LOWREG: rebuild the base context (cheap) instead of keeping it alive across the leg pass -- pays off once two waves
-// share a SIMD (register cap 256), costs ~2 % when a wave has the register file to itself.
-// BAKED: the compiled-in robot, constants are literals and the lane works in its leg's quarter-turn frame.  Otherwise `C`
-// is the model table staged in LDS and every lane reads the constants of its own leg (k) from it -- any model numbers.
-// DYN: per-env dynamics (D) and, with `xon` (wave-uniform), the external wrenches X of this lane's leg and of the FRAME
-template <bool BAKED, bool LOWREG, bool DYN = false>
-DEV void substep_quad(const KModel &C, float cm, float sm, BaseState &B, LegState &L, bool want_sensors, float *__restrict__ row, int k, float &zaxis_z,
-                      const KDyn &D = KDyn{}, bool xon = false, const KXfrcQuad *X = nullptr) {
-    const float h = C.h;
-    const BaseCtx bc0 = quad_prelude<BAKED && !LOWREG>(C, B);
-    V3 gb_keep;
-    Sym6 Ic;
-    SV fc, Fu;
-    float Y0[6], Y1[6], Y2[6], u[3];
-    {
-        const BaseCtx &bc = bc0;
-        gb_keep = bc.gb;
-        if (want_sensors) {          // the step's sensordata describes the state at the start of its last substep
-            zaxis_z = bc.cz.z;
-            row[3 * k + 0] = L.q[0]; row[3 * k + 1] = L.q[1]; row[3 * k + 2] = L.q[2];
-            if (k == 0) {
-                row[15] = B.wb.x; row[16] = B.wb.y; row[17] = B.wb.z;
-                row[18] = B.pw.x; row[19] = B.pw.y; row[20] = B.pw.z;
-                row[21] = B.vw.x; row[22] = B.vw.y; row[23] = B.vw.z;
-                row[24] = bc.cx.x; row[25] = bc.cx.y; row[26] = bc.cx.z;
-                row[27] = bc.cz.x; row[28] = bc.cz.y; row[29] = bc.cz.z;
-                row[30] = bc.vb.x; row[31] = bc.vb.y; row[32] = bc.vb.z;
-            }
-        }
-        Sym6 YFt;
-        SV F[3];
-        float Hd[3], H01, H02, H12, bj[3];
-        if constexpr (BAKED) {
-            // this lane's leg, in the frame turned by its quarter turn: there it is leg 0
-            Fr Ek = {v3(cm, sm, 0.f), v3(-sm, cm, 0.f), v3(0.f, 0.f, 1.f)};
-            leg_pass<float, true, true, LOWREG, false>(C, 0, Ek, L.q, L.qd, L.act, bc, B.pw.z, h, Ic, fc, F, Hd, H01, H02, H12, bj, L.sc);
-        } else {
-            Fr E0 = {v3(1.f, 0.f, 0.f), v3(0.f, 1.f, 0.f), v3(0.f, 0.f, 1.f)};
-            if constexpr (DYN)
-                leg_pass<float, false, false, LOWREG, false, DYN>(C, k, E0, L.q, L.qd, L.act, bc, B.pw.z, h, Ic, fc, F, Hd, H01, H02, H12, bj, L.sc, D,
-                                                                  xon, X->link);
-            else
-                leg_pass<float, false, false, LOWREG, false, DYN>(C, k, E0, L.q, L.qd, L.act, bc, B.pw.z, h, Ic, fc, F, Hd, H01, H02, H12, bj, L.sc, D);
-        }
-        leg_eliminate(F, Hd, H01, H02, H12, bj, Y0, Y1, Y2, u, YFt, Fu);
-        sub(Ic, YFt);                       // this leg's Schur complement
-    }
-    float x6[6];
-    {
-        const BaseCtx bc = LOWREG ? quad_prelude<BAKED && !LOWREG>(C, B) : bc0;      // rebuilt (cheap) rather than kept alive across the leg pass
-        SV p0;
-        Sym6 Ic0;
-        frame_body<DYN>(C, bc, h, p0, Ic0, D);
-        SV b;
-        {   // FRAME contact: this lane evaluates its quarter turn of the three base sample points
-            float wsum = 0.f;
-            V3 s = v3(0.f, 0.f, 0.f);
-            float zb = C.contact_margin - B.pw.z;
-#pragma unroll
-            for (int o = 0; o < 3; ++o) {
-                if constexpr (BAKED) {
-                    V3 r0 = ld3(C.cp0[4 * o]);
-                    contact_point(v3(cm * r0.x - sm * r0.y, sm * r0.x + cm * r0.y, r0.z), bc.n, zb, wsum, s);
-                } else {
-                    contact_point(ld3(C.cp0[3 * k + o]), bc.n, zb, wsum, s);   // any partition of the 12 points over the 4 lanes
-                }
-            }
-            wsum = quad_sum(wsum);
-            // the sums over the quad sit right in front of their uses: the compiler fuses a DPP move into the add that consumes it only
-            // when the two end up within a few instructions of each other in one basic block (33 unfused moves per substep otherwise)
-            quad_sum(Ic);
-            fc.a = quad_sum(fc.a); fc.l = quad_sum(fc.l);
-            Fu.a = quad_sum(Fu.a); Fu.l = quad_sum(Fu.l);
-            add(Ic0, Ic);
-            b.a = v3(0.f, 0.f, 0.f) - Fu.a - p0.a - fc.a;
-            b.l = v3(0.f, 0.f, 0.f) - Fu.l - p0.l - fc.l;
-            // Wave-uniform skip: under actuation the robot stands on its feet and the FRAME practically never touches the
-            // floor; when no env of the wave has a FRAME sample point below the margin every term below is exactly zero.
-            // (A/B on one box: +3.4 % at 4096 envs, +6.5 % at 262 144.  The same skip per leg link does NOT pay: a taken
-            // branch over a large block stalls the instruction fetch of a wave that is alone on its SIMD.)
-            // The branch updates the assembled block IN PLACE (round 3): with the block assembled after it, the usual path -- no
-            // contact -- had to materialise the FRAME's constant entries as the other arm of a phi, 17 moves per substep.
-            if (__any(wsum > 0.f)) {
-                s = quad_sum(s);
-                Fr E0 = {v3(1.f, 0.f, 0.f), v3(0.f, 1.f, 0.f), v3(0.f, 0.f, 1.f)};
-                SV fe;
-                if constexpr (DYN) contact_finish(wsum, s, E0, v3(0.f, 0.f, 0.f), bc.n, bc.V0, D.kc, D.cc, C.contact_inv_ramp, D.mu, h, fe, Ic0);
-                else contact_finish(wsum, s, E0, v3(0.f, 0.f, 0.f), bc.n, bc.V0, C.contact_k, C.contact_c, C.contact_inv_ramp, C.contact_mu, h, fe, Ic0);
-                b.a = b.a + fe.a;
-                b.l = b.l + fe.l;
-            }
-            if constexpr (DYN) {
-                if (xon) {      // the FRAME's external wrench (and push): every lane of the env, as the rest of the base block
-                    const SV xw = xfrc_spatial(bc, X->frame, X->com0);
-                    b.a = b.a + xw.a;
-                    b.l = b.l + xw.l;
-                }
-            }
-        }
-        if constexpr (BAKED) pk3::base_solve(Ic0, b, x6);      // packed row pairs: fewer instructions for a wave alone on its SIMD, as many
-        else base_solve(Ic0, b, x6);                            // issue cycles at two waves per SIMD; the generic robot's register budget has no room for the pairs
-    }
-    V3 wdot = v3(x6[0], x6[1], x6[2]);
-    V3 acl = v3(x6[3], x6[4], x6[5]);
-    if (want_sensors && k == 0) {
-        row[12] = acl.x - gb_keep.x; row[13] = acl.y - gb_keep.y; row[14] = acl.z - gb_keep.z;   // accelerometer
-    }
-    // back-substitution and integration of this lane's three hinges
-    const float *Y[3] = {Y0, Y1, Y2};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float acc = u[i];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) acc = fmaf(-Y[i][r], x6[r], acc);
-        L.qd[i] = fmaf(h, acc, L.qd[i]);
-        L.q[i] = fmaf(h, L.qd[i], L.q[i]);
-        hinge_advance(h * L.qd[i], L.sc[2 * i], L.sc[2 * i + 1]);
-        L.act[i] = fmaf(L.u[i] - L.act[i], link_of<BAKED>(C, k, i).act_decay, L.act[i]);
-    }
-    {
-        const BaseCtx bc = LOWREG ? quad_prelude<BAKED && !LOWREG>(C, B) : bc0;
-        quad_integrate<BAKED && !LOWREG>(bc, h, wdot, acl, B);
-    }
-}
-
-#define QGK_QUAD_ENVS 16    // envs per wave in the one-leg-per-lane kernel
 #define QG_PO_COPY_K 4      // 16-byte groups per lane and substep of the fused observation pack's history copy (po_row_copy_*)
 // po_row_copy_load issues its K loads unpredicated: the last batch of a row may read up to (K - 1) * LPE groups + one group past the
 // lane's share, i.e. past the end of the LAST env's doubled ring for some (window, rotation) pairs -- windows 8, 13, 18, 40, 45, ...
@@ -1532,769 +1280,4 @@ DEV void po_wave_epilogue(const KPoLaunch &PK, const KWalkLaunch &WK, const KSte
     QG_MARK(7);                                      // frame built
     po_wave_emit<LPE>(PK.P, PK.S, env0, live_envs, lane, el, j, s_new_all[wave], s_rst_all[wave], s_slot_all[wave], s_fin_all[wave], PK.out, PK.term_out);
     QG_MARK(8);                                      // rows written
-}
-
-// WPE = waves per SIMD the register allocation is capped for: 1 (all 512 registers) is fastest while the grid has at
-// most one wave per SIMD (n <= 16384); 2 lets a second wave share the SIMD once the grid is larger.
-// WALK: the walking task layer fused in (qg_walk_dev.h) -- the whole WalkingQuadrupedEnv.step (walking_quad.py:128-148) is this
-// one launch: settling-time action mask and the estimator update of the lane's three control channels in the prologue (they
-// need data.ctrl of the PREVIOUS step, which is still in place there), ideal-position integration, the eleven reward terms and
-// the episode bookkeeping in the epilogue on the sensor row the wave has just staged in LDS.
-// WAVES: waves per workgroup (1, or 4 = one per SIMD of a CU for grids of more than 256 waves: fewer workgroups to dispatch,
-// see qg_step_kernel_pair); the waves of a workgroup do not interact.
-// PO (with WALK; round 3): the partially observable observation pack fused in as in qg_step_kernel_pair<.., PO> (history copy on the
-// substep loop, frame by the env's lead lane, new frames written by the wave); the register-capped development variants (WPE > 2) have none.
-// HELP (with WALK, two-waves-per-SIMD register budget): as in qg_step_kernel_link<.., HELP> -- WAVES more waves per workgroup run the
-// estimator update of their partner wave's channels while that wave goes straight into the substep loop; for grids of at most one
-// physics wave per SIMD (<= 16 384 envs), where the partner's issue slots are otherwise idle.  With the observation pack the helper also
-// copies the history rows ring -> out (po_copy_history_now), so that nothing of the copy rides on the physics wave's substep loop: the
-// first version, which kept the in-loop copy with the physics wave, lost to the one-role kernel (48.6 against 46.9 us per step at
-// 16 384 envs, frame_skip 10: at this register budget the copy cannot park in AGPRs across a substep); this one measures 45.4.
-// DYN (generic tables only): per-env dynamics -- `Mp` is a KModelDyn and each lane takes its env's row into registers (dyn_load);
-// in wrench mode also its leg's and the FRAME's external wrench rows
-template <int WPE, bool BAKED, bool WALK = false, int WAVES = 1, bool PO = false, bool HELP = false, bool DYN = false>
-__global__ __launch_bounds__(QGK_WAVE * WAVES * (HELP ? 2 : 1), WPE) void qg_step_kernel_quad(const KModel *__restrict__ Mp, const KTask *__restrict__ T, KStepArgs P,
-                                                                             const typename WalkArgT<WALK>::type WK,
-                                                                             const typename PoArgT<PO>::type PK) {
-    static_assert(WALK || !PO, "the observation pack rides on the walking task layer");
-    static_assert(WPE == 1 || WPE == 2, "register budget: one wave per SIMD (all 512 registers) or two");
-    static_assert(!HELP || (WALK && WPE == 2), "helper waves: the walking forms at the two-waves-per-SIMD register budget");
-    static_assert(!DYN || (!BAKED && !HELP), "per-env dynamics: the table-driven variants");
-    constexpr bool PO_COPY = PO && !HELP;          // HELP: the helper wave copies the history rows, nothing of it rides on the substep loop
-    __shared__ float tile_all[WAVES][QGK_QUAD_ENVS * 35];
-    __shared__ KModel smodel;                       // generic variant: the link / joint tables staged in LDS (3.2 KB)
-    constexpr bool RWDH = HELP && !PO;              // walking without the observation pack: the helper wave also evaluates the reward
-    constexpr bool POH = HELP && PO;                // with it: the helper wave builds the new frame and writes the rows, the reward stays here
-    __shared__ float s_est[HELP ? WAVES : 1][QGK_WAVE][6];      // HELP: (f_est, a_est) of the lane's three channels, helper -> physics wave
-    __shared__ float s_done[HELP ? WAVES : 1][QGK_QUAD_ENVS];   // HELP: the step's termination flags, physics -> helper
-    __shared__ float s_q[POH ? WAVES : 1][QGK_QUAD_ENVS][4];    // POH: data.qpos[3:7] as the step leaves it (after the auto-reset), physics -> helper
-    const int lane = threadIdx.x & (QGK_WAVE - 1);
-    const int wave = HELP ? ((threadIdx.x >> 6) % WAVES) : (threadIdx.x >> 6);      // HELP: waves WAVES .. 2 WAVES - 1 shadow waves 0 .. WAVES - 1
-    const bool helper = HELP && (int)(threadIdx.x >> 6) >= WAVES;
-    float *tile = tile_all[wave];
-    QG_MARK(0);
-    QG_STAGE_MODEL(C, BAKED, smodel, Mp, QGK_WAVE * WAVES * (HELP ? 2 : 1));
-    const int k = lane & 3;                         // leg of this lane
-    const int el = lane >> 2;                       // env within the wave
-    const int env0 = (blockIdx.x * WAVES + wave) * QGK_QUAD_ENVS;
-    const int n = P.n;
-    const bool live = env0 + el < n;
-    const int env = live ? env0 + el : n - 1;       // tail quads shadow the last env; their stores are masked
-    // quarter turn of this lane's leg: (cos, sin)(90 deg * k)
-    const float cm = (k == 0) ? 1.f : (k == 2) ? -1.f : 0.f;
-    const float sm = (k == 1) ? 1.f : (k == 3) ? -1.f : 0.f;
-    KDyn D = {};
-    if constexpr (DYN) D = dyn_load(Mp, C, n, env);     // this env's dynamics row, once per launch
-    // external wrenches (wrench mode: KModelDyn::xfrc != NULL, wave-uniform): the rows of this lane's three links and the FRAME's with
-    // this launch's push, once per launch; nothing is loaded with the mode off
-    bool xon = false;
-    typename XfrcQuadT<DYN>::type XQ = {};
-    if constexpr (DYN) {
-        const KModelDyn *Md = reinterpret_cast<const KModelDyn *>(Mp);
-        xon = Md->xfrc != nullptr;
-        if (xon) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) XQ.link[i] = xfrc_row(Md->xfrc, env, 1 + 3 * k + i);
-            XQ.frame = xfrc_frame(Md, P, env, T->frame_skip);
-            XQ.com0 = v3(Md->com0[0], Md->com0[1], Md->com0[2]);
-        }
-    }
-
-    if constexpr (HELP) {
-        if (helper) {
-            const int ht[3] = {env * 12 + 3 * k + 0, env * 12 + 3 * k + 1, env * 12 + 3 * k + 2};
-            const int hcalls = WK.S.calls[env];
-            float hx[3], hf[3] = {0.f, 0.f, 0.f}, ha[3] = {0.f, 0.f, 0.f};
-            // RWDH: what the reward needs and does not come out of the physics, loaded ahead of the estimator's stores
-            float h_aclip[3] = {0.f, 0.f, 0.f}, h_wprev[3] = {0.f, 0.f, 0.f};
-            WalkChanTargets h_wtg[3] = {};
-            WalkEnvIn hwin = {};
-            if constexpr (HELP) {
-                const bool hsettle = P.st.nstep[env] < WK.P.settle_substeps;        // data.time < settling_time (walking_quad.py:142-143)
-                if constexpr (RWDH) walk_ldv<3>(WK.S.prev_ctrl + ht[0], h_wprev);
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    if constexpr (RWDH) h_wtg[i] = walk_channel_targets(WK.P, 3 * k + i);
-                    float a_in = P.actions[(size_t)env * 12 + 3 * k + i];
-                    if (hsettle) a_in = WK.P.joint_centers[3 * k + i];
-                    h_aclip[i] = fminf(fmaxf(a_in, -1.f), 1.f);                      // quadruped.py:160
-                }
-                if (k == 0) {
-                    hwin = walk_env_load(WK.S, n, env);
-                    hwin.episode_key = P.st.episode[env];      // not advanced yet: the physics wave does that behind the barrier
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i) hx[i] = P.st.ctrl[(3 * k + i) * n + env];   // data.ctrl of the PREVIOUS step (walking_quad.py:136)
-            WalkEstIn<3> hw;
-            walk_estimator_load_n<3, true>(WK.P, WK.S, n, ht, hcalls, hw, live);     // block entry in rolled groups: no scratch at 256 registers
-            if (live) walk_estimator_finish_n<3>(WK.P, WK.S, n, ht, hx, hcalls, hw, hf, ha);    // math_utils.py:53-131
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { s_est[wave][lane][i] = hf[i]; s_est[wave][lane][3 + i] = ha[i]; }
-            if constexpr (PO) {
-                int slot = PK.S.head[env] + 1;                     // the ring slot the NEW frame will take
-                if (slot >= PK.P.window) slot = 0;
-                if (PK.P.window > 1) po_copy_history_now<4>(PK.P, PK.S, (size_t)env * (PK.P.window * QG_PO_FRAME), slot, k, PK.out, live);
-            }
-            // (partner: the physics waves' __syncthreads() behind their auto-reset block, "partner of the helper waves' one barrier"
-            // below.  Exactly one barrier per wave on every path: a second one in either role, or a return in front of it, deadlocks
-            // the workgroup -- and on this pool a hung workgroup is a hung GPU.)
-            __syncthreads();      // the one barrier of the workgroup: behind it the physics waves read s_est and write what this wave read
-            if constexpr (RWDH) {
-                // the reward of the step, on the sensor tile the physics wave has finished (LDS), while that wave goes on with the resets and
-                // the state stores
-                const bool hdone = s_done[wave][el] != 0.f;
-                WalkSums sum = {0.f, 0.f, 0.f, 0.f};
-                if (live) {
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) walk_channel_terms(WK.S, env, 3 * k + i, h_wtg[i], h_aclip[i], h_wprev[i], hf[i], ha[i], sum);
-                    walk_stv<3>(WK.S.prev_ctrl + (size_t)env * 12 + 3 * k, h_aclip);                         // previous_ctrl moves on (:260-262)
-                }
-                sum.cost = quad_sum(sum.cost); sum.posture = quad_sum(sum.posture); sum.amp = quad_sum(sum.amp); sum.frq = quad_sum(sum.frq);
-                if (live && k == 0)
-                    walk_reward_env(WK.P, WK.S, n, env, tile + el * 35, sum, hwin, hdone, P.reward, WK.comps, WK.sample, P.seed, P.env_index_base);
-            }
-            if constexpr (POH) {
-                // the observation pack's new frame and rows, on the finished sensor tile and the orientation the physics wave handed over,
-                // while that wave evaluates the reward and stores the state
-                BaseState hb = {};
-                hb.qw = s_q[wave][el][0]; hb.qx = s_q[wave][el][1]; hb.qy = s_q[wave][el][2]; hb.qz = s_q[wave][el][3];
-                const int h_live_envs = max(0, min(QGK_QUAD_ENVS, n - env0));
-                po_wave_epilogue<QGK_QUAD_ENVS, 4, WAVES, true>(PK, WK, P, n, env, env0, h_live_envs, wave, lane, el, k, live, live && k == 0, PoEnvIn{},
-                                                                tile + el * 35, hb, hwin, s_done[wave][el] != 0.f, h_aclip);
-            }
-            return;
-        }
-    }
-    BaseState B;
-    QG_BASE_LOAD(B, P.st, QG_AT, n, env);
-    quat_unit(B);   // unit quaternion once per launch (qg_set_state may hand in any length); the substeps keep it normalised (base_prelude<UNIT>)
-    LegState L;
-    const int nstep0 = P.st.nstep[env];
-    float aclip0[3];
-    bool settle = false;
-    int calls = 0;
-    WalkEnvIn win = {};
-    if constexpr (WALK) {
-        settle = nstep0 < WK.P.settle_substeps;                     // data.time < settling_time (walking_quad.py:142-143)
-        if constexpr (!HELP) calls = WK.S.calls[env];
-    }
-    // WALK: every load of the task layer goes out here, among the state loads, and every store of its prologue part comes after the
-    // last load of the kernel's prologue (a load behind a store would wait for that store: vmcnt counts in order)
-    const int tt[3] = {env * 12 + 3 * k + 0, env * 12 + 3 * k + 1, env * 12 + 3 * k + 2};     // task state: [n][12]
-    float xx[3] = {0.f, 0.f, 0.f}, wprev[3] = {0.f, 0.f, 0.f}, wf[3] = {0.f, 0.f, 0.f}, wa[3] = {0.f, 0.f, 0.f}, a_eff[3] = {0.f, 0.f, 0.f};
-    WalkEstIn<3> west;
-    WalkChanTargets wtg[3] = {};
-    if constexpr (WALK) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) if constexpr (!HELP) xx[i] = P.st.ctrl[(3 * k + i) * n + env];   // data.ctrl of the PREVIOUS step: what the estimator takes (walking_quad.py:136)
-        walk_ldv<3>(WK.S.prev_ctrl + tt[0], wprev);   // previous_ctrl of the control cost (:260-262)
-        if constexpr (!HELP) walk_estimator_load_n<3>(WK.P, WK.S, n, tt, calls, west);
-        if constexpr (WPE == 1) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) wtg[i] = walk_channel_targets(WK.P, 3 * k + i);
-            if (k == 0) {                                   // what the reward epilogue reads: fetched now, behind the physics
-                win = walk_env_load(WK.S, n, env);
-                win.episode_key = P.st.episode[env];        // not advanced yet: the key of the episode that begins if this one ends
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int j = 3 * k + i;
-        float a_in = P.actions[(size_t)env * 12 + j];
-        if constexpr (WALK) {
-            if (settle) a_in = WK.P.joint_centers[j];                // the joint centres while the robot settles
-            a_eff[i] = a_in;
-        }
-        float a = fminf(fmaxf(a_in, -1.f), 1.f);    // quadruped.py:160
-        aclip0[i] = a;
-        L.u[i] = fminf(fmaxf(a, link_of<BAKED>(C, k, i).ctrl_lo), link_of<BAKED>(C, k, i).ctrl_hi);
-        QG_HINGE_LOAD(L.q[i], L.qd[i], L.act[i], P.st, QG_AT, n, env, j);
-        sincos_f(L.q[i] - link_of<BAKED>(C, k, i).ref, L.sc[2 * i], L.sc[2 * i + 1]);
-    }
-    // PO: the env's filter state (lead lane) and ring position, this lane's share of its env's row copy ring -> out -- its loads go
-    // out here, among the state loads and before the task layer's stores (see qg_step_kernel_pair)
-    PoEnvIn pin = {};
-    PoCopyState pcs = {};
-    const int live_envs = max(0, min(QGK_QUAD_ENVS, n - env0));
-    const int el_c = min(el, max(live_envs - 1, 0));     // row of this lane's env in the wave's block (tail lanes: the last live one)
-    unsigned long long po_ring = 0, po_out = 0;          // the wave's block of the frame ring / of the output rows (scalar registers)
-    if constexpr (PO) {
-        const size_t po_block = (size_t)(live_envs > 0 ? env0 : 0) * (size_t)(PK.P.window * QG_PO_FRAME);
-        po_ring = po_uniform_addr(PK.S.stack + 2 * po_block);
-        po_out = po_uniform_addr(PK.out + po_block);
-        if (k == 0) pin = po_env_load(PK.S, n, env);
-        if constexpr (PO_COPY) po_row_copy_init<4>(PK.P, el_c, PK.S.head[env], k, pcs);
-    }
-    if constexpr (WALK) {
-        // every state value is in its register before the first store of the task layer is issued: the waits for those loads
-        // would otherwise sit behind the stores (vmcnt is in order) right in front of the substep loop
-        asm volatile("" :: "v"(B.pw.x), "v"(B.pw.y), "v"(B.pw.z), "v"(B.qw), "v"(B.qx), "v"(B.qy), "v"(B.qz), "v"(B.vw.x), "v"(B.vw.y), "v"(B.vw.z),
-                     "v"(B.wb.x), "v"(B.wb.y), "v"(B.wb.z), "v"(L.q[0]), "v"(L.q[1]), "v"(L.q[2]), "v"(L.qd[0]), "v"(L.qd[1]), "v"(L.qd[2]),
-                     "v"(L.act[0]), "v"(L.act[1]), "v"(L.act[2]), "v"(L.u[0]), "v"(L.u[1]), "v"(L.u[2]) : "memory");
-        if (live) {
-            if constexpr (!HELP) walk_estimator_finish_n<3>(WK.P, WK.S, n, tt, xx, calls, west, wf, wa);    // math_utils.py:53-131
-            walk_stv<3>(WK.S.eff_actions + (size_t)env * 12 + 3 * k, a_eff);                        // the action actually applied (the PO pack reads it)
-        }
-    }
-
-    // the sensor values of the step go straight into this env's row of the output tile (full 33-value layout; the
-    // 21-value pack is compacted below)
-    float *srow = tile + el * 35;
-    float zaxis_z = 1.f;
-    const int fs = T->frame_skip;
-    const bool lag = T->sensor_lag != 0;
-    // Un-lagged sensors (task.sensor_lag = 0) take one extra forward pass whose state changes are discarded: the same loop body
-    // runs once more with the state parked in LDS meanwhile -- one copy of the substep code and no extra live registers.
-    // (Register caps for three / four waves per SIMD were built and measured in round 2 -- 197 / 255 us against 200 us at 262 144 envs,
-    // slower below: profiles/r02/wpe_ab.txt, docs/EXPERIMENTS.md -- and removed in round 4: WPE is 1 or 2.)
-    int env_e = env, k_e = k;
-    int nstep;
-    float aclip[3];
-    {
-        // Code placement: a wave that is alone on its SIMD is sensitive to where the 14 KB loop body falls relative to the
-        // instruction-fetch lines -- the same loop, shifted by one dword through an unrelated edit of the prologue, measured
-        // 18.57 instead of 18.36 us per launch at 4096 envs (same-box A/B of eight paddings).  Pinning the loop to a 64-byte
-        // boundary makes its layout independent of what precedes it.
-        QG_MARK(1);                                  // state in registers, prologue stores issued
-        asm volatile(".p2align 6");
-        // the history copy's loads at the head of a substep and its stores at the tail -- or both at the head where the registers in
-        // between are taken: with two waves per SIMD the partner covers the latency, and the table-driven variant has none to spare
-        constexpr bool PO_DEFER = PO && WPE == 1 && BAKED;
-#pragma unroll 1
-        for (int s = 0; s < fs; ++s) {
-            PoCopyRegs<PO ? QG_PO_COPY_K : 1> pcr;
-            if constexpr (PO_COPY) po_row_copy_load<QG_PO_COPY_K, 4>(PK.P, po_ring, k, s == 0, pcs, pcr);
-            if constexpr (PO_COPY && !PO_DEFER) po_row_copy_store<QG_PO_COPY_K, 4>(PK.P, po_out, live, k, s == 0, pcs, pcr);
-            substep_quad<BAKED, (WPE > 1), DYN>(C, cm, sm, B, L, lag && (s == fs - 1), srow, k, zaxis_z, D, xon, xfrc_quad_ptr(XQ));
-            if constexpr (PO_DEFER) po_row_copy_store<QG_PO_COPY_K, 4>(PK.P, po_out, live, k, s == 0, pcs, pcr);
-        }
-        if constexpr (PO_COPY) po_row_copy_rest<QG_PO_COPY_K, 4>(PK.P, po_ring, po_out, live, k, pcs);
-        // the epilogue's addresses are derived from (env, leg) AFTER the loop: visible, they are computed before it and carried through
-        // it (see the register-capped variants below; with two waves per SIMD that was 60 bytes of scratch in the walking variant)
-        if constexpr (WPE > 1 || !BAKED) asm volatile("" : "+v"(env_e), "+v"(k_e));
-        QG_MARK(2);                                  // physics done
-        if (!lag) {   // un-lagged sensors (task.sensor_lag = 0): one extra forward pass on a scratch copy of the state
-            BaseState B2 = B;
-            LegState L2 = L;
-            substep_quad<BAKED, (WPE > 1), DYN>(C, cm, sm, B2, L2, true, srow, k, zaxis_z, D, xon, xfrc_quad_ptr(XQ));
-        }
-        nstep = nstep0 + fs;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) aclip[i] = aclip0[i];
-    }
-    float ssq = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ssq = fmaf(aclip[i], aclip[i], ssq);
-    ssq = quad_sum(ssq);
-
-    QG_REWARD_TERMS(T->, B, ssq, nstep);
-    QG_DONE_IF_BAD_STATE(B, quad_sum(L.q[0] + L.q[1] + L.q[2] + L.qd[0] + L.qd[1] + L.qd[2]));
-
-    const int od = T->obs_mode == 1 ? 21 : 33;
-    const int row = P.packed ? od + 2 : od;
-    QG_DONE_IF_FLIPPED(T->, zaxis_z);
-    if (k == 0) {                                                  // lane 0 of the quad wrote these entries itself
-        if (od == 21) { srow[18] = srow[30]; srow[19] = srow[31]; srow[20] = srow[32]; }   // IMU pack: velocimeter follows the gyro
-        if (P.packed) { srow[od] = reward; srow[od + 1] = done ? 1.f : 0.f; }
-    }
-    wave_sync();                                                   // the tile is this wave's own
-    if constexpr (!PO) {
-        const int total = live_envs * row;                               // (a whole wave may lie past the last env: live_envs = 0)
-        float *dst = (P.packed ? P.packed : P.obs) + (size_t)env0 * row;
-        QG_TILE_COPY_OUT(dst, tile, lane, total, row);
-    }
-    QG_MARK(3);                                      // obs tile written out
-    const bool lead = live && k_e == 0;
-    if (lead && !P.packed) {
-        if constexpr (!WALK) P.reward[env_e] = reward;
-        P.done[env_e] = done ? 1 : 0;
-    }
-    bool rst_done = false;
-    if constexpr (POH) {
-        // the auto-reset of the base FIRST (the reward below does not look at B): the helper wave's frame shows data.qpos[3:7] as the step
-        // leaves it
-        if (done && T->auto_reset) QG_BASE_RESET(B, nstep, C.qpos0, T->, P, env_e, P.st.episode[env_e]);
-        rst_done = true;
-        if (k_e == 0) {
-            s_done[wave][lane >> 2] = done ? 1.f : 0.f;
-            s_q[wave][lane >> 2][0] = B.qw; s_q[wave][lane >> 2][1] = B.qx; s_q[wave][lane >> 2][2] = B.qy; s_q[wave][lane >> 2][3] = B.qz;
-        }
-    }
-    if constexpr (WALK) {
-        WalkSums sum = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (WPE > 1) {       // two waves share the SIMD: read the task state again here (the other wave covers the latency)
-#pragma unroll                        // instead of carrying 21 values through the substep loop
-            for (int i = 0; i < 3; ++i) {
-                const int t = env_e * 12 + 3 * k_e + i;
-                if constexpr (!RWDH) wprev[i] = WK.S.prev_ctrl[t];
-                if constexpr (!HELP) { wf[i] = WK.S.f_est[t]; wa[i] = WK.S.a_est[t]; }
-                if constexpr (!RWDH) wtg[i] = walk_channel_targets(WK.P, 3 * k_e + i);
-            }
-            if ((!RWDH || PO) && lead) {
-                win = walk_env_load(WK.S, n, env_e);
-                win.episode_key = P.st.episode[env_e];
-            }
-        }
-        if constexpr (HELP) {
-            // the helper wave of this SIMD finished its first job long ago (its estimator stores have landed: the barrier's wait covers
-            // them); from here on this wave may overwrite what the helper read at entry (data.ctrl, the episode counter), and (RWDH)
-            // the helper evaluates the reward on the finished sensor tile
-            if constexpr (RWDH) { if (k_e == 0) s_done[wave][lane >> 2] = done ? 1.f : 0.f; }
-            __syncthreads();      // partner of the helper waves' one barrier
-            if constexpr (!RWDH) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) { wf[i] = s_est[wave][lane][i]; wa[i] = s_est[wave][lane][3 + i]; }
-            }
-        }
-        if (!RWDH && live) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) walk_channel_terms(WK.S, env_e, 3 * k_e + i, wtg[i], aclip[i], wprev[i], wf[i], wa[i], sum);
-            walk_stv<3>(WK.S.prev_ctrl + (size_t)env_e * 12 + 3 * k_e, aclip);                       // previous_ctrl moves on (:260-262)
-        }
-        if constexpr (!RWDH) { sum.cost = quad_sum(sum.cost); sum.posture = quad_sum(sum.posture); sum.amp = quad_sum(sum.amp); sum.frq = quad_sum(sum.frq); }
-        QG_MARK(4);                                  // channel terms + sums
-        if (!RWDH && lead) walk_reward_env(WK.P, WK.S, n, env_e, tile + (lane >> 2) * 35, sum, win, done, P.reward, WK.comps, WK.sample, P.seed, P.env_index_base);
-    }
-    QG_COMPS_STORE(lead, P, env_e);
-
-    const bool rst = done && T->auto_reset;
-    if (rst && !rst_done) QG_BASE_RESET(B, nstep, C.qpos0, T->, P, env_e, P.st.episode[env_e]);
-    if (lead) {
-        QG_BASE_STORE(B, nstep, P.st, QG_PUT, n, env_e);
-        if (rst) P.st.episode[env_e] += 1;
-    }
-    if (live) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int j = 3 * k_e + i;
-            QG_HINGE_STORE(rst ? C.qpos0[7 + (BAKED ? i : j)] : L.q[i], rst ? 0.f : L.qd[i], rst ? 0.f : L.act[i], P.st, QG_PUT, n, env_e, j);
-            if (P.track_ctrl) P.st.ctrl[j * n + env_e] = rst ? T->default_ctrl[j] : aclip[i];
-        }
-    }
-    if constexpr (PO && !POH)
-        po_wave_epilogue<QGK_QUAD_ENVS, 4, WAVES, (WPE > 1)>(PK, WK, P, n, env, env0, live_envs, wave, lane, el, k, live, lead, pin, srow, B, win, done, aclip);
-}
-
-// ------------------------------------------------------------------------------------------
-// env-step kernel, TWO LEGS PER LANE (packed FP32): the two lanes 2e, 2e+1 share env e; lane h owns legs 2h and
-// 2h+1 as the two components of f2 quantities, so every fma / mul / add of the leg physics is ONE v_pk_* instruction for
-// both legs.  32 envs per wave.  Base prelude, FRAME terms, 6x6 solve and base integration are scalar and redundant in the
-// two lanes; leg terms are summed over the two components (a scalar add of the two halves of the register pair) and over the
-// lane pair (one DPP add).  Per env this issues 0.59x the instructions of one leg per lane.  v_pk_*_f32 is half rate on gfx950
-// (tools/ubench/valu_rate.hip), so this pays only where a wave has its SIMD to itself anyway -- a lone wave issues at most
-// every ~4.5 cycles, packed or not: grids of 16-32 Ki envs and, by a smaller margin, >= 56 Ki.  Compiled-in robot only.
-// ------------------------------------------------------------------------------------------
-DEV float pair_sum(float x) {                                     // quad_perm [1,0,3,2]: the other lane of the pair
-#pragma clang fp contract(off)
-    return x + dpp_quad<0xB1>(x);
-}
-DEV float hsum(f2 v) {
-#pragma clang fp contract(off)
-    return v.x + v.y;
-}
-DEV V3 hsum(V3T<f2> v) { return v3<float>(hsum(v.x), hsum(v.y), hsum(v.z)); }
-DEV V3 pair_sum(V3 a) { return v3<float>(pair_sum(a.x), pair_sum(a.y), pair_sum(a.z)); }
-DEV Sym3 hpsum(const Sym3T<f2> &a) {
-    Sym3 r = {pair_sum(hsum(a.xx)), pair_sum(hsum(a.yy)), pair_sum(hsum(a.zz)), pair_sum(hsum(a.xy)), pair_sum(hsum(a.xz)), pair_sum(hsum(a.yz))};
-    return r;
-}
-DEV Sym6 hpsum(const Sym6T<f2> &a) {
-    Sym6 r;
-    r.AA = hpsum(a.AA);
-    r.LL = hpsum(a.LL);
-    r.AL.r0 = pair_sum(hsum(a.AL.r0)); r.AL.r1 = pair_sum(hsum(a.AL.r1)); r.AL.r2 = pair_sum(hsum(a.AL.r2));
-    return r;
-}
-DEV SV hpsum(const SVT<f2> &v) { SV r = {pair_sum(hsum(v.a)), pair_sum(hsum(v.l))}; return r; }
-
-struct LegPair { f2 q[3], qd[3], act[3], u[3], sc[6]; };   // sc: sin, cos of (q[i] - ref_i) of both legs, advanced with the hinges
-
-DEV void substep_pair(const KModel &C, f2 cm, f2 sm, BaseState &B, LegPair &L, bool want_sensors, float *__restrict__ row, int half, float &zaxis_z) {
-    const float h = C.h;
-    const BaseCtx bc0 = base_prelude<true>(C, B);
-    V3 gb_keep;
-    Sym6 Ic;
-    SV fc, Fu;
-    f2 Y0[6], Y1[6], Y2[6], u[3];
-    {
-        const BaseCtx &bc = bc0;
-        gb_keep = bc.gb;
-        if (want_sensors) {          // the step's sensordata describes the state at the start of its last substep
-            zaxis_z = bc.cz.z;
-            float *jr = row + 6 * half;                  // legs 2*half and 2*half + 1
-            jr[0] = L.q[0].x; jr[1] = L.q[1].x; jr[2] = L.q[2].x;
-            jr[3] = L.q[0].y; jr[4] = L.q[1].y; jr[5] = L.q[2].y;
-            if (half == 0) {
-                row[15] = B.wb.x; row[16] = B.wb.y; row[17] = B.wb.z;
-                row[18] = B.pw.x; row[19] = B.pw.y; row[20] = B.pw.z;
-                row[21] = B.vw.x; row[22] = B.vw.y; row[23] = B.vw.z;
-                row[24] = bc.cx.x; row[25] = bc.cx.y; row[26] = bc.cx.z;
-                row[27] = bc.cz.x; row[28] = bc.cz.y; row[29] = bc.cz.z;
-                row[30] = bc.vb.x; row[31] = bc.vb.y; row[32] = bc.vb.z;
-            }
-        }
-        // both legs of this lane, each in the frame turned by its quarter turn: there each of them is leg 0
-        const f2 z2 = f2(0.f), o2 = f2(1.f);
-        FrT<f2> Ek = {v3<f2>(cm, sm, z2), v3<f2>(-sm, cm, z2), v3<f2>(z2, z2, o2)};
-        Sym6T<f2> Ic2, YFt2;
-        SVT<f2> fc2, F2[3], Fu2;
-        f2 Hd[3], H01, H02, H12, bj[3];
-        leg_pass<f2, true, true, false, true>(C, 0, Ek, L.q, L.qd, L.act, bc, B.pw.z, h, Ic2, fc2, F2, Hd, H01, H02, H12, bj, L.sc);
-        leg_eliminate<f2>(F2, Hd, H01, H02, H12, bj, Y0, Y1, Y2, u, YFt2, Fu2);
-        sub(Ic2, YFt2);                     // the two legs' Schur complements
-        // Sum over the two legs of the lane and over the two lanes of the env, HERE, far from the uses: the DPP moves then stay unfused
-        // (33 v_mov_b32_dpp per substep: the compiler fuses a move into its add only when the two are close, see substep_quad), but
-        // with the sums right in front of the 6x6 solve the lone wave of this kernel ran 2.6 % slower at 32 768 and at 262 144 envs
-        // (same-box A/B, round 3: 25.0 -> 25.65 us; the dependent chain sum -> assemble -> solve has nothing to overlap with there)
-        Ic = hpsum(Ic2);
-        fc = hpsum(fc2);
-        Fu = hpsum(Fu2);
-    }
-    float x6[6];
-    {
-        const BaseCtx &bc = bc0;
-        SV p0;
-        Sym6 Ic0;
-        frame_body(C, bc, h, p0, Ic0);
-        SV b;
-        {   // FRAME contact: this lane evaluates two quarter turns of the three base sample points
-            f2 wsum2 = f2(0.f);
-            V3T<f2> s2 = v3<f2>(f2(0.f), f2(0.f), f2(0.f));
-            const f2 zb = f2(C.contact_margin - B.pw.z);
-            const V3T<f2> n2 = splat3<f2>(bc.n);
-#pragma unroll
-            for (int o = 0; o < 3; ++o) {
-                V3 r0 = ld3(C.cp0[4 * o]);
-                contact_point(v3<f2>(cm * r0.x - sm * r0.y, sm * r0.x + cm * r0.y, f2(r0.z)), n2, zb, wsum2, s2);
-            }
-            float wsum = pair_sum(hsum(wsum2));
-            add(Ic0, Ic);
-            b.a = v3<float>(0.f, 0.f, 0.f) - Fu.a - p0.a - fc.a;
-            b.l = v3<float>(0.f, 0.f, 0.f) - Fu.l - p0.l - fc.l;
-            if (__any(wsum > 0.f)) {        // wave-uniform skip, as in the quad kernel (the block is updated in place)
-                V3 s = pair_sum(hsum(s2));
-                Fr E0 = {v3<float>(1.f, 0.f, 0.f), v3<float>(0.f, 1.f, 0.f), v3<float>(0.f, 0.f, 1.f)};
-                SV fe;
-                contact_finish<float>(wsum, s, E0, v3<float>(0.f, 0.f, 0.f), bc.n, bc.V0, C.contact_k, C.contact_c, C.contact_inv_ramp, C.contact_mu, h, fe, Ic0);
-                b.a = b.a + fe.a;
-                b.l = b.l + fe.l;
-            }
-        }
-        base_solve(Ic0, b, x6);     // (pk3::base_solve: 36 instructions fewer and 2.7 % SLOWER here, 24.96 -> 25.64 us at 32 768 envs: the solve sits on
-                                     // this kernel's dependent tail, and a dependent packed instruction costs a lone wave ~1.5 plain ones; the same right-looking
-                                     // order in plain FP32, 15 instructions fewer: no difference, 24.9-25.1 us either way)
-    }
-    V3 wdot = v3<float>(x6[0], x6[1], x6[2]);
-    V3 acl = v3<float>(x6[3], x6[4], x6[5]);
-    if (want_sensors && half == 0) {
-        row[12] = acl.x - gb_keep.x; row[13] = acl.y - gb_keep.y; row[14] = acl.z - gb_keep.z;   // accelerometer
-    }
-    // back-substitution and integration of this lane's six hinges
-    const f2 *Y[3] = {Y0, Y1, Y2};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        f2 acc = u[i];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) acc = fma_(-Y[i][r], f2(x6[r]), acc);
-        L.qd[i] = fma_(f2(h), acc, L.qd[i]);
-        L.q[i] = fma_(f2(h), L.qd[i], L.q[i]);
-        hinge_advance(f2(h) * L.qd[i], L.sc[2 * i], L.sc[2 * i + 1]);
-        L.act[i] = fma_(L.u[i] - L.act[i], f2(C.link[i].act_decay), L.act[i]);
-    }
-    {
-        const BaseCtx &bc = bc0;
-        base_integrate<true>(bc, h, wdot, acl, B);
-    }
-}
-
-#define QGK_PAIR_ENVS 32    // envs per wave in the two-legs-per-lane kernel
-
-
-// One wave per SIMD by construction (381 registers): capping it to 256 for two resident waves spills 592 B per lane and
-// measured slower than this variant at every size (profiles/r01/pair_sweep.txt), so there is only this one.
-// WAVES: waves per workgroup (1 or 4, one per SIMD of a CU; they do not interact).  A grid of 1024 one-wave workgroups costs ~1.6 us
-// more fixed time per launch than 256 four-wave ones (the dispatch of the workgroups themselves: tools/fs_sweep.sh on the
-// one-link-per-lane kernel), so grids of more than 256 waves are launched as four-wave workgroups.
-// WALK: the walking task layer fused in as in qg_step_kernel_quad<.., WALK>; the lane owns the six control channels of its two legs
-// (6 * half .. 6 * half + 5, contiguous in the env-major task state).
-// PO (with WALK; round 3): the partially observable observation pack fused in as well -- POWalkingQuadrupedEnv.step is this one launch
-// also at the batch sizes this kernel serves.  The copy of the W - 1 frames the new stack keeps rides on the substep loop
-// (po_row_copy_*, qg_po_dev.h: loads at the head of a substep, stores at its tail), the env's lead lane runs the orientation filter
-// on the step's sensors in the epilogue, the wave writes the new frames.  The 33 sensors themselves are not written to memory.
-template <int WAVES, bool WALK = false, bool PO = false>
-__global__ __launch_bounds__(QGK_WAVE * WAVES, 1) void qg_step_kernel_pair(const KTask *__restrict__ T, KStepArgs P,
-                                                                           const typename WalkArgT<WALK>::type WK,
-                                                                           const typename PoArgT<PO>::type PK) {
-    static_assert(WALK || !PO, "the observation pack rides on the walking task layer");
-    __shared__ float tile_all[WAVES][QGK_PAIR_ENVS * 35];
-    QG_MARK(0);
-    const KModel &C = QG_BAKED_MODEL;
-    const int lane = threadIdx.x & (QGK_WAVE - 1);
-    const int wave = threadIdx.x >> 6;
-    float *tile = tile_all[wave];
-    const int half = lane & 1;                      // legs 2*half, 2*half + 1
-    const int el = lane >> 1;                       // env within the wave
-    const int env0 = (blockIdx.x * WAVES + wave) * QGK_PAIR_ENVS;
-    const int n = P.n;
-    const bool live = env0 + el < n;
-    int env = live ? env0 + el : n - 1;             // tail pairs shadow the last env; their stores are masked
-    // quarter turns of this lane's two legs: (cos, sin)(90 deg * k), k = 2*half and 2*half + 1
-    f2 cm, sm;
-    cm.x = half ? -1.f : 1.f; cm.y = 0.f;
-    sm.x = 0.f; sm.y = half ? -1.f : 1.f;
-
-    BaseState B;
-    QG_BASE_LOAD(B, P.st, QG_AT, n, env);
-    quat_unit(B);   // unit quaternion once per launch (qg_set_state may hand in any length); the substeps keep it normalised (base_prelude<UNIT>)
-    int nstep = P.st.nstep[env];
-    LegPair L;
-    float aclip[6];
-    float ssq = 0.f;
-    // WALK: every load of the task layer goes out among the state loads, every store of its prologue part after the last of them
-    // (see qg_step_kernel_quad)
-    bool settle = false;
-    int calls = 0;
-    WalkEnvIn win = {};
-    int tt[6] = {0, 0, 0, 0, 0, 0};
-    float xx[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, wprev[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, wf[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
-          wa[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, a_eff[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    WalkEstIn<6> west;
-    WalkChanTargets wtg[6] = {};
-    if constexpr (WALK) {
-        settle = nstep < WK.P.settle_substeps;                      // data.time < settling_time (walking_quad.py:142-143)
-        calls = WK.S.calls[env];
-#pragma unroll
-        for (int c6 = 0; c6 < 6; ++c6) {
-            tt[c6] = env * 12 + 6 * half + c6;
-            xx[c6] = P.st.ctrl[(6 * half + c6) * n + env];           // data.ctrl of the PREVIOUS step (walking_quad.py:136)
-        }
-        {
-            float pc[6];
-            walk_ldv<6>(WK.S.prev_ctrl + env * 12 + 6 * half, pc);    // previous_ctrl of the control cost (:260-262)
-#pragma unroll
-            for (int c6 = 0; c6 < 6; ++c6) wprev[c6] = pc[c6];
-        }
-        walk_estimator_load_n<6>(WK.P, WK.S, n, tt, calls, west);
-#pragma unroll
-        for (int c6 = 0; c6 < 6; ++c6) wtg[c6] = walk_channel_targets(WK.P, 6 * half + c6);
-        if (half == 0) {
-            win = walk_env_load(WK.S, n, env);
-            win.episode_key = P.st.episode[env];              // not advanced yet: the key of the episode that begins if this one ends
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int j = 3 * (2 * half + c) + i;
-            float a_in = P.actions[(size_t)env * 12 + j];
-            if constexpr (WALK) {
-                if (settle) a_in = WK.P.joint_centers[j];            // the joint centres while the robot settles
-                a_eff[3 * c + i] = a_in;
-            }
-            float a = fminf(fmaxf(a_in, -1.f), 1.f);    // quadruped.py:160
-            aclip[3 * c + i] = a;
-            ssq = fmaf(a, a, ssq);
-            float uu = fminf(fmaxf(a, C.link[i].ctrl_lo), C.link[i].ctrl_hi);
-            float qq, qv, aa;
-            QG_HINGE_LOAD(qq, qv, aa, P.st, QG_AT, n, env, j);
-            if (c == 0) { L.u[i].x = uu; L.q[i].x = qq; L.qd[i].x = qv; L.act[i].x = aa; }
-            else { L.u[i].y = uu; L.q[i].y = qq; L.qd[i].y = qv; L.act[i].y = aa; }
-        }
-    }
-    ssq = pair_sum(ssq);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) sincos_f(L.q[i] - f2(C.link[i].ref), L.sc[2 * i], L.sc[2 * i + 1]);
-    // PO: the env's filter state (lead lane) and ring position, this lane's share of its env's row copy ring -> out -- its loads go
-    // out here, among the state loads and before the task layer's stores
-    PoEnvIn pin = {};
-    PoCopyState pcs = {};
-    const int live_envs = max(0, min(QGK_PAIR_ENVS, n - env0));
-    const int el_c = min(el, max(live_envs - 1, 0));     // row of this lane's env in the wave's block (tail lanes: the last live one)
-    unsigned long long po_ring = 0, po_out = 0;          // the wave's block of the frame ring / of the output rows (scalar registers)
-    if constexpr (PO) {
-        // (a wave that lies wholly past the last env copies nothing, but its loads are unpredicated: they read block 0)
-        const size_t po_block = (size_t)(live_envs > 0 ? env0 : 0) * (size_t)(PK.P.window * QG_PO_FRAME);
-        po_ring = po_uniform_addr(PK.S.stack + 2 * po_block);
-        po_out = po_uniform_addr(PK.out + po_block);
-        if (half == 0) pin = po_env_load(PK.S, n, env);
-        po_row_copy_init<2>(PK.P, el_c, PK.S.head[env], half, pcs);
-    }
-    if constexpr (WALK) {
-        asm volatile("" :: "v"(B.pw.x), "v"(B.pw.y), "v"(B.pw.z), "v"(B.qw), "v"(B.qx), "v"(B.qy), "v"(B.qz), "v"(B.vw.x), "v"(B.vw.y), "v"(B.vw.z),
-                     "v"(B.wb.x), "v"(B.wb.y), "v"(B.wb.z), "v"(L.q[0].x), "v"(L.q[1].x), "v"(L.q[2].x), "v"(L.q[0].y), "v"(L.q[1].y), "v"(L.q[2].y),
-                     "v"(L.qd[0].x), "v"(L.qd[1].x), "v"(L.qd[2].x), "v"(L.qd[0].y), "v"(L.qd[1].y), "v"(L.qd[2].y),
-                     "v"(L.act[0].x), "v"(L.act[1].x), "v"(L.act[2].x), "v"(L.act[0].y), "v"(L.act[1].y), "v"(L.act[2].y) : "memory");
-        if (live) {
-            walk_estimator_finish_n<6>(WK.P, WK.S, n, tt, xx, calls, west, wf, wa);    // math_utils.py:53-131
-            walk_stv<6>(WK.S.eff_actions + (size_t)env * 12 + 6 * half, a_eff);
-        }
-    }
-
-    // data.ctrl of this step (quadruped.py:164: the env-clipped action) is known here: it goes out now, behind the loads (the task
-    // layer has read the PREVIOUS one above), instead of among the epilogue's stores -- at 32 768 envs all 1024 waves reach their 12.7 MB
-    // of epilogue stores at the same moment; an env the step resets gets the default there.  (Same-box A/B, round 3: -0.9 % here, but
-    // +0.4 us in the one-link-per-lane kernel at 4096 envs and +0.5 % in the one-leg-per-lane kernel at 16 384: only this kernel has it.)
-    if (live && P.track_ctrl) {
-#pragma unroll
-        for (int c6 = 0; c6 < 6; ++c6) P.st.ctrl[(6 * half + c6) * n + env] = aclip[c6];
-    }
-    float *srow = tile + el * 35;
-    float zaxis_z = 1.f;
-    const int fs = T->frame_skip;
-    const bool lag = T->sensor_lag != 0;
-    // PO: the env's filter state (lead lane) and ring position, this lane's share of its env's row copy ring -> out
-    QG_MARK(1);                                      // state in registers, prologue stores issued
-#pragma unroll 1
-    for (int s = 0; s < fs; ++s) {
-        PoCopyRegs<PO ? QG_PO_COPY_K : 1> pcr;
-        if constexpr (PO) po_row_copy_load<QG_PO_COPY_K, 2>(PK.P, po_ring, half, s == 0, pcs, pcr);
-        substep_pair(C, cm, sm, B, L, lag && (s == fs - 1), srow, half, zaxis_z);
-        if constexpr (PO) po_row_copy_store<QG_PO_COPY_K, 2>(PK.P, po_out, live, half, s == 0, pcs, pcr);
-    }
-    if constexpr (PO) po_row_copy_rest<QG_PO_COPY_K, 2>(PK.P, po_ring, po_out, live, half, pcs);
-    nstep += fs;
-    // the epilogue's store addresses are derived from `env` AFTER the loop: left visible, the compiler computes two dozen 64-bit
-    // addresses before the loop and carries them through it -- ~60 registers of a kernel that already parks values in AGPRs
-    // (tools/asm_liveness.py found the same in the one-leg-per-lane kernel in round 2)
-    asm volatile("" : "+v"(env));
-    QG_MARK(2);                                      // physics done
-    if (!lag) {
-        BaseState B2 = B;
-        LegPair L2 = L;
-        substep_pair(C, cm, sm, B2, L2, true, srow, half, zaxis_z);
-    }
-
-    QG_REWARD_TERMS(T->, B, ssq, nstep);
-    QG_DONE_IF_BAD_STATE(B, pair_sum(hsum(L.q[0]) + hsum(L.q[1]) + hsum(L.q[2]) + hsum(L.qd[0]) + hsum(L.qd[1]) + hsum(L.qd[2])));
-    const int od = T->obs_mode == 1 ? 21 : 33;
-    const int row = P.packed ? od + 2 : od;
-    QG_DONE_IF_FLIPPED(T->, zaxis_z);
-    if (half == 0) {
-        if (od == 21) { srow[18] = srow[30]; srow[19] = srow[31]; srow[20] = srow[32]; }
-        if (P.packed) { srow[od] = reward; srow[od + 1] = done ? 1.f : 0.f; }
-    }
-    wave_sync();                                                   // the tile is this wave's own
-    if constexpr (!PO) {
-        const int total = live_envs * row;                               // (a whole wave may lie past the last env: live_envs = 0)
-        float *dst = (P.packed ? P.packed : P.obs) + (size_t)env0 * row;
-        QG_TILE_COPY_OUT(dst, tile, lane, total, row);
-    }
-    QG_MARK(3);                                      // obs tile written out
-    const bool lead = live && half == 0;
-    if (lead && !P.packed) {
-        if constexpr (!WALK) P.reward[env] = reward;
-        P.done[env] = done ? 1 : 0;
-    }
-    if constexpr (WALK) {
-        WalkSums sum = {0.f, 0.f, 0.f, 0.f};
-        if (live) {
-#pragma unroll
-            for (int c6 = 0; c6 < 6; ++c6) walk_channel_terms(WK.S, env, 6 * half + c6, wtg[c6], aclip[c6], wprev[c6], wf[c6], wa[c6], sum);
-            walk_stv<6>(WK.S.prev_ctrl + (size_t)env * 12 + 6 * half, aclip);                          // previous_ctrl moves on (:260-262)
-        }
-        sum.cost = pair_sum(sum.cost); sum.posture = pair_sum(sum.posture); sum.amp = pair_sum(sum.amp); sum.frq = pair_sum(sum.frq);
-        QG_MARK(4);                                  // channel terms + sums
-        if (lead) walk_reward_env(WK.P, WK.S, n, env, tile + el * 35, sum, win, done, P.reward, WK.comps, WK.sample, P.seed, P.env_index_base);
-        QG_MARK(5);                                  // reward
-    }
-    QG_COMPS_STORE(lead, P, env);
-
-    const bool rst = done && T->auto_reset;
-    if (rst) QG_BASE_RESET(B, nstep, C.qpos0, T->, P, env, P.st.episode[env]);
-    if (lead) {
-        QG_BASE_STORE(B, nstep, P.st, QG_PUT, n, env);
-        if (rst) P.st.episode[env] += 1;
-    }
-    if (live) {
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int j = 3 * (2 * half + c) + i;
-                QG_HINGE_STORE(rst ? C.qpos0[7 + i] : (c == 0 ? L.q[i].x : L.q[i].y), rst ? 0.f : (c == 0 ? L.qd[i].x : L.qd[i].y), rst ? 0.f : (c == 0 ? L.act[i].x : L.act[i].y), P.st, QG_PUT, n, env, j);
-                if (P.track_ctrl && rst) P.st.ctrl[j * n + env] = T->default_ctrl[j];          // (the step's data.ctrl went out in the prologue)
-            }
-        }
-    }
-    QG_MARK(6);                                      // reset block, state stores issued
-    if constexpr (PO)
-        po_wave_epilogue<QGK_PAIR_ENVS, 2, WAVES, false>(PK, WK, P, n, env, env0, live_envs, wave, lane, el, half, live, lead, pin, srow, B, win, done, aclip);
-    QG_MARK(9);
-}
-
-// ------------------------------------------------------------------------------------------
-// reset (quadruped.py:115-139): mj_resetData, time = 0, ctrl = default; optional random yaw and hinge jitter
-// ------------------------------------------------------------------------------------------
-__global__ void qg_reset_kernel(const KModel *__restrict__ M, const KTask *__restrict__ T, KState st, int n, const uint8_t *mask,
-                                uint64_t seed, uint64_t env_index_base, uint32_t flags, int count_episode) {
-    int env = blockIdx.x * blockDim.x + threadIdx.x;
-    if (env >= n) return;
-    if (mask && !mask[env]) return;
-    const int ep = st.episode[env];
-    for (int j = 0; j < 19; ++j) st.qpos[j * n + env] = M->qpos0[j];
-    if (flags & 2u) {
-        for (int j = 0; j < 12; ++j)
-            st.qpos[(7 + j) * n + env] = jittered_hinge(M->qpos0[7 + j], M->link[j].lo, M->link[j].hi, T->reset_joint_jitter, seed,
-                                                        env_index_base + (uint64_t)env, ep, j);
-    }
-    if (flags & 1u)
-        QG_RESET_HEADING(seed, env_index_base + (uint64_t)env, ep, st.qpos[3 * n + env], st.qpos[4 * n + env], st.qpos[5 * n + env], st.qpos[6 * n + env]);
-    for (int j = 0; j < 18; ++j) st.qvel[j * n + env] = 0.f;
-    for (int j = 0; j < 12; ++j) { st.act[j * n + env] = 0.f; st.ctrl[j * n + env] = T->default_ctrl[j]; }
-    st.nstep[env] = 0;
-    if (count_episode) st.episode[env] += 1;
-}
-
-// QG_RESET_JOINT_JITTER for the envs the step kernel has just auto-reset: their hinges stand at qpos0 and their episode counter
-// has advanced, so the key of the episode that begins is episode - 1 (the one its reset yaw used).  A separate launch, issued
-// only when the task asks for jitter: inside the step kernels even a never-taken branch of this size measured +0.9 % at 4096
-// envs and +2 % at 32 768 (same-box A/B).  One thread per (hinge, env); `done` is the step's done output, either as bytes
-// or as the last column of the packed rows.
-__global__ void qg_jitter_kernel(const KModel *__restrict__ M, const KTask *__restrict__ T, KState st, int n, const uint8_t *__restrict__ done,
-                                 const float *__restrict__ packed, int row, uint64_t seed, uint64_t env_index_base) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 12 * n) return;
-    const int j = t / n, env = t - j * n;
-    const bool was_reset = done ? (done[env] != 0) : (packed[(size_t)env * row + (row - 1)] > 0.5f);
-    if (!was_reset) return;
-    st.qpos[(7 + j) * n + env] = jittered_hinge(M->qpos0[7 + j], M->link[j].lo, M->link[j].hi, T->reset_joint_jitter, seed,
-                                                env_index_base + (uint64_t)env, st.episode[env] - 1, j);
-}
-
-// QG_RESET_DYNAMICS: column c of env i drawn for episode e as lo + (hi - lo) u, u = uniform24s(seed, base + i, e, 16 + c) -- streams of
-// their own, so the yaw (0), hinge (1..12) and command (13..15) draws are the same with the flag as without.  One thread per (column,
-// env).  Behind qg_reset (`mask`: the envs reset, NULL: all; key = the episode counter before the reset advances it, key_offset 0) and,
-// as qg_jitter_kernel and for its reason, as a launch of its own behind a step that auto-resets (`done` bytes or the packed rows' last
-// column: the envs that finished; their counter has advanced, key_offset -1).
-#define QG_STREAM_DYNAMICS 16u
-__global__ void qg_dyn_draw_kernel(float *__restrict__ rows, KDynRange R, const int32_t *__restrict__ episode, int n, const uint8_t *__restrict__ mask,
-                                   const uint8_t *__restrict__ done, const float *__restrict__ packed, int row, int key_offset, uint64_t seed,
-                                   uint64_t env_index_base) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= QGK_NDYN * n) return;
-    const int c = t / n, env = t - c * n;
-    if (mask && !mask[env]) return;
-    if (!mask && (done || packed)) {
-        const bool was_reset = done ? (done[env] != 0) : (packed[(size_t)env * row + (row - 1)] > 0.5f);
-        if (!was_reset) return;
-    }
-    const float u = uniform24s(seed, env_index_base + (uint64_t)env, (uint64_t)(episode[env] + key_offset), QG_STREAM_DYNAMICS + (uint32_t)c);
-    rows[(size_t)c * n + env] = fmaf(R.hi[c] - R.lo[c], u, R.lo[c]);
-}
-
-// env-major [n][w] <-> field-major [w][n] (state snapshot / restore at the ABI)
-__global__ void qg_transpose_in(const float *__restrict__ src, float *__restrict__ dst, int n, int w) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n * w) return;
-    int f = i / n, e = i - f * n;
-    dst[i] = src[(size_t)e * w + f];
-}
-__global__ void qg_transpose_out(const float *__restrict__ src, float *__restrict__ dst, int n, int w) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n * w) return;
-    int e = i / w, f = i - e * w;
-    dst[i] = src[(size_t)f * n + e];
 }

@@ -1,7 +1,7 @@
 // qg_step_shell.h -- the shell of an env-step around the physics substeps, ONCE for every step kernel: base-state load and store,
 // plain reward and terminations, auto-reset of the base with the random heading, copy-out of the output tile, staging of the model
-// tables, the register snapshot of the task.  The per-launch kernels (qg_kernels.hip, qg_kernel_link.hip) and the many-steps-per-launch
-// forms (qg_kernel_resident.hip) expand the same text, so a change to the shell is made here and reaches all of them.
+// tables, the register snapshot of the task.  The per-launch kernels and the many-steps-per-launch
+// forms (qg_kernel_link.hip with qg_kernel_resident.hip, qg_kernel_quad.hip, qg_kernel_pair.hip) expand the same text, so a change to the shell is made here and reaches all of them.
 //
 // Statement MACROS, not device functions, on purpose: the macros expand to the very tokens the kernels held before and leave all 65
 // kernels of the code object instruction for instruction what they were (tools/asm_diff.py, profiles/r09/asm_diff.txt), while the same

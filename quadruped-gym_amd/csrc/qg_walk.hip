@@ -13,7 +13,7 @@
 //                        between reads it), the 11 reward terms of input_control_reward (:352-428) on the step's
 //                        sensordata and data.ctrl, their sum, episode bookkeeping of envs that finished.
 // These three launches serve the one-env-per-lane and two-legs-per-lane mappings; with the default one-leg-per-lane mapping the
-// whole walking env-step is ONE launch: qg_step_kernel_quad<.., WALK = true> (qg_kernels.hip) runs the estimator update of
+// whole walking env-step is ONE launch: qg_step_kernel_quad<.., WALK = true> (qg_kernel_quad.hip) runs the estimator update of
 // its three channels per lane in the prologue and the reward in the epilogue, through the same device functions
 // (qg_walk_dev.h).
 // The estimator's amplitude is max - min over a sliding window of 2 / (min_freq * dt) samples (250 at frame_skip

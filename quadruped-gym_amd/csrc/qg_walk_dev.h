@@ -1,5 +1,5 @@
 // qg_walk_dev.h -- per-env device functions of the walking task layer, shared by the stand-alone task kernels (qg_walk.hip)
-// and by the fused walking variant of the step kernel (qg_kernels.hip, qg_step_kernel_quad<.., WALK = true>): the control-signal
+// and by the fused walking variant of the step kernel (qg_kernel_quad.hip, qg_step_kernel_quad<.., WALK = true>): the control-signal
 // frequency / amplitude estimator (src/envs/math_utils.py:11-158), the command sampler (src/envs/control_inputs.py:74-115) and
 // the eleven reward terms of input_control_reward (src/envs/walking_quad.py:352-428).
 #pragma once

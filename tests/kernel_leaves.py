@@ -1,6 +1,7 @@
 """Every step-kernel instantiation a handle can launch, and how a test reaches it.
 
-``LEAVES`` holds one row per per-launch leaf of ``select_step`` (quadruped-gym_amd/csrc/qg_capi.hip), keyed by the name
+``LEAVES`` holds one row per per-launch leaf of the ``select_step_*`` functions (one per mapping, in the step-kernel unit that holds the
+mapping's kernels: ``STEP_UNITS``), keyed by the name
 ``BatchedSim.last_step_kernel`` reports: tests/test_kernel_leaves_gpu.py steps each one against the f64 oracle.  The many-env-steps
 forms (``launch_*_multi``) are pinned bit for bit to a per-launch leaf by a case of tests/test_resident_gpu.py: ``MULTI_TWINS``
 names that case and the leaf.  tests/test_kernel_census.py parses the launch sites and checks that both tables list exactly the
@@ -11,7 +12,9 @@ from dataclasses import dataclass
 from itertools import product
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CAPI = os.path.join(ROOT, "quadruped-gym_amd", "csrc", "qg_capi.hip")
+CSRC = os.path.join(ROOT, "quadruped-gym_amd", "csrc")
+# the translation units that hold the step kernels' launch sites: one per kernel family (the census reads them joined)
+STEP_UNITS = tuple(os.path.join(CSRC, f) for f in ("qg_kernel_link.hip", "qg_kernel_quad.hip", "qg_kernel_pair.hip"))
 
 # envs per wave of each mapping (QGK_LINK_ENVS / QGK_QUAD_ENVS / QGK_PAIR_ENVS): AUTO's boundaries are "one wave per SIMD" sizes
 LINK_ENVS, QUAD_ENVS, PAIR_ENVS = 4, 16, 32
@@ -153,18 +156,18 @@ def launcher_parameters(src):
     return out
 
 
-def _function_body(src, signature):
-    start = src.index(signature)
-    end = src.index("\n}\n", start)
-    return src[start:end]
+def _selector_bodies(src):
+    """the bodies of the per-mapping selectors: `static void select_step_link(` .. and `void qg_select_step_pair(` .."""
+    for m in re.finditer(r"void (?:qg_)?select_step_\w+\(", src):
+        yield src[m.start():src.index("\n}\n", m.start())]
 
 
 def launched_instantiations(src):
-    """Every step-kernel name the launch sites can produce: the calls in select_step and every launch_*_multi call, defaults filled
-    in from the launcher declarations, DYN expanded to {0, 1}."""
+    """Every step-kernel name the launch sites can produce: the calls in the select_step_* functions and every launch_*_multi call,
+    defaults filled in from the launcher declarations, DYN expanded to {0, 1}."""
     params = launcher_parameters(src)
-    sites = [(m.group(1), m.group(2)) for m in
-             re.finditer(r"launch_(lane|link|quad|pair)<([^<>]*)>\s*\(", _function_body(src, "static void select_step("))]
+    sites = [(m.group(1), m.group(2)) for body in _selector_bodies(src)
+             for m in re.finditer(r"launch_(lane|link|quad|pair)<([^<>]*)>\s*\(", body)]
     sites += [(m.group(1), m.group(2)) for m in re.finditer(r"launch_((?:link|quad|pair)_multi)<([^<>]*)>\s*\(", src)]
     names = set()
     for fam, args in sites:

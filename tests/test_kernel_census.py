@@ -1,4 +1,4 @@
-"""The leaf matrix is complete (no GPU): every step-kernel instantiation the launch sites of qg_capi.hip can produce has a row in
+"""The leaf matrix is complete (no GPU): every step-kernel instantiation the launch sites of the step-kernel units can produce has a row in
 tests/kernel_leaves.py -- an oracle case in tests/test_kernel_leaves_gpu.py, or a bit-identical twin case in tests/test_resident_gpu.py
 for the many-env-steps forms -- and the tables list nothing the source cannot launch."""
 import os
@@ -13,7 +13,7 @@ import kernel_leaves as K  # noqa: E402
 
 @pytest.fixture(scope="module")
 def src():
-    return open(K.CAPI).read()
+    return "\n".join(open(p).read() for p in K.STEP_UNITS)
 
 
 def test_launch_sites_equal_the_matrix(src):
@@ -29,9 +29,9 @@ def test_census_parses_defaults_and_dyn(src):
     assert [p for p, _ in params["quad"]] == ["WPE", "BAKED", "WALK", "WAVES", "PO", "HELP", "DYN"]
     assert [d for _, d in params["quad"]][4:] == [0, 0, 0]
     assert set(params) == {"lane", "link", "quad", "pair", "link_multi", "quad_multi", "pair_multi"}
-    # a leaf added to select_step without a row is caught
-    body_end = src.index("static void select_step(")
-    extra = src[:body_end] + src[body_end:].replace("        break;\n", "        launch_quad<2, true, false, 1>(L);\n        break;\n", 1)
+    # a leaf added to a selector without a row is caught
+    body_end = src.index("static void select_step_quad(")
+    extra = src[:body_end] + src[body_end:].replace("\n}\n", "\n    launch_quad<2, true, false, 1>(L);\n}\n", 1)
     assert K.launched_instantiations(extra) - set(K.LEAVES) - set(K.MULTI_TWINS) == {"qg_step_kernel_quad<2,1,0,1,0,0,0>"}
 
 
@@ -56,7 +56,7 @@ def test_step_shell_exists_once():
     """The shell of an env-step (state load / store, reward, terminations, auto-reset, tile copy-out) is text of qg_step_shell.h that the
     step kernels expand, not a copy per kernel: each fragment occurs once in the .hip / .h / .inc files of csrc/.  A copy that stays
     for the listing's sake (tools/asm_diff.py) is named here with its reason, and the count is what the tree has."""
-    csrc = os.path.dirname(K.CAPI)
+    csrc = K.CSRC
     text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".inc"))}
     assert "qg_step_shell.h" in text
 
@@ -76,11 +76,11 @@ def test_step_shell_exists_once():
     assert files("lk_st(P.st.qpos, 3 * n4") == []
     # ... and the one place that spells the plain index out is not a copy of it: qg_reset_kernel has no BaseState and hands
     # st.qpos[3 * n + env] .. [6 * n + env] to QG_RESET_HEADING as the heading's destination
-    assert files(".qpos[3 * n") == ["qg_kernels.hip"]
+    assert files(".qpos[3 * n") == ["qg_capi.hip"]
     assert all("QG_RESET_HEADING(" in ln for _, ln in sites(".qpos[3 * n"))
     # the bad-state termination: the shell's, and the one-env-per-lane kernel's own (it adds the base first and its 24 hinge values
     # one by one from LDS -- another order of the additions, so another rounding: not the shell's probe)
-    assert files("state_is_bad(probe)") == ["qg_kernels.hip", "qg_step_shell.h"]
+    assert files("state_is_bad(probe)") == ["qg_kernel_quad.hip", "qg_step_shell.h"]
     # tile copy-out multipliers, model staging, task snapshot, reward components
     for needle in ("const unsigned magic =", "reinterpret_cast<float *>(&smodel)", "Tk = {T->frame_skip", "P.comps[(size_t)env * 3 + 0]"):
         assert files(needle) == shell, needle

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Instruction histogram of one kernel of a device listing (make -C quadruped-gym_amd/csrc asm writes one per translation unit,
-/tmp/qg_asm/<unit>-hip-amdgcn-amd-amdhsa-gfx950.s; the step kernels are in qg_capi's).
+/tmp/qg_asm/<unit>-hip-amdgcn-amd-amdhsa-gfx950.s; the step kernels are in qg_kernel_link's, qg_kernel_quad's and
+qg_kernel_pair's, one family each).
 
 usage: asm_hist.py <listing.s> <substring of the mangled kernel name> [--loop]
 

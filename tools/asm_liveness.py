@@ -1,5 +1,5 @@
 """Live-VGPR profile of one kernel's main loop from the compiler's assembly listing (make -C quadruped-gym_amd/csrc asm writes one
-per translation unit, /tmp/qg_asm/<unit>-hip-amdgcn-amd-amdhsa-gfx950.s; the step kernels are in qg_capi's).  Approximate: the loop body is treated as straight-line code (forward branches
+per translation unit, /tmp/qg_asm/<unit>-hip-amdgcn-amd-amdhsa-gfx950.s; the step kernels are in qg_kernel_link's, qg_kernel_quad's and qg_kernel_pair's).  Approximate: the loop body is treated as straight-line code (forward branches
 ignored), the loop-carried set is found by iterating.  Prints the live count every `stride` instructions with the instruction
 there, and the peak -- enough to see WHERE in the substep the register pressure sits.
 usage: python tools/asm_liveness.py <listing.s> <kernel-symbol-substring> [stride]"""

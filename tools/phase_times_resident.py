@@ -1,5 +1,5 @@
 """Where an env-step of the RESIDENT kernel goes in closed loop (one ring per env-step), from inside the kernels: the first wave of the
-resident grid and the ring kernel stamp the 100 MHz clock (QG_MARK in qg_kernel_resident.hip; development build, tools/phase_times.sh).
+resident grid and the ring kernel stamp the 100 MHz clock (QG_MARK in qg_kernel_resident.hip, part of the qg_kernel_link unit; development build, tools/phase_times.sh).
 usage (GPU box): QUADGYM_LIB=tools/lib_phase.so python tools/phase_times_resident.py [n_envs] [frame_skip]"""
 import ctypes as C
 import os

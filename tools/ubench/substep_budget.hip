@@ -1,8 +1,7 @@
 // Static VALU budget of the pieces of one substep (baked one-leg-per-lane form): each piece in its own probe kernel.
 // build + count (from quadruped-gym_amd/csrc): hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffinite-math-only -fno-signed-zeros -fno-slp-vectorize \
 //   -mllvm -amdgpu-sched-strategy=max-ilp --cuda-device-only -I. -S -o /tmp/budget.s ../../tools/ubench/substep_budget.hip ; count v_* per kernel
-#include "qg_device.h"
-#include "qg_kernels.hip"
+#include "qg_step_dev.h"     // (the shared device code of the step-kernel units; it includes the HIP runtime and qg_device.h)
 // isolated pieces of one substep (baked quad form): static instruction budget of each
 #define LD(i) in[(i) * 64 + threadIdx.x]
 __device__ __forceinline__ BaseState ldB(const float *in) { BaseState B; B.pw = v3(LD(0), LD(1), LD(2)); B.qw = LD(3); B.qx = LD(4); B.qy = LD(5); B.qz = LD(6); B.vw = v3(LD(7), LD(8), LD(9)); B.wb = v3(LD(10), LD(11), LD(12)); return B; }
