@@ -3,26 +3,54 @@ the HIP stream of a call, and the checks of the torch tensors whose pointers are
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 from . import _abi
 
 
 class Handle:
     """A subclass names the ABI's destroy function in ``_destroy``, sets ``device`` and stores what its create call returned in
-    ``_h``."""
+    ``_h``.  A handle bound to another one (a task layer to its simulator) passes it as ``parent``: the C side's destroy of the child
+    dereferences the parent, so a parent is never destroyed while a child is open.  The child holds the parent (dropping references
+    destroys the child first), the parent knows its children weakly (``close()`` closes them first) and counts the open ones."""
 
     _destroy: str = ""
     _h = None
+    _parent = None
+    _children = ()
+    _open_children = 0
+    _close_pending = False
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, parent=None):
         self._lib = _abi.load_library()
         self.device = int(device)
+        if parent is not None:
+            if not parent._h:
+                raise ValueError(f"{type(parent).__name__} is closed: nothing can be bound to it")
+            parent._children = [r for r in parent._children if r() is not None] + [weakref.ref(self)]
+            parent._open_children += 1
+            self._parent = parent
 
     # -- lifetime ---------------------------------------------------------------------------
     def close(self):
+        children, self._children = self._children, ()
+        for ref in reversed(children):                      # most recently bound first
+            child = ref()
+            if child is not None:
+                child.close()
+        if self._open_children:
+            # only when the cycle collector finalises a parent before its children: it clears the weak references to them before it
+            # runs any finaliser.  The last child to close comes back here.
+            self._close_pending = True
+            return
         if getattr(self, "_h", None):
             getattr(self._lib, self._destroy)(self._h)
             self._h = None
+        parent, self._parent = self._parent, None
+        if parent is not None:
+            parent._open_children -= 1
+            if parent._close_pending:
+                parent.close()
 
     def __del__(self):
         try:

@@ -142,7 +142,92 @@ class CallableDataView:
         self._time[:] = nstep.astype(np.float64) * timestep
 
 
-class QuadrupedVecEnv(_VecEnvBase):
+class BatchedEnvBase:
+    """What the batched envs share: the simulator with its randomisations, the spaces, and the part of SB3's VecEnv protocol that
+    does not depend on the task.  A mixin AHEAD of SB3's ``VecEnv`` in the bases, so that it supplies that class's abstract methods.
+    Public facts for wrappers: ``device``, ``obs_dim`` and ``packed_step`` (``step_tensor`` returns packed ``[N, obs_dim + 2]`` rows
+    instead of filling separate obs / reward / done buffers)."""
+
+    packed_step = False
+    _infos_mode_error = "infos_mode must be 'lazy' or 'finished'"
+
+    def _init_common(self, num_envs, loaded_model, max_time, frame_skip, infos_mode, seed):
+        """``loaded_model``: what ``load_model(model_path)`` returned.  Returns its ``QgModel``."""
+        if infos_mode not in ("lazy", "finished"):
+            raise ValueError(self._infos_mode_error)
+        self.infos_mode = infos_mode
+        qg_model, layout = loaded_model
+        self.model = ModelView(qg_model, layout)
+        self.num_envs = int(num_envs)
+        self.frame_skip, self.max_time = int(frame_skip), float(max_time)
+        self._seed = int(seed)
+        self._actions = None
+        self.render_mode = None
+        return qg_model
+
+    def _make_sim(self, task, qg_model, device, env_index_base, dynamics_randomization, push_randomization, sim_class=BatchedSim):
+        self._sim = sim_class(self.num_envs, device=device, model=qg_model, task=task, env_index_base=env_index_base)
+        self.device = self._sim.device
+        if dynamics_randomization is not None:
+            self._sim.set_dynamics_range(dynamics_randomization)
+        if push_randomization is not None:          # random pushes on the base (seconds -> env-steps of timestep x frame_skip)
+            self._sim.set_push_schedule(_abi.push_schedule_steps(push_randomization, qg_model.timestep * self.frame_skip))
+
+    def _init_spaces(self, obs_dim):
+        self.obs_dim = int(obs_dim)
+        self.action_space = Box(low=-1.0, high=1.0, shape=(12,), dtype=np.float32)
+        self.observation_space = Box(low=-np.inf, high=np.inf, shape=(self.obs_dim,), dtype=np.float32)
+        if HAVE_SB3:  # pragma: no cover - stable_baselines3 is absent from the build image
+            _VecEnvBase.__init__(self, self.num_envs, self.observation_space, self.action_space)
+
+    def dynamics(self):
+        """``[num_envs, 11]`` f32: each env's dynamics row (columns ``_abi.DYN_COLUMNS``; identity rows without randomisation)."""
+        return self._sim.get_dynamics()
+
+    def set_external_wrench(self, rows, indices=None):
+        """MuJoCo's ``data.xfrc_applied`` for the envs ``indices`` (all: None): ``[len, 13, 6]`` world-frame force and torque per body."""
+        self._sim.set_external_wrench_of(rows, indices)
+
+    def external_wrench(self):
+        """``[num_envs, 13, 6]`` f32: the external wrench rows (without the pushes of ``push_randomization``)."""
+        return self._sim.get_external_wrench()
+
+    def step_async(self, actions):
+        self._actions = np.ascontiguousarray(actions, dtype=np.float32)
+
+    def step(self, actions):
+        self.step_async(actions)
+        return self.step_wait()
+
+    def close(self):
+        """Destroys the simulator and, before it, every task layer bound to it (``Handle.close``)."""
+        if getattr(self, "_sim", None) is not None:
+            self._sim.close()
+            self._sim = None
+
+    def seed(self, seed=None):
+        self._seed = 0 if seed is None else int(seed)
+        return [self._seed + i for i in range(self.num_envs)]
+
+    def _indices(self, indices):
+        return range(self.num_envs) if indices is None else ([indices] if isinstance(indices, int) else indices)
+
+    def get_attr(self, attr_name, indices=None):
+        return [getattr(self, attr_name) for _ in self._indices(indices)]
+
+    def set_attr(self, attr_name, value, indices=None):
+        setattr(self, attr_name, value)
+
+    def env_method(self, method_name, *args, indices=None, **kwargs):
+        return [getattr(self, method_name)(*args, **kwargs) for _ in self._indices(indices)]
+
+    def env_is_wrapped(self, wrapper_class, indices=None):
+        return [False for _ in self._indices(indices)]
+
+
+class QuadrupedVecEnv(BatchedEnvBase, _VecEnvBase):
+    packed_step = True
+
     def __init__(self, num_envs: int, model_path: str | None = "builtin", max_time: float = 10.0, frame_skip: int = 4,
                  reward_fns: dict | None = None, termination_fns: dict | None = None, use_default_termination: bool = True,
                  obs_mode: int = _abi.OBS_FULL, random_init: bool = False, device: int = 0, env_index_base: int = 0,
@@ -150,14 +235,7 @@ class QuadrupedVecEnv(_VecEnvBase):
                  push_randomization: dict | None = None):
         if callable_mode not in ("per_env", "batched"):
             raise ValueError("callable_mode must be 'per_env' or 'batched'")
-        if infos_mode not in ("lazy", "finished"):
-            raise ValueError("infos_mode must be 'lazy' or 'finished'")
-        self.infos_mode = infos_mode
-        qg_model, layout = load_model(model_path)
-        self.model = ModelView(qg_model, layout)
-        self.num_envs = int(num_envs)
-        self.frame_skip = int(frame_skip)
-        self.max_time = float(max_time)
+        qg_model = self._init_common(num_envs, load_model(model_path), max_time, frame_skip, infos_mode, seed)
         self.callable_mode = callable_mode
         # the reference's dicts (quadruped.py:97-100): mutable, looked at again at every step
         self.reward_fns = dict(reward_fns) if reward_fns is not None else {"default": self._default_reward}
@@ -169,22 +247,11 @@ class QuadrupedVecEnv(_VecEnvBase):
             self._reset_flags |= _abi.RESET_DYNAMICS
         self._obs_mode = obs_mode
         task, self._host_rewards, self._host_terms = self._plan()
-        self._sim = BatchedSim(self.num_envs, device=device, model=qg_model, task=task, env_index_base=env_index_base)
-        if dynamics_randomization is not None:
-            self._sim.set_dynamics_range(dynamics_randomization)
-        if push_randomization is not None:          # random pushes on the base (seconds -> env-steps of timestep x frame_skip)
-            self._sim.set_push_schedule(_abi.push_schedule_steps(push_randomization, qg_model.timestep * self.frame_skip))
+        self._make_sim(task, qg_model, device, env_index_base, dynamics_randomization, push_randomization)
         self._task_key = self._key(task)
-        self._seed = int(seed)
-        self.obs_dim = self._sim.obs_dim
-        self.action_space = Box(low=-1.0, high=1.0, shape=(12,), dtype=np.float32)
-        self.observation_space = Box(low=-np.inf, high=np.inf, shape=(self.obs_dim,), dtype=np.float32)
-        if HAVE_SB3:  # pragma: no cover
-            _VecEnvBase.__init__(self, self.num_envs, self.observation_space, self.action_space)
+        self._init_spaces(self._sim.obs_dim)
         self.data = CallableDataView(self.num_envs, self.obs_dim)
         self._snapshot = BatchedData(self.num_envs, self.obs_dim)
-        self._actions = None
-        self.render_mode = None
 
     # -- the reference's defaults (quadruped.py:145-151): markers here, evaluated on the device ---------------------------
     def _default_reward(self):
@@ -258,21 +325,6 @@ class QuadrupedVecEnv(_VecEnvBase):
         self._sim.reset(seed=self._seed, flags=self._reset_flags)
         return np.zeros((self.num_envs, self.obs_dim), np.float32)      # the reference's first obs is all zeros
 
-    def step_async(self, actions):
-        self._actions = np.asarray(actions, dtype=np.float32)
-
-    def dynamics(self):
-        """``[num_envs, 11]`` f32: each env's dynamics row (columns ``_abi.DYN_COLUMNS``; identity rows without randomisation)."""
-        return self._sim.get_dynamics()
-
-    def set_external_wrench(self, rows, indices=None):
-        """MuJoCo's ``data.xfrc_applied`` for the envs ``indices`` (all: None): ``[len, 13, 6]`` world-frame force and torque per body."""
-        self._sim.set_external_wrench_of(rows, indices)
-
-    def external_wrench(self):
-        """``[num_envs, 13, 6]`` f32: the external wrench rows (without the pushes of ``push_randomization``)."""
-        return self._sim.get_external_wrench()
-
     def _eval_callables(self, obs, state=None):
         """Host evaluation of the Python callables over ``self.data``; returns (components {name: [N]}, done [N])."""
         n = self.num_envs
@@ -342,34 +394,6 @@ class QuadrupedVecEnv(_VecEnvBase):
             obs = obs.copy()
             obs[done] = 0.0                                 # envs that finished were reset: their next obs is the reset obs
         return obs, rew, done, infos
-
-    def step(self, actions):
-        self.step_async(actions)
-        return self.step_wait()
-
-    def close(self):
-        if getattr(self, "_sim", None) is not None:
-            self._sim.close()
-            self._sim = None
-
-    def seed(self, seed=None):
-        self._seed = 0 if seed is None else int(seed)
-        return [self._seed + i for i in range(self.num_envs)]
-
-    def get_attr(self, attr_name, indices=None):
-        idx = range(self.num_envs) if indices is None else ([indices] if isinstance(indices, int) else indices)
-        return [getattr(self, attr_name) for _ in idx]
-
-    def set_attr(self, attr_name, value, indices=None):
-        setattr(self, attr_name, value)
-
-    def env_method(self, method_name, *args, indices=None, **kwargs):
-        idx = range(self.num_envs) if indices is None else ([indices] if isinstance(indices, int) else indices)
-        return [getattr(self, method_name)(*args, **kwargs) for _ in idx]
-
-    def env_is_wrapped(self, wrapper_class, indices=None):
-        idx = range(self.num_envs) if indices is None else ([indices] if isinstance(indices, int) else indices)
-        return [False for _ in idx]
 
     # -- zero-copy path for policies that live on the GPU --------------------------------------------------
     def step_tensor(self, actions, packed=None, stream=None):

@@ -5,28 +5,18 @@ command, settling-time action mask, control-signal frequency / amplitude estimat
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from .. import _abi
-from .._abi import NWALKREWARD, QgWalkParams, check
 from ..model.loader import load_model
 from ..sim import BatchedSim
-from .quadruped import ModelView
+from ..task_layers import ObsPack, WalkLayer, default_walk_params  # noqa: F401  (default_walk_params: re-exported)
 from .infos import LazyInfos, finished_only_infos
-from .vec_env import HAVE_SB3, _VecEnvBase
-from .spaces import Box
+from .vec_env import BatchedEnvBase, _VecEnvBase
 
 REWARD_KEYS = ["alive_bonus", "control_cost", "progress_direction_reward_local", "progress_speed_cost_local",
                "heading_reward", "orientation_reward", "body_height_cost", "joint_posture_cost",
                "control_amplitude_cost", "control_frequency_cost", "diff_ideal_position_cost"]   # walking_quad.py:332-351
-
-
-def default_walk_params() -> QgWalkParams:
-    p = QgWalkParams()
-    check(_abi.load_library().qg_walk_default_params(C.byref(p)), "qg_walk_default_params")
-    return p
 
 
 def sample_command(options=None, uniform=None):
@@ -59,25 +49,20 @@ def _component_infos(n, comps, extra, mode="lazy"):
     return LazyInfos(n, make)
 
 
-class WalkingQuadrupedVecEnv(_VecEnvBase):      # SB3's VecEnv where that package is importable (what `PPO(..., env)` checks for), else object
+class WalkingQuadrupedVecEnv(BatchedEnvBase, _VecEnvBase):      # SB3's VecEnv where importable (what `PPO(..., env)` checks for), else object
     """N walking robots; SB3 VecEnv calling convention (replaces ``SubprocVecEnv([make_env]*N)`` at
     ``src/train_quadruped.py:50``).  ``infos[i]`` is the reward-component dict the reference returns as
     ``info`` (``walking_quad.py:146-148,419``), which ``RewardCallback`` reads (``train_quadruped.py:86-97``)."""
 
     reward_keys = REWARD_KEYS
+    _infos_mode_error = ("infos_mode must be 'lazy' (every env's component dict, built when touched) or 'finished' (content "
+                         "for the envs that finished only; `last_components` holds every env's components as one array)")
 
     def __init__(self, num_envs, settling_time=0, random_controls=False, random_init=False, reset_options=None,
                  model_path="builtin", max_time=10.0, frame_skip=4, device=0, env_index_base=0, seed=0, walk_params=None,
                  device_commands=False, auto_reset=True, use_default_termination=True, infos_mode="lazy", nan_direction=True,
                  dynamics_randomization=None, push_randomization=None):
-        if infos_mode not in ("lazy", "finished"):
-            raise ValueError("infos_mode must be 'lazy' (every env's component dict, built when touched) or 'finished' (content "
-                             "for the envs that finished only; `last_components` holds every env's components as one array)")
-        self.infos_mode = infos_mode
-        qg_model, layout = load_model(model_path)
-        self.model = ModelView(qg_model, layout)
-        self.num_envs = int(num_envs)
-        self.frame_skip, self.max_time = int(frame_skip), float(max_time)
+        qg_model = self._init_common(num_envs, load_model(model_path), max_time, frame_skip, infos_mode, seed)
         self.random_controls, self.random_init, self.reset_options = random_controls, random_init, reset_options
         task = _abi.default_task()
         task.frame_skip = self.frame_skip
@@ -92,12 +77,7 @@ class WalkingQuadrupedVecEnv(_VecEnvBase):      # SB3's VecEnv where that packag
         task.reset_flags = _abi.RESET_RANDOM_YAW if random_init else 0     # walking_quad.py:68-75,118-119
         if dynamics_randomization is not None:      # a new dynamics row per env at every reset and auto-reset
             task.reset_flags |= _abi.RESET_DYNAMICS
-        self._sim = BatchedSim(self.num_envs, device=device, model=qg_model, task=task, env_index_base=env_index_base)
-        if dynamics_randomization is not None:
-            self._sim.set_dynamics_range(dynamics_randomization)
-        if push_randomization is not None:          # random pushes on the base (seconds -> env-steps of timestep x frame_skip)
-            self._sim.set_push_schedule(_abi.push_schedule_steps(push_randomization, qg_model.timestep * self.frame_skip))
-        self._lib = _abi.load_library()
+        self._make_sim(task, qg_model, device, env_index_base, dynamics_randomization, push_randomization, BatchedSim)
         self.params = walk_params if walk_params is not None else default_walk_params()
         self.params.settling_time = float(settling_time)
         # nan_direction=True is the reference: unit() of an exactly zero local velocity (or command) is NaN and so are the direction
@@ -106,96 +86,56 @@ class WalkingQuadrupedVecEnv(_VecEnvBase):      # SB3's VecEnv where that packag
         self.nan_direction = bool(nan_direction)
         if not self.nan_direction:
             self.params.unit_zero = 1
-        h = C.c_void_p()
-        check(self._lib.qg_walk_create(self._sim._h, C.byref(self.params), C.byref(h)), "qg_walk_create")
-        self._w = h
-        self._seed = int(seed)
+        self._walk = WalkLayer(self._sim, self.params)
         self._flags = task.reset_flags
         # random_controls (walking_quad.py:121-122).  device_commands=False: commands are redrawn on the host with
         # np.random.uniform in the reference's order (VelocityHeadingControls.sample); True: on the GPU, inside reset and
         # the step's auto-reset, from the env's own counter-based stream -- rollouts through step_tensor never touch the host.
         self.device_commands = bool(device_commands) and bool(random_controls)
         if self.device_commands:
-            sampler = _abi.QgCommandSampler.from_options(reset_options)
-            check(self._lib.qg_walk_set_command_sampler(self._w, C.byref(sampler)), "qg_walk_set_command_sampler")
-        self.action_space = Box(low=-1.0, high=1.0, shape=(12,), dtype=np.float32)
-        self.observation_space = Box(low=-np.inf, high=np.inf, shape=(33,), dtype=np.float32)
-        if HAVE_SB3:  # pragma: no cover - stable_baselines3 is absent from the build image
-            _VecEnvBase.__init__(self, self.num_envs, self.observation_space, self.action_space)
+            self._walk.set_command_sampler(_abi.QgCommandSampler.from_options(reset_options))
+        self._init_spaces(self._walk.obs_dim)
         self.velocity = np.zeros((self.num_envs, 2), np.float32)
         self.heading = np.zeros((self.num_envs, 2), np.float32)
         self.dt = qg_model.timestep * self.frame_skip
-        self.render_mode = None
 
     # -- commands ---------------------------------------------------------------------------------
     def set_commands(self, velocity_xy, heading_xy):
         self.velocity[:] = np.asarray(velocity_xy, np.float32).reshape(self.num_envs, 2)
         self.heading[:] = np.asarray(heading_xy, np.float32).reshape(self.num_envs, 2)
-        check(self._lib.qg_walk_set_commands(self._w, self.velocity.ctypes.data, self.heading.ctypes.data), "qg_walk_set_commands")
+        self._walk.set_commands(self.velocity, self.heading)
 
     def commands(self):
         """``(velocity_xy, heading_xy)`` as they stand on the device, ``[num_envs, 2]`` each."""
-        check(self._lib.qg_walk_get_commands(self._w, self.velocity.ctypes.data, self.heading.ctypes.data), "qg_walk_get_commands")
+        self._walk.get_commands(self.velocity, self.heading)
         return self.velocity, self.heading
 
-    def dynamics(self):
-        """``[num_envs, 11]`` f32: each env's dynamics row (columns ``_abi.DYN_COLUMNS``; identity rows without randomisation)."""
-        return self._sim.get_dynamics()
-
-    def set_external_wrench(self, rows, indices=None):
-        """MuJoCo's ``data.xfrc_applied`` for the envs ``indices`` (all: None): ``[len, 13, 6]`` world-frame force and torque per body."""
-        self._sim.set_external_wrench_of(rows, indices)
-
-    def external_wrench(self):
-        """``[num_envs, 13, 6]`` f32: the external wrench rows (without the pushes of ``push_randomization``)."""
-        return self._sim.get_external_wrench()
+    def estimates(self):
+        return self._walk.estimates()
 
     # -- checkpoint / resume (SURVEY section 5; the reference resumes the policy only, train_quadruped.py:114-141) -------------------
     def snapshot(self):
         """Everything this env keeps per robot -- physics state, reset streams, the walking layer's task state (estimator included)
         and, for the partially observable env, the filter estimate and the frame ring -- as a ``dict`` of NumPy arrays.
         ``restore(snapshot)`` on an env of the same shape continues bit for bit."""
-        snap = {"sim": self._sim.snapshot()}
-        blob = np.empty(self._blob_bytes(self._lib.qg_walk_state_bytes, self._w, "qg_walk_state_bytes"), np.uint8)
-        check(self._lib.qg_walk_get_state(self._w, blob.ctypes.data), "qg_walk_get_state")
-        snap["walk"] = blob
-        if getattr(self, "_po", None):
-            pblob = np.empty(self._blob_bytes(self._lib.qg_po_state_bytes, self._po, "qg_po_state_bytes"), np.uint8)
-            check(self._lib.qg_po_get_state(self._po, pblob.ctypes.data), "qg_po_get_state")
-            snap["po"] = pblob
-        snap["velocity"], snap["heading"] = self.velocity.copy(), self.heading.copy()
-        return snap
+        return {"sim": self._sim.snapshot(), "walk": self._walk.state(), "velocity": self.velocity.copy(), "heading": self.heading.copy()}
 
-    def _blob_bytes(self, fn, handle, what):
-        nbytes = int(fn(handle))
-        if nbytes <= 0:                   # the C side reports errors as small negative numbers
-            check(nbytes if nbytes < 0 else -1, what)
-        return nbytes
-
-    def restore(self, snap):
-        """All-or-nothing: every part of the snapshot is checked against this env BEFORE anything is written.  Continues bit for
-        bit with ``device_commands=True`` (or fixed commands); with host-side command sampling the commands an auto-reset re-draws
-        come from NumPy's global generator, which a snapshot does not hold."""
-        po = getattr(self, "_po", None)
-        blob = np.ascontiguousarray(snap["walk"], dtype=np.uint8)
-        if blob.size != self._blob_bytes(self._lib.qg_walk_state_bytes, self._w, "qg_walk_state_bytes"):
-            raise ValueError("the snapshot was taken from an env of another shape (num_envs / estimator window)")
-        pblob = None
-        if po:
-            if "po" not in snap:
-                raise ValueError("the snapshot holds no observation-pack state (it was taken from an env without one)")
-            pblob = np.ascontiguousarray(snap["po"], dtype=np.uint8)
-            if pblob.size != self._blob_bytes(self._lib.qg_po_state_bytes, po, "qg_po_state_bytes"):
-                raise ValueError("the snapshot was taken from an env of another shape (num_envs / obs_window)")
+    def _check_snapshot(self, snap):
+        """Raises unless every part of ``snap`` fits this env; writes nothing."""
+        self._walk.check_state(snap["walk"])
         sim = snap["sim"]
         if np.asarray(sim["qpos"]).shape != (self.num_envs, 19) or np.asarray(sim["episode"]).shape != (self.num_envs,):
             raise ValueError("the snapshot was taken from an env of another size")
         if np.asarray(snap["velocity"]).shape != self.velocity.shape or np.asarray(snap["heading"]).shape != self.heading.shape:
             raise ValueError("the snapshot's commands do not fit this env")
-        self._sim.restore(sim)
-        check(self._lib.qg_walk_set_state(self._w, blob.ctypes.data), "qg_walk_set_state")
-        if po:
-            check(self._lib.qg_po_set_state(po, pblob.ctypes.data), "qg_po_set_state")
+
+    def restore(self, snap):
+        """All-or-nothing: every part of the snapshot is checked against this env BEFORE anything is written.  Continues bit for
+        bit with ``device_commands=True`` (or fixed commands); with host-side command sampling the commands an auto-reset re-draws
+        come from NumPy's global generator, which a snapshot does not hold."""
+        self._check_snapshot(snap)
+        self._sim.restore(snap["sim"])
+        self._walk.load_state(snap["walk"])
         self.velocity[:], self.heading[:] = snap["velocity"], snap["heading"]
 
     def _resample(self, idx):
@@ -204,86 +144,49 @@ class WalkingQuadrupedVecEnv(_VecEnvBase):      # SB3's VecEnv where that packag
         for i in idx:
             v, hd = sample_command(self.reset_options)
             self.velocity[i], self.heading[i] = v, hd
-        check(self._lib.qg_walk_set_commands(self._w, self.velocity.ctypes.data, self.heading.ctypes.data), "qg_walk_set_commands")
+        self._walk.set_commands(self.velocity, self.heading)
 
     # -- VecEnv protocol ------------------------------------------------------------------------------
-    def reset(self):
-        check(self._lib.qg_walk_reset(self._w, None, self._seed, self._flags), "qg_walk_reset")
-        if self.random_controls:                              # walking_quad.py:121-122
-            self._resample(range(self.num_envs))
+    _zero_finished = True                 # a finished env's row of the step is its terminal observation; its reset observation is zeros
+
+    def _layer_reset(self):
+        self._walk.reset(self._seed, self._flags)
         return np.zeros((self.num_envs, 33), np.float32)
 
-    def step_async(self, actions):
-        self._actions = np.ascontiguousarray(actions, dtype=np.float32)
+    def _layer_step(self):
+        """``(obs, reward, done, components, terminal)``: ``terminal[i]`` is what env ``i`` ended with, if it finished."""
+        obs, rew, done, comps = self._walk.step(self._actions)
+        return obs, rew, done, comps, obs
+
+    def reset(self):
+        obs = self._layer_reset()
+        if self.random_controls:                              # walking_quad.py:121-122
+            self._resample(range(self.num_envs))
+        return obs
 
     def step_wait(self):
-        n = self.num_envs
-        a = self._actions
-        if a.shape != (n, 12):
-            raise ValueError(f"actions must have shape ({n}, 12)")
-        obs = np.empty((n, 33), np.float32)
-        rew = np.empty(n, np.float32)
-        done = np.empty(n, np.uint8)
-        comps = np.empty((n, NWALKREWARD), np.float32)
-        check(self._lib.qg_walk_step(self._w, a.ctypes.data, obs.ctypes.data, rew.ctypes.data, done.ctypes.data, comps.ctypes.data),
-              "qg_walk_step")
+        obs, rew, done, comps, term = self._layer_step()
         dones = done.astype(bool)
-        extra = {}
-        if self.auto_reset:
-            for i in np.nonzero(dones)[0]:
-                extra[int(i)] = {"terminal_observation": obs[i].copy(), "TimeLimit.truncated": False}
-        infos = _component_infos(n, comps, extra, self.infos_mode)
-        if self.auto_reset and dones.any():
-            obs = obs.copy()
-            obs[dones] = 0.0
+        finished = np.nonzero(dones)[0] if self.auto_reset else ()
+        extra = {int(i): {"terminal_observation": term[i].copy(), "TimeLimit.truncated": False} for i in finished}
+        infos = _component_infos(self.num_envs, comps, extra, self.infos_mode)
+        if len(finished):
+            if self._zero_finished:
+                obs = obs.copy()
+                obs[dones] = 0.0
             if self.random_controls:
-                self._resample(np.nonzero(dones)[0])
+                self._resample(finished)
         self.last_components = comps
         return obs, rew, dones, infos
 
-    def step(self, actions):
-        self.step_async(actions)
-        return self.step_wait()
-
-    def estimates(self):
-        f = np.empty((self.num_envs, 12), np.float32)
-        a = np.empty((self.num_envs, 12), np.float32)
-        ideal = np.empty((self.num_envs, 2), np.float32)
-        check(self._lib.qg_walk_get_estimates(self._w, f.ctypes.data, a.ctypes.data, ideal.ctypes.data), "qg_walk_get_estimates")
-        return f, a, ideal
-
     def step_tensor(self, actions, obs, reward, done, components=None, stream=None):
-        """Zero-copy step on CUDA tensors (float32 ``[N,12]``, ``[N,33]``, ``[N]``, uint8 ``[N]``, ``[N,11]``)."""
-        check(self._lib.qg_walk_step_device(self._w, actions.data_ptr(), obs.data_ptr(), reward.data_ptr(), done.data_ptr(),
-                                            components.data_ptr() if components is not None else None,
-                                            self._sim._stream_ptr(stream)), "qg_walk_step_device")
+        """Zero-copy step on CUDA tensors of this env's device, contiguous: float32 ``[N,12]``, ``[N,33]``, ``[N]``, uint8 (or bool)
+        ``[N]``, ``[N,11]``.  Anything else raises ``ValueError`` before the launch."""
+        self._walk.step_device(actions, obs, reward, done, components, stream)
 
     def close(self):
-        if getattr(self, "_w", None):
-            self._lib.qg_walk_destroy(self._w)
-            self._w = None
-        if getattr(self, "_sim", None) is not None:
-            self._sim.close()
-            self._sim = None
-
-    def seed(self, seed=None):
-        self._seed = 0 if seed is None else int(seed)
-        return [self._seed + i for i in range(self.num_envs)]
-
-    def get_attr(self, attr_name, indices=None):
-        idx = range(self.num_envs) if indices is None else ([indices] if isinstance(indices, int) else indices)
-        return [getattr(self, attr_name) for _ in idx]
-
-    def set_attr(self, attr_name, value, indices=None):
-        setattr(self, attr_name, value)
-
-    def env_method(self, method_name, *args, indices=None, **kwargs):
-        idx = range(self.num_envs) if indices is None else ([indices] if isinstance(indices, int) else indices)
-        return [getattr(self, method_name)(*args, **kwargs) for _ in idx]
-
-    def env_is_wrapped(self, wrapper_class, indices=None):
-        idx = range(self.num_envs) if indices is None else ([indices] if isinstance(indices, int) else indices)
-        return [False for _ in idx]
+        super().close()
+        self._walk = None
 
 
 def _facade_kwargs(kwargs, allowed):
@@ -307,18 +210,15 @@ def _facade_kwargs(kwargs, allowed):
     return args
 
 
-class WalkingQuadrupedEnv:
-    """One walking robot with the reference's constructor (``walking_quad.py:11``): ``settling_time``,
-    ``random_controls``, ``random_init``, ``reset_options`` plus the base env's keyword arguments;
-    ``step`` returns ``(obs, reward, terminated, False, info)`` with ``info`` = the component dict."""
+class _SingleRobotFacade:
+    """The reference's single-robot calling convention over a batched env of one robot without auto-reset (``self._vec``)."""
 
     reward_keys = REWARD_KEYS
 
-    def __init__(self, settling_time=0, random_controls=False, random_init=False, reset_options=None, **kwargs):
-        args = _facade_kwargs(kwargs, {"model_path", "max_time", "frame_skip", "device", "use_default_termination"})
-        self._vec = WalkingQuadrupedVecEnv(1, settling_time, random_controls, random_init, reset_options, auto_reset=False, **args)
-        self.action_space, self.observation_space = self._vec.action_space, self._vec.observation_space
-        self.model = self._vec.model
+    def _wrap(self, vec):
+        self._vec = vec
+        self.action_space, self.observation_space = vec.action_space, vec.observation_space
+        self.model = vec.model
         self.info = {}
 
     def reset(self, seed=None, options=None):
@@ -333,11 +233,21 @@ class WalkingQuadrupedEnv:
         self.info = dict(infos[0])                             # walking_quad.py:146-148: info = the component dict
         return obs[0].astype(np.float64), float(rew[0]), bool(dones[0]), False, self.info
 
-    def set_command(self, velocity_xy, heading_xy):
-        self._vec.set_commands([velocity_xy], [heading_xy])
-
     def close(self):
         self._vec.close()
+
+
+class WalkingQuadrupedEnv(_SingleRobotFacade):
+    """One walking robot with the reference's constructor (``walking_quad.py:11``): ``settling_time``,
+    ``random_controls``, ``random_init``, ``reset_options`` plus the base env's keyword arguments;
+    ``step`` returns ``(obs, reward, terminated, False, info)`` with ``info`` = the component dict."""
+
+    def __init__(self, settling_time=0, random_controls=False, random_init=False, reset_options=None, **kwargs):
+        args = _facade_kwargs(kwargs, {"model_path", "max_time", "frame_skip", "device", "use_default_termination"})
+        self._wrap(WalkingQuadrupedVecEnv(1, settling_time, random_controls, random_init, reset_options, auto_reset=False, **args))
+
+    def set_command(self, velocity_xy, heading_xy):
+        self._vec.set_commands([velocity_xy], [heading_xy])
 
 
 class POWalkingQuadrupedVecEnv(WalkingQuadrupedVecEnv):
@@ -346,92 +256,54 @@ class POWalkingQuadrupedVecEnv(WalkingQuadrupedVecEnv):
     (``:48-56``); rewards and terminations are the walking task's."""
 
     FRAME = 26
+    _zero_finished = False                # a finished env's row of the step already holds its reset stack
 
     def __init__(self, num_envs, obs_window=1, **kwargs):
         super().__init__(num_envs, **kwargs)
-        self.obs_window = int(obs_window)
-        h = C.c_void_p()
-        check(self._lib.qg_po_create(self._w, self.obs_window, C.byref(h)), "qg_po_create")
-        self._po = h
-        self.obs_dim = int(self._lib.qg_po_obs_dim(self._po))
-        self.observation_space = Box(low=-np.inf, high=np.inf, shape=(self.obs_dim,), dtype=np.float32)   # po_walking_quad.py:27
-        if HAVE_SB3:  # pragma: no cover
-            _VecEnvBase.__init__(self, self.num_envs, self.observation_space, self.action_space)
+        self._obs_pack = ObsPack(self._walk, obs_window)
+        self.obs_window = self._obs_pack.obs_window
+        self._init_spaces(self._obs_pack.obs_dim)              # po_walking_quad.py:27
 
-    def reset(self):
-        obs = np.empty((self.num_envs, self.obs_dim), np.float32)
-        check(self._lib.qg_po_reset(self._po, None, self._seed, self._flags, obs.ctypes.data), "qg_po_reset")
-        if self.random_controls:
-            self._resample(range(self.num_envs))
-        return obs
+    def _layer_reset(self):
+        return self._obs_pack.reset(self._seed, self._flags)
 
-    def step_wait(self):
-        n = self.num_envs
-        a = self._actions
-        if a.shape != (n, 12):
-            raise ValueError(f"actions must have shape ({n}, 12)")
-        obs = np.empty((n, self.obs_dim), np.float32)
-        if getattr(self, "_term_buf", None) is None:       # scratch for the library's terminal stacks (rows are copied out below)
-            self._term_buf = np.empty((n, self.obs_dim), np.float32)
-        term = self._term_buf
-        rew = np.empty(n, np.float32)
-        done = np.empty(n, np.uint8)
-        comps = np.empty((n, NWALKREWARD), np.float32)
-        check(self._lib.qg_po_step(self._po, a.ctypes.data, obs.ctypes.data, rew.ctypes.data, done.ctypes.data, comps.ctypes.data,
-                                   term.ctypes.data), "qg_po_step")
-        dones = done.astype(bool)
-        extra = {}
-        if self.auto_reset:
-            for i in np.nonzero(dones)[0]:
-                extra[int(i)] = {"terminal_observation": term[i].copy(), "TimeLimit.truncated": False}
-        infos = _component_infos(n, comps, extra, self.infos_mode)
-        if self.auto_reset and dones.any() and self.random_controls:
-            self._resample(np.nonzero(dones)[0])
-        self.last_components = comps
-        return obs, rew, dones, infos
+    def _layer_step(self):
+        return self._obs_pack.step(self._actions)
+
+    def snapshot(self):
+        snap = super().snapshot()
+        snap["po"] = self._obs_pack.state()
+        return snap
+
+    def _check_snapshot(self, snap):
+        super()._check_snapshot(snap)
+        if "po" not in snap:
+            raise ValueError("the snapshot holds no observation-pack state (it was taken from an env without one)")
+        self._obs_pack.check_state(snap["po"])
+
+    def restore(self, snap):
+        super().restore(snap)             # checks every part, "po" included, before it writes
+        self._obs_pack.load_state(snap["po"])
 
     def step_tensor(self, actions, obs, reward, done, components=None, terminal_obs=None, stream=None):
         """Zero-copy step on CUDA tensors: ``actions`` float32 ``[N,12]`` -> ``obs`` float32 ``[N, 26 * obs_window]`` (the
-        stacked frames; rows of envs that finished already hold the reset stack), ``reward`` ``[N]``, ``done`` uint8
-        ``[N]``, optionally ``components`` ``[N,11]`` and ``terminal_obs`` (the stack each finished env ended with)."""
-        check(self._lib.qg_po_step_device(self._po, actions.data_ptr(), obs.data_ptr(), reward.data_ptr(), done.data_ptr(),
-                                          components.data_ptr() if components is not None else None,
-                                          terminal_obs.data_ptr() if terminal_obs is not None else None,
-                                          self._sim._stream_ptr(stream)), "qg_po_step_device")
+        stacked frames; rows of envs that finished already hold the reset stack), ``reward`` ``[N]``, ``done`` uint8 (or bool)
+        ``[N]``, optionally ``components`` ``[N,11]`` and ``terminal_obs`` (the stack each finished env ended with).  All on this
+        env's device and contiguous; anything else raises ``ValueError`` before the launch."""
+        self._obs_pack.step_device(actions, obs, reward, done, components, terminal_obs, stream)
 
     def close(self):
-        if getattr(self, "_po", None):
-            self._lib.qg_po_destroy(self._po)
-            self._po = None
         super().close()
+        self._obs_pack = None
 
 
-class POWalkingQuadrupedEnv:
+class POWalkingQuadrupedEnv(_SingleRobotFacade):
     """One robot with the reference's constructor ``POWalkingQuadrupedEnv(obs_window=1, **kwargs)``
     (``po_walking_quad.py:10``; ``train_quadruped.py:16-22`` builds it with ``obs_window=10``)."""
-
-    reward_keys = REWARD_KEYS
 
     def __init__(self, obs_window=1, **kwargs):
         args = _facade_kwargs(kwargs, {"settling_time", "random_controls", "random_init", "reset_options", "model_path", "max_time",
                                        "frame_skip", "device", "use_default_termination"})
-        self._vec = POWalkingQuadrupedVecEnv(1, obs_window=obs_window, auto_reset=False, **args)
+        self._wrap(POWalkingQuadrupedVecEnv(1, obs_window=obs_window, auto_reset=False, **args))
         self.obs_window = obs_window
-        self.action_space, self.observation_space = self._vec.action_space, self._vec.observation_space
-        self.model = self._vec.model
-        self.info = {}
 
-    def reset(self, seed=None, options=None):
-        if options is not None:
-            self._vec.reset_options = options
-        obs = self._vec.reset()
-        self.info = {}
-        return obs[0].astype(np.float64), self.info
-
-    def step(self, action):
-        obs, rew, dones, infos = self._vec.step(np.asarray(action, np.float32)[None])
-        self.info = dict(infos[0])
-        return obs[0].astype(np.float64), float(rew[0]), bool(dones[0]), False, self.info
-
-    def close(self):
-        self._vec.close()

@@ -130,11 +130,9 @@ class DeviceVecNormalize:
 
     def __init__(self, venv, **options):
         self.venv = venv
-        obs_dim = int(getattr(venv, "obs_dim", 0) or venv.observation_space.shape[0])
-        self._packed = not hasattr(venv, "_w")              # the plain env steps into packed [N, obs_dim + 2] rows
-        device = options.pop("device", venv._sim.device)
-        self.normalizer = RunningNormalizer(venv.num_envs, obs_dim, device=device, **options)
-        self._obs_dim = obs_dim
+        self._packed = venv.packed_step                     # the plain env steps into packed [N, obs_dim + 2] rows
+        device = options.pop("device", venv.device)
+        self.normalizer = RunningNormalizer(venv.num_envs, venv.obs_dim, device=device, **options)
         self.old_obs = self.old_reward = None
 
     def __getattr__(self, name):                            # only reached for what this class does not define
