@@ -74,8 +74,7 @@ struct qg_comm {
 
 extern "C" int qg_comm_unique_id(uint8_t id[QG_COMM_ID_BYTES]) {
     if (!id) return fail(QG_ERR_ARG, "qg_comm_unique_id: null output");
-    int rc = qg_rccl_load();
-    if (rc != QG_OK) return rc;
+    QG_TRY(qg_rccl_load());
     qg_nccl_unique_id u;
     RCCL_TRY(g_rccl.GetUniqueId(&u));
     memcpy(id, u.internal, QG_COMM_ID_BYTES);
@@ -99,8 +98,7 @@ extern "C" int qg_comm_destroy(qg_comm *c) {
 extern "C" int qg_comm_create(qg_sim *s, int32_t rank, int32_t world, const uint8_t id[QG_COMM_ID_BYTES], qg_comm **out) {
     if (!s || !id || !out || world < 1 || rank < 0 || rank >= world) return fail(QG_ERR_ARG, "qg_comm_create: bad argument");
     *out = nullptr;
-    int rc = qg_rccl_load();
-    if (rc != QG_OK) return rc;
+    QG_TRY(qg_rccl_load());
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     qg_comm *c = new (std::nothrow) qg_comm();
     if (!c) return fail(QG_ERR_ALLOC, "out of host memory");
@@ -140,8 +138,7 @@ extern "C" int qg_comm_rollout(qg_comm *c, const float *const *actions, int32_t 
         const int b = k & 1;
         // the step may overwrite packed[b] only after the gather that read it (two steps ago) has finished
         if (c->consumed_valid[b]) HIP_TRY(hipStreamWaitEvent(s->stream, c->consumed[b], 0), QG_ERR_DEVICE);
-        int rc = qg_launch_step(s, actions[k % n_actions], nullptr, nullptr, nullptr, nullptr, packed[b], s->stream);
-        if (rc != QG_OK) return rc;
+        QG_TRY(qg_launch_step(s, actions[k % n_actions], nullptr, nullptr, nullptr, nullptr, packed[b], s->stream));
         HIP_TRY(hipEventRecord(c->produced[b], s->stream), QG_ERR_DEVICE);
         HIP_TRY(hipStreamWaitEvent(c->comm_stream, c->produced[b], 0), QG_ERR_DEVICE);
         RCCL_TRY(g_rccl.GroupStart());

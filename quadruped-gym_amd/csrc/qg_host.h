@@ -1,13 +1,24 @@
-// qg_host.h -- what every host translation unit of the library shares: the error record, opening a device, and the owner of a
-// handle's device allocations.  Internal: not installed, and nothing in here is exported (libquadgym.map).
+// qg_host.h -- what every host translation unit of the library shares: the error record and the two status-forwarding macros, the
+// finite test, opening a device, and the owner of a handle's device allocations.  Internal: not installed, and nothing in here is exported (libquadgym.map).
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 #include "../../include/quadgym.h"
 
 int qg_fail(int code, const char *fmt, ...);   // records the message for qg_last_error() and returns `code` (qg_capi.hip)
 #define fail qg_fail
+// a status of the library's own that is only forwarded (the message is the callee's)
+#define QG_TRY(expr) do { int rc_ = (expr); if (rc_ != QG_OK) return rc_; } while (0)
+
+// (exponent bits, not std::isfinite: the device pass, which parses the host code too, is compiled with finite-math assumptions and
+// warns about the latter)
+static inline bool qg_finite32(float x) {
+    uint32_t u;
+    memcpy(&u, &x, sizeof u);
+    return (u & 0x7f800000u) != 0x7f800000u;
+}
 
 #ifdef __HIPCC__   // (qg_tables.h, which the plain-C++ generator of the baked table includes, needs the line above only)
 #include <hip/hip_runtime.h>

@@ -856,7 +856,7 @@ template <bool BAKED, bool DOOR> static void launch_link_multi(const qg_sim *s, 
 template <bool DYN> static void select_step_link(const StepLaunch &L) {
     const qg_sim *s = L.s;
     const bool walk = L.walk, po = L.po;
-    if (!s->baked) {
+    if (!qg_sim_baked(s)) {
         if (po) launch_link<true, true, false, false, DYN>(L);
         else if (walk) launch_link<true, false, false, false, DYN>(L);
         else launch_link<false, false, false, false, DYN>(L);
@@ -876,12 +876,12 @@ void qg_select_step_link(const StepLaunch &L, bool dyn) {
 
 void qg_select_seq_link(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
     QG_PHASE_UNIT();
-    if (s->baked) launch_link_multi<true, false>(s, st, P, R);
+    if (qg_sim_baked(s)) launch_link_multi<true, false>(s, st, P, R);
     else launch_link_multi<false, false>(s, st, P, R);
 }
 void qg_select_resident(const qg_sim *s, const KStepArgs &P) {
     QG_PHASE_UNIT();
-    if (s->baked) launch_link_multi<true, true>(s, s->stream, P, s->res.k);
+    if (qg_sim_baked(s)) launch_link_multi<true, true>(s, s->stream, P, s->res.k);
     else launch_link_multi<false, true>(s, s->stream, P, s->res.k);
 }
 void qg_launch_resident_ctl(hipStream_t st, unsigned long long *door, int op) {

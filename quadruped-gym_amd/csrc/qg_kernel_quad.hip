@@ -748,7 +748,7 @@ template <int WPE, bool BAKED> static void launch_quad_multi(const qg_sim *s, hi
 template <bool DYN> static void select_step_quad(const StepLaunch &L) {
     const qg_sim *s = L.s;
     const bool walk = L.walk, po = L.po;
-    if (!s->baked) {
+    if (!qg_sim_baked(s)) {
         // tables in LDS: the 256-register cap spills 888 B per lane and measured 2x slower at every grid size (363 vs 741 us
         // at 262 144 envs), so any other robot runs the one-wave-per-SIMD form throughout
         if (po) launch_quad<1, false, true, 4, true, false, DYN>(L);     // qg_po_fusable(): four-wave workgroups
@@ -778,14 +778,14 @@ void qg_select_step_quad(const StepLaunch &L, bool dyn) {
 }
 void qg_select_step_lane(const StepLaunch &L) {
     QG_PHASE_UNIT();
-    if (L.s->baked) launch_lane<true>(L);
+    if (qg_sim_baked(L.s)) launch_lane<true>(L);
     else launch_lane<false>(L);
 }
 
 // as select_step_quad: the whole register file while the grid is one wave per SIMD
 void qg_select_seq_quad(const qg_sim *s, hipStream_t st, const KStepArgs &P, const KResident &R) {
     QG_PHASE_UNIT();
-    if (!s->baked) launch_quad_multi<1, false>(s, st, P, R);       // (tables in LDS: always the one-wave form)
+    if (!qg_sim_baked(s)) launch_quad_multi<1, false>(s, st, P, R);       // (tables in LDS: always the one-wave form)
     else if (quad_one_wave(s)) launch_quad_multi<1, true>(s, st, P, R);
     else launch_quad_multi<2, true>(s, st, P, R);
 }

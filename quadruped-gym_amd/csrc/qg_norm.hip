@@ -306,9 +306,8 @@ static int norm_upload(qg_norm *p, const double *mean, const double *var, const 
 extern "C" int qg_norm_create(int32_t device_id, const qg_norm_desc *desc, qg_norm **out) {
     if (!out) return fail(QG_ERR_ARG, "qg_norm_create: null output");
     *out = nullptr;
-    int rc = norm_validate(desc);
-    if (rc != QG_OK) return rc;
-    if ((rc = qg_open_device(device_id, nullptr)) != QG_OK) return rc;
+    QG_TRY(norm_validate(desc));
+    QG_TRY(qg_open_device(device_id, nullptr));
     qg_norm *p = new (std::nothrow) qg_norm();
     if (!p) return fail(QG_ERR_ALLOC, "out of host memory");
     memset(p, 0, sizeof *p);
@@ -320,7 +319,7 @@ extern "C" int qg_norm_create(int32_t device_id, const qg_norm_desc *desc, qg_no
         qg_norm_destroy(p);
         return QG_ERR_ALLOC;
     }
-    rc = norm_upload(p, nullptr, nullptr, nullptr, 0.0, 1.0, 1e-4, nullptr);
+    const int rc = norm_upload(p, nullptr, nullptr, nullptr, 0.0, 1.0, 1e-4, nullptr);
     if (rc != QG_OK) {
         qg_norm_destroy(p);
         return rc;
@@ -394,10 +393,7 @@ extern "C" int qg_norm_step_device(qg_norm *p, int32_t n, const float *obs_in, i
     }
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     const hipStream_t st = (hipStream_t)stream;
-    if (training) {
-        int rc = norm_update(p, n, p->desc.norm_obs ? obs_in : nullptr, in_stride, reward_in, reward_in_stride, st);
-        if (rc != QG_OK) return rc;
-    }
+    if (training) QG_TRY(norm_update(p, n, p->desc.norm_obs ? obs_in : nullptr, in_stride, reward_in, reward_in_stride, st));
     return norm_apply(p, n, obs_in, in_stride, obs_out, out_stride, reward_in, reward_in_stride, reward_out, reward_out_stride,
                       reward_in ? done : nullptr, done_kind, done_stride, training != 0, st);
 }

@@ -156,8 +156,7 @@ extern "C" int qg_po_reset(qg_po *p, const uint8_t *mask, uint64_t seed, uint32_
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);   // device-pointer steps may be in flight on a caller's stream
     if (mask) HIP_TRY(hipMemcpy(s->d_mask, mask, (size_t)s->n, hipMemcpyHostToDevice), QG_ERR_DEVICE);
-    int rc = po_reset_kernel(p, mask ? s->d_mask : nullptr, p->d_out);
-    if (rc != QG_OK) return rc;
+    QG_TRY(po_reset_kernel(p, mask ? s->d_mask : nullptr, p->d_out));
     if (obs) HIP_TRY(hipMemcpy(obs, p->d_out, (size_t)s->n * p->kp.window * QG_PO_FRAME * 4, hipMemcpyDeviceToHost), QG_ERR_DEVICE);
     return qg_walk_reset(p->walk, mask, seed, flags);
 }
@@ -178,8 +177,7 @@ extern "C" int qg_po_step_device(qg_po *p, const float *actions, float *obs, flo
         pl.sample = w->kp.cmd_sample ? 1 : 0;
         return qg_walk_step_core(w, actions, nullptr, reward, done, components, stream, true, &pl);
     }
-    int rc = qg_walk_step_core(w, actions, p->d_obs33, reward, done, components, stream, true);
-    if (rc != QG_OK) return rc;
+    QG_TRY(qg_walk_step_core(w, actions, p->d_obs33, reward, done, components, stream, true));
     int blocks = (s->n + QG_PO_ENVS - 1) / QG_PO_ENVS;
     hipLaunchKernelGGL(qg_po_frame_kernel, dim3(blocks), dim3(QG_PO_THREADS), 0, (hipStream_t)stream, p->kp, p->st, s->n, (const float *)p->d_obs33,
                        (const float *)w->st.eff_actions, (const float *)s->st.qpos, w->kp, w->st, (const uint8_t *)done, obs, terminal_obs,
@@ -195,11 +193,10 @@ extern "C" int qg_po_step(qg_po *p, const float *actions, float *obs, float *rew
     const size_t n = (size_t)s->n, width = (size_t)p->kp.window * QG_PO_FRAME;
     const HostOut out[4] = {{obs, p->d_out, n * width * 4}, {reward, w->d_reward, n * 4}, {done, w->d_done, n},
                             {components, w->d_comps, n * QG_NWALKREWARD * 4}};
-    int rc = host_step(s, actions, w->d_actions, out, [&] {
+    QG_TRY(host_step(s, actions, w->d_actions, out, [&] {
         return qg_po_step_device(p, w->d_actions, p->d_out, w->d_reward, w->d_done, components ? w->d_comps : nullptr,
                                  terminal_obs ? p->d_term : nullptr, s->stream);
-    });
-    if (rc != QG_OK) return rc;
+    }));
     if (terminal_obs) {
         // the terminal stacks only exist for envs that finished: the [n][obs_dim] transfer (4.3 MB at 4096 envs and window 10 -- as much
         // as the observation itself) is skipped on the steps where none did

@@ -304,8 +304,7 @@ extern "C" int qg_policy_create(int32_t device_id, const qg_policy_desc *desc, q
     const int count = policy_layout(desc, &k);
     if (count < 0) return count;
     int simds;
-    int rc = qg_open_device(device_id, &simds);
-    if (rc != QG_OK) return rc;
+    QG_TRY(qg_open_device(device_id, &simds));
     qg_policy *p = new (std::nothrow) qg_policy();
     if (!p) return fail(QG_ERR_ALLOC, "out of host memory");
     memset(p, 0, sizeof *p);
@@ -319,7 +318,7 @@ extern "C" int qg_policy_create(int32_t device_id, const qg_policy_desc *desc, q
         qg_policy_destroy(p);
         return QG_ERR_ALLOC;
     }
-    rc = policy_pack(p, nullptr);
+    int rc = policy_pack(p, nullptr);
     if (rc == QG_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(QG_ERR_LAUNCH, "qg_policy_create: the packing launch failed");
     if (rc != QG_OK) {
         qg_policy_destroy(p);
@@ -334,8 +333,7 @@ extern "C" int qg_policy_set_params(qg_policy *p, const float *host_params) {
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);         // forward passes on a caller's stream read the image this rewrites
     HIP_TRY(hipMemcpy(p->d_params, host_params, (size_t)p->n_params * sizeof(float), hipMemcpyHostToDevice), QG_ERR_DEVICE);
-    int rc = policy_pack(p, nullptr);
-    if (rc != QG_OK) return rc;
+    QG_TRY(policy_pack(p, nullptr));
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
     return QG_OK;
 }

@@ -375,13 +375,6 @@ static void grad_layout(const KPolicy &k, KGrad *g) {
     g->n_items = item + 1;
 }
 
-// (bits, not std::isfinite: the device pass of this file is compiled with finite-math assumptions and warns about the latter)
-static bool finite32(float x) {
-    uint32_t u;
-    memcpy(&u, &x, sizeof u);
-    return (u & 0x7f800000u) != 0x7f800000u;
-}
-
 template <class T> static void grad_release(qg_policy *p, T *&ptr) {
     for (int i = 0; ptr && i < p->mem.count; i++)
         if (p->mem.ptr[i] == (void *)ptr) {
@@ -411,8 +404,7 @@ extern "C" int qg_policy_reserve_grad(qg_policy *p, int32_t max_batch) {
         p->mem.alloc(p->d_slot_misc, slots * QGG_MISC * sizeof(double), true) ||
         p->mem.alloc(p->d_partial, slots * (size_t)p->n_params * sizeof(float)))
         return QG_ERR_ALLOC;
-    int rc = qg_policy_pack_transposed(p, nullptr);
-    if (rc != QG_OK) return rc;
+    QG_TRY(qg_policy_pack_transposed(p, nullptr));
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
     p->grad_max = max_batch;
     return QG_OK;
@@ -426,8 +418,8 @@ extern "C" int qg_policy_ppo_grad_device(qg_policy *p, const qg_ppo_params *pp, 
     if (bt->struct_size != (int32_t)sizeof(qg_ppo_batch))
         return fail(QG_ERR_ARG, "qg_ppo_batch.struct_size is %d, this library's is %d", bt->struct_size, (int)sizeof(qg_ppo_batch));
     if (pp->reserved != 0) return fail(QG_ERR_ARG, "qg_ppo_params.reserved must be 0");
-    if (!finite32(pp->clip_range) || !(pp->clip_range > 0.f)) return fail(QG_ERR_ARG, "qg_ppo_params.clip_range must be finite and > 0");
-    if (!finite32(pp->clip_range_vf) || !finite32(pp->ent_coef) || !finite32(pp->vf_coef))
+    if (!qg_finite32(pp->clip_range) || !(pp->clip_range > 0.f)) return fail(QG_ERR_ARG, "qg_ppo_params.clip_range must be finite and > 0");
+    if (!qg_finite32(pp->clip_range_vf) || !qg_finite32(pp->ent_coef) || !qg_finite32(pp->vf_coef))
         return fail(QG_ERR_ARG, "qg_ppo_params: clip_range_vf, ent_coef and vf_coef must be finite");
     if (B < 1) return fail(QG_ERR_ARG, "qg_policy_ppo_grad_device: B must be >= 1");
     if (B > p->grad_max)

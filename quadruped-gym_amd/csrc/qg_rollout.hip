@@ -325,9 +325,8 @@ extern "C" int qg_rollout_destroy(qg_rollout *p) {
 extern "C" int qg_rollout_create(int32_t device_id, const qg_rollout_desc *desc, const qg_rollout_storage *storage, qg_rollout **out) {
     if (!out) return fail(QG_ERR_ARG, "qg_rollout_create: null output");
     *out = nullptr;
-    int rc = rollout_validate(desc, storage);
-    if (rc != QG_OK) return rc;
-    if ((rc = qg_open_device(device_id, nullptr)) != QG_OK) return rc;
+    QG_TRY(rollout_validate(desc, storage));
+    QG_TRY(qg_open_device(device_id, nullptr));
     qg_rollout *p = new (std::nothrow) qg_rollout();
     if (!p) return fail(QG_ERR_ALLOC, "out of host memory");
     memset(p, 0, sizeof *p);
@@ -367,8 +366,7 @@ extern "C" int qg_rollout_begin_device(qg_rollout *p, const float *obs, int32_t 
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     const bool vec = D % 4 == 0 && rollout_aligned(p->st.obs, 16) && (!obs || (obs_stride % 4 == 0 && rollout_aligned(obs, 16)));
     int64_t blocks;
-    int rc = rollout_blocks(n, D / (vec ? 4 : 1), &blocks);
-    if (rc != QG_OK) return rc;
+    QG_TRY(rollout_blocks(n, D / (vec ? 4 : 1), &blocks));
     const hipStream_t st = (hipStream_t)stream;
     if (vec) qg_rollout_begin_kernel<true><<<(unsigned)blocks, QGR_BLOCK, 0, st>>>(n, D, p->d_ctl, p->st.obs, obs, obs_stride);
     else qg_rollout_begin_kernel<false><<<(unsigned)blocks, QGR_BLOCK, 0, st>>>(n, D, p->d_ctl, p->st.obs, obs, obs_stride);
@@ -409,9 +407,8 @@ extern "C" int qg_rollout_add_device(qg_rollout *p, const qg_rollout_step *s, vo
     a.cur_length = p->d_cur_length, a.fin_length = p->d_fin_length, a.fin_count = p->d_fin_count;
     const bool vec = D % 4 == 0 && s->next_obs_stride % 4 == 0 && rollout_aligned(s->next_obs, 16) && rollout_aligned(p->st.obs, 16);
     int64_t ob, ab;
-    int rc = rollout_blocks(n, D / (vec ? 4 : 1), &ob);
-    if (rc == QG_OK) rc = rollout_blocks(n, A, &ab);
-    if (rc != QG_OK) return rc;
+    QG_TRY(rollout_blocks(n, D / (vec ? 4 : 1), &ob));
+    QG_TRY(rollout_blocks(n, A, &ab));
     a.obs_blocks = (int32_t)ob, a.act_blocks = (int32_t)ab;
     const int64_t blocks = ob + ab + ((int64_t)n + QGR_BLOCK - 1) / QGR_BLOCK;
     if (blocks > INT32_MAX) return fail(QG_ERR_ARG, "qg_rollout_add_device: %d envs are more than one launch takes", n);
@@ -454,10 +451,8 @@ extern "C" int qg_rollout_gather_device(qg_rollout *p, const int64_t *idx, int32
     a.o_advantages = out->advantages, a.o_returns = out->returns;
     const bool vec = D % 4 == 0 && rollout_aligned(p->st.obs, 16) && rollout_aligned(out->obs, 16);
     int64_t ob = 0, ab = 0;
-    int rc = QG_OK;
-    if (out->obs) rc = rollout_blocks(B, D / (vec ? 4 : 1), &ob);
-    if (rc == QG_OK && out->actions) rc = rollout_blocks(B, A, &ab);
-    if (rc != QG_OK) return rc;
+    if (out->obs) QG_TRY(rollout_blocks(B, D / (vec ? 4 : 1), &ob));
+    if (out->actions) QG_TRY(rollout_blocks(B, A, &ab));
     a.obs_blocks = (int32_t)ob, a.act_blocks = (int32_t)ab;
     const int64_t blocks = ob + ab + ((int64_t)B + QGR_BLOCK - 1) / QGR_BLOCK;
     if (blocks > INT32_MAX) return fail(QG_ERR_ARG, "qg_rollout_gather_device: %d rows are more than one launch takes", B);

@@ -1,7 +1,7 @@
-// qg_sim.h -- the simulator handle and the few functions of the core (qg_capi.hip) and of the walking layer (qg_walk.hip) that the
-// layers bound to a simulator -- qg_comm.hip, qg_walk.hip, qg_po.hip -- call across translation units (what the core and the
-// step-kernel units share on top of it is in qg_step_launch.h).  Internal: not installed, and
-// nothing in here is exported (libquadgym.map).
+// qg_sim.h -- the simulator handle and the few functions that cross translation units: those of the simulator's own four units
+// (qg_capi.hip the core, qg_sim_host.hip, qg_sim_multi.hip, qg_sim_modes.hip) and of the walking layer (qg_walk.hip) that each other
+// and the layers bound to a simulator -- qg_comm.hip, qg_walk.hip, qg_po.hip -- call (what the core and the step-kernel units share
+// on top of it is in qg_step_launch.h).  Internal: not installed, and nothing in here is exported (libquadgym.map).
 #pragma once
 #include "qg_host.h"
 #include "qg_device.h"
@@ -23,7 +23,7 @@ struct qg_sim {
     int32_t caller_inflight;  // a device-pointer step has been enqueued on a caller's stream since the last device-wide wait
     int32_t captured_once;    // a device-pointer step of this handle has been CAPTURED into a hipGraph: replays enqueue steps the library
                               // never sees, so from then on every host-pointer call takes the device-wide wait (sticky)
-    uint8_t *h_pin;           // page-locked staging of the host-pointer entry points (see pin_reserve)
+    uint8_t *h_pin;           // page-locked staging of the host-pointer entry points (qg_sim_host.hip)
     size_t h_pin_cap;
     uint8_t *d_done, *d_mask;
     hipStream_t stream;       // the library's own stream (host-pointer calls, timing)
@@ -32,8 +32,7 @@ struct qg_sim {
     uint64_t env_index_base;
     int32_t track_ctrl;
     int32_t link_helpers;     // walking forms of the one-link-per-lane kernel run with helper waves (QG_LINK_HELPERS at qg_create; default 1)
-    int32_t baked;            // 1: the model equals the compiled-in default, the literal-constant kernel variant runs
-    int32_t model_baked;      // what `baked` is with the per-env dynamics off (the mode runs the table-driven kernels)
+    int32_t model_baked;      // the model equals the compiled-in default (set once by qg_create; what runs: qg_sim_baked below)
     // per-env dynamics (qg_set_dynamics_range / qg_set_dynamics)
     int32_t dyn;              // the mode is on: the per-env forms of the table-driven step kernels run
     int32_t dyn_range_set;    // QG_RESET_DYNAMICS may draw
@@ -66,9 +65,24 @@ struct qg_sim {
     } res;
 };
 
+// either mode that runs the per-env forms of the table-driven step kernels is on
+static inline bool qg_sim_per_env(const qg_sim *s) { return s->dyn || s->xfrc; }
+// the literal-constant kernel variants run: the compiled-in robot, and no per-env mode
+static inline bool qg_sim_baked(const qg_sim *s) { return s->model_baked && !qg_sim_per_env(s); }
+// The refusal of what the per-env modes do not cover; `fmt` takes the mode's name and the call that ends it.
+static inline int qg_refuse_per_env(const qg_sim *s, const char *fmt) {
+    if (s->dyn) return fail(QG_ERR_ARG, fmt, "per-env dynamics", "qg_clear_dynamics");
+    if (s->xfrc) return fail(QG_ERR_ARG, fmt, "external wrenches", "qg_clear_xfrc");
+    return QG_OK;
+}
+// hinge jitter of the envs a step auto-resets: a launch of its own behind every step
+static inline bool qg_jitter_at_reset(const qg_sim *s) { return s->task.auto_reset && (s->task.reset_flags & QG_RESET_JOINT_JITTER); }
+
 // ---- the core (qg_capi.hip) ----------------------------------------------------------------------------------------------------------
 // the resident kernel hands the state back, then whatever is in flight on any stream -- a caller's included -- has run
 int qg_retire_and_sync(qg_sim *s);
+// a device-pointer call has been enqueued on `stream`: what the next host-pointer call has to wait for
+void qg_note_caller_stream(qg_sim *s, hipStream_t stream);
 // the mapping AUTO resolves to for this handle, and whether its step kernel carries the fused observation pack (KPoLaunch)
 int qg_effective_mapping(const qg_sim *s);
 bool qg_po_fusable(const qg_sim *s);
@@ -76,9 +90,18 @@ bool qg_po_fusable(const qg_sim *s);
 // `po` != NULL (with `walk`): the partially observable observation pack fused in as well.
 int qg_launch_step(qg_sim *s, const float *d_actions, float *d_obs, float *d_reward, uint8_t *d_done, float *d_comps, float *d_packed,
                    hipStream_t stream, const KWalkLaunch *walk = nullptr, const KPoLaunch *po = nullptr);
-// src [w][n] -> dst [n][w] on the library's stream (the state's layout into the caller's)
+// src [w][n] -> dst [n][w] on the library's stream (the state's layout into the caller's), and back
 int qg_transpose_out_launch(qg_sim *s, const float *src, float *dst, int w);
+int qg_transpose_in_launch(qg_sim *s, const float *src, float *dst, int w);
 
+// ---- many env-steps per launch (qg_sim_multi.hip) ---------------------------------------------------------------------------------------
+// the resident kernel stores the state it holds in registers and leaves (no-op while none is launched); its mailbox released
+int qg_resident_retire(qg_sim *s);
+void qg_resident_free(qg_sim *s);
+// the handle can run the sequence / resident forms of the one-link-per-lane kernel; else the refusal, in `who`'s name
+int qg_multi_step_usable(const qg_sim *s, const char *who);
+
+// ---- the host-pointer path (qg_sim_host.hip) ----------------------------------------------------------------------------------------------
 // One host-pointer step: the actions in through the page-locked arena's first bytes, `step` enqueues the device-pointer step from
 // `d_actions` on the library's stream, the four outputs (obs, reward, done, components: the caller's array, its device source, its
 // size) -- and for qg_step_mirror the state snapshot -- come back through the arena behind the actions, with ONE synchronisation.

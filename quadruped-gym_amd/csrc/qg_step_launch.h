@@ -1,5 +1,5 @@
-// qg_step_launch.h -- what the core (qg_capi.hip) and the step-kernel units (qg_kernel_link.hip, qg_kernel_quad.hip,
-// qg_kernel_pair.hip) both read: what a launch takes, the grid predicates every step-kernel choice is made with, and the entry points
+// qg_step_launch.h -- what the simulator units that enqueue steps (qg_capi.hip: one env-step; qg_sim_multi.hip: many per launch) and
+// the step-kernel units (qg_kernel_link.hip, qg_kernel_quad.hip, qg_kernel_pair.hip) both read: what a launch takes, the grid predicates every step-kernel choice is made with, and the entry points
 // of the units.  Each unit is a code object of its own and holds its kernels, their launchers and the leaves of its mapping: the core
 // decides the mapping, the unit names the instantiation.  Internal: not installed, and nothing in here is exported (libquadgym.map).
 #pragma once
@@ -66,8 +66,8 @@ void qg_launch_resident_ring(hipStream_t st, const KResident &R, unsigned count,
 #ifdef QG_PHASE_TIMES
 typedef hipError_t (*QgPhaseReader)(uint64_t out[16]);
 void qg_phase_unit(QgPhaseReader reader);
-static hipError_t phase_read(uint64_t out[16]) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(qg_phase_times), 16 * sizeof(uint64_t)); }
-#define QG_PHASE_UNIT() qg_phase_unit(phase_read)
+// (a macro, so that a unit without device code -- qg_sim_multi.hip -- can include this file: it has no qg_phase_times to name)
+#define QG_PHASE_UNIT() qg_phase_unit([](uint64_t out[16]) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(qg_phase_times), 16 * sizeof(uint64_t)); })
 #else
 #define QG_PHASE_UNIT() ((void)0)
 #endif

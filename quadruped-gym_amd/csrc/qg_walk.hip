@@ -303,15 +303,12 @@ extern "C" int qg_walk_reset(qg_walk *w, const uint8_t *mask, uint64_t seed, uin
     if (!w) return fail(QG_ERR_ARG, "null handle");
     qg_sim *s = w->sim;
     if ((flags & QG_RESET_DYNAMICS) && !s->dyn_range_set) return fail(QG_ERR_ARG, "qg_walk_reset: QG_RESET_DYNAMICS without a range (qg_set_dynamics_range)");
-    int rc = qg_reset(s, mask, seed, flags);           // uploads the mask into s->d_mask
-    if (rc != QG_OK) return rc;
+    QG_TRY(qg_reset(s, mask, seed, flags));            // uploads the mask into s->d_mask
     int threads = 256, blocks = (s->n + threads - 1) / threads;
     hipLaunchKernelGGL(qg_walk_reset_kernel, dim3(blocks), dim3(threads), 0, s->stream, w->kp, w->st, s->n, mask ? s->d_mask : nullptr);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
-    if (!s->creating) {                                // walking_quad.py:121-122 (not for the constructor's own reset)
-        rc = walk_sample_commands(w, mask ? s->d_mask : nullptr, s->stream);
-        if (rc != QG_OK) return rc;
-    }
+    // walking_quad.py:121-122 (not for the constructor's own reset)
+    if (!s->creating) QG_TRY(walk_sample_commands(w, mask ? s->d_mask : nullptr, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream), QG_ERR_LAUNCH);
     return QG_OK;
 }
@@ -337,8 +334,7 @@ int qg_walk_step_core(qg_walk *w, const float *actions, float *obs, float *rewar
     hipLaunchKernelGGL(qg_walk_pre_kernel, dim3((total + threads - 1) / threads), dim3(threads), 0, st, w->kp, w->st, s->n, actions,
                        (const float *)s->st.ctrl, (const int32_t *)s->st.nstep);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
-    int rc = qg_launch_step(s, w->st.eff_actions, obs, reward, done, nullptr, nullptr, st);
-    if (rc != QG_OK) return rc;
+    QG_TRY(qg_launch_step(s, w->st.eff_actions, obs, reward, done, nullptr, nullptr, st));
     hipLaunchKernelGGL(qg_walk_post_kernel, dim3((s->n + threads - 1) / threads), dim3(threads), 0, st, w->kp, w->st, s->n, (const float *)obs,
                        (const uint8_t *)done, reward, components, (w->kp.cmd_sample && !po_follows) ? 1 : 0, s->seed, s->env_index_base,
                        (const int32_t *)s->st.episode);
@@ -371,8 +367,7 @@ extern "C" int qg_walk_get_estimates(qg_walk *w, float *f_est, float *a_est, flo
     if (f_est) HIP_TRY(hipMemcpy(f_est, w->st.f_est, (size_t)s->n * 12 * 4, hipMemcpyDeviceToHost), QG_ERR_DEVICE);
     if (a_est) HIP_TRY(hipMemcpy(a_est, w->st.a_est, (size_t)s->n * 12 * 4, hipMemcpyDeviceToHost), QG_ERR_DEVICE);
     if (ideal_xy) {
-        int rc = qg_transpose_out_launch(s, w->st.ideal, w->d_tmp, 2);
-        if (rc != QG_OK) return rc;
+        QG_TRY(qg_transpose_out_launch(s, w->st.ideal, w->d_tmp, 2));
         HIP_TRY(hipMemcpyAsync(ideal_xy, w->d_tmp, (size_t)s->n * 2 * 4, hipMemcpyDeviceToHost, s->stream), QG_ERR_DEVICE);
         HIP_TRY(hipStreamSynchronize(s->stream), QG_ERR_LAUNCH);
     }

@@ -282,6 +282,59 @@ def test_clear_dynamics_restores_the_baked_kernel():
     a.close(); b.close()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("robot", ["baked", "table"])
+def test_baked_flag_follows_the_two_modes(robot):
+    """qg_uses_baked_model is the compiled-in robot with neither per-env mode on, through every order of switching the two modes on and
+    off and after a refused request, and the step kernel that runs agrees with it.  64 envs: the LINK mapping, one partial wave.  The
+    table robot (servo gains x 1.1) answers 0 throughout."""
+    import torch
+    from quadruped_gym_amd._abi import QuadGymError
+    from quadruped_gym_amd.sim import BatchedSim
+    n = 64
+    model = None
+    if robot == "table":
+        model = _abi.default_model()
+        for j in range(12):
+            model.act_kp[j] *= 1.1
+    sim = BatchedSim(n, model=model)
+    dev = torch.device("cuda:0")
+    actions, packed = torch.zeros((n, 12), device=dev), torch.empty((n, sim.obs_dim + 2), device=dev)
+    identity = np.tile(_abi.identity_dynamics_row(sim.model), (n, 1))
+    zeros = np.zeros((n, 13, 6), np.float32)
+    plain = "qg_step_kernel_link<0,0,1,0,0>" if robot == "baked" else "qg_step_kernel_link<0,0,0,0,0>"
+
+    def check(dyn, xfrc):
+        want = int(robot == "baked" and not dyn and not xfrc)
+        assert sim._lib.qg_uses_baked_model(sim._h) == want and sim.baked == bool(want)
+        assert (sim.dynamics_on, sim.wrench_on) == (dyn, xfrc)
+        sim.step_device_packed(actions, packed)
+        torch.cuda.synchronize()
+        assert sim.last_step_kernel == ("qg_step_kernel_link<0,0,0,0,1>" if dyn or xfrc else plain)
+
+    check(False, False)
+    for call, dyn, xfrc in ((lambda: sim.set_dynamics(identity), True, False),
+                            (lambda: sim.set_external_wrench(zeros), True, True),
+                            (sim.clear_dynamics, False, True),
+                            (sim.clear_external_wrench, False, False),
+                            (lambda: sim.set_external_wrench(zeros), False, True),
+                            (lambda: sim.set_dynamics(identity), True, True),
+                            (sim.clear_external_wrench, True, False),
+                            (sim.clear_dynamics, False, False)):
+        call()
+        check(dyn, xfrc)
+    # a mode request refused under a LANE mapping request switches nothing on (the step after it is taken back under AUTO: the
+    # one-env-per-lane kernel is no form of the one-link-per-lane kernel)
+    sim.set_mapping(_abi.MAP_LANE)
+    for call in (lambda: sim.set_dynamics(identity), lambda: sim.set_external_wrench(zeros)):
+        with pytest.raises(QuadGymError):
+            call()
+        assert sim._lib.qg_uses_baked_model(sim._h) == int(robot == "baked")
+    sim.set_mapping(_abi.MAP_AUTO)
+    check(False, False)
+    sim.close()
+
+
 def expected_rows(oracle, spec, model, seed, envs, episodes):
     """lo + (hi - lo) u per column, u of stream 16 + k of the (seed, env, episode) key; in f64 from the f32 lo, hi - lo and u."""
     r = _abi.dynamics_range(spec, model)
