@@ -5,7 +5,17 @@ m seeded states -- random-action rollout states, 32 with the FRAME pressing on t
 with its state's oracle row at O(m) oracle cost.  The layout puts every state once at the front, then 64-env blocks of states
 whose FRAME and femurs stay off the floor, each with exactly ONE FRAME- or femur-contact env at a lane position that moves from
 block to block (the wave-uniform contact skips and the femur cull in both directions), and at the back states that neither touch
-nor terminate (the last, partial workgroup holds one at n = 4097 and 32 769).  Tolerances: TOL["A"] of tests/test_parity_gpu.py."""
+nor terminate (the last, partial workgroup holds one at n = 4097 and 32 769).  Tolerances: TOL["A"] of tests/test_parity_gpu.py.
+
+What is pinned per leaf.  Every leaf: qpos, qvel, act and the step counter.  Plain and walking leaves: the 33-value observation.  Plain
+leaves: reward and terminations.  Walking AND partially observable leaves (tests/po_step_reference.py, a chain of the oracles that
+takes nothing from the GPU: settling gate and clip -> C physics oracle -> walking reward on the ORACLE's sensors -> Madgwick frame and
+FIFO on the oracle's sensors and quaternion): the 11 reward components and the reward, and for the PO leaves the WHOLE returned stack
+of obs_window = 3 frames -- gyro, accelerometer, Euler angles, body velocity, data.ctrl, command, the frame's place in the FIFO and the
+reset frames behind it.  Those leaves take a SECOND env-step from the same states with other actions (beyond the clip) and per-state
+commands: the first step after a reset has a zero derived reward term (component 10) and a filter estimate that aliases qpos, the
+second exercises both.  With QG_PO_PARITY_OUT=<file> every leaf appends its maxima per column group and reward component to that
+file (profiles/r20/po_frame_parity.txt)."""
 import json
 import os
 import sys
@@ -18,8 +28,9 @@ from quadruped_gym_amd import _abi
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
+import po_step_reference as R  # noqa: E402
 from kernel_leaves import LEAVES  # noqa: E402
-from test_dynamics_gpu import oracle_per_env  # noqa: E402
+from test_dynamics_gpu import env_model, oracle_per_env  # noqa: E402
 from test_parity_gpu import TOL, close  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -28,6 +39,8 @@ GOLD = os.path.join(HERE, "golden", "step_vectors.npz")
 M_SAMPLE, M_CONTACT, BLOCK, TAIL = 256, 32, 64, 16
 MAPS = {"lane": _abi.MAP_LANE, "quad": _abi.MAP_QUAD, "pair": _abi.MAP_PAIR, "link": _abi.MAP_LINK}
 CASES = [(name, k) for name, leaf in LEAVES.items() for k in range(len(leaf.sizes))]
+PO_WINDOW = 3                 # the PO leaves' obs_window: the newest frame's place in the FIFO is part of the check
+RECORD = "QG_PO_PARITY_OUT"
 
 
 def _simds():
@@ -35,8 +48,9 @@ def _simds():
     return 4 * torch.cuda.get_device_properties(0).multi_processor_count
 
 
-@pytest.fixture(scope="module")
-def states(oracle):
+def build_states(oracle):
+    """The leaf test's states, actions, per-env dynamics rows and -- for the walking and PO leaves -- the second step's actions and the
+    commands (no GPU: tests/test_po_step_reference.py runs the checker's own tests on exactly these)."""
     from make_golden import sample_states
     model, task = oracle.default_model(), oracle.default_task()
     # the FRAME and femur contacts: the 2 x 32 contact_states of the golden fixture (drawing them takes minutes of rejection sampling)
@@ -54,7 +68,61 @@ def states(oracle):
     rows[:, 1] = rng.uniform(-0.05, 0.2, m)
     rows[:, 2:5] = rng.uniform(-0.01, 0.01, (m, 3))
     rows[:, 5:] = rng.uniform(0.7, 1.3, (m, 6))
-    return dict(state=(q, v, a, ns), actions=actions, touch=frame | femur, rows=rows.astype(np.float32), m=m)
+    # walking / PO leaves: a second env-step from the same states with actions that reach beyond the clip, and a command per state
+    rng = np.random.default_rng(66)
+    actions2 = rng.uniform(-1.3, 1.3, (m, 12)).astype(np.float32)
+    speed, alpha, theta = rng.uniform(0.2, 1.0, m), rng.uniform(-np.pi, np.pi, m), rng.uniform(-np.pi, np.pi, m)
+    velocity = np.stack([speed * np.cos(alpha), speed * np.sin(alpha)], 1).astype(np.float32)
+    heading = np.stack([np.cos(theta), np.sin(theta)], 1).astype(np.float32)
+    return dict(state=(q, v, a, ns), actions=actions, touch=frame | femur, rows=rows.astype(np.float32), m=m, actions2=actions2,
+                velocity=velocity, heading=heading)
+
+
+def walking_task(frame_skip=4, max_time=10.0):
+    """The task a walking / PO env of the leaf test runs (envs/walking.py: flip and time-limit terminations, no fall)."""
+    task = _abi.default_task()
+    task.frame_skip, task.max_time, task.use_time_limit, task.use_fall, task.use_flip = frame_skip, max_time, 1, 0, 1
+    return task
+
+
+def _task_numbers(task):
+    return (task.frame_skip, task.max_time, task.use_time_limit, task.use_fall, task.use_flip, task.sensor_lag, task.obs_mode)
+
+
+def expected_chain(oracle, st, model, task, dyn):
+    """The two env-steps of a walking / PO leaf on the checker: the reset stack, the outputs of both steps and the reward components'
+    sensitivity per step.  One chain serves the walking and the PO leaves of one robot (the frames do not feed the reward)."""
+    chk = R.StepChecker(oracle, st["m"], task.frame_skip, settling_time=0.0, obs_window=PO_WINDOW, unit_zero=True)
+    reset_stack = chk.reset()                                   # commands are still zero when the env is reset
+    chk.set_commands(st["velocity"], st["heading"])
+    models = [env_model(oracle, model, row) for row in st["rows"]] if dyn else model
+    schedule = [(st["state"], st["actions"]), (st["state"], st["actions2"])]
+    sensitivity, outs = R.reward_sensitivity(chk, models, task, schedule, TOL["A"], patterns=8, seed=67)
+    return dict(reset=reset_stack, outs=outs, sensitivity=sensitivity, dt=chk.dt)
+
+
+@pytest.fixture(scope="module")
+def states(oracle):
+    return build_states(oracle)
+
+
+@pytest.fixture(scope="module")
+def chains(oracle, states):
+    """(robot, dyn) -> expected_chain, computed once per robot and shared by its leaves; prints the measured sensitivities."""
+    cache = {}
+
+    def get(robot, dyn, model, task):
+        key = (robot, dyn)
+        if key not in cache:
+            c = expected_chain(oracle, states, model, task, dyn)
+            c["task"] = _task_numbers(task)
+            for k, row in enumerate(c["sensitivity"]):
+                R.record(RECORD, f"sensitivity robot={robot} dyn={int(dyn)} step={k + 1}: " + " ".join(f"{x:.3e}" for x in row))
+            cache[key] = c
+        c = cache[key]
+        assert c["task"] == _task_numbers(task) == _task_numbers(walking_task()), "the walking and PO leaves run one task"
+        return c
+    return get
 
 
 @pytest.fixture(scope="module")
@@ -100,7 +168,8 @@ def _handle(leaf, n, robot, monkeypatch):
         sim, env = BatchedSim(n, model=model, task=task), None
     else:
         cls = POWalkingQuadrupedVecEnv if leaf.layer == "po" else WalkingQuadrupedVecEnv
-        env = cls(n, nan_direction=False, seed=3, model_path=path)
+        kw = dict(obs_window=PO_WINDOW) if leaf.layer == "po" else {}
+        env = cls(n, nan_direction=False, seed=3, model_path=path, **kw)
         sim = env._sim
     if leaf.mapping != "auto":
         sim.set_mapping(MAPS[leaf.mapping])
@@ -109,7 +178,7 @@ def _handle(leaf, n, robot, monkeypatch):
 
 
 @pytest.mark.parametrize("name,k", CASES, ids=[f"{name}-{k}" for name, k in CASES])
-def test_leaf_matches_oracle(oracle, states, table_robot, monkeypatch, name, k):
+def test_leaf_matches_oracle(oracle, states, chains, table_robot, monkeypatch, name, k):
     leaf = LEAVES[name]
     n = leaf.sizes[k](_simds())
     sim, env = _handle(leaf, n, table_robot, monkeypatch)
@@ -123,9 +192,14 @@ def test_leaf_matches_oracle(oracle, states, table_robot, monkeypatch, name, k):
     if leaf.dyn:
         obs_o, rew_o, _, q_o, v_o, a_o = oracle_per_env(oracle, sim.model, task, states["rows"], states["state"], actions)
     tail_ok = ~done_o
+    chain = None
+    if env is not None:
+        chain = chains(leaf.robot, leaf.dyn, sim.model, task)
+        tail_ok = tail_ok & ~chain["outs"][0]["done"] & ~chain["outs"][1]["done"]
     idx = layout(n, m, states["touch"], tail_ok)
     if env is not None:
-        env.reset()
+        first = env.reset()
+        env.set_commands(states["velocity"][idx], states["heading"][idx])
     if leaf.dyn:
         sim.set_dynamics(states["rows"][idx])
     sim.set_state(q[idx], v[idx], a[idx], None, ns[idx])
@@ -133,9 +207,15 @@ def test_leaf_matches_oracle(oracle, states, table_robot, monkeypatch, name, k):
         obs, rew, done, _ = sim.step(actions[idx])
     else:
         obs, rew, done, _ = env.step(actions[idx])
+        comps = env.last_components.copy()
     assert sim.last_step_kernel == name
     q1, v1, a1, _, n1 = sim.get_state()
     if env is not None:
+        # the second env-step: the same states again (the task layers keep their histories), other actions
+        sim.set_state(q[idx], v[idx], a[idx], None, ns[idx])
+        obs2, rew2, done2, _ = env.step(states["actions2"][idx])
+        comps2 = env.last_components.copy()
+        assert sim.last_step_kernel == name
         env.close()
     else:
         sim.close()
@@ -160,3 +240,33 @@ def test_leaf_matches_oracle(oracle, states, table_robot, monkeypatch, name, k):
         if not leaf.dyn:
             sure = np.abs(q_o[idx, 2] - 0.05) > 1e-4
             assert np.array_equal(np.asarray(done, bool)[sure], done_o[idx][sure])
+    if env is None:
+        return
+    # ---- walking and PO leaves: rewards, and the whole stack, against the composed checker (tests/po_step_reference.py) -----------
+    # Reward components: the f32 reward against the f64 one on equal sensors is held to 2e-4 / 2e-4 (component 10: its own formula)
+    # by test_walking_rewards_match_oracle; here the sensors are the ORACLE's, so each component may also move by its sensitivity to
+    # sensors that differ within TOL["A"], measured on the oracle alone (fixture `chains`: 8 seeded sign patterns, largest change
+    # over the states, per step).
+    # Euler angles (R.angle_bound): 2e-4, the bound of test_po_frames_match_oracle for the f32 filter on EQUAL inputs, plus
+    # 2 * GAIN_IMU * dt -- the filter's correction is a step of length gain * dt along the UNIT gradient, whose direction is
+    # discontinuous in the accelerometer input where the estimate is aligned with gravity, so an accelerometer reading within its
+    # tolerance can turn that step around -- plus dt * (atol + rtol * |gyro|), the gyro's obs tolerance integrated over the step.
+    # Everything else of a frame: gyro and body velocity TOL obs, accelerometer TOL accel, ctrl and command 1e-6 (exact values in
+    # f32); the frames behind the computed ones are the reset frame, exact values only.
+    both = keep & ~np.asarray(done2, bool)
+    if n > 4 * TAIL:
+        assert both[-TAIL:].all(), "the tail (the last, partial workgroup) is compared in the second step too"
+    assert both.sum() >= min(n, m) // 2
+    maxima = {}
+    dt = chain["dt"]
+    steps = ((keep, obs, rew, comps), (both, obs2, rew2, comps2))
+    for s, (sel, o_s, r_s, c_s) in enumerate(steps):
+        exp, rows, js = chain["outs"][s], np.flatnonzero(sel), idx[sel]
+        what = f"step {s + 1}"
+        R.compare_rewards(c_s[sel], np.asarray(r_s)[sel], exp["comps"][js], exp["reward"][js], chain["sensitivity"][s], dt,
+                          what + " reward", rows=rows, maxima=maxima, sens=exp["sens"][js], tol=t)
+        if leaf.layer == "po":
+            R.compare_stack(np.asarray(o_s)[sel], exp["stack"][js], t, dt, computed=s + 1, what=what + " stack", rows=rows, maxima=maxima)
+    if leaf.layer == "po":
+        assert np.allclose(first, chain["reset"][idx], rtol=0, atol=R.EXACT), "the stack reset() returns"
+    R.record(RECORD, f"{name} n={n} compared={int(keep.sum())}/{int(both.sum())}\n    " + R.format_maxima(maxima))

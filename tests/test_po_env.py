@@ -1,10 +1,23 @@
 """The partially observable pack (qg_po_*) against oracle/po_oracle.py.  The Madgwick filter of the
 reference comes from the `ahrs` package, which is not available offline: the oracle restates the published
-algorithm -- parity unpinned, stated here.  The oracle is driven with the GPU's own sensor values."""
+algorithm -- parity unpinned, stated here.
+
+Two kinds of check.  test_po_frames_match_oracle drives the oracle with the GPU's OWN sensor values: it pins what the pack computes
+(the filter's Euler angles, the settling gate, the FIFO, terminal and reset stacks) and, for the pass-through columns, only their
+place.  test_po_rollout_frames_match_oracle_driven_from_the_state pins the pass-through columns themselves -- gyro, accelerometer,
+body velocity, data.ctrl, command -- over rollouts with auto-resets: at every step the composed checker (tests/po_step_reference.py:
+settling gate and clip -> f64 physics oracle -> frame) is restarted from the device's STATE and takes none of its sensors.
+tests/test_kernel_leaves_gpu.py holds the whole stack of every fused PO instantiation to the same checker over one and two steps."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from oracle import po_oracle as P
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import po_step_reference as R  # noqa: E402
 
 
 def test_madgwick_restatement_properties():
@@ -30,8 +43,8 @@ def test_po_frames_match_oracle(window, settle):
     setting (src/train_quadruped.py:16-19: obs_window 10, frame_skip 10, settling_time 0.5).
     What this test does and does not check: the oracle is fed the GPU's OWN frame for the gyro, accelerometer, body-velocity and
     data.ctrl columns (0-5, 9-10, 11-22 of a frame) -- those are pass-through values here (the physics behind them is checked in
-    tests/test_parity_gpu.py), so for them the comparison only proves that they sit at the right place of the right frame of the
-    stack.  The columns the observation pack COMPUTES are the real checks: the Madgwick-IMU Euler angles (6-8; filter update, the
+    test_po_rollout_frames_match_oracle_driven_from_the_state below and, per fused instantiation, in tests/test_kernel_leaves_gpu.py),
+    so for them the comparison only proves that they sit at the right place of the right frame of the stack.  The columns the observation pack COMPUTES are the real checks: the Madgwick-IMU Euler angles (6-8; filter update, the
     settling-time gate on the f64 clock, the aliasing of the estimate with data.qpos after a reset), the command columns (23-25: the
     command in force, its heading angle), the FIFO order over `window` frames, and the terminal / reset stacks at auto-resets."""
     from quadruped_gym_amd.envs.walking import POWalkingQuadrupedVecEnv
@@ -76,6 +89,63 @@ def test_po_frames_match_oracle(window, settle):
                 t[i] = 0.0
         vel, head = env.velocity.copy(), env.heading.copy()                  # commands re-sampled after the step
     assert saw_done
+    env.close()
+
+
+def _link_grid_plus_one():
+    import torch
+    from kernel_leaves import link_max
+    return link_max(4 * torch.cuda.get_device_properties(0).multi_processor_count) + 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size,window,settle,steps", [("small", 10, 0.0, 40), ("small", 10, 0.08, 40), ("first_quad", 4, 0.08, 12)])
+def test_po_rollout_frames_match_oracle_driven_from_the_state(oracle, size, window, settle, steps):
+    """The pass-through columns of the newest frame -- gyro 0-2, accelerometer 3-5, body velocity 9-10, data.ctrl 11-22, command 23-25
+    -- against the composed checker driven from the device's STATE, not from its sensors: before every env-step the state is read, and
+    the checker (tests/po_step_reference.py) gates and clips the action on the f64 clock of that state's step counter, steps the f64
+    physics oracle from that state and lays its sensors out as a frame with the command in force.  A finished env is compared through
+    the newest frame of its terminal stack.  Tolerances: TOL["A"] of tests/test_parity_gpu.py (one env-step at frame_skip 4 from an
+    identical f32 state: obs for gyro and body velocity, accel for the accelerometer), 1e-6 for ctrl and command (exact values in
+    f32).  Every (env, step) is compared, none is left out: the columns compared do not pass through the orientation estimate, so the
+    estimate aliasing qpos at a termination (what test_po_frames_match_oracle skips) does not matter here.  The angle columns keep
+    their check in test_po_frames_match_oracle.
+    n = 40: 2.5 workgroups of the link kernel, 40 steps at max_time 0.12 s = 15 env-steps per episode: every env passes two
+    auto-resets (random yaw, re-drawn commands), with and without the settling gate.  The third case is the first quad grid -- one
+    env more than the link kernel serves, the last workgroup holding ONE env -- on a seeded sample of 256 envs plus the last 16;
+    its 12 steps end before the time limit, and the settling gate opens after the tenth."""
+    from quadruped_gym_amd.envs.walking import POWalkingQuadrupedVecEnv
+    from test_parity_gpu import TOL
+    n = 40 if size == "small" else _link_grid_plus_one()
+    fs = 4
+    env = POWalkingQuadrupedVecEnv(n, obs_window=window, settling_time=settle, frame_skip=fs, max_time=0.12, random_init=True,
+                                   random_controls=True)
+    sim = env._sim
+    model, task = sim.model, sim.get_task()
+    assert task.frame_skip == fs and task.sensor_lag == 1
+    pick = np.arange(n) if n <= 272 else np.unique(np.r_[np.random.default_rng(7).choice(n - 16, 256, replace=False), np.arange(n - 16, n)])
+    np.random.seed(6)
+    env.reset()
+    rng = np.random.default_rng(3)
+    maxima, compared, finished, resets = {}, 0, 0, np.zeros(n, int)
+    for k in range(steps):
+        a = rng.uniform(-1.2, 1.2, (n, 12)).astype(np.float32)
+        q, v, act, _, ns = sim.get_state()
+        vel, head = env.velocity.copy(), env.heading.copy()                  # the command in force: re-drawn after the step
+        obs, rew, dones, infos = env.step(a)
+        applied, ctrl = R.gated_control(ns[pick], a[pick], settle)
+        out = R.physics(oracle, model, task, (q[pick], v[pick], act[pick], ns[pick]), applied)
+        exp = R.frame_columns(out["sens"], ctrl, vel[pick], head[pick])
+        got = np.stack([(infos[i]["terminal_observation"] if dones[i] else obs[i])[-26:] for i in pick])
+        R.compare_newest(got, exp, TOL["A"], 0.002 * fs, what="newest", angles=False, rows=pick, maxima=maxima)
+        compared += len(pick)
+        finished += int(dones[pick].sum())
+        resets += dones
+    assert compared == len(pick) * steps
+    if size == "small":
+        assert finished > 0 and resets.min() >= 2
+    R.record("QG_PO_PARITY_OUT", f"rollout n={n} window={window} settle={settle} steps={steps} compared={compared} finished={finished}: "
+             + R.format_maxima(maxima))
     env.close()
 
 

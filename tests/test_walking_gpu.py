@@ -1,6 +1,7 @@
 """The device walking task layer (qg_walk_*) against the walking oracle, which is itself pinned to the
 reference's estimator / command code by tests/test_walking_oracle.py.  The oracle is fed the GPU's own
-observations, so the comparison isolates the task layer from the (chaotic) physics rollout."""
+observations, so the comparison isolates the task layer from the (chaotic) physics rollout; the reward of every fused
+step-kernel instantiation on the ORACLE's own sensors is held in tests/test_kernel_leaves_gpu.py (tests/po_step_reference.py)."""
 import numpy as np
 import pytest
 
