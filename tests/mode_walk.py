@@ -1,0 +1,536 @@
+"""The modes a live simulator handle can be walked through, and what a FRESH handle in each of them looks like.
+
+tests/test_mode_walk_gpu.py takes one handle from mode A into mode B with the API's own switches, builds a second handle directly in B
+(``Mode.fresh``), hands it the walked handle's state through the public snapshot calls only (``adopt``) and steps both with the same
+actions through every step form of the mode (``run_form``): every output, the final snapshot and ``last_step_kernel`` must be the same
+bits.  tests/test_mode_walk_census.py checks the tables in here without a GPU.  Nothing in this module touches the GPU at import.
+
+A mode is a tuple of FEATURES, each with one switch on and one switch off.  ``switch`` switches off the features of A that B lacks
+(latest first) and then on the features of B that A lacks, so M6 -> M5 is ``clear_dynamics`` on a handle that keeps its wrenches and
+M7 -> M8 binds an observation pack to a walking layer that has stepped: the places where stale mode state would survive.
+``Mode.enter`` / ``Mode.leave`` are the same switches from and to the plain handle."""
+import os
+import re
+from dataclasses import dataclass
+
+import numpy as np
+
+from quadruped_gym_amd import _abi
+
+from kernel_leaves import LINK_ENVS, PAIR_ENVS, QUAD_ENVS, link_max, quad_max
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER = os.path.join(os.path.dirname(HERE), "include", "quadgym.h")
+
+FRAME_SKIP, MAX_TIME = 4, 0.2           # 100 substeps = 25 env-steps per episode: the staggered step counters end episodes early
+PO_WINDOW, SLOTS, SEQ_K = 3, 2, 4      # SEQ_K: the env-steps in B, and so the length of the sequence launch
+N_SMALL = 37                            # a ragged last wave in every mapping (4, 16, 32 and 64 envs per wave)
+PUSH = {"interval": 2, "duration": 1, "probability": 0.5, "force": (5.0, 20.0)}
+WRENCH_BODIES = (0, 2, 7)               # FRAME, a shin, a femur
+DYN_RANGE = {"friction": (0.3, 1.5), "payload_mass": (-0.05, 0.2), "payload_pos": ((-0.01, 0.01),) * 3, "kp_scale": (0.7, 1.3),
+             "kv_scale": (0.7, 1.3), "force_scale": (0.7, 1.3), "damping_scale": (0.7, 1.3), "contact_stiffness_scale": (0.7, 1.3),
+             "contact_damping_scale": (0.7, 1.3)}
+MAPS = {"lane": _abi.MAP_LANE, "quad": _abi.MAP_QUAD, "pair": _abi.MAP_PAIR}
+
+
+def base_task():
+    """The task of the plain mode M0, and of every mode that does not say otherwise."""
+    t = _abi.default_task()
+    t.frame_skip, t.max_time, t.use_time_limit, t.auto_reset = FRAME_SKIP, MAX_TIME, 1, 1
+    t.use_fall, t.use_flip, t.reset_flags = 0, 0, 0
+    return t
+
+
+def task_fields(task):
+    return tuple(tuple(v) if hasattr(v, "__len__") else v for v in (getattr(task, name) for name, _ in task._fields_))
+
+
+def dynamics_rows(n, model):
+    """Random valid rows, drawn as tests/test_kernel_leaves_gpu.py: build_states draws them."""
+    rows = np.tile(_abi.identity_dynamics_row(model), (n, 1))
+    rng = np.random.default_rng(65)
+    rows[:, 0] = rng.uniform(0.3, 1.5, n)
+    rows[:, 1] = rng.uniform(-0.05, 0.2, n)
+    rows[:, 2:5] = rng.uniform(-0.01, 0.01, (n, 3))
+    rows[:, 5:] = rng.uniform(0.7, 1.3, (n, 6))
+    return rows.astype(np.float32)
+
+
+def wrench_rows(n):
+    rng = np.random.default_rng(66)
+    rows = np.zeros((n, _abi.NBODY, _abi.NXFRC), np.float32)
+    for b in WRENCH_BODIES:
+        rows[:, b, :3] = rng.uniform(-2.0, 2.0, (n, 3))
+        rows[:, b, 3:] = rng.uniform(-0.1, 0.1, (n, 3))
+    return rows
+
+
+def commands(n):
+    rng = np.random.default_rng(67)
+    speed, alpha, theta = rng.uniform(0.2, 1.0, n), rng.uniform(-np.pi, np.pi, n), rng.uniform(-np.pi, np.pi, n)
+    velocity = np.stack([speed * np.cos(alpha), speed * np.sin(alpha)], 1).astype(np.float32)
+    heading = np.stack([np.cos(theta), np.sin(theta)], 1).astype(np.float32)
+    return np.ascontiguousarray(velocity), np.ascontiguousarray(heading)
+
+
+class Ctx:
+    """A simulator handle with what the modes bind to it, and the features that are on (in the order they were switched on)."""
+
+    def __init__(self, n, model=None):
+        from quadruped_gym_amd.sim import BatchedSim
+        self.sim = BatchedSim(n, model=model, task=base_task())
+        self.walk = self.po = self.mail = None
+        self.features = []
+        self.track_ctrl = True            # qg_set_track_ctrl as the caller left it (the ABI has no getter; qg_create switches it on)
+
+    def set_track_ctrl(self, on):
+        """Not while a walking layer is bound: the layer switches the write-back on for its estimator and gives the caller's setting
+        back when it is destroyed."""
+        if self.walk is None:
+            self.sim.set_track_ctrl(on)
+            self.track_ctrl = bool(on)
+
+    def close(self):
+        if self.sim is not None:
+            if self.mail is not None:
+                self.sim.resident_stop()
+            self.sim.close()              # closes the layers first (Handle.close)
+        self.sim = self.walk = self.po = self.mail = None
+
+
+# ---- the features: one switch on, one switch off ----------------------------------------------------------------------------------
+def _mapping_on(which):
+    def on(c):
+        c.sim.set_mapping(MAPS[which])
+    return on
+
+
+def _mapping_off(c):
+    c.sim.set_mapping(_abi.MAP_AUTO)
+
+
+def _dyn_on(c):
+    c.sim.set_dynamics_range(DYN_RANGE)
+    c.sim.set_dynamics(dynamics_rows(c.sim.n, c.sim.model))
+    t = c.sim.get_task()
+    t.reset_flags |= _abi.RESET_DYNAMICS
+    c.sim.set_task(t)
+
+
+def _dyn_off(c):
+    t = c.sim.get_task()
+    t.reset_flags &= ~_abi.RESET_DYNAMICS
+    c.sim.set_task(t)
+    c.sim.clear_dynamics()
+
+
+def _xfrc_on(c):
+    c.sim.set_external_wrench(wrench_rows(c.sim.n))
+    c.sim.set_push_schedule(PUSH)
+
+
+def _xfrc_off(c):
+    c.sim.clear_external_wrench()
+
+
+def _walk_on(c):
+    from quadruped_gym_amd.task_layers import WalkLayer, default_walk_params
+    p = default_walk_params()
+    p.unit_zero = 1
+    c.walk = WalkLayer(c.sim, p)
+    c.walk.set_commands(*commands(c.sim.n))
+
+
+def _walk_off(c):
+    walk, c.walk = c.walk, None
+    walk.close()
+
+
+def _sampler_on(c):
+    c.walk.set_command_sampler(_abi.QgCommandSampler.from_options({"min_speed": 0.2, "max_speed": 1.0}))
+
+
+def _sampler_off(c):
+    _abi.check(c.walk._lib.qg_walk_set_command_sampler(c.walk._h, None), "qg_walk_set_command_sampler")
+
+
+def _po_on(c):
+    from quadruped_gym_amd.task_layers import ObsPack
+    c.po = ObsPack(c.walk, PO_WINDOW)
+
+
+def _po_off(c):
+    po, c.po = c.po, None
+    po.close()
+
+
+def _task9_on(c):
+    t = c.sim.get_task()
+    t.sensor_lag, t.use_fall, t.fall_height = 0, 1, 0.05
+    t.reset_flags |= _abi.RESET_JOINT_JITTER | _abi.RESET_RANDOM_YAW
+    c.sim.set_task(t)
+
+
+def _task9_off(c):
+    c.sim.set_task(base_task())
+
+
+def _resident_on(c):
+    import torch
+    dev = torch.device(f"cuda:{c.sim.device}")
+    mail = (torch.zeros((SLOTS, c.sim.n, 12), device=dev), torch.zeros((SLOTS, c.sim.n, c.sim.obs_dim + 2), device=dev))
+    c.sim.resident_start(*mail, idle_timeout_us=5000)
+    c.mail = mail
+
+
+def _resident_off(c):
+    c.sim.resident_stop()
+    c.mail = None
+
+
+FEATURES = {"quad": (_mapping_on("quad"), _mapping_off), "pair": (_mapping_on("pair"), _mapping_off), "lane": (_mapping_on("lane"), _mapping_off),
+            "dyn": (_dyn_on, _dyn_off), "xfrc": (_xfrc_on, _xfrc_off), "walk": (_walk_on, _walk_off), "sampler": (_sampler_on, _sampler_off),
+            "po": (_po_on, _po_off), "task9": (_task9_on, _task9_off), "resident": (_resident_on, _resident_off)}
+
+# ---- the step forms ----------------------------------------------------------------------------------------------------------------
+# form -> the entry point of include/quadgym.h it goes through
+FORMS = {"step": "qg_step", "step_mirror": "qg_step_mirror", "step_device": "qg_step_device", "step_device_packed": "qg_step_device_packed",
+         "step_device_seq": "qg_step_device_seq", "resident": "qg_resident_step_device", "walk_step": "qg_walk_step",
+         "walk_step_device": "qg_walk_step_device", "po_step": "qg_po_step", "po_step_device": "qg_po_step_device"}
+SIM_FORMS = ("step", "step_mirror", "step_device", "step_device_packed")
+
+
+def header_step_entries():
+    """Every entry point of the header that advances the envs (qg_time_step_kernel times launches, qg_norm_step_device is the
+    normaliser's update)."""
+    src = open(HEADER).read()
+    names = set(re.findall(r"\bint\s+(qg_\w*step\w*)\s*\(", src))
+    return {n for n in names if n not in ("qg_time_step_kernel", "qg_norm_step_device")}
+
+
+def forms_of(features):
+    """What the header offers a handle with these features.  The per-launch forms of the simulator always; the sequence form unless a
+    per-env mode is on or a walking layer is bound (refused: EXPECTED_REFUSALS of the GPU test); rings while the resident mode is on;
+    the layers' own steps while they are bound."""
+    f = set(features)
+    forms = list(SIM_FORMS)
+    if not f & {"dyn", "xfrc", "walk"}:
+        forms.append("step_device_seq")
+    if "resident" in f:
+        forms.append("resident")
+    if "walk" in f:
+        forms += ["walk_step", "walk_step_device"]
+    if "po" in f:
+        forms += ["po_step", "po_step_device"]
+    # the first form runs on the walked handle before anything is restored into it: the top layer's host step, which reads the state back
+    # after every env-step (the oracle anchor uses the first)
+    lead = "po_step" if "po" in f else "walk_step" if "walk" in f else "step"
+    return (lead,) + tuple(x for x in forms if x != lead)
+
+
+# ---- which instantiation runs: the selection of qg_capi.hip (qg_effective_mapping) and the select_step_* functions, restated ---------
+def _name(family, *args):
+    return "qg_step_kernel%s<%s>" % (family, ",".join(str(int(a)) for a in args))
+
+
+def effective_mapping(request, n, simds, baked, lag):
+    if request in ("lane", "quad"):
+        return request
+    if request == "pair":
+        return "pair" if baked else "quad"
+    if lag and n <= simds * LINK_ENVS:
+        return "link"
+    if baked and n > simds * QUAD_ENVS and (n <= simds * PAIR_ENVS or n >= (simds + 3 * (simds // 4)) * PAIR_ENVS):
+        return "pair"
+    return "quad"
+
+
+def expected_kernel(features, n, simds, form, robot="baked"):
+    f = set(features)
+    per_env = bool(f & {"dyn", "xfrc"})
+    baked = robot == "baked" and not per_env
+    lag, jitter = "task9" not in f, "task9" in f
+    helpers = os.environ.get("QG_LINK_HELPERS", "1") != "0"
+    request = next((m for m in MAPS if m in f), "auto")
+    emap = effective_mapping(request, n, simds, baked, lag)
+    walk = form.startswith(("walk_", "po_"))
+    po = form.startswith("po_")
+    qblocks, pblocks = -(-n // QUAD_ENVS), -(-n // PAIR_ENVS)
+    quad_wg4, pair_wg4, one_wave = qblocks > simds // 4, pblocks > simds // 4, qblocks <= simds
+    if form == "resident":
+        return _name("_link_multi", baked, 1)
+    if form == "step_device_seq":
+        if emap == "pair" and baked and lag and not jitter:
+            return _name("_pair_multi", 4 if pair_wg4 else 1)
+        if emap == "quad" and lag and quad_wg4 and not jitter:
+            return _name("_quad_multi", 1, 0) if not baked else _name("_quad_multi", 1 if one_wave else 2, 1)
+        if emap == "link" and n <= simds * LINK_ENVS and not jitter:
+            return _name("_link_multi", baked, 0)
+        # (anything else: SEQ_K launches of the per-launch leaf)
+    if emap == "lane":
+        return _name("", baked)
+    if emap == "link":
+        if not baked:
+            return _name("_link", walk, po, 0, 0, per_env)
+        return _name("_link", walk, po, 1, walk and helpers, 0)
+    if emap == "pair":
+        return _name("_pair", 4 if (po or pair_wg4) else 1, walk, po)
+    if not baked:
+        return _name("_quad", 1, 0, walk, 4 if (po or quad_wg4) else 1, po, 0, per_env)
+    if walk:
+        if one_wave and helpers:
+            return _name("_quad", 2, 1, 1, 4, po, 1, 0)
+        if one_wave:
+            return _name("_quad", 1, 1, 1, 4 if (po or quad_wg4) else 1, po, 0, 0)
+        return _name("_quad", 2, 1, 1, 4, po, 0, 0)
+    if one_wave:
+        return _name("_quad", 1, 1, 0, 4 if quad_wg4 else 1, 0, 0, 0)
+    return _name("_quad", 2, 1, 0, 4, 0, 0, 0)
+
+
+# ---- the modes -------------------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Mode:
+    name: str
+    features: tuple
+    what: str
+    table: bool = False       # also run on the table robot (rollout_recordings.table_robot)
+    oracle: bool = False      # the f64 oracle can express the configuration
+
+    @property
+    def forms(self):
+        return forms_of(self.features)
+
+    def enter(self, ctx):
+        switch(ctx, self.features)
+
+    def leave(self, ctx):
+        switch(ctx, ())
+
+    def fresh(self, n, model=None):
+        return build(n, self.features, model)
+
+    def kernel(self, n, simds, form=None, robot="baked"):
+        return expected_kernel(self.features, n, simds, form or self.forms[0], robot)
+
+
+MODES = {m.name: m for m in (
+    Mode("M0", (), "plain, AUTO", table=True, oracle=True),
+    Mode("M1", ("quad",), "plain, explicit QUAD", table=True, oracle=True),
+    Mode("M2", ("pair",), "plain, explicit PAIR", oracle=True),
+    Mode("M3", ("lane",), "plain, explicit LANE", oracle=True),
+    Mode("M4", ("dyn",), "per-env dynamics rows, a range, RESET_DYNAMICS at auto-reset", table=True, oracle=True),
+    Mode("M5", ("xfrc",), "wrench rows on three bodies and a push schedule"),
+    Mode("M6", ("dyn", "xfrc"), "M4 and M5 together"),
+    Mode("M7", ("walk", "sampler"), "walking layer bound, device command sampler on", table=True),
+    Mode("M8", ("walk", "po"), "PO pack bound, obs_window 3", table=True),
+    Mode("M9", ("task9",), "task variant: unlagged sensors, joint jitter and random yaw at auto-reset, fall termination", oracle=True),
+    Mode("M10", ("resident",), "resident stepping on, 2 slots"),
+)}
+ORDER = tuple(MODES)
+TABLE_MODES = tuple(m for m in ORDER if MODES[m].table)
+PAIRS = tuple((a, b) for a in ORDER for b in ORDER if a != b)
+TABLE_PAIRS = tuple((a, b) for a in TABLE_MODES for b in TABLE_MODES if a != b)
+RING = ORDER + (ORDER[0],)
+RINGS = {"forward": tuple(zip(RING[:-1], RING[1:])), "reversed": tuple(zip(RING[::-1][:-1], RING[::-1][1:]))}
+BOUNDARY_SIZES = {"first_quad": lambda simds: link_max(simds) + 1, "first_pair": lambda simds: quad_max(simds) + 1}
+
+
+def switch(ctx, features):
+    """Off with what ``features`` lacks (latest first), on with what it adds.  A refused switch raises and leaves ``ctx.features`` as
+    far as the walk got."""
+    for f in [f for f in reversed(ctx.features) if f not in features]:
+        FEATURES[f][1](ctx)
+        ctx.features.remove(f)
+    for f in features:
+        if f not in ctx.features:
+            FEATURES[f][0](ctx)
+            ctx.features.append(f)
+
+
+def build(n, features, model=None):
+    ctx = Ctx(n, model)
+    try:
+        switch(ctx, features)
+    except Exception:
+        ctx.close()
+        raise
+    return ctx
+
+
+# ---- state through the public API ------------------------------------------------------------------------------------------------------
+def snapshot(ctx):
+    """Everything the handle and its layers keep per env (BatchedSim.snapshot, WalkLayer.state, ObsPack.state)."""
+    snap = {"sim": ctx.sim.snapshot()}
+    if ctx.walk is not None:
+        snap["walk"] = ctx.walk.state()
+    if ctx.po is not None:
+        snap["po"] = ctx.po.state()
+    return snap
+
+
+def restore(ctx, snap):
+    ctx.sim.restore(snap["sim"])
+    if ctx.walk is not None:
+        ctx.walk.load_state(snap["walk"])
+    if ctx.po is not None:
+        ctx.po.load_state(snap["po"])
+
+
+def adopt(twin, snap, track_ctrl=True):
+    """The walked handle's state into a fresh twin, and the caller's data.ctrl write-back setting (which a bound walking layer
+    overrides on both).  The task, the mapping and the baked flag are NOT copied: a handle walked into a mode must have the ones a
+    fresh handle has, so they are compared by the caller."""
+    twin.set_track_ctrl(track_ctrl)
+    restore(twin, snap)
+
+
+def flat(x, prefix=""):
+    """A snapshot (nested dicts of arrays and numbers) as {path: bytes}."""
+    if isinstance(x, dict):
+        out = {}
+        for k in sorted(x):
+            out.update(flat(x[k], f"{prefix}{k}."))
+        return out
+    if x is None or isinstance(x, (int, float, str, tuple)):
+        return {prefix[:-1]: repr(x).encode()}
+    a = np.ascontiguousarray(x)
+    return {prefix[:-1]: str((a.dtype, a.shape)).encode() + a.tobytes()}
+
+
+def differing(a, b):
+    """The paths at which two snapshots (or lists of outputs) differ in any bit."""
+    fa, fb = flat(a), flat(b)
+    return sorted(k for k in set(fa) | set(fb) if fa.get(k) != fb.get(k))
+
+
+# ---- stepping --------------------------------------------------------------------------------------------------------------------------
+def actions(seed, steps, n):
+    """Finite, within +-1.3: beyond the clip of the action space, as the leaf tests' second step."""
+    return np.random.default_rng(1000 + seed).uniform(-1.3, 1.3, (steps, n, 12)).astype(np.float32)
+
+
+def stagger(sim, plan):
+    """The handle's own state back into it (set_state(get_state())) with the step counters staggered so that the time limit ends the
+    episodes of env i after ``plan[i % 4]`` env-steps (0: not within this test), and every eighth env upside down 0.35 m up (the flip
+    termination of the walking layers ends it; no other mode does)."""
+    q, v, a, c, ns = sim.get_state()
+    k = np.asarray(plan)[np.arange(sim.n) % 4]
+    ns = np.where(k > 0, sim.limit_substeps - FRAME_SKIP * k, 0).astype(np.int32)
+    flip = np.arange(sim.n) % 8 == 7
+    q[flip, 2] = 0.35
+    q[flip, 3:7] = (0.0, 1.0, 0.0, 0.0)
+    sim.set_state(q, v, a, c, ns)
+
+
+PLAN_A = (2, 5, 7, 0)       # ends inside the 3 steps in A / inside the 4 steps in B (twice) / not at all
+PLAN_B = (2, 4, 0, 0)
+
+
+def run_form(ctx, form, acts):
+    """``len(acts)`` env-steps through ``form``.  Returns ({name: array} of every output of every step, done [steps, n])."""
+    import torch
+    sim, n, steps = ctx.sim, ctx.sim.n, len(acts)
+    out, dones = {}, np.zeros((steps, n), bool)
+    dev = torch.device(f"cuda:{sim.device}")
+
+    def put(k, **arrays):
+        for name, a in arrays.items():
+            out[f"{k}.{name}"] = a.cpu().numpy() if hasattr(a, "cpu") else np.array(a)
+
+    if form in ("step", "step_mirror"):
+        for k in range(steps):
+            if form == "step":
+                (obs, rew, done, comps), state = sim.step(acts[k], want_components=True), sim.get_state()
+            else:
+                (obs, rew, done, comps), state = sim.step_mirror(acts[k], want_components=True)
+            put(k, obs=obs, reward=rew, done=done, comps=comps, **dict(zip(("qpos", "qvel", "act", "ctrl", "nstep"), state)))
+            dones[k] = done
+    elif form in ("walk_step", "po_step"):
+        layer = ctx.po if form == "po_step" else ctx.walk
+        for k in range(steps):
+            res = layer.step(acts[k])
+            obs, rew, done, comps = res[:4]
+            put(k, obs=obs, reward=rew, done=done, comps=comps, **dict(zip(("qpos", "qvel", "act", "ctrl", "nstep"), sim.get_state())))
+            if form == "po_step":         # the terminal stacks exist for the envs that finished only
+                put(k, terminal=np.where(done.astype(bool)[:, None], res[4], 0.0))
+            dones[k] = done.astype(bool)
+    else:
+        a = torch.from_numpy(acts).to(dev)
+        if form == "step_device_seq":
+            packed = torch.zeros((steps, n, sim.obs_dim + 2), device=dev)
+            sim.step_device_seq(a, packed)
+            torch.cuda.current_stream().synchronize()
+            put(0, packed=packed)
+            dones[:] = packed[:, :, -1].cpu().numpy() > 0.5
+        elif form == "step_device_packed":
+            packed = torch.zeros((steps, n, sim.obs_dim + 2), device=dev)
+            for k in range(steps):
+                sim.step_device_packed(a[k], packed[k])
+            torch.cuda.current_stream().synchronize()
+            put(0, packed=packed)
+            dones[:] = packed[:, :, -1].cpu().numpy() > 0.5
+        elif form == "resident":
+            mail_a, mail_p = ctx.mail
+            rows = torch.zeros((steps, n, sim.obs_dim + 2), device=dev)
+            for k in range(steps):
+                slot = sim.resident_status()["rung"] % SLOTS
+                mail_a[slot].copy_(a[k])
+                sim.resident_ensure()
+                sim.resident_step(1)
+                rows[k].copy_(mail_p[slot])
+                torch.cuda.current_stream().synchronize()
+            put(0, packed=rows)
+            dones[:] = rows[:, :, -1].cpu().numpy() > 0.5
+        else:
+            layer = {"step_device": sim, "walk_step_device": ctx.walk, "po_step_device": ctx.po}[form]
+            width = layer.obs_dim
+            obs, rew = torch.zeros((steps, n, width), device=dev), torch.zeros((steps, n), device=dev)
+            done = torch.zeros((steps, n), device=dev, dtype=torch.uint8)
+            comps = torch.zeros((steps, n, _abi.NREWARD if layer is sim else _abi.NWALKREWARD), device=dev)
+            term = torch.zeros((steps, n, width), device=dev) if form == "po_step_device" else None
+            for k in range(steps):
+                if term is not None:
+                    layer.step_device(a[k], obs[k], rew[k], done[k], comps[k], term[k])
+                else:
+                    layer.step_device(a[k], obs[k], rew[k], done[k], comps[k])
+            torch.cuda.current_stream().synchronize()
+            put(0, obs=obs, reward=rew, done=done, comps=comps)
+            if term is not None:
+                put(0, terminal=torch.where(done.bool()[:, :, None], term, torch.zeros_like(term)))
+            dones[:] = done.cpu().numpy() != 0
+    return out, dones
+
+
+# ---- seeded random walks ---------------------------------------------------------------------------------------------------------------
+WALK_SEEDS, WALK_OPS, WALK_CHECK_EVERY = (0, 1, 2, 3), 30, 5
+WALK_SIZES = {"small": lambda simds: N_SMALL, "first_quad": BOUNDARY_SIZES["first_quad"]}
+
+
+def random_walk(seed):
+    """The operations of one walk, a pure function of the seed: ("mode", name) | ("reset", mask seed) | ("set_get",) | ("snap_restore",)
+    | ("track_ctrl",) (toggle the data.ctrl write-back) | ("step", form index, action seed).  Two of every five operations change the mode, along a seeded permutation of the modes, so
+    one walk enters every mode at least once."""
+    rng = np.random.default_rng(7000 + seed)
+    cycle = [ORDER[i] for i in rng.permutation(len(ORDER))]
+    ops, at, current = [], 0, "M0"
+    for j in range(WALK_OPS):
+        if j % 5 in (0, 2):
+            while cycle[at % len(cycle)] == current:
+                at += 1
+            current = cycle[at % len(cycle)]
+            at += 1
+            ops.append(("mode", current))
+            continue
+        kind = int(rng.integers(0, 5))
+        if kind == 0:
+            ops.append(("reset", int(rng.integers(0, 1 << 30))))
+        elif kind == 1:
+            ops.append(("set_get",))
+        elif kind == 2:
+            ops.append(("snap_restore",))
+        elif kind == 3:
+            ops.append(("track_ctrl",))
+        else:
+            ops.append(("step", int(rng.integers(0, 64)), int(rng.integers(0, 1 << 30))))
+    return ops

@@ -1,7 +1,12 @@
 """Randomised API sequences against the C ABI (through BatchedSim): random batch sizes, mappings and task flags, then a random walk
 over step / step_device_packed on side streams / masked reset / set_state / get_state / set_task / set_mapping.  Checked after every
 operation that reads the state back: everything finite, the per-env substep counters equal a host-side model of them, quaternions of
-unit length, an auto-reset env stands at its start pose.  usage (GPU box): python tools/fuzz_api_gpu.py [seconds] [seed]"""
+unit length, an auto-reset env stands at its start pose.  usage (GPU box): python tools/fuzz_api_gpu.py [seconds] [seed]
+
+What the suite covers since tests/test_mode_walk_gpu.py: walks over the MODES of a handle -- mappings, per-env dynamics, wrenches and
+pushes, the walking and PO layers, a task change, the sequence and resident forms -- with every step compared bit for bit against a
+fresh handle in the same mode, and the refusals on the way.  This tool remains for what that test does not draw: random batch sizes
+and task flags, side streams, and runs as long as the budget given."""
 import os
 import sys
 import time
