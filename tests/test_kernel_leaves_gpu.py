@@ -15,7 +15,24 @@ of obs_window = 3 frames -- gyro, accelerometer, Euler angles, body velocity, da
 reset frames behind it.  Those leaves take a SECOND env-step from the same states with other actions (beyond the clip) and per-state
 commands: the first step after a reset has a zero derived reward term (component 10) and a filter estimate that aliases qpos, the
 second exercises both.  With QG_PO_PARITY_OUT=<file> every leaf appends its maxima per column group and reward component to that
-file (profiles/r20/po_frame_parity.txt)."""
+file (profiles/r20/po_frame_parity.txt).
+
+A SECOND POOL (``cell_states``; tests/contact_cells.py) runs through every leaf in the same layout with the same assertions: in place
+of the 2 x 32 tilted-robot states it holds 60 built states -- the 16 cull-edge states (the farthest sample point of a femur, shin or
+foot straight down, grazing the floor: what a bounding-sphere cull with too small a radius drops) and one state for every sample
+point of the FRAME and of the four femurs (pressed, and upright where the point allows it) -- the per-point constants behind the
+wave-uniform skips.  For both pools a FRAME- or femur-contact env gives the same bits wherever it sits: its rows in the blocks equal
+its row at the front.
+
+Which touching states become a block's contact env depends on the leaf.  A plain step does not restart an env that finishes and
+compares it, so there every touching state may (a robot with its FRAME on the floor is below the fall height and finishes): all 60
+built states, as many as the grid has blocks (59 at the one-link-per-lane sizes, 11 at n = 1000, all 60 once the grid has 60 blocks: the leaves of 16 383 envs and more).  The
+walking and PO layers restart a finished env, so their blocks hold only states that end no episode in either step: of the built
+states the 30 that stand upright (FRAME points 4-7, femur points 1, 3, 4 and 6, ten cull-edge states) and whatever else survives
+(measured: one more cull-edge state, 31 in every such leaf of 4093 envs and more).
+ONLY_ON_ITS_BACK names the points those leaves never see in a block -- the FRAME's top corners and top face and femur points 0, 2, 5
+and 7 touch the floor only with the robot overturned, which the flip termination ends.  check_leaf asserts which built states land in
+a block and prints the count."""
 import json
 import os
 import sys
@@ -28,6 +45,7 @@ from quadruped_gym_amd import _abi
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
+import contact_cells as CC  # noqa: E402
 import po_step_reference as R  # noqa: E402
 from kernel_leaves import LEAVES  # noqa: E402
 from test_dynamics_gpu import env_model, oracle_per_env  # noqa: E402
@@ -48,20 +66,71 @@ def _simds():
     return 4 * torch.cuda.get_device_properties(0).multi_processor_count
 
 
-def build_states(oracle):
+UPRIGHT = 0.05                 # z component of the base's z axis above which a built state counts as upright (3 degrees from lying on its side)
+# the points of the second pool that only touch the floor with the robot on its back: the FRAME's top corners and top face, and
+# points 0, 2, 5 and 7 of every femur.  Every state of their cells ends a walking / PO episode (flip termination), so those leaves
+# step them at the front only; the plain-step leaves put them into blocks
+ONLY_ON_ITS_BACK = {(0, i) for i in (0, 1, 2, 3, 8, 9, 10, 11)} | {(b, i) for b in (1, 4, 7, 10) for i in (0, 2, 5, 7)}
+
+
+def _upright(qpos):
+    return 1.0 - 2.0 * (qpos[..., 4] ** 2 + qpos[..., 5] ** 2) > UPRIGHT
+
+
+def cell_contact_states(oracle):
+    """The contact part of the second pool, from tests/golden/contact_cells.npz: the cull-edge states, then one state per sample point
+    of the FRAME and of the femurs -- of the point's cells the first pressed state that stands upright (the walking and PO leaves end
+    the episode of a robot on its back), else the first grazing one that does, else the first pressed one.  Returns the states, their
+    (kind, body, point) labels and which of them stand upright."""
+    fix = CC.load()
+    cells = CC.cell_index(fix)
+    pick = [int(e) for e in np.flatnonzero(fix["kind"] == CC.KIND_EDGE)]
+    assert len(pick) == 16
+    for b in (0, 1, 4, 7, 10):
+        for i in range(12 if b == 0 else 8):
+            cand = cells[(b, i, CC.PRESS)] + cells[(b, i, CC.GRAZE)]
+            up = [e for e in cand if _upright(fix["qpos"][e])]
+            pick.append(up[0] if up else cand[0])
+    pick = np.array(pick)
+    label = np.stack([fix[k][pick] for k in ("kind", "body", "point")], 1)
+    up = _upright(fix["qpos"][pick])
+    cellpts = label[:, 0] == CC.KIND_CELL
+    assert {(int(b), int(i)) for _, b, i in label[cellpts & ~up]} == ONLY_ON_ITS_BACK
+    return [fix[k][pick] for k in ("qpos", "qvel", "act", "nstep")], label, up
+
+
+def build_states(oracle, pool="golden"):
     """The leaf test's states, actions, per-env dynamics rows and -- for the walking and PO leaves -- the second step's actions and the
-    commands (no GPU: tests/test_po_step_reference.py runs the checker's own tests on exactly these)."""
+    commands (no GPU: tests/test_po_step_reference.py runs the checker's own tests on exactly these).  `pool`: "golden" or "cells"
+    (module docstring)."""
     from make_golden import sample_states
     model, task = oracle.default_model(), oracle.default_task()
-    # the FRAME and femur contacts: the 2 x 32 contact_states of the golden fixture (drawing them takes minutes of rejection sampling)
-    gold = np.load(GOLD)
-    contact = [gold[k][-2 * M_CONTACT:] for k in ("qpos", "qvel", "act", "nstep")]
+    if pool == "golden":
+        # the FRAME and femur contacts: the 2 x 32 contact_states of the golden fixture (drawing them takes minutes of rejection sampling)
+        gold = np.load(GOLD)
+        contact = [gold[k][-2 * M_CONTACT:] for k in ("qpos", "qvel", "act", "nstep")]
+    else:
+        contact, label, upright = cell_contact_states(oracle)
     q, v, a, ns = (np.concatenate(x) for x in zip(sample_states(model, task, M_SAMPLE, seed=61), contact))
     m = len(q)
     actions = np.random.default_rng(64).uniform(-1, 1, (m, 12)).astype(np.float32)
     census = oracle.contact_census(model, task.frame_skip, q, v, a, ns, actions, extra=0)
     frame, femur = census[:, :, 0].any(1), census[:, :, [1, 4, 7, 10]].any((1, 2))
-    assert frame[M_SAMPLE:M_SAMPLE + M_CONTACT].sum() >= 24 and femur[M_SAMPLE + M_CONTACT:].sum() >= 24
+    touch = frame | femur
+    if pool == "golden":
+        assert frame[M_SAMPLE:M_SAMPLE + M_CONTACT].sum() >= 24 and femur[M_SAMPLE + M_CONTACT:].sum() >= 24
+        extra = {}
+    else:
+        cellpts = label[:, 0] == CC.KIND_CELL
+        assert frame[M_SAMPLE:][cellpts & (label[:, 1] == 0)].all() and femur[M_SAMPLE:][cellpts & (label[:, 1] > 0)].all()
+        touch[M_SAMPLE:] = True                               # the shins' and feet's cull-edge states take a block of their own too
+        # the rollout states that touch with the FRAME or a femur leave this pool: the blocks go to the built states only (which of
+        # them, per leaf, is up to the terminations: check_leaf asserts and prints it)
+        stay = np.r_[~touch[:M_SAMPLE], np.ones(m - M_SAMPLE, bool)]
+        q, v, a, ns, actions, touch = q[stay], v[stay], a[stay], ns[stay], actions[stay], touch[stay]
+        m = len(q)
+        extra = dict(built=np.flatnonzero(touch), label=label, upright=upright)
+        assert len(extra["built"]) == len(label) == 60
     rows = np.tile(_abi.identity_dynamics_row(_abi.default_model()), (m, 1))
     rng = np.random.default_rng(65)
     rows[:, 0] = rng.uniform(0.3, 1.5, m)
@@ -74,8 +143,8 @@ def build_states(oracle):
     speed, alpha, theta = rng.uniform(0.2, 1.0, m), rng.uniform(-np.pi, np.pi, m), rng.uniform(-np.pi, np.pi, m)
     velocity = np.stack([speed * np.cos(alpha), speed * np.sin(alpha)], 1).astype(np.float32)
     heading = np.stack([np.cos(theta), np.sin(theta)], 1).astype(np.float32)
-    return dict(state=(q, v, a, ns), actions=actions, touch=frame | femur, rows=rows.astype(np.float32), m=m, actions2=actions2,
-                velocity=velocity, heading=heading)
+    return dict(state=(q, v, a, ns), actions=actions, touch=touch, rows=rows.astype(np.float32), m=m, actions2=actions2,
+                velocity=velocity, heading=heading, pool=pool, **extra)
 
 
 def walking_task(frame_skip=4, max_time=10.0):
@@ -107,7 +176,11 @@ def states(oracle):
 
 
 @pytest.fixture(scope="module")
-def chains(oracle, states):
+def cell_states(oracle):
+    return build_states(oracle, pool="cells")
+
+
+def _chain_cache(oracle, states):
     """(robot, dyn) -> expected_chain, computed once per robot and shared by its leaves; prints the measured sensitivities."""
     cache = {}
 
@@ -117,12 +190,22 @@ def chains(oracle, states):
             c = expected_chain(oracle, states, model, task, dyn)
             c["task"] = _task_numbers(task)
             for k, row in enumerate(c["sensitivity"]):
-                R.record(RECORD, f"sensitivity robot={robot} dyn={int(dyn)} step={k + 1}: " + " ".join(f"{x:.3e}" for x in row))
+                R.record(RECORD, f"sensitivity pool={states['pool']} robot={robot} dyn={int(dyn)} step={k + 1}: " + " ".join(f"{x:.3e}" for x in row))
             cache[key] = c
         c = cache[key]
         assert c["task"] == _task_numbers(task) == _task_numbers(walking_task()), "the walking and PO leaves run one task"
         return c
     return get
+
+
+@pytest.fixture(scope="module")
+def chains(oracle, states):
+    return _chain_cache(oracle, states)
+
+
+@pytest.fixture(scope="module")
+def cell_chains(oracle, cell_states):
+    return _chain_cache(oracle, cell_states)
 
 
 @pytest.fixture(scope="module")
@@ -139,10 +222,11 @@ def table_robot(tmp_path_factory):
     return path, load_model(path)[0]
 
 
-def layout(n, m, touch, tail_ok):
-    """State index of every env (see the module docstring)."""
+def layout(n, m, touch, tail_ok, block_ok=None):
+    """State index of every env (see the module docstring).  `tail_ok`: the states that may fill the blocks and the tail (they neither
+    touch nor terminate); `block_ok`: the touching states that may be a block's one contact env (default: those of `tail_ok`)."""
     quiet = np.flatnonzero(~touch & tail_ok)
-    contact = np.flatnonzero(touch & tail_ok)
+    contact = np.flatnonzero(touch & (tail_ok if block_ok is None else block_ok))
     idx = np.empty(n, np.int64)
     front = min(n, m)
     idx[:front] = np.arange(front)
@@ -179,6 +263,34 @@ def _handle(leaf, n, robot, monkeypatch):
 
 @pytest.mark.parametrize("name,k", CASES, ids=[f"{name}-{k}" for name, k in CASES])
 def test_leaf_matches_oracle(oracle, states, chains, table_robot, monkeypatch, name, k):
+    check_leaf(oracle, states, chains, table_robot, monkeypatch, name, k)
+
+
+@pytest.mark.parametrize("name,k", CASES, ids=[f"{name}-{k}" for name, k in CASES])
+def test_leaf_matches_oracle_on_contact_cells(oracle, cell_states, cell_chains, table_robot, monkeypatch, name, k):
+    """The second pool: cull-edge states and every sample point of the FRAME and the femurs (module docstring: which of them a leaf
+    puts into blocks)."""
+    check_leaf(oracle, cell_states, cell_chains, table_robot, monkeypatch, name, k)
+
+
+def same_bits_wherever_it_sits(idx, touch, m, restarted, arrays):
+    """A touching state's env in a block gives the bits of its env at the front (another lane, other neighbours in its wave): the
+    wave-uniform contact skips and the femur cull change nothing for the env that does touch.  A grazing contact dropped by a skip
+    moves the step by less than TOL["A"]; only this comparison sees it.  `restarted`: the envs a task layer restarted in the step
+    with draws of their own (left out; a plain step restarts none).  `arrays`: name -> per-env array.  Returns how many envs were
+    compared."""
+    restarted = np.asarray(restarted, bool)
+    later = np.flatnonzero(touch[idx] & (np.arange(len(idx)) >= m) & ~restarted)
+    assert not restarted[idx[later]].any()
+    for name, x in arrays.items():
+        x = np.ascontiguousarray(x)
+        here, front = (x[e].reshape(len(later), -1).view(np.uint8) for e in (later, idx[later]))
+        bad = later[(here != front).any(1)]
+        assert not len(bad), f"{name}: envs {bad[:8].tolist()} differ from the envs {idx[bad[:8]].tolist()} that hold the same touching states"
+    return len(later)
+
+
+def check_leaf(oracle, states, chains, table_robot, monkeypatch, name, k):
     leaf = LEAVES[name]
     n = leaf.sizes[k](_simds())
     sim, env = _handle(leaf, n, table_robot, monkeypatch)
@@ -196,7 +308,21 @@ def test_leaf_matches_oracle(oracle, states, chains, table_robot, monkeypatch, n
     if env is not None:
         chain = chains(leaf.robot, leaf.dyn, sim.model, task)
         tail_ok = tail_ok & ~chain["outs"][0]["done"] & ~chain["outs"][1]["done"]
-    idx = layout(n, m, states["touch"], tail_ok)
+    # a plain step does not restart an env that finishes, and compares it: there every touching state may be a block's contact env (a
+    # robot with its FRAME on the floor is below the fall height); the walking and PO layers restart it, so theirs must not terminate
+    idx = layout(n, m, states["touch"], tail_ok, block_ok=np.ones(m, bool) if env is None else tail_ok)
+    in_block = np.unique(idx[m:][states["touch"][idx[m:]]]) if n > m else np.zeros(0, np.int64)
+    if "built" in states and n > m:
+        # the second pool: which built states are the one touching env of a block in this leaf
+        may = states["built"] if env is None else states["built"][tail_ok[states["built"]]]
+        if env is not None:
+            assert tail_ok[states["built"][states["upright"]]].all(), "a built state that stands upright ends no walking episode"
+        slots = int((states["touch"][idx[m:]]).sum())
+        assert np.array_equal(in_block, may[:min(slots, len(may))]) and len(in_block) >= min(slots, int(states["upright"].sum()))
+        lab = states["label"][np.searchsorted(states["built"], in_block)]
+        print(f"{name} n={n}: {len(in_block)} of {len(states['built'])} built states sit alone in a block ({slots} blocks): "
+              f"{int((lab[:, 0] == CC.KIND_EDGE).sum())} cull-edge, {int(((lab[:, 0] == CC.KIND_CELL) & (lab[:, 1] == 0)).sum())} FRAME points, "
+              f"{int(((lab[:, 0] == CC.KIND_CELL) & (lab[:, 1] > 0)).sum())} femur points")
     if env is not None:
         first = env.reset()
         env.set_commands(states["velocity"][idx], states["heading"][idx])
@@ -210,6 +336,10 @@ def test_leaf_matches_oracle(oracle, states, chains, table_robot, monkeypatch, n
         comps = env.last_components.copy()
     assert sim.last_step_kernel == name
     q1, v1, a1, _, n1 = sim.get_state()
+    if n > m:                                                   # every state sits once at the front: env e < m holds state e
+        assert np.array_equal(idx[:m], np.arange(m))
+        same_bits_wherever_it_sits(idx, states["touch"], m, np.zeros(n, bool) if env is None else done,
+                                   dict(qpos=q1, qvel=v1, act=a1, nstep=n1, obs=obs, reward=rew, done=np.asarray(done, bool)))
     if env is not None:
         # the second env-step: the same states again (the task layers keep their histories), other actions
         sim.set_state(q[idx], v[idx], a[idx], None, ns[idx])
@@ -269,4 +399,4 @@ def test_leaf_matches_oracle(oracle, states, chains, table_robot, monkeypatch, n
             R.compare_stack(np.asarray(o_s)[sel], exp["stack"][js], t, dt, computed=s + 1, what=what + " stack", rows=rows, maxima=maxima)
     if leaf.layer == "po":
         assert np.allclose(first, chain["reset"][idx], rtol=0, atol=R.EXACT), "the stack reset() returns"
-    R.record(RECORD, f"{name} n={n} compared={int(keep.sum())}/{int(both.sum())}\n    " + R.format_maxima(maxima))
+    R.record(RECORD, f"{name} pool={states['pool']} n={n} compared={int(keep.sum())}/{int(both.sum())}\n    " + R.format_maxima(maxima))

@@ -3,11 +3,15 @@ vectors.  Floating point: the kernels compute in f32, the oracle in f64; toleran
 per quantity below and hold for ONE env-step from identical f32 states (longer rollouts diverge
 chaotically in any precision and are compared through invariants instead)."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from quadruped_gym_amd import _abi
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import contact_cells as CC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -257,6 +261,60 @@ def test_generic_variant_matches_oracle_on_a_modified_robot(oracle, mapping):
     close(obs[:, mask], obs_o[:, mask], t["obs"], "obs")
     close(rew, rew_o, t["reward"], "reward")
     sim.close()
+
+
+def test_every_contact_point_matches_oracle(oracle):
+    """tests/golden/contact_cells.npz (tests/contact_cells.py; its reach is checked GPU-free by tests/test_contact_cells_census.py): every
+    one of the 108 ground-contact sample points on the floor, grazing and pressed, plus the cull-edge states -- one env-step through
+    every mapping of the compiled-in robot (the kernels that carry each point as literals, the one-link-per-lane kernel with points i
+    and i + 4 packed in pairs) and through lane, quad and link on a robot that differs in one servo gain only (the kernels that read
+    the points from tables), at frame_skip 4 and 1: 14 launches, all at TOL["A"].  A failure names the body, the point and the depth
+    class.  Prints the largest error per quantity over all launches."""
+    from quadruped_gym_amd.sim import BatchedSim
+    fix = CC.load()
+    n = len(fix["qpos"])
+    qpos, qvel, act, nstep, actions = (fix[k] for k in CC.STATE_KEYS)
+    names = [("cull edge: " if fix["kind"][e] == CC.KIND_EDGE else "") + CC.cell_name(int(fix["body"][e]), int(fix["point"][e]),
+                                                                                     int(fix["depth_class"][e])) for e in range(n)]
+
+    def tweak(m):
+        m.act_kp[4] = 90.0                  # harmless to contact: the robot only leaves the compiled-in numbers
+        return m
+    t, rest = TOL["A"], np.r_[0:12, 15:33]
+    failures, worst = [], {}
+    for fs in (4, 1):
+        for robot, mappings in (("baked", ["lane", "quad", "pair", "link"]), ("table", ["lane", "quad", "link"])):
+            omodel, otask = oracle.default_model(), configure(oracle.default_task(), "A")
+            gmodel, gtask = _abi.default_model(), configure(_abi.default_task(), "A")
+            otask.frame_skip = gtask.frame_skip = fs
+            if robot == "table":
+                omodel, gmodel = tweak(omodel), tweak(gmodel)
+            b = oracle.Batch(omodel, otask, n)
+            b.set_state(qpos.astype(np.float64), qvel.astype(np.float64), act.astype(np.float64), None, nstep)
+            obs_o, rew_o, done_o, _ = b.step(actions.astype(np.float64))
+            q_o, v_o, a_o, c_o, n_o = b.get_state()
+            for mapping in mappings:
+                sim = BatchedSim(n, model=gmodel if robot == "table" else None, task=gtask)
+                sim.set_mapping(MAPPINGS[mapping])
+                assert sim.baked == (robot == "baked") and sim.mapping == MAPPINGS[mapping]
+                sim.set_state(qpos, qvel, act, None, nstep)
+                obs, rew, done, _ = sim.step(actions)
+                q1, v1, a1, c1, n1 = sim.get_state()
+                sim.close()
+                where = f"frame_skip {fs}, {robot} robot, {mapping}"
+                assert np.isfinite(obs).all() and np.isfinite(q1).all() and np.isfinite(v1).all(), where
+                assert np.array_equal(n1, n_o) and np.array_equal(c1, c_o.astype(np.float32)), where
+                sure = np.abs(q_o[:, 2] - 0.05) > 1e-4
+                assert np.array_equal(np.asarray(done, bool)[sure], done_o[sure]), where
+                for what, got, ref in (("qpos", q1, q_o), ("qvel", v1, v_o), ("act", a1, a_o), ("obs", obs[:, rest], obs_o[:, rest]),
+                                       ("accel", obs[:, 12:15], obs_o[:, 12:15]), ("reward", np.asarray(rew)[:, None], rew_o[:, None])):
+                    err = np.abs(np.asarray(got, np.float64) - ref)
+                    excess = (err / (t[what][0] + t[what][1] * np.abs(ref))).max(1)
+                    worst[what] = max(worst.get(what, 0.0), float(err.max()))
+                    for e in np.flatnonzero(~(excess <= 1.0)):
+                        failures.append(f"{where}: {what} of env {e} [{names[e]}] at {excess[e]:.2f} x its bound (error {err[e].max():.3e})")
+    print("contact cells, largest error over 14 launches: " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    assert not failures, f"{len(failures)} comparisons beyond TOL['A']:\n" + "\n".join(failures[:40])
 
 
 def test_reset_contract_and_first_observation():
