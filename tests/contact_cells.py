@@ -279,7 +279,7 @@ def _ratio(got, ref, tol):
 
 def step_ratio(a, ref, tol):
     """Largest |a - ref| / (atol + rtol |ref|) over qpos, qvel, obs and the accelerometer, in units of `tol` (the callers pass
-    TOL["A"] of tests/test_parity_gpu.py)."""
+    TOL["A"] of tests/parity.py)."""
     rest = np.r_[0:12, 15:33]
     return max(_ratio(a[0], ref[0], tol["qpos"]), _ratio(a[1], ref[1], tol["qvel"]), _ratio(a[2][rest], ref[2][rest], tol["obs"]),
                _ratio(a[2][12:15], ref[2][12:15], tol["accel"]))
@@ -401,7 +401,7 @@ def _single(s):
 
 def generate(oracle, tol, seed=SEED, candidates=3, log=None):
     """The fixture: dict of f32 states (STATE_KEYS) and their labels (LABEL_KEYS), cells first (body, point, class, style), then the
-    cull-edge states.  `tol`: TOL["A"] of tests/test_parity_gpu.py, the unit of ``shift_excess``.  Deterministic in `seed`: every
+    cull-edge states.  `tol`: TOL["A"] of tests/parity.py, the unit of ``shift_excess``.  Deterministic in `seed`: every
     cell draws from its own stream."""
     model, task = oracle.default_model(), task_a(oracle)
     placer, shifted = Placer(oracle, model), ShiftedModels(oracle)

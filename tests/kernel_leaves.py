@@ -5,7 +5,8 @@ mapping's kernels: ``STEP_UNITS``), keyed by the name
 ``BatchedSim.last_step_kernel`` reports: tests/test_kernel_leaves_gpu.py steps each one against the f64 oracle.  The many-env-steps
 forms (``launch_*_multi``) are pinned bit for bit to a per-launch leaf by a case of tests/test_resident_gpu.py: ``MULTI_TWINS``
 names that case and the leaf.  tests/test_kernel_census.py parses the launch sites and checks that both tables list exactly the
-instantiations the source can launch."""
+instantiations the source can launch.  ``open_leaf`` opens the handle a row describes, for every test that steps one.  Importing this
+module needs neither a GPU nor torch: the product is imported where a handle is opened."""
 import os
 import re
 from dataclasses import dataclass
@@ -40,6 +41,43 @@ class Leaf:
     layer: str = "none"   # "none" (plain step), "walk" (walking task layer fused in), "po" (and the PO observation pack)
     dyn: bool = False     # per-env dynamics rows
     helpers: bool = True  # QG_LINK_HELPERS at qg_create
+
+
+PO_WINDOW = 3                 # the PO handles' obs_window in the leaf, mode-walk and rollout tests: the newest frame's place in the FIFO is part of the checks
+
+
+def open_leaf(leaf, n, table=None, fs=4, auto_reset=False, reset_flags=0, seed=3, obs_window=1, **env_kw):
+    """The handle `leaf` describes (its ``robot``, ``layer``, ``mapping`` and ``helpers``; a rollout_recordings.Form will do): a
+    BatchedSim with the fall termination at 0.05 m for a plain step, else a walking / PO VecEnv (``env_kw`` go to it) -- (sim, env or
+    None).  `table`: (path, qg_model) of the table robot (helpers.table_robot).  `auto_reset` and `reset_flags` are the plain step's
+    task.  QG_LINK_HELPERS is read at qg_create: it is set for the call only."""
+    from parity import MAPPINGS
+    from quadruped_gym_amd import _abi
+    from quadruped_gym_amd.envs.walking import POWalkingQuadrupedVecEnv, WalkingQuadrupedVecEnv
+    from quadruped_gym_amd.sim import BatchedSim
+    path, model = table if leaf.robot == "table" else ("builtin", None)
+    old = os.environ.get("QG_LINK_HELPERS")
+    os.environ["QG_LINK_HELPERS"] = "1" if leaf.helpers else "0"
+    try:
+        if leaf.layer == "none":
+            task = _abi.default_task()
+            task.use_fall, task.fall_height, task.frame_skip = 1, 0.05, fs
+            task.auto_reset, task.reset_flags = int(auto_reset), reset_flags
+            sim, env = BatchedSim(n, model=model, task=task), None
+        else:
+            if leaf.layer == "po":
+                env = POWalkingQuadrupedVecEnv(n, obs_window=obs_window, nan_direction=False, seed=seed, model_path=path, frame_skip=fs, **env_kw)
+            else:
+                env = WalkingQuadrupedVecEnv(n, nan_direction=False, seed=seed, model_path=path, frame_skip=fs, **env_kw)
+            sim = env._sim
+    finally:
+        if old is None:
+            del os.environ["QG_LINK_HELPERS"]
+        else:
+            os.environ["QG_LINK_HELPERS"] = old
+    if leaf.mapping != "auto":
+        sim.set_mapping(MAPPINGS[leaf.mapping])
+    return sim, env
 
 
 def _ragged_link(S):

@@ -3,7 +3,8 @@
 tests/test_mode_walk_gpu.py takes one handle from mode A into mode B with the API's own switches, builds a second handle directly in B
 (``Mode.fresh``), hands it the walked handle's state through the public snapshot calls only (``adopt``) and steps both with the same
 actions through every step form of the mode (``run_form``): every output, the final snapshot and ``last_step_kernel`` must be the same
-bits.  tests/test_mode_walk_census.py checks the tables in here without a GPU.  Nothing in this module touches the GPU at import.
+bits.  The calls the API documents as refused, and the transitions that meet one, are listed here too (``EXPECTED_REFUSALS``).
+tests/test_mode_walk_census.py checks the tables in here without a GPU.  Nothing in this module touches the GPU at import.
 
 A mode is a tuple of FEATURES, each with one switch on and one switch off.  ``switch`` switches off the features of A that B lacks
 (latest first) and then on the features of B that A lacks, so M6 -> M5 is ``clear_dynamics`` on a handle that keeps its wrenches and
@@ -17,20 +18,19 @@ import numpy as np
 
 from quadruped_gym_amd import _abi
 
-from kernel_leaves import LINK_ENVS, PAIR_ENVS, QUAD_ENVS, link_max, quad_max
+from kernel_leaves import CSRC, LINK_ENVS, PAIR_ENVS, PO_WINDOW, QUAD_ENVS, ROOT, link_max, quad_max  # noqa: F401  (CSRC: the census reads it)
+from parity import MAPPINGS
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-HEADER = os.path.join(os.path.dirname(HERE), "include", "quadgym.h")
+HEADER = os.path.join(ROOT, "include", "quadgym.h")
 
 FRAME_SKIP, MAX_TIME = 4, 0.2           # 100 substeps = 25 env-steps per episode: the staggered step counters end episodes early
-PO_WINDOW, SLOTS, SEQ_K = 3, 2, 4      # SEQ_K: the env-steps in B, and so the length of the sequence launch
+SLOTS, SEQ_K = 2, 4                     # SEQ_K: the env-steps in B, and so the length of the sequence launch
 N_SMALL = 37                            # a ragged last wave in every mapping (4, 16, 32 and 64 envs per wave)
 PUSH = {"interval": 2, "duration": 1, "probability": 0.5, "force": (5.0, 20.0)}
 WRENCH_BODIES = (0, 2, 7)               # FRAME, a shin, a femur
 DYN_RANGE = {"friction": (0.3, 1.5), "payload_mass": (-0.05, 0.2), "payload_pos": ((-0.01, 0.01),) * 3, "kp_scale": (0.7, 1.3),
              "kv_scale": (0.7, 1.3), "force_scale": (0.7, 1.3), "damping_scale": (0.7, 1.3), "contact_stiffness_scale": (0.7, 1.3),
              "contact_damping_scale": (0.7, 1.3)}
-MAPS = {"lane": _abi.MAP_LANE, "quad": _abi.MAP_QUAD, "pair": _abi.MAP_PAIR}
 
 
 def base_task():
@@ -46,7 +46,7 @@ def task_fields(task):
 
 
 def dynamics_rows(n, model):
-    """Random valid rows, drawn as tests/test_kernel_leaves_gpu.py: build_states draws them."""
+    """Random valid rows, drawn as tests/leaf_states.py: build_states draws them."""
     rows = np.tile(_abi.identity_dynamics_row(model), (n, 1))
     rng = np.random.default_rng(65)
     rows[:, 0] = rng.uniform(0.3, 1.5, n)
@@ -101,7 +101,7 @@ class Ctx:
 # ---- the features: one switch on, one switch off ----------------------------------------------------------------------------------
 def _mapping_on(which):
     def on(c):
-        c.sim.set_mapping(MAPS[which])
+        c.sim.set_mapping(MAPPINGS[which])
     return on
 
 
@@ -210,7 +210,7 @@ def header_step_entries():
 
 def forms_of(features):
     """What the header offers a handle with these features.  The per-launch forms of the simulator always; the sequence form unless a
-    per-env mode is on or a walking layer is bound (refused: EXPECTED_REFUSALS of the GPU test); rings while the resident mode is on;
+    per-env mode is on or a walking layer is bound (refused: EXPECTED_REFUSALS); rings while the resident mode is on;
     the layers' own steps while they are bound."""
     f = set(features)
     forms = list(SIM_FORMS)
@@ -251,7 +251,7 @@ def expected_kernel(features, n, simds, form, robot="baked"):
     baked = robot == "baked" and not per_env
     lag, jitter = "task9" not in f, "task9" in f
     helpers = os.environ.get("QG_LINK_HELPERS", "1") != "0"
-    request = next((m for m in MAPS if m in f), "auto")
+    request = next((m for m in MAPPINGS if m in f), "auto")
     emap = effective_mapping(request, n, simds, baked, lag)
     walk = form.startswith(("walk_", "po_"))
     po = form.startswith("po_")
@@ -294,7 +294,7 @@ class Mode:
     name: str
     features: tuple
     what: str
-    table: bool = False       # also run on the table robot (rollout_recordings.table_robot)
+    table: bool = False       # also run on the table robot (helpers.write_table_robot)
     oracle: bool = False      # the f64 oracle can express the configuration
 
     @property
@@ -334,6 +334,82 @@ TABLE_PAIRS = tuple((a, b) for a in TABLE_MODES for b in TABLE_MODES if a != b)
 RING = ORDER + (ORDER[0],)
 RINGS = {"forward": tuple(zip(RING[:-1], RING[1:])), "reversed": tuple(zip(RING[::-1][:-1], RING[::-1][1:]))}
 BOUNDARY_SIZES = {"first_quad": lambda simds: link_max(simds) + 1, "first_pair": lambda simds: quad_max(simds) + 1}
+TRANSITIONS, TABLE_TRANSITIONS = PAIRS, TABLE_PAIRS      # (a) of the GPU test: every ordered pair
+
+
+# ---- (e) the documented refusals -----------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Refusal:
+    mode: str               # the mode the handle is in when the call is made
+    call: object            # ctx -> the refused call
+    quote: str              # the words of the refusal: part of the error message, and of `source`
+    source: str             # where the sentence stands: include/quadgym.h or the unit (under CSRC) whose fail(...) says it
+    size: str = "small"     # "small" (n = 37) or a key of BOUNDARY_SIZES
+    robot: str = "baked"
+    during: tuple = ()      # the transitions of (a) - (c) that meet it: (A, B, size)
+
+
+def _second_walk_layer(c):
+    from quadruped_gym_amd.task_layers import WalkLayer
+    WalkLayer(c.sim)
+
+
+def _other_obs_mode(c):
+    t = c.sim.get_task()
+    t.obs_mode = _abi.OBS_IMU
+    c.sim.set_task(t)
+
+
+def _seq(c):
+    import torch
+    dev = torch.device(f"cuda:{c.sim.device}")
+    c.sim.step_device_seq(torch.zeros((2, c.sim.n, 12), device=dev), torch.zeros((2, c.sim.n, c.sim.obs_dim + 2), device=dev))
+
+
+_BOUNDARY_INTO_RESIDENT = tuple((a, "M10", size) for size in BOUNDARY_SIZES for a in ("M9", "M0")) + \
+    tuple((a, "M10", "first_quad") for a in ORDER if a != "M10")
+EXPECTED_REFUSALS = {
+    "set_mapping(LANE) with per-env dynamics": Refusal(
+        "M4", lambda c: c.sim.set_mapping(_abi.MAP_LANE), "run in the LINK and QUAD mappings only (", "qg_capi.hip"),
+    "set_mapping(PAIR) with external wrenches": Refusal(
+        "M5", lambda c: c.sim.set_mapping(_abi.MAP_PAIR), "run in the LINK and QUAD mappings only (", "qg_capi.hip"),
+    "set_mapping(PAIR) on the table robot": Refusal(
+        "M0", lambda c: c.sim.set_mapping(_abi.MAP_PAIR), "the two-legs-per-lane kernel serves the compiled-in robot only", "qg_capi.hip",
+        robot="table"),
+    "per-env dynamics on LANE": Refusal(
+        "M3", _dyn_on, "run in the LINK and QUAD mappings only (qg_set_mapping AUTO, LINK or QUAD first)", "qg_sim_modes.hip"),
+    "external wrenches on PAIR": Refusal(
+        "M2", _xfrc_on, "run in the LINK and QUAD mappings only (qg_set_mapping AUTO, LINK or QUAD first)", "qg_sim_modes.hip"),
+    "set_task with a walking layer bound": Refusal(
+        "M7", lambda c: c.sim.set_task(base_task()), "a walking task layer is bound to this handle (it holds a copy of the task)",
+        "qg_capi.hip"),
+    "set_task with another obs_mode": Refusal("M0", _other_obs_mode, "obs_mode is fixed at qg_create", "qg_capi.hip"),
+    "step_device_seq with a walking layer bound": Refusal(
+        "M7", _seq, "qg_step_device_seq: a walking task layer is bound to this handle", "qg_sim_multi.hip"),
+    "step_device_seq with per-env dynamics": Refusal("M4", _seq, "qg_step_device_seq: not available with", "qg_sim_multi.hip"),
+    "step_device_seq with external wrenches": Refusal("M5", _seq, "qg_step_device_seq: not available with", "qg_sim_multi.hip"),
+    "resident_start with an observation pack bound": Refusal(
+        "M8", _resident_on, "a walking task layer is bound to this handle", "qg_sim_multi.hip"),
+    "resident_start with external wrenches": Refusal("M5", _resident_on, "qg_resident_start: not available with", "qg_sim_multi.hip"),
+    "resident_start above one wave per SIMD": Refusal(
+        "M0", _resident_on, "needs the one-link-per-lane mapping (AUTO up to 4096 envs, lagged sensors)", "qg_sim_multi.hip",
+        size="first_quad", during=_BOUNDARY_INTO_RESIDENT),
+    "set_mapping with the resident mode on": Refusal(
+        "M10", lambda c: c.sim.set_mapping(_abi.MAP_QUAD), "qg_set_mapping: the resident step mode is on (qg_resident_stop first)",
+        "qg_capi.hip"),
+    "a second walking layer": Refusal(
+        "M7", _second_walk_layer, "a walking task layer is already bound to this simulator (destroy it first)", "qg_walk.hip"),
+    "reset(RESET_DYNAMICS) without a range": Refusal(
+        "M0", lambda c: c.sim.reset(flags=_abi.RESET_DYNAMICS), "QG_RESET_DYNAMICS without a range (qg_set_dynamics_range)", "qg_capi.hip"),
+}
+
+
+def expected_refusal(err, a, b, size):
+    """The entry of EXPECTED_REFUSALS an error met on the way from A to B belongs to, or None."""
+    for key, r in EXPECTED_REFUSALS.items():
+        if r.quote in str(err) and (a, b, size) in r.during:
+            return key
+    return None
 
 
 def switch(ctx, features):

@@ -24,6 +24,8 @@ import numpy as np
 from oracle import po_oracle as P
 from oracle import walking_oracle as W
 
+from helpers import oracle_step_each
+
 FRAME = P.FRAME
 TIMESTEP = 0.002
 DEFAULT_CTRL = np.array([0.0, 0.0, -0.5] * 4)
@@ -46,7 +48,7 @@ def clock(nstep):
 
 
 def sensor_bound(sens, tol):
-    """|error| the one-step parity tolerance ``tol`` (TOL["A"] of tests/test_parity_gpu.py) allows on each of the 33 sensors."""
+    """|error| the one-step parity tolerance ``tol`` (TOL["A"] of tests/parity.py) allows on each of the 33 sensors."""
     sens = np.asarray(sens, np.float64)
     bound = tol["obs"][0] + tol["obs"][1] * np.abs(sens)
     bound[..., 12:15] = tol["accel"][0] + tol["accel"][1] * np.abs(sens[..., 12:15])
@@ -58,25 +60,22 @@ def physics(oracle, models, task, state, ctrl, unlagged=False):
     (post-step), ``qpos`` / ``qvel`` / ``act`` / ``nstep`` (post-step), ``done``, ``time`` (the clock after the step) and -- with
     ``unlagged`` -- ``sens_unlagged``: the sensors OF the post-step state (what a kernel that forgot the one-substep lag would show)."""
     qpos, qvel, act, nstep = state
-    m = len(qpos)
-    shared = not isinstance(models, (list, tuple))
-    batches = [oracle.Batch(models, task, m)] if shared else [oracle.Batch(models[i], task, 1) for i in range(m)]
-    out = dict(sens=np.zeros((m, 33)), qpos=np.zeros((m, 19)), qvel=np.zeros((m, 18)), act=np.zeros((m, 12)), nstep=np.zeros(m, np.int32),
-               done=np.zeros(m, bool))
-    if unlagged:
-        out["sens_unlagged"] = np.zeros((m, 33))
     ctrl = np.asarray(ctrl, np.float64)
-    for k, b in enumerate(batches):
-        sl = slice(0, m) if shared else slice(k, k + 1)
-        b.set_state(np.asarray(qpos[sl], np.float64), np.asarray(qvel[sl], np.float64), np.asarray(act[sl], np.float64), None, nstep[sl])
-        obs, _, done, _ = b.step(ctrl[sl])
+    if isinstance(models, (list, tuple)):
+        each = oracle_step_each(oracle, models, task, state, ctrl)
+        batches = each["batches"]
+        out = dict(sens=each["obs"], **{k: each[k] for k in ("done", "qpos", "qvel", "act", "nstep")})
+    else:
+        b = oracle.Batch(models, task, len(qpos))
+        b.set_state(np.asarray(qpos, np.float64), np.asarray(qvel, np.float64), np.asarray(act, np.float64), None, nstep)
+        obs, _, done, _ = b.step(ctrl)
         q, v, a, _, ns = b.get_state()
-        out["sens"][sl], out["done"][sl] = obs, done
-        out["qpos"][sl], out["qvel"][sl], out["act"][sl], out["nstep"][sl] = q, v, a, ns
-        if unlagged:
-            for j in range(b.n):
-                tmp = type(b.envs[j]).from_buffer_copy(b.envs[j])
-                out["sens_unlagged"][sl.start + j] = oracle.substep(b.model, tmp, np.clip(ctrl[sl.start + j], -1, 1), want_sensors=True)[0]
+        batches = [b]
+        out = dict(sens=obs, done=done, qpos=q, qvel=v, act=a, nstep=ns)
+    if unlagged:
+        envs = [(b.model, b.envs[j]) for b in batches for j in range(b.n)]
+        out["sens_unlagged"] = np.array([oracle.substep(model, type(e).from_buffer_copy(e), np.clip(ctrl[i], -1, 1), want_sensors=True)[0]
+                                         for i, (model, e) in enumerate(envs)])
     out["quat"] = out["qpos"][:, 3:7].copy()
     out["time"] = clock(out["nstep"])
     return out

@@ -10,7 +10,6 @@ The rollout: STEPS env-steps of frame_skip 4 from a reset, actions ``default_rng
 auto-reset with a random yaw -- a few of 256 envs fall within 40 env-steps (none in the first 10), so every recording crosses
 the reset path of its kernel."""
 import contextlib
-import json
 import os
 from dataclasses import dataclass
 
@@ -18,9 +17,12 @@ import numpy as np
 
 from quadruped_gym_amd import _abi
 
+from helpers import write_table_robot
+from kernel_leaves import PO_WINDOW, open_leaf
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "rollouts")
-STEPS, KEEP, SEED, ACTION_SEED, FALL_HEIGHT, PO_WINDOW = 40, 256, 3, 7, 0.05, 3
+STEPS, KEEP, SEED, ACTION_SEED, FALL_HEIGHT = 40, 256, 3, 7, 0.05
 
 
 @dataclass(frozen=True)
@@ -31,6 +33,7 @@ class Form:
     layer: str = "none"     # "none" (plain step, packed rows), "walk", "po"
     dyn: bool = False       # identity per-env dynamics rows: the DYN instantiation on the shared model's numbers
     helpers: bool = True    # QG_LINK_HELPERS at qg_create
+    mapping: str = "auto"   # every recording runs the mapping AUTO picks at its size
 
 
 FORMS = {
@@ -48,19 +51,6 @@ FORMS = {
     "quad_8192": Form("qg_step_kernel_quad<1,1,0,4,0,0,0>", n=8192),
     "pair_32768": Form("qg_step_kernel_pair<4,0,0>", n=32768),
 }
-
-
-def table_robot(robot_dir):
-    """A slightly modified robot (servo gains +10 %, contact stiffness -10 %, as tests/test_kernel_leaves_gpu.py): path of its JSON."""
-    root = os.path.dirname(HERE)
-    d = json.load(open(os.path.join(root, "quadruped-gym_amd", "model", "quadruped_model.json")))
-    for act in d["actuators"]:
-        act["kp"] *= 1.1
-    d["contact"]["stiffness"] *= 0.9
-    path = os.path.join(str(robot_dir), "tweaked.json")
-    with open(path, "w") as fh:
-        json.dump(d, fh)
-    return path
 
 
 def _task(task):
@@ -86,29 +76,19 @@ def _falling_walkers():
 
 
 def rollout(form: Form, robot_dir):
-    from quadruped_gym_amd.envs.walking import POWalkingQuadrupedVecEnv, WalkingQuadrupedVecEnv
     from quadruped_gym_amd.model.loader import load_model
-    from quadruped_gym_amd.sim import BatchedSim
     n = form.n
-    path = table_robot(robot_dir) if form.robot == "table" else "builtin"
-    old = os.environ.get("QG_LINK_HELPERS")
-    os.environ["QG_LINK_HELPERS"] = "1" if form.helpers else "0"
-    try:
-        if form.layer == "none":
-            model = load_model(path)[0] if form.robot == "table" else None
-            sim, env = BatchedSim(n, model=model, task=_task(_abi.default_task())), None
-            sim.reset(seed=SEED, flags=_abi.RESET_RANDOM_YAW)
-        else:
-            kw = dict(nan_direction=False, seed=SEED, model_path=path, random_init=True)
-            with _falling_walkers():
-                env = POWalkingQuadrupedVecEnv(n, obs_window=PO_WINDOW, **kw) if form.layer == "po" else WalkingQuadrupedVecEnv(n, **kw)
-            sim = env._sim
-            env.reset()
-    finally:
-        if old is None:
-            del os.environ["QG_LINK_HELPERS"]
-        else:
-            os.environ["QG_LINK_HELPERS"] = old
+    table = None
+    if form.robot == "table":
+        path = write_table_robot(robot_dir)
+        table = (path, load_model(path)[0])
+    with _falling_walkers():
+        sim, env = open_leaf(form, n, table, auto_reset=True, reset_flags=_abi.RESET_RANDOM_YAW, seed=SEED, obs_window=PO_WINDOW,
+                             random_init=True)
+    if env is None:
+        sim.reset(seed=SEED, flags=_abi.RESET_RANDOM_YAW)
+    else:
+        env.reset()
     if form.dyn:
         sim.set_dynamics(np.tile(_abi.identity_dynamics_row(sim.model), (n, 1)).astype(np.float32))
     assert sim.baked == (form.robot == "baked" and not form.dyn)

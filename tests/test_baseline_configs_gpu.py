@@ -5,13 +5,13 @@ config 3: 32 768 envs on one MI355X, randomized initial heading (QG_RESET_RANDOM
           whole shard through size-independent invariants over > 100 env-steps including auto-resets.
 config 4: 262 144 envs = 8 x 32 768; the total batch on ONE GPU through the invariants, and rank r's shard (env_index_base =
           r * 32 768) bit for bit against the same rows of the whole batch -- sharding must not change results.
-The one-step tolerances are the ones stated in tests/test_parity_gpu.py (f32 kernel vs f64 oracle).
+The one-step tolerances are the ones stated in tests/parity.py (f32 kernel vs f64 oracle).
 """
 import numpy as np
 import pytest
 
 from quadruped_gym_amd import _abi
-from test_parity_gpu import TOL, close
+from parity import TOL, close
 
 pytestmark = pytest.mark.gpu
 

@@ -7,15 +7,12 @@ takes every branch of the contact law; and moving any cp[b][i] by 1 mm moves the
 one state of every cell of that point -- so a kernel with a wrong constant there cannot pass tests/test_parity_gpu.py::
 test_every_contact_point_matches_oracle."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-import contact_cells as CC  # noqa: E402
-from test_parity_gpu import TOL  # noqa: E402
+import contact_cells as CC
+from parity import TOL
 
 
 @pytest.fixture(scope="module")

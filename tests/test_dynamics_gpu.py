@@ -2,24 +2,21 @@
 against the CPU oracle run on THAT env's own qg_model, derived here from the row table of the header (not by product code)."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 import pytest
 
 from quadruped_gym_amd import _abi
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_parity_gpu import TOL, close  # noqa: E402
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+from helpers import oracle_per_env, table_model, write_table_robot
+from leaf_states import sample_states
+from parity import MAPPINGS, TOL, close
 
 WIDE = {"friction": (0.3, 1.5), "payload_mass": (-0.1, 0.3), "payload_pos": ((-0.015, 0.015),) * 3, "kp_scale": (0.6, 1.4),
         "kv_scale": (0.6, 1.4), "force_scale": (0.6, 1.4), "damping_scale": (0.6, 1.4), "contact_stiffness_scale": (0.5, 2.0),
         "contact_damping_scale": (0.5, 2.0)}
 # (payload -0.1 .. 0.3 kg: at +-2 cm the -0.1 kg corners leave the 0.242 kg FRAME with an inertia about its centre of mass that is not
 # positive definite -- smallest eigenvalue -1.2e-5 kg m^2 -- which qg_set_dynamics_range refuses (test_refusals); +-1.5 cm passes)
-MAPS = {"link": _abi.MAP_LINK, "quad": _abi.MAP_QUAD}
 
 
 def test_header_columns_match_the_binding():
@@ -56,54 +53,7 @@ def test_dynamics_range_layout_matches_the_c_side(tmp_path):
     assert off_hi == _abi.QgDynamicsRange.hi.offset
 
 
-def env_model(oracle, base, row):
-    """The qg_model one env runs with `row` (f32 values, the table of include/quadgym.h), in f64: the payload combined with the FRAME
-    by the parallel-axis rule, the FRAME's inertia expressed about the new centre of mass."""
-    m = oracle.default_model()
-    C.memmove(C.byref(m), C.byref(base), C.sizeof(m))
-    row = np.asarray(row, np.float64)
-    m.contact_friction = row[0]
-    dm, p = row[1], row[2:5]
-    m0, c0 = base.body_mass[0], np.array(base.body_ipos[0][:])
-    I = base.body_inertia[0]
-    I0 = np.array([[I[0], I[3], I[4]], [I[3], I[1], I[5]], [I[4], I[5], I[2]]])
-    m1 = m0 + dm
-    c1 = (m0 * c0 + dm * p) / m1
-
-    def shift(mass, d):
-        return mass * (np.dot(d, d) * np.eye(3) - np.outer(d, d))
-    I1 = I0 + shift(m0, c0 - c1) + shift(dm, p - c1)
-    m.body_mass[0] = m1
-    for i in range(3):
-        m.body_ipos[0][i] = c1[i]
-    for i, v in enumerate([I1[0, 0], I1[1, 1], I1[2, 2], I1[0, 1], I1[0, 2], I1[1, 2]]):
-        m.body_inertia[0][i] = v
-    for j in range(12):
-        m.act_kp[j] = base.act_kp[j] * row[5]
-        m.act_kv[j] = base.act_kv[j] * row[6]
-        m.act_forcerange[j][0] = base.act_forcerange[j][0] * row[7]
-        m.act_forcerange[j][1] = base.act_forcerange[j][1] * row[7]
-        m.jnt_damping[j] = base.jnt_damping[j] * row[8]
-    m.contact_stiffness = base.contact_stiffness * row[9]
-    m.contact_damping = base.contact_damping * row[10]
-    return m
-
-
-def oracle_per_env(oracle, base, task, rows, state, actions):
-    """One env-step of every env on its own model; returns (obs, reward, comps, qpos, qvel, act) stacked."""
-    qpos, qvel, act, nstep = state
-    outs = []
-    for i in range(len(rows)):
-        b = oracle.Batch(env_model(oracle, base, rows[i]), task, 1)
-        b.set_state(qpos[i:i + 1].astype(np.float64), qvel[i:i + 1].astype(np.float64), act[i:i + 1].astype(np.float64), None, nstep[i:i + 1])
-        obs, rew, done, comps = b.step(actions[i:i + 1].astype(np.float64))
-        q, v, a, _, _ = b.get_state()
-        outs.append((obs[0], rew[0], comps[0], q[0], v[0], a[0]))
-    return [np.array(x) for x in zip(*outs)]
-
-
 def sampled(oracle, n, seed):
-    from make_golden import sample_states
     return sample_states(oracle.default_model(), oracle.default_task(), n, seed=seed)
 
 
@@ -118,9 +68,9 @@ def test_heterogeneous_batch_matches_per_env_oracle(oracle, mapping, fs):
     otask = oracle.default_task()
     otask.frame_skip = fs
     sim = BatchedSim(n, task=task)
-    sim.set_mapping(MAPS[mapping])
+    sim.set_mapping(MAPPINGS[mapping])
     sim.set_dynamics_range(WIDE)
-    assert sim.mapping == MAPS[mapping] and not sim.baked
+    assert sim.mapping == MAPPINGS[mapping] and not sim.baked
     sim.reset(seed=11, flags=_abi.RESET_DYNAMICS)
     rows = sim.get_dynamics()
     assert np.unique(rows[:, 0]).size > n // 2                      # the rows differ from env to env
@@ -179,11 +129,8 @@ def test_walking_and_po_steps_with_per_env_dynamics(oracle, po):
 
 
 def tweaked_model():
-    m = _abi.default_model()
-    for j in range(12):
-        m.act_kp[j] *= 1.1
+    m = table_model(_abi.default_model())
     m.body_mass[0] *= 1.05
-    m.contact_stiffness *= 0.9
     return m
 
 
@@ -207,7 +154,7 @@ def test_identity_rows_change_nothing(mapping):
     model = tweaked_model()
     a, b = BatchedSim(n, model=model, task=task), BatchedSim(n, model=model, task=task)
     for s in (a, b):
-        s.set_mapping(MAPS[mapping])
+        s.set_mapping(MAPPINGS[mapping])
         s.reset(seed=3, flags=_abi.RESET_RANDOM_YAW | _abi.RESET_JOINT_JITTER)
     b.set_dynamics(np.tile(_abi.identity_dynamics_row(model), (n, 1)))
     assert b.dynamics_on and a.mapping == b.mapping
@@ -227,15 +174,8 @@ def test_identity_rows_change_nothing(mapping):
 def test_identity_rows_change_nothing_walking(po, n, tmp_path):
     """Walking / PO envs on a tweaked robot (LINK at 128 envs, QUAD at 5000): identity rows give the bits of the handle without the
     mode, auto-resets included."""
-    import json
     from quadruped_gym_amd.envs.walking import POWalkingQuadrupedVecEnv, WalkingQuadrupedVecEnv
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    d = json.load(open(os.path.join(root, "quadruped-gym_amd", "model", "quadruped_model.json")))
-    for act in d["actuators"]:
-        act["kp"] *= 1.1
-    d["contact"]["stiffness"] *= 0.9
-    path = str(tmp_path / "tweaked.json")
-    json.dump(d, open(path, "w"))
+    path = write_table_robot(tmp_path)
     res = []
     for with_rows in (False, True):
         cls = POWalkingQuadrupedVecEnv if po else WalkingQuadrupedVecEnv
@@ -292,11 +232,7 @@ def test_baked_flag_follows_the_two_modes(robot):
     from quadruped_gym_amd._abi import QuadGymError
     from quadruped_gym_amd.sim import BatchedSim
     n = 64
-    model = None
-    if robot == "table":
-        model = _abi.default_model()
-        for j in range(12):
-            model.act_kp[j] *= 1.1
+    model = table_model(_abi.default_model(), stiffness=1.0) if robot == "table" else None
     sim = BatchedSim(n, model=model)
     dev = torch.device("cuda:0")
     actions, packed = torch.zeros((n, 12), device=dev), torch.empty((n, sim.obs_dim + 2), device=dev)

@@ -1,6 +1,6 @@
 """The checker that tests/test_external_wrench_gpu.py builds its expected results with, pinned without a GPU.
 
-``generalized_force`` turns world-frame body wrenches (a force at each body's centre of mass, a torque) into the generalized force
+``generalized_force`` (tests/helpers.py) turns world-frame body wrenches (a force at each body's centre of mass, a torque) into the generalized force
 tau = sum_b J_com,b^T F_b + J_w,b^T T_b in MuJoCo's coordinates -- free joint: linear in the world frame, angular in the FRAME's axes;
 then the twelve hinges -- from what the oracle exports: kinematics() (xpos, xmat, xcom; a joint's anchor is its child body's origin)
 and jnt_axis (child-body axes).  With F_b = m_b dg it must be what a change of gravity does to the oracle's own inverse dynamics; its
@@ -10,39 +10,14 @@ import os
 import re
 import shutil
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from quadruped_gym_amd import _abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-NV, NBODY = 18, 13
-
-
-def _leg_bodies(j):
-    """Bodies hinge j moves: its child body j + 1 and the links below it on the same leg."""
-    leg = j // 3
-    return range(j + 1, 3 * leg + 4)
-
-
-def generalized_force(oracle, model, qpos, F, T):
-    """tau [18] of world-frame forces F [13, 3] (at each body's centre of mass) and torques T [13, 3]."""
-    xpos, xmat, xcom = oracle.kinematics(model, qpos)
-    F, T = np.asarray(F, np.float64), np.asarray(T, np.float64)
-    tau = np.zeros(NV)
-    p0, R0 = xpos[0], xmat[0]
-    for b in range(NBODY):
-        tau[0:3] += F[b]
-        tau[3:6] += R0.T @ (T[b] + np.cross(xcom[b] - p0, F[b]))
-    for j in range(12):
-        axis = xmat[j + 1] @ np.array(model.jnt_axis[j][:])
-        anchor = xpos[j + 1]
-        for b in _leg_bodies(j):
-            tau[6 + j] += axis @ (T[b] + np.cross(xcom[b] - anchor, F[b]))
-    return tau
+from helpers import NBODY, NV, ROOT, generalized_force
+from leaf_states import sample_states
 
 
 def _quat_mul(a, b):
@@ -76,7 +51,6 @@ def gravity_model(oracle, base, dg):
 
 @pytest.fixture(scope="module")
 def seeded(oracle):
-    from make_golden import sample_states
     q, v, _, _ = sample_states(oracle.default_model(), oracle.default_task(), 12, seed=23)
     return q, v
 

@@ -1,12 +1,10 @@
 """External body wrenches (qg_set_xfrc*, MuJoCo's data.xfrc_applied) and the push schedule (qg_set_push), on the GPU.
 
 The oracle has no external-force input, so the expected results come from what it exports: a force m_b dg on every body is a change
-of gravity; any other wrench adds h A^-1 tau to one substep's velocity (A = M + h D and tau from tests/test_external_wrench_checker.py).
+of gravity; any other wrench adds h A^-1 tau to one substep's velocity (A = M + h D; tau: generalized_force of tests/helpers.py).
 Every check runs on the per-env-dynamics leaves of tests/kernel_leaves.py (the kernels wrench mode runs), with their sizes and the
-seeded, FRAME-contact and femur-contact states of tests/test_kernel_leaves_gpu.py."""
+seeded, FRAME-contact and femur-contact states of tests/leaf_states.py."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -14,14 +12,10 @@ import pytest
 from quadruped_gym_amd import _abi
 from quadruped_gym_amd._abi import QuadGymError
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
-from kernel_leaves import LEAVES  # noqa: E402
-from test_dynamics_gpu import env_model  # noqa: E402
-from test_external_wrench_checker import generalized_force  # noqa: E402
-from test_kernel_leaves_gpu import MAPS, TAIL, _simds, layout, states, table_robot  # noqa: E402,F401
-from test_parity_gpu import TOL, close  # noqa: E402
+from helpers import env_model, generalized_force, oracle_step_each, table_robot  # noqa: F401  (table_robot: a fixture)
+from kernel_leaves import LEAVES, open_leaf
+from leaf_states import TAIL, layout, states  # noqa: F401  (states: a fixture)
+from parity import MAPPINGS, TOL, close, simds
 
 pytestmark = pytest.mark.gpu
 
@@ -30,25 +24,6 @@ DYN_CASES = [(name, k) for name, leaf in LEAVES.items() if leaf.dyn for k in ran
 PLAIN_DYN = [name for name, leaf in LEAVES.items() if leaf.dyn and leaf.layer == "none"]
 IDS = [f"{name}-{k}" for name, k in DYN_CASES]
 PUSH = {"interval": 3, "duration": 2, "probability": 0.6, "force": (4.0, 12.0)}
-
-
-def make_handle(leaf, n, robot, monkeypatch, fs=4, auto_reset=False, seed=3):
-    """The handle (and VecEnv) of a per-env-dynamics leaf; frame_skip `fs`."""
-    from quadruped_gym_amd.envs.walking import POWalkingQuadrupedVecEnv, WalkingQuadrupedVecEnv
-    from quadruped_gym_amd.sim import BatchedSim
-    monkeypatch.setenv("QG_LINK_HELPERS", "1" if leaf.helpers else "0")
-    path, model = robot if leaf.robot == "table" else ("builtin", None)
-    if leaf.layer == "none":
-        task = _abi.default_task()
-        task.use_fall, task.fall_height, task.frame_skip, task.auto_reset = 1, 0.05, fs, int(auto_reset)
-        sim, env = BatchedSim(n, model=model, task=task), None
-    else:
-        cls = POWalkingQuadrupedVecEnv if leaf.layer == "po" else WalkingQuadrupedVecEnv
-        env = cls(n, nan_direction=False, seed=seed, model_path=path, frame_skip=fs)
-        sim = env._sim
-    if leaf.mapping != "auto":
-        sim.set_mapping(MAPS[leaf.mapping])
-    return sim, env
 
 
 def copy_model(oracle, base, dg=None):
@@ -62,15 +37,8 @@ def copy_model(oracle, base, dg=None):
 
 def oracle_each(oracle, models, task, state, actions):
     """One env-step of state i on models[i]: (obs, done, qpos, qvel, act)."""
-    q, v, a, ns = state
-    outs = []
-    for i, mdl in enumerate(models):
-        b = oracle.Batch(mdl, task, 1)
-        b.set_state(q[i:i + 1].astype(np.float64), v[i:i + 1].astype(np.float64), a[i:i + 1].astype(np.float64), None, ns[i:i + 1])
-        obs, _, done, _ = b.step(actions[i:i + 1].astype(np.float64))
-        qo, vo, ao, _, _ = b.get_state()
-        outs.append((obs[0], done[0], qo[0], vo[0], ao[0]))
-    return [np.array(x) for x in zip(*outs)]
+    out = oracle_step_each(oracle, models, task, state, actions)
+    return [out[k] for k in ("obs", "done", "qpos", "qvel", "act")]
 
 
 def body_frame(obs, vec):
@@ -108,12 +76,12 @@ def compare(leaf, n, got, ref, idx, done, accel_shift, what):
 # ---- 1. gravity equivalence, and 6. combined with per-env dynamics --------------------------------------------------------------------
 @pytest.mark.parametrize("combined", [False, True], ids=["wrench", "with-dynamics"])
 @pytest.mark.parametrize("name,k", DYN_CASES, ids=IDS)
-def test_body_forces_equal_a_gravity_change(oracle, states, table_robot, monkeypatch, name, k, combined):
+def test_body_forces_equal_a_gravity_change(oracle, states, table_robot, name, k, combined):
     """F_b = m_b dg_i on all 13 bodies (dg_i with horizontal components, per state) against the oracle run with gravity g + dg_i;
     `combined`: friction and servo dynamics rows as well, the oracle on each state's own model."""
     leaf = LEAVES[name]
-    n = leaf.sizes[k](_simds())
-    sim, env = make_handle(leaf, n, table_robot, monkeypatch)
+    n = leaf.sizes[k](simds())
+    sim, env = open_leaf(leaf, n, table_robot)
     m, state, actions = states["m"], states["state"], states["actions"]
     dg = np.random.default_rng(71).uniform(-3.0, 3.0, (m, 3))
     rows_dyn = None
@@ -162,12 +130,12 @@ def quat_step(q0, w, h):
 
 
 @pytest.mark.parametrize("name,k", DYN_CASES, ids=IDS)
-def test_arbitrary_wrenches_add_h_Ainv_tau(oracle, states, table_robot, monkeypatch, name, k):
+def test_arbitrary_wrenches_add_h_Ainv_tau(oracle, states, table_robot, name, k):
     """Random forces and torques on the FRAME, a femur and a foot at frame_skip 1: qvel = oracle + h A^-1 tau, qpos by the oracle's
     integrator from that velocity, the accelerometer moved by R^T (A^-1 tau)[0:3]."""
     leaf = LEAVES[name]
-    n = leaf.sizes[k](_simds())
-    sim, env = make_handle(leaf, n, table_robot, monkeypatch, fs=1)
+    n = leaf.sizes[k](simds())
+    sim, env = open_leaf(leaf, n, table_robot, fs=1)
     m, state, actions = states["m"], states["state"], states["actions"]
     q, v, a, ns = state
     task = sim.get_task()
@@ -210,14 +178,14 @@ def test_arbitrary_wrenches_add_h_Ainv_tau(oracle, states, table_robot, monkeypa
 
 # ---- 3. zero rows ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,k", DYN_CASES, ids=IDS)
-def test_zero_rows_keep_the_bits(states, table_robot, monkeypatch, name, k):
+def test_zero_rows_keep_the_bits(states, table_robot, name, k):
     """50 auto-resetting env-steps: zero rows in wrench mode give the bits of the mode off on the same per-env kernel (identity dynamics
     rows in both); clear_external_wrench() returns to the kernel the handle ran before."""
     leaf = LEAVES[name]
-    n = leaf.sizes[k](_simds())
+    n = leaf.sizes[k](simds())
     runs = []
     for wrench in (False, True):
-        sim, env = make_handle(leaf, n, table_robot, monkeypatch, auto_reset=True)
+        sim, env = open_leaf(leaf, n, table_robot, auto_reset=True)
         sim.set_dynamics(np.tile(_abi.identity_dynamics_row(sim.model), (n, 1)))
         after = None
         if wrench:
@@ -285,14 +253,14 @@ def expected_push(L, seed, env_index, episode, s, p):
 
 
 @pytest.mark.parametrize("name", PLAIN_DYN)
-def test_push_schedule_matches_explicit_rows(oracle, states, table_robot, monkeypatch, name):
+def test_push_schedule_matches_explicit_rows(oracle, states, table_robot, name):
     """A handle with the schedule, one env-step at a time over two episodes, against a twin that gets the expected push as explicit
     FRAME rows from the same state."""
     leaf = LEAVES[name]
-    n = leaf.sizes[0](_simds())
+    n = leaf.sizes[0](simds())
     L = oracle.lib()
-    sim, _ = make_handle(leaf, n, table_robot, monkeypatch)
-    twin, _ = make_handle(leaf, n, table_robot, monkeypatch)
+    sim, _ = open_leaf(leaf, n, table_robot)
+    twin, _ = open_leaf(leaf, n, table_robot)
     sim.set_push_schedule(PUSH)
     twin.set_external_wrench(np.zeros((n, NBODY, NX), np.float32))
     q, v, a, _ = states["state"]
@@ -355,8 +323,8 @@ def test_sharding_snapshots_and_device_form(table_robot, mapping):
     rng = np.random.default_rng(76)
     acts = [rng.uniform(-1, 1, (n, 12)).astype(np.float32) for _ in range(12)]
     # one handle of n against two of n / 2 with env_index_base
-    whole = _plain(n, model, MAPS[mapping])
-    parts = [_plain(h, model, MAPS[mapping], base=b) for b in (0, h)]
+    whole = _plain(n, model, MAPPINGS[mapping])
+    parts = [_plain(h, model, MAPPINGS[mapping], base=b) for b in (0, h)]
     for s in [whole] + parts:
         s.set_push_schedule(PUSH)
         s.reset(seed=31)
@@ -385,7 +353,7 @@ def test_sharding_snapshots_and_device_form(table_robot, mapping):
     assert all(np.array_equal(x, y) for x, y in zip(first, again))
     # the device form: eager, and captured into a graph on one stream, against the host form
     dev = torch.device("cuda:0")
-    host, eager, graph = (_plain(n, model, MAPS[mapping]) for _ in range(3))
+    host, eager, graph = (_plain(n, model, MAPPINGS[mapping]) for _ in range(3))
     for s in (host, eager, graph):
         s.set_push_schedule(PUSH)
         s.reset(seed=32)

@@ -1,26 +1,10 @@
 """The committed golden vectors (tests/golden/step_vectors.npz, written by tools/make_golden.py)
 must be reproduced exactly by the CPU oracle -- this pins the oracle against silent changes and
 keeps the fixture honest.  (The reference holds no golden vectors for this path)"""
-import os
-
 import numpy as np
 import pytest
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "step_vectors.npz")
-
-
-@pytest.fixture(scope="module")
-def gold():
-    return dict(np.load(GOLD))
-
-
-def configure(task, case):
-    task.use_fall = 1
-    task.fall_height = 0.05
-    if case == "B":
-        task.frame_skip = 20
-        task.obs_mode = 1
-    return task
+from parity import configure, gold  # noqa: F401  (gold: a fixture)
 
 
 @pytest.mark.parametrize("case", ["A", "B"])

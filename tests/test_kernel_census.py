@@ -3,12 +3,10 @@ tests/kernel_leaves.py -- an oracle case in tests/test_kernel_leaves_gpu.py, or 
 for the many-env-steps forms -- and the tables list nothing the source cannot launch."""
 import os
 import re
-import sys
 
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import kernel_leaves as K  # noqa: E402
+import kernel_leaves as K
 
 
 @pytest.fixture(scope="module")

@@ -5,7 +5,8 @@ m seeded states -- random-action rollout states, 32 with the FRAME pressing on t
 with its state's oracle row at O(m) oracle cost.  The layout puts every state once at the front, then 64-env blocks of states
 whose FRAME and femurs stay off the floor, each with exactly ONE FRAME- or femur-contact env at a lane position that moves from
 block to block (the wave-uniform contact skips and the femur cull in both directions), and at the back states that neither touch
-nor terminate (the last, partial workgroup holds one at n = 4097 and 32 769).  Tolerances: TOL["A"] of tests/test_parity_gpu.py.
+nor terminate (the last, partial workgroup holds one at n = 4097 and 32 769).  Tolerances: TOL["A"] of tests/parity.py.  The pools, the
+layout and the expected chains live in tests/leaf_states.py, the handle builder in tests/kernel_leaves.py.
 
 What is pinned per leaf.  Every leaf: qpos, qvel, act and the step counter.  Plain and walking leaves: the 33-value observation.  Plain
 leaves: reward and terminations.  Walking AND partially observable leaves (tests/po_step_reference.py, a chain of the oracles that
@@ -33,267 +34,44 @@ states the 30 that stand upright (FRAME points 4-7, femur points 1, 3, 4 and 6, 
 ONLY_ON_ITS_BACK names the points those leaves never see in a block -- the FRAME's top corners and top face and femur points 0, 2, 5
 and 7 touch the floor only with the robot overturned, which the flip termination ends.  check_leaf asserts which built states land in
 a block and prints the count."""
-import json
-import os
-import sys
-
 import numpy as np
 import pytest
 
-from quadruped_gym_amd import _abi
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
-import contact_cells as CC  # noqa: E402
-import po_step_reference as R  # noqa: E402
-from kernel_leaves import LEAVES  # noqa: E402
-from test_dynamics_gpu import env_model, oracle_per_env  # noqa: E402
-from test_parity_gpu import TOL, close  # noqa: E402
+import contact_cells as CC
+import po_step_reference as R
+from helpers import oracle_per_env, table_robot  # noqa: F401  (table_robot: a fixture)
+from kernel_leaves import LEAVES, PO_WINDOW, open_leaf
+from leaf_states import RECORD, TAIL, cell_chains, cell_states, chains, layout, same_bits_wherever_it_sits, states  # noqa: F401  (fixtures)
+from parity import TOL, close, simds
 
 pytestmark = pytest.mark.gpu
 
-GOLD = os.path.join(HERE, "golden", "step_vectors.npz")
-M_SAMPLE, M_CONTACT, BLOCK, TAIL = 256, 32, 64, 16
-MAPS = {"lane": _abi.MAP_LANE, "quad": _abi.MAP_QUAD, "pair": _abi.MAP_PAIR, "link": _abi.MAP_LINK}
 CASES = [(name, k) for name, leaf in LEAVES.items() for k in range(len(leaf.sizes))]
-PO_WINDOW = 3                 # the PO leaves' obs_window: the newest frame's place in the FIFO is part of the check
-RECORD = "QG_PO_PARITY_OUT"
 
 
-def _simds():
-    import torch
-    return 4 * torch.cuda.get_device_properties(0).multi_processor_count
-
-
-UPRIGHT = 0.05                 # z component of the base's z axis above which a built state counts as upright (3 degrees from lying on its side)
-# the points of the second pool that only touch the floor with the robot on its back: the FRAME's top corners and top face, and
-# points 0, 2, 5 and 7 of every femur.  Every state of their cells ends a walking / PO episode (flip termination), so those leaves
-# step them at the front only; the plain-step leaves put them into blocks
-ONLY_ON_ITS_BACK = {(0, i) for i in (0, 1, 2, 3, 8, 9, 10, 11)} | {(b, i) for b in (1, 4, 7, 10) for i in (0, 2, 5, 7)}
-
-
-def _upright(qpos):
-    return 1.0 - 2.0 * (qpos[..., 4] ** 2 + qpos[..., 5] ** 2) > UPRIGHT
-
-
-def cell_contact_states(oracle):
-    """The contact part of the second pool, from tests/golden/contact_cells.npz: the cull-edge states, then one state per sample point
-    of the FRAME and of the femurs -- of the point's cells the first pressed state that stands upright (the walking and PO leaves end
-    the episode of a robot on its back), else the first grazing one that does, else the first pressed one.  Returns the states, their
-    (kind, body, point) labels and which of them stand upright."""
-    fix = CC.load()
-    cells = CC.cell_index(fix)
-    pick = [int(e) for e in np.flatnonzero(fix["kind"] == CC.KIND_EDGE)]
-    assert len(pick) == 16
-    for b in (0, 1, 4, 7, 10):
-        for i in range(12 if b == 0 else 8):
-            cand = cells[(b, i, CC.PRESS)] + cells[(b, i, CC.GRAZE)]
-            up = [e for e in cand if _upright(fix["qpos"][e])]
-            pick.append(up[0] if up else cand[0])
-    pick = np.array(pick)
-    label = np.stack([fix[k][pick] for k in ("kind", "body", "point")], 1)
-    up = _upright(fix["qpos"][pick])
-    cellpts = label[:, 0] == CC.KIND_CELL
-    assert {(int(b), int(i)) for _, b, i in label[cellpts & ~up]} == ONLY_ON_ITS_BACK
-    return [fix[k][pick] for k in ("qpos", "qvel", "act", "nstep")], label, up
-
-
-def build_states(oracle, pool="golden"):
-    """The leaf test's states, actions, per-env dynamics rows and -- for the walking and PO leaves -- the second step's actions and the
-    commands (no GPU: tests/test_po_step_reference.py runs the checker's own tests on exactly these).  `pool`: "golden" or "cells"
-    (module docstring)."""
-    from make_golden import sample_states
-    model, task = oracle.default_model(), oracle.default_task()
-    if pool == "golden":
-        # the FRAME and femur contacts: the 2 x 32 contact_states of the golden fixture (drawing them takes minutes of rejection sampling)
-        gold = np.load(GOLD)
-        contact = [gold[k][-2 * M_CONTACT:] for k in ("qpos", "qvel", "act", "nstep")]
-    else:
-        contact, label, upright = cell_contact_states(oracle)
-    q, v, a, ns = (np.concatenate(x) for x in zip(sample_states(model, task, M_SAMPLE, seed=61), contact))
-    m = len(q)
-    actions = np.random.default_rng(64).uniform(-1, 1, (m, 12)).astype(np.float32)
-    census = oracle.contact_census(model, task.frame_skip, q, v, a, ns, actions, extra=0)
-    frame, femur = census[:, :, 0].any(1), census[:, :, [1, 4, 7, 10]].any((1, 2))
-    touch = frame | femur
-    if pool == "golden":
-        assert frame[M_SAMPLE:M_SAMPLE + M_CONTACT].sum() >= 24 and femur[M_SAMPLE + M_CONTACT:].sum() >= 24
-        extra = {}
-    else:
-        cellpts = label[:, 0] == CC.KIND_CELL
-        assert frame[M_SAMPLE:][cellpts & (label[:, 1] == 0)].all() and femur[M_SAMPLE:][cellpts & (label[:, 1] > 0)].all()
-        touch[M_SAMPLE:] = True                               # the shins' and feet's cull-edge states take a block of their own too
-        # the rollout states that touch with the FRAME or a femur leave this pool: the blocks go to the built states only (which of
-        # them, per leaf, is up to the terminations: check_leaf asserts and prints it)
-        stay = np.r_[~touch[:M_SAMPLE], np.ones(m - M_SAMPLE, bool)]
-        q, v, a, ns, actions, touch = q[stay], v[stay], a[stay], ns[stay], actions[stay], touch[stay]
-        m = len(q)
-        extra = dict(built=np.flatnonzero(touch), label=label, upright=upright)
-        assert len(extra["built"]) == len(label) == 60
-    rows = np.tile(_abi.identity_dynamics_row(_abi.default_model()), (m, 1))
-    rng = np.random.default_rng(65)
-    rows[:, 0] = rng.uniform(0.3, 1.5, m)
-    rows[:, 1] = rng.uniform(-0.05, 0.2, m)
-    rows[:, 2:5] = rng.uniform(-0.01, 0.01, (m, 3))
-    rows[:, 5:] = rng.uniform(0.7, 1.3, (m, 6))
-    # walking / PO leaves: a second env-step from the same states with actions that reach beyond the clip, and a command per state
-    rng = np.random.default_rng(66)
-    actions2 = rng.uniform(-1.3, 1.3, (m, 12)).astype(np.float32)
-    speed, alpha, theta = rng.uniform(0.2, 1.0, m), rng.uniform(-np.pi, np.pi, m), rng.uniform(-np.pi, np.pi, m)
-    velocity = np.stack([speed * np.cos(alpha), speed * np.sin(alpha)], 1).astype(np.float32)
-    heading = np.stack([np.cos(theta), np.sin(theta)], 1).astype(np.float32)
-    return dict(state=(q, v, a, ns), actions=actions, touch=touch, rows=rows.astype(np.float32), m=m, actions2=actions2,
-                velocity=velocity, heading=heading, pool=pool, **extra)
-
-
-def walking_task(frame_skip=4, max_time=10.0):
-    """The task a walking / PO env of the leaf test runs (envs/walking.py: flip and time-limit terminations, no fall)."""
-    task = _abi.default_task()
-    task.frame_skip, task.max_time, task.use_time_limit, task.use_fall, task.use_flip = frame_skip, max_time, 1, 0, 1
-    return task
-
-
-def _task_numbers(task):
-    return (task.frame_skip, task.max_time, task.use_time_limit, task.use_fall, task.use_flip, task.sensor_lag, task.obs_mode)
-
-
-def expected_chain(oracle, st, model, task, dyn):
-    """The two env-steps of a walking / PO leaf on the checker: the reset stack, the outputs of both steps and the reward components'
-    sensitivity per step.  One chain serves the walking and the PO leaves of one robot (the frames do not feed the reward)."""
-    chk = R.StepChecker(oracle, st["m"], task.frame_skip, settling_time=0.0, obs_window=PO_WINDOW, unit_zero=True)
-    reset_stack = chk.reset()                                   # commands are still zero when the env is reset
-    chk.set_commands(st["velocity"], st["heading"])
-    models = [env_model(oracle, model, row) for row in st["rows"]] if dyn else model
-    schedule = [(st["state"], st["actions"]), (st["state"], st["actions2"])]
-    sensitivity, outs = R.reward_sensitivity(chk, models, task, schedule, TOL["A"], patterns=8, seed=67)
-    return dict(reset=reset_stack, outs=outs, sensitivity=sensitivity, dt=chk.dt)
-
-
-@pytest.fixture(scope="module")
-def states(oracle):
-    return build_states(oracle)
-
-
-@pytest.fixture(scope="module")
-def cell_states(oracle):
-    return build_states(oracle, pool="cells")
-
-
-def _chain_cache(oracle, states):
-    """(robot, dyn) -> expected_chain, computed once per robot and shared by its leaves; prints the measured sensitivities."""
-    cache = {}
-
-    def get(robot, dyn, model, task):
-        key = (robot, dyn)
-        if key not in cache:
-            c = expected_chain(oracle, states, model, task, dyn)
-            c["task"] = _task_numbers(task)
-            for k, row in enumerate(c["sensitivity"]):
-                R.record(RECORD, f"sensitivity pool={states['pool']} robot={robot} dyn={int(dyn)} step={k + 1}: " + " ".join(f"{x:.3e}" for x in row))
-            cache[key] = c
-        c = cache[key]
-        assert c["task"] == _task_numbers(task) == _task_numbers(walking_task()), "the walking and PO leaves run one task"
-        return c
-    return get
-
-
-@pytest.fixture(scope="module")
-def chains(oracle, states):
-    return _chain_cache(oracle, states)
-
-
-@pytest.fixture(scope="module")
-def cell_chains(oracle, cell_states):
-    return _chain_cache(oracle, cell_states)
-
-
-@pytest.fixture(scope="module")
-def table_robot(tmp_path_factory):
-    """A slightly modified robot (servo gains +10 %, contact stiffness -10 %): the table-driven kernels run it."""
-    from quadruped_gym_amd.model.loader import load_model
-    root = os.path.dirname(HERE)
-    d = json.load(open(os.path.join(root, "quadruped-gym_amd", "model", "quadruped_model.json")))
-    for act in d["actuators"]:
-        act["kp"] *= 1.1
-    d["contact"]["stiffness"] *= 0.9
-    path = str(tmp_path_factory.mktemp("robot") / "tweaked.json")
-    json.dump(d, open(path, "w"))
-    return path, load_model(path)[0]
-
-
-def layout(n, m, touch, tail_ok, block_ok=None):
-    """State index of every env (see the module docstring).  `tail_ok`: the states that may fill the blocks and the tail (they neither
-    touch nor terminate); `block_ok`: the touching states that may be a block's one contact env (default: those of `tail_ok`)."""
-    quiet = np.flatnonzero(~touch & tail_ok)
-    contact = np.flatnonzero(touch & (tail_ok if block_ok is None else block_ok))
-    idx = np.empty(n, np.int64)
-    front = min(n, m)
-    idx[:front] = np.arange(front)
-    rest = np.arange(front, n)
-    idx[rest] = quiet[rest % len(quiet)]
-    blk, off = (rest - m) // BLOCK, (rest - m) % BLOCK
-    one = off == (blk * 41 + 7) % BLOCK                   # 41: odd, so the position walks through all 64 lanes of the block
-    idx[rest[one]] = contact[blk[one] % len(contact)]
-    if n > 4 * TAIL:
-        idx[-TAIL:] = quiet[np.arange(TAIL) % len(quiet)]
-    return idx
-
-
-def _handle(leaf, n, robot, monkeypatch):
+def _handle(leaf, n, robot):
     """The handle (and the VecEnv, for walking / PO leaves) the row describes."""
-    from quadruped_gym_amd.envs.walking import POWalkingQuadrupedVecEnv, WalkingQuadrupedVecEnv
-    from quadruped_gym_amd.sim import BatchedSim
-    monkeypatch.setenv("QG_LINK_HELPERS", "1" if leaf.helpers else "0")
-    path, model = robot if leaf.robot == "table" else ("builtin", None)
-    if leaf.layer == "none":
-        task = _abi.default_task()
-        task.use_fall, task.fall_height = 1, 0.05
-        sim, env = BatchedSim(n, model=model, task=task), None
-    else:
-        cls = POWalkingQuadrupedVecEnv if leaf.layer == "po" else WalkingQuadrupedVecEnv
-        kw = dict(obs_window=PO_WINDOW) if leaf.layer == "po" else {}
-        env = cls(n, nan_direction=False, seed=3, model_path=path, **kw)
-        sim = env._sim
-    if leaf.mapping != "auto":
-        sim.set_mapping(MAPS[leaf.mapping])
+    sim, env = open_leaf(leaf, n, robot, obs_window=PO_WINDOW)
     assert sim.baked == (leaf.robot == "baked")
     return sim, env
 
 
 @pytest.mark.parametrize("name,k", CASES, ids=[f"{name}-{k}" for name, k in CASES])
-def test_leaf_matches_oracle(oracle, states, chains, table_robot, monkeypatch, name, k):
-    check_leaf(oracle, states, chains, table_robot, monkeypatch, name, k)
+def test_leaf_matches_oracle(oracle, states, chains, table_robot, name, k):
+    check_leaf(oracle, states, chains, table_robot, name, k)
 
 
 @pytest.mark.parametrize("name,k", CASES, ids=[f"{name}-{k}" for name, k in CASES])
-def test_leaf_matches_oracle_on_contact_cells(oracle, cell_states, cell_chains, table_robot, monkeypatch, name, k):
+def test_leaf_matches_oracle_on_contact_cells(oracle, cell_states, cell_chains, table_robot, name, k):
     """The second pool: cull-edge states and every sample point of the FRAME and the femurs (module docstring: which of them a leaf
     puts into blocks)."""
-    check_leaf(oracle, cell_states, cell_chains, table_robot, monkeypatch, name, k)
+    check_leaf(oracle, cell_states, cell_chains, table_robot, name, k)
 
 
-def same_bits_wherever_it_sits(idx, touch, m, restarted, arrays):
-    """A touching state's env in a block gives the bits of its env at the front (another lane, other neighbours in its wave): the
-    wave-uniform contact skips and the femur cull change nothing for the env that does touch.  A grazing contact dropped by a skip
-    moves the step by less than TOL["A"]; only this comparison sees it.  `restarted`: the envs a task layer restarted in the step
-    with draws of their own (left out; a plain step restarts none).  `arrays`: name -> per-env array.  Returns how many envs were
-    compared."""
-    restarted = np.asarray(restarted, bool)
-    later = np.flatnonzero(touch[idx] & (np.arange(len(idx)) >= m) & ~restarted)
-    assert not restarted[idx[later]].any()
-    for name, x in arrays.items():
-        x = np.ascontiguousarray(x)
-        here, front = (x[e].reshape(len(later), -1).view(np.uint8) for e in (later, idx[later]))
-        bad = later[(here != front).any(1)]
-        assert not len(bad), f"{name}: envs {bad[:8].tolist()} differ from the envs {idx[bad[:8]].tolist()} that hold the same touching states"
-    return len(later)
-
-
-def check_leaf(oracle, states, chains, table_robot, monkeypatch, name, k):
+def check_leaf(oracle, states, chains, table_robot, name, k):
     leaf = LEAVES[name]
-    n = leaf.sizes[k](_simds())
-    sim, env = _handle(leaf, n, table_robot, monkeypatch)
+    n = leaf.sizes[k](simds())
+    sim, env = _handle(leaf, n, table_robot)
     m, (q, v, a, ns), actions = states["m"], states["state"], states["actions"]
     # the oracle on the handle's own numbers: its model (per-env dynamics: each state's row applied to it) and the task it runs
     task = sim.get_task()

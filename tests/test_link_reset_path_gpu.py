@@ -5,17 +5,12 @@ that restarts (the task's ``default_ctrl``, fetched ahead of the state stores) a
 One env-step from states of which a seeded subset stands below the fall height (n = 259: a last wave of three envs; n = 4: one wave
 in one workgroup), then twenty env-steps under a time limit of three, where every env restarts again and again, in four forms of
 the kernel."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-import rollout_recordings as R  # noqa: E402
+from helpers import write_table_robot
 
-from quadruped_gym_amd import _abi  # noqa: E402
+from quadruped_gym_amd import _abi
 
 pytestmark = pytest.mark.gpu
 
@@ -118,7 +113,7 @@ def test_counter_advance_equals_the_number_of_dones_under_a_short_time_limit(for
         sim = env._sim
         env.reset()
     else:
-        model = load_model(R.table_robot(tmp_path))[0] if form == "table" else _abi.default_model()
+        model = load_model(write_table_robot(tmp_path))[0] if form == "table" else _abi.default_model()
         sim = BatchedSim(N, model=model if form == "table" else None, task=_limit_task(model))
         sim.reset(seed=SEED, flags=_abi.RESET_RANDOM_YAW)
     try:

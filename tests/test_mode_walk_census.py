@@ -2,15 +2,11 @@
 pair, every step form the header offers, every documented refusal, names that the leaf tables know, walks that enter every mode, and
 step counters that give the resets the GPU test asks for -- on the f64 oracle alone."""
 import os
-import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-import mode_walk as W  # noqa: E402
-import test_mode_walk_gpu as G  # noqa: E402
-from kernel_leaves import LEAVES, MULTI_TWINS  # noqa: E402
+import mode_walk as W
+from kernel_leaves import LEAVES, MULTI_TWINS
 
 SIMDS = 1024                  # an MI355X
 MODE_NAMES = ("M0", "M1", "M2", "M3", "M4", "M5", "M6", "M7", "M8", "M9", "M10")
@@ -27,10 +23,10 @@ DOCUMENTED = ("set_mapping(LANE) with per-env dynamics", "set_mapping(PAIR) with
 def test_every_mode_and_every_ordered_pair_is_walked():
     assert tuple(W.MODES) == MODE_NAMES
     want = {(a, b) for a in MODE_NAMES for b in MODE_NAMES if a != b}
-    assert len(want) == 110 and set(G.TRANSITIONS) == want and len(G.TRANSITIONS) == 110
+    assert len(want) == 110 and set(W.TRANSITIONS) == want and len(W.TRANSITIONS) == 110
     table = ("M0", "M1", "M4", "M7", "M8")
     assert W.TABLE_MODES == table
-    assert set(G.TABLE_TRANSITIONS) == {(a, b) for a in table for b in table if a != b}
+    assert set(W.TABLE_TRANSITIONS) == {(a, b) for a in table for b in table if a != b}
     for ring in W.RINGS.values():          # each ring visits every mode once and comes back
         assert len(ring) == 11 and {a for a, _ in ring} == set(MODE_NAMES) == {b for _, b in ring}
         assert all(ring[k][1] == ring[k + 1][0] for k in range(10)) and ring[0][0] == ring[-1][1] == "M0"
@@ -58,7 +54,7 @@ def test_every_expected_kernel_is_a_known_instantiation():
 
 def test_every_step_form_of_the_header_is_walked():
     assert W.header_step_entries() == set(W.FORMS.values())
-    blocked_seq = [set(W.MODES[r.mode].features) for r in G.EXPECTED_REFUSALS.values() if r.call is G._seq]
+    blocked_seq = [set(W.MODES[r.mode].features) for r in W.EXPECTED_REFUSALS.values() if r.call is W._seq]
     needs = {"resident": "resident", "walk_step": "walk", "walk_step_device": "walk", "po_step": "po", "po_step_device": "po"}
     for mode in W.MODES.values():
         assert len(set(mode.forms)) == len(mode.forms)
@@ -71,13 +67,13 @@ def test_every_step_form_of_the_header_is_walked():
 
 
 def test_expected_refusals_are_documented_and_reached():
-    assert set(G.EXPECTED_REFUSALS) == set(DOCUMENTED)
+    assert set(W.EXPECTED_REFUSALS) == set(DOCUMENTED)
     ring_pairs = {p for ring in W.RINGS.values() for p in ring}
-    for key, r in G.EXPECTED_REFUSALS.items():
+    for key, r in W.EXPECTED_REFUSALS.items():
         assert r.mode in W.MODES and r.robot in ("baked", "table"), key
         assert r.size == "small" or r.size in W.BOUNDARY_SIZES, key
         assert r.robot == "baked" or W.MODES[r.mode].table, key
-        assert r.quote in open(os.path.join(G.CSRC, r.source)).read(), key
+        assert r.quote in open(os.path.join(W.CSRC, r.source)).read(), key
         reached = 0
         for a, b, size in r.during:
             assert a in W.MODES and b in W.MODES and a != b, key

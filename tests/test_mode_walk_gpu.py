@@ -7,7 +7,7 @@ load_state, ObsPack.state / load_state -- and both take the same env-steps throu
 BITS: every output of every step, the final snapshot (physics, reset streams, dynamics rows, wrench rows, layer blobs) and
 last_step_kernel, which is also the name tests/kernel_leaves.py pins against the f64 oracle.  The task, the effective mapping and the
 baked flag are not copied into the twin: the walked handle must have the ones a fresh handle has.  No tolerance is involved, except in
-the oracle anchor (d), which uses TOL["A"] and close() of tests/test_parity_gpu.py.
+the oracle anchor (d), which uses TOL["A"] and close() of tests/parity.py.
 
 (a) every ordered pair of modes at n = 37, one case per source mode (and the pairs of the table robot's modes);
 (b) two rings through all modes at the two sizes where AUTO's mapping changes;
@@ -19,115 +19,34 @@ the oracle anchor (d), which uses TOL["A"] and close() of tests/test_parity_gpu.
 
 With QG_MODE_WALK_OUT=<file> every transition appends a line: A -> B, n, kernel, forms compared, resets seen."""
 import os
-import sys
-from dataclasses import dataclass
 
 import numpy as np
 import pytest
 
 from quadruped_gym_amd import _abi
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
-import mode_walk as W  # noqa: E402
-from kernel_leaves import LEAVES, MULTI_TWINS  # noqa: E402
-from rollout_recordings import table_robot  # noqa: E402
-from test_dynamics_gpu import env_model  # noqa: E402
-from test_parity_gpu import TOL, close  # noqa: E402
+import mode_walk as W
+import parity
+from helpers import env_model, write_table_robot
+from kernel_leaves import LEAVES, MULTI_TWINS
+from mode_walk import EXPECTED_REFUSALS, expected_refusal
+from parity import TOL, close
 
 pytestmark = pytest.mark.gpu
 
 RECORD = "QG_MODE_WALK_OUT"
-CSRC = os.path.join(os.path.dirname(HERE), "quadruped-gym_amd", "csrc")
-
-
-# ---- (e) the documented refusals -----------------------------------------------------------------------------------------------------
-@dataclass(frozen=True)
-class Refusal:
-    mode: str               # the mode the handle is in when the call is made
-    call: object            # ctx -> the refused call
-    quote: str              # the words of the refusal: part of the error message, and of `source`
-    source: str             # where the sentence stands: include/quadgym.h or the unit whose fail(...) says it
-    size: str = "small"     # "small" (n = 37) or a key of mode_walk.BOUNDARY_SIZES
-    robot: str = "baked"
-    during: tuple = ()      # the transitions of (a) - (c) that meet it: (A, B, size)
-
-
-def _second_walk_layer(c):
-    from quadruped_gym_amd.task_layers import WalkLayer
-    WalkLayer(c.sim)
-
-
-def _other_obs_mode(c):
-    t = c.sim.get_task()
-    t.obs_mode = _abi.OBS_IMU
-    c.sim.set_task(t)
-
-
-def _seq(c):
-    import torch
-    dev = torch.device(f"cuda:{c.sim.device}")
-    c.sim.step_device_seq(torch.zeros((2, c.sim.n, 12), device=dev), torch.zeros((2, c.sim.n, c.sim.obs_dim + 2), device=dev))
-
-
-_BOUNDARY_INTO_RESIDENT = tuple((a, "M10", size) for size in W.BOUNDARY_SIZES for a in ("M9", "M0")) + \
-    tuple((a, "M10", "first_quad") for a in W.ORDER if a != "M10")
-EXPECTED_REFUSALS = {
-    "set_mapping(LANE) with per-env dynamics": Refusal(
-        "M4", lambda c: c.sim.set_mapping(_abi.MAP_LANE), "run in the LINK and QUAD mappings only (", "qg_capi.hip"),
-    "set_mapping(PAIR) with external wrenches": Refusal(
-        "M5", lambda c: c.sim.set_mapping(_abi.MAP_PAIR), "run in the LINK and QUAD mappings only (", "qg_capi.hip"),
-    "set_mapping(PAIR) on the table robot": Refusal(
-        "M0", lambda c: c.sim.set_mapping(_abi.MAP_PAIR), "the two-legs-per-lane kernel serves the compiled-in robot only", "qg_capi.hip",
-        robot="table"),
-    "per-env dynamics on LANE": Refusal(
-        "M3", W._dyn_on, "run in the LINK and QUAD mappings only (qg_set_mapping AUTO, LINK or QUAD first)", "qg_sim_modes.hip"),
-    "external wrenches on PAIR": Refusal(
-        "M2", W._xfrc_on, "run in the LINK and QUAD mappings only (qg_set_mapping AUTO, LINK or QUAD first)", "qg_sim_modes.hip"),
-    "set_task with a walking layer bound": Refusal(
-        "M7", lambda c: c.sim.set_task(W.base_task()), "a walking task layer is bound to this handle (it holds a copy of the task)",
-        "qg_capi.hip"),
-    "set_task with another obs_mode": Refusal("M0", _other_obs_mode, "obs_mode is fixed at qg_create", "qg_capi.hip"),
-    "step_device_seq with a walking layer bound": Refusal(
-        "M7", _seq, "qg_step_device_seq: a walking task layer is bound to this handle", "qg_sim_multi.hip"),
-    "step_device_seq with per-env dynamics": Refusal("M4", _seq, "qg_step_device_seq: not available with", "qg_sim_multi.hip"),
-    "step_device_seq with external wrenches": Refusal("M5", _seq, "qg_step_device_seq: not available with", "qg_sim_multi.hip"),
-    "resident_start with an observation pack bound": Refusal(
-        "M8", W._resident_on, "a walking task layer is bound to this handle", "qg_sim_multi.hip"),
-    "resident_start with external wrenches": Refusal("M5", W._resident_on, "qg_resident_start: not available with", "qg_sim_multi.hip"),
-    "resident_start above one wave per SIMD": Refusal(
-        "M0", W._resident_on, "needs the one-link-per-lane mapping (AUTO up to 4096 envs, lagged sensors)", "qg_sim_multi.hip",
-        size="first_quad", during=_BOUNDARY_INTO_RESIDENT),
-    "set_mapping with the resident mode on": Refusal(
-        "M10", lambda c: c.sim.set_mapping(_abi.MAP_QUAD), "qg_set_mapping: the resident step mode is on (qg_resident_stop first)",
-        "qg_capi.hip"),
-    "a second walking layer": Refusal(
-        "M7", _second_walk_layer, "a walking task layer is already bound to this simulator (destroy it first)", "qg_walk.hip"),
-    "reset(RESET_DYNAMICS) without a range": Refusal(
-        "M0", lambda c: c.sim.reset(flags=_abi.RESET_DYNAMICS), "QG_RESET_DYNAMICS without a range (qg_set_dynamics_range)", "qg_capi.hip"),
-}
-
-
-def expected_refusal(err, a, b, size):
-    """The entry of EXPECTED_REFUSALS an error met on the way from A to B belongs to, or None."""
-    for key, r in EXPECTED_REFUSALS.items():
-        if r.quote in str(err) and (a, b, size) in r.during:
-            return key
-    return None
 
 
 # ---- fixtures ------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def simds():
-    import torch
-    return 4 * torch.cuda.get_device_properties(0).multi_processor_count
+    return parity.simds()
 
 
 @pytest.fixture(scope="module")
 def models(tmp_path_factory):
     from quadruped_gym_amd.model.loader import load_model
-    return {"baked": None, "table": load_model(table_robot(tmp_path_factory.mktemp("robot")))[0]}
+    return {"baked": None, "table": load_model(write_table_robot(tmp_path_factory.mktemp("robot")))[0]}
 
 
 def record(line):
@@ -256,20 +175,16 @@ def one_transition(a, b, n, robot, models, simds, oracle, seed):
 
 
 # ---- (a) every ordered pair ---------------------------------------------------------------------------------------------------------
-TRANSITIONS = W.PAIRS
-TABLE_TRANSITIONS = W.TABLE_PAIRS
-
-
 @pytest.mark.parametrize("a", W.ORDER)
 def test_walked_handle_steps_like_a_fresh_one(oracle, models, simds, a):
-    for k, (src, b) in enumerate(TRANSITIONS):
+    for k, (src, b) in enumerate(W.TRANSITIONS):
         if src == a:
             one_transition(a, b, W.N_SMALL, "baked", models, simds, oracle, seed=20 + k)
 
 
 @pytest.mark.parametrize("a", W.TABLE_MODES)
 def test_walked_handle_steps_like_a_fresh_one_on_the_table_robot(oracle, models, simds, a):
-    for k, (src, b) in enumerate(TABLE_TRANSITIONS):
+    for k, (src, b) in enumerate(W.TABLE_TRANSITIONS):
         if src == a:
             one_transition(a, b, W.N_SMALL, "table", models, simds, oracle, seed=200 + k)
 
@@ -372,7 +287,7 @@ def test_a_refused_call_leaves_no_trace(models, simds, key):
         with pytest.raises(_abi.QuadGymError) as info:
             r.call(ctx)
         assert r.quote in str(info.value), str(info.value)
-        assert r.quote in open(os.path.join(CSRC, r.source)).read()
+        assert r.quote in open(os.path.join(W.CSRC, r.source)).read()
         del info
         assert tuple(ctx.features) == feats
         assert not W.differing(before, W.snapshot(ctx)), "the snapshot bytes after the refused call"

@@ -1,19 +1,16 @@
 """The running normaliser without a GPU: the float64 checker of tests/normalize_reference.py against itself, the host-only part of the
 C ABI (qg_norm_create validates before the device check, no CPU backend) and RunningNormalizer's tensor checks."""
 import ctypes as C
-import os
-import sys
 import types
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import normalize_reference as R  # noqa: E402
+import normalize_reference as R
 
-from quadruped_gym_amd import _abi  # noqa: E402
-from quadruped_gym_amd import normalize as N  # noqa: E402
+from quadruped_gym_amd import _abi
+from quadruped_gym_amd import normalize as N
 
 QG_ERR_ARG, QG_ERR_DEVICE = -1, -2
 

@@ -8,19 +8,17 @@ With QG_NORM_PARITY_OUT=<file> every case appends its largest errors, as fractio
 (profiles/r12/normalize_parity.txt)."""
 import functools
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import normalize_reference as R  # noqa: E402
+import normalize_reference as R
+from policy_checks import DEV
 
-from quadruped_gym_amd.normalize import DeviceVecNormalize, RunningNormalizer  # noqa: E402
+from quadruped_gym_amd.normalize import DeviceVecNormalize, RunningNormalizer
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 STEPS = 6
 # Not the defaults: an outlier among N rows that enter the statistics lies at most sqrt(N) standard deviations out, and the small
 # shapes have seen fewer than 100 rows when the outliers come (steps 4 and 5), so a clip of 10 could not be met there.

@@ -1,80 +1,18 @@
 """Parity of the HIP path (through the C ABI) against the CPU oracle and the committed golden
 vectors.  Floating point: the kernels compute in f32, the oracle in f64; tolerances are stated
-per quantity below and hold for ONE env-step from identical f32 states (longer rollouts diverge
+per quantity in tests/parity.py and hold for ONE env-step from identical f32 states (longer rollouts diverge
 chaotically in any precision and are compared through invariants instead)."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
 from quadruped_gym_amd import _abi
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import contact_cells as CC  # noqa: E402
+import contact_cells as CC
+from leaf_states import sample_states
+# the stated one-step tolerances (TOL, ACCEL_B_STEADY) and close() live in tests/parity.py
+from parity import MAPPINGS, TOL, accel_slice, close, close_accel_b, configure, gold  # noqa: F401  (gold: a fixture)
 
 pytestmark = pytest.mark.gpu
-
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "step_vectors.npz")
-
-# ---- stated tolerances: |gpu - oracle| <= atol + rtol * |oracle| after one env-step ----------
-# The absolute terms are <= 5x the largest error MEASURED over 4096 seeded states per frame_skip and every work mapping
-# (tools/parity_report.py -> profiles/r02/parity_report.txt; frame_skip 4: qpos 1.2e-6, qvel 4.3e-4, act 8.2e-8, obs 7.5e-5,
-# accelerometer 5.3e-3 m/s^2, reward 3.5e-6), so a regression that costs an order of magnitude of accuracy fails.  frame_skip
-# 20 compounds 20 substeps and a contact can switch inside the step (measured maxima qpos 1.5e-4, qvel 7.7e-2, obs 5.8e-4,
-# accelerometer 0.85, reward 3.0e-4).
-TOL = {
-    "A": dict(qpos=(5e-6, 2e-6), qvel=(2e-3, 1e-4), act=(4e-7, 1e-6), obs=(3.5e-4, 1e-4), accel=(0.025, 1e-3), reward=(1.5e-5, 1e-5)),
-    "B": dict(qpos=(4e-4, 1e-4), qvel=(5e-2, 2e-2), act=(6e-7, 1e-6), obs=(3e-3, 2e-3), accel=(2.0, 5e-2), reward=(1.5e-3, 1e-3)),
-}
-# frame_skip 20, accelerometer (round 4): the 2.0 m/s^2 above is set by the handful of states where a contact switches inside the
-# step -- a body touches down or lifts off at a slightly different substep in f32 and the reading of the last substep jumps.  States
-# whose contact census (the oracle's contact_W > 0 per body) does NOT change around the substep the sensors describe (the last one and
-# two before it, one after: oracle.contact_switch_near_sensors) are held to this bound instead; the loose one only covers the rest.
-ACCEL_B_STEADY = (0.01, 1e-3)        # measured: 4.2e-4 on the golden states (every mapping), 1.7e-3 on config 5's 4096-env sample
-
-
-def close_accel_b(oracle, got, ref, model, frame_skip, state, actions, keep=None):
-    qpos, qvel, act, nstep = state
-    changed = oracle.contact_switch_near_sensors(model, frame_skip, qpos, qvel, act, nstep, actions)
-    if keep is not None:
-        got, ref, changed = got[keep], ref[keep], changed[keep]
-    steady = ~changed
-    assert steady.sum() >= 20, "enough states keep their contacts around the sensor substep"
-    worst = close(got[steady], ref[steady], ACCEL_B_STEADY, "accelerometer (contact census steady)")
-    if changed.any():
-        close(got[changed], ref[changed], TOL["B"]["accel"], "accelerometer (a contact switches inside the step)")
-    return worst, int(changed.sum())
-
-
-def configure(task, case):
-    task.use_fall = 1
-    task.fall_height = 0.05
-    if case == "B":
-        task.frame_skip = 20
-        task.obs_mode = 1
-    return task
-
-
-def close(got, ref, tol, what):
-    atol, rtol = tol
-    err = np.abs(np.asarray(got, np.float64) - ref)
-    bound = atol + rtol * np.abs(ref)
-    worst = np.unravel_index(np.argmax(err - bound), err.shape)
-    assert (err <= bound).all(), f"{what}: max excess at {worst}: got {np.asarray(got)[worst]}, ref {ref[worst]}, err {err[worst]:.3e}"
-    return float(err.max())
-
-
-def accel_slice(case):
-    return slice(12, 15)
-
-
-@pytest.fixture(scope="module")
-def gold():
-    return dict(np.load(GOLD))
-
-
-MAPPINGS = {"lane": _abi.MAP_LANE, "quad": _abi.MAP_QUAD, "pair": _abi.MAP_PAIR, "link": _abi.MAP_LINK}
 
 
 @pytest.mark.parametrize("mapping", ["lane", "quad", "pair", "link"])
@@ -121,9 +59,6 @@ def test_step_matches_oracle_on_fresh_states(oracle, mapping):
     """Seeded states the fixture does not hold, through the device-pointer entry points."""
     import torch
     from quadruped_gym_amd.sim import BatchedSim
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    from make_golden import sample_states
     model, task = oracle.default_model(), configure(oracle.default_task(), "A")
     n = 200                                               # ragged: 3 full waves + 8 lanes
     qpos, qvel, act, nstep = sample_states(model, task, n, seed=99)
@@ -224,9 +159,6 @@ def test_generic_variant_matches_oracle_on_a_modified_robot(oracle, mapping):
     device memory instead of literals).  Heavier feet, a different servo gain and a shifted hip mount
     must track the oracle given the same modified model."""
     from quadruped_gym_amd.sim import BatchedSim
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    from make_golden import sample_states
 
     def tweak(m):
         for k in range(4):
@@ -611,9 +543,6 @@ def test_tiny_and_ragged_batches(oracle, mapping, n):
     """A single env, less than one quad-wave's 16 envs, and one env past the pair-wave's 32: the tail lanes shadow the last
     env and must neither write nor disturb it."""
     from quadruped_gym_amd.sim import BatchedSim
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    from make_golden import sample_states
     model, task = oracle.default_model(), configure(oracle.default_task(), "A")
     qpos, qvel, act, nstep = sample_states(model, task, n, seed=300 + n)
     actions = np.random.default_rng(n).uniform(-1, 1, (n, 12)).astype(np.float32)
@@ -706,9 +635,6 @@ def _one_step_against_oracle(oracle, n, seed, mapping, sensor_lag=1, frame_skip=
     """n seeded states (tools/make_golden.sample_states), one env-step through `mapping` and through the oracle; returns nothing,
     asserts the stated tolerances on state, observation, reward."""
     from quadruped_gym_amd.sim import BatchedSim
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    from make_golden import sample_states
     model, otask = oracle.default_model(), configure(oracle.default_task(), "A")
     otask.sensor_lag, otask.frame_skip = sensor_lag, frame_skip
     qpos, qvel, act, nstep = sample_states(model, otask, n, seed=seed)
@@ -915,10 +841,7 @@ def test_random_task_and_model_variants_match_oracle(oracle, trial):
     parameters -- the kernel variants that read the model tables from LDS / scalar loads), frame_skip 1 ... 8, either observation pack,
     random reward weights and fall height, every mapping that serves the variant.  One env-step from seeded rollout states against the
     oracle run on the SAME perturbed numbers, within the frame_skip-4 bounds scaled by frame_skip / 4 (the error compounds per substep)."""
-    import sys
     from quadruped_gym_amd.sim import BatchedSim
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    from make_golden import sample_states
     rng = np.random.default_rng(1000 + trial)
     fs = int(rng.choice([1, 2, 3, 5, 8]))
     obs_mode = int(rng.integers(0, 2))

@@ -8,16 +8,12 @@ place.  test_po_rollout_frames_match_oracle_driven_from_the_state pins the pass-
 body velocity, data.ctrl, command -- over rollouts with auto-resets: at every step the composed checker (tests/po_step_reference.py:
 settling gate and clip -> f64 physics oracle -> frame) is restarted from the device's STATE and takes none of its sensors.
 tests/test_kernel_leaves_gpu.py holds the whole stack of every fused PO instantiation to the same checker over one and two steps."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
 from oracle import po_oracle as P
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import po_step_reference as R  # noqa: E402
+import po_step_reference as R
 
 
 def test_madgwick_restatement_properties():
@@ -93,9 +89,9 @@ def test_po_frames_match_oracle(window, settle):
 
 
 def _link_grid_plus_one():
-    import torch
     from kernel_leaves import link_max
-    return link_max(4 * torch.cuda.get_device_properties(0).multi_processor_count) + 1
+    from parity import simds
+    return link_max(simds()) + 1
 
 
 @pytest.mark.gpu
@@ -105,7 +101,7 @@ def test_po_rollout_frames_match_oracle_driven_from_the_state(oracle, size, wind
     -- against the composed checker driven from the device's STATE, not from its sensors: before every env-step the state is read, and
     the checker (tests/po_step_reference.py) gates and clips the action on the f64 clock of that state's step counter, steps the f64
     physics oracle from that state and lays its sensors out as a frame with the command in force.  A finished env is compared through
-    the newest frame of its terminal stack.  Tolerances: TOL["A"] of tests/test_parity_gpu.py (one env-step at frame_skip 4 from an
+    the newest frame of its terminal stack.  Tolerances: TOL["A"] of tests/parity.py (one env-step at frame_skip 4 from an
     identical f32 state: obs for gyro and body velocity, accel for the accelerometer), 1e-6 for ctrl and command (exact values in
     f32).  Every (env, step) is compared, none is left out: the columns compared do not pass through the orientation estimate, so the
     estimate aliasing qpos at a termination (what test_po_frames_match_oracle skips) does not matter here.  The angle columns keep
@@ -115,7 +111,7 @@ def test_po_rollout_frames_match_oracle_driven_from_the_state(oracle, size, wind
     env more than the link kernel serves, the last workgroup holding ONE env -- on a seeded sample of 256 envs plus the last 16;
     its 12 steps end before the time limit, and the settling gate opens after the tenth."""
     from quadruped_gym_amd.envs.walking import POWalkingQuadrupedVecEnv
-    from test_parity_gpu import TOL
+    from parity import TOL
     n = 40 if size == "small" else _link_grid_plus_one()
     fs = 4
     env = POWalkingQuadrupedVecEnv(n, obs_window=window, settling_time=settle, frame_skip=fs, max_time=0.12, random_init=True,

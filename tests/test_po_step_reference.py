@@ -1,21 +1,15 @@
 """The composed walking / PO checker (tests/po_step_reference.py) and the comparisons the GPU tests apply with it, on the CPU.
 
-Run on the states, actions and commands of tests/test_kernel_leaves_gpu.py (``build_states``), with the two env-steps the walking and
+Run on the states, actions and commands of the leaf tests (tests/leaf_states.py: ``build_states``), with the two env-steps the walking and
 PO leaves take: the comparisons pass on the checker's own frames (rounded to f32, and rebuilt from sensors moved within the one-step
 parity tolerance), and fail for each of eight deliberate miswirings of a step kernel's gather -- so the chosen states and the stated
 tolerances separate those mistakes."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
-import po_step_reference as R  # noqa: E402
-from test_kernel_leaves_gpu import PO_WINDOW, build_states, expected_chain, walking_task  # noqa: E402
-from test_parity_gpu import TOL  # noqa: E402
+import po_step_reference as R
+from leaf_states import PO_WINDOW, build_states, expected_chain, walking_task
+from parity import TOL
 
 T = TOL["A"]
 

@@ -5,17 +5,15 @@ import ctypes as C
 import math
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import policy_reference as R  # noqa: E402
+import policy_reference as R
 
-from quadruped_gym_amd import _abi  # noqa: E402
-from quadruped_gym_amd import policy as P  # noqa: E402
+from quadruped_gym_amd import _abi
+from quadruped_gym_amd import policy as P
 
 QG_ERR_ARG, QG_ERR_DEVICE = -1, -2
 

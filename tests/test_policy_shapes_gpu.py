@@ -12,19 +12,17 @@ spacing at the largest reference magnitude of that output) -- an f32 result cann
 worst ratio of a fused error to its bound is 0.50 (value, 33-144-12; action mean 0.33, log-probability 0.12).
 With QG_POLICY_PARITY_OUT=<file> every case of (a) appends its maxima and bounds to that file (profiles/r11/policy_shape_parity.txt)."""
 import functools
-import os
-import sys
 import zlib
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import policy_reference as R  # noqa: E402
-from test_policy_gpu import DEV, _observations, _record, _run, _torch_tower  # noqa: E402
+import parity
+import policy_reference as R
+from policy_checks import DEV, observations, record, run, torch_tower
 
-from quadruped_gym_amd.policy import FusedMlpPolicy  # noqa: E402
+from quadruped_gym_amd.policy import FusedMlpPolicy
 
 pytestmark = pytest.mark.gpu
 N = 83
@@ -41,10 +39,6 @@ def _id(i):
     return "%d-%s-%d" % (obs_dim, "-".join(str(h) for h in hidden), act_dim)
 
 
-def _simds():
-    return 4 * torch.cuda.get_device_properties(0).multi_processor_count
-
-
 @functools.lru_cache(maxsize=None)
 def _inputs(i, init):
     """Parameters and inputs of table row i, made once and read-only: actor, critic, log_std ~ U(-1.5, 0.3), observations with
@@ -54,7 +48,7 @@ def _inputs(i, init):
     actor = R.random_layers(rng, R.tower_shapes(obs_dim, hidden, act_dim), init)
     critic = R.random_layers(rng, R.tower_shapes(obs_dim, hidden, 1), init, head_gain=1.0)
     log_std = rng.uniform(-1.5, 0.3, act_dim).astype(np.float32)
-    obs = _observations(rng, N, obs_dim)
+    obs = observations(rng, N, obs_dim)
     eps = rng.standard_normal((N, act_dim)).astype(np.float32)
     for a in [log_std, obs, eps] + [x for W, b in actor + critic for x in (W, b)]:
         a.setflags(write=False)
@@ -83,7 +77,7 @@ def _make(i, init, out_tanh, waves, monkeypatch):
     pol.load_layers(actor, log_std, critic)
     for n in (1, 17, N):
         for value in (False, True):
-            want = R.launch_shape(hidden, n, 2 if value else 1, _simds(), force_waves=waves)
+            want = R.launch_shape(hidden, n, 2 if value else 1, parity.simds(), force_waves=waves)
             assert pol.launch_shape(n, value) == want, (n, value, pol.launch_shape(n, value), want)
             assert not waves or want[0] == waves
     return pol
@@ -94,8 +88,8 @@ def _t(a):
 
 
 def _sampled(pol, obs, eps):
-    """(action, log_prob, value) of a sampled forward pass; outputs pre-filled with NaN by _run."""
-    return _run(pol, obs if torch.is_tensor(obs) else _t(obs), _t(eps))
+    """(action, log_prob, value) of a sampled forward pass; outputs pre-filled with NaN by run."""
+    return run(pol, obs if torch.is_tensor(obs) else _t(obs), _t(eps))
 
 
 def _same_bits(a, b, rows=slice(None)):
@@ -111,7 +105,7 @@ def test_default_launch_shape_follows_the_rule(monkeypatch):
     """Without QG_POLICY_WAVES: four waves for the wide rows at both sizes; the narrow ones change to one wave where tiles x towers
     reaches the SIMD count (n = 16 x SIMDs: one tile per SIMD with the actor alone)."""
     monkeypatch.delenv("QG_POLICY_WAVES", raising=False)
-    simds = _simds()
+    simds = parity.simds()
     seen = set()
     for i in TABLE:
         obs_dim, hidden, act_dim = R.SHAPE_TABLE[i]
@@ -135,20 +129,20 @@ def test_forward_matches_float64_checker(i, out_tanh, waves, monkeypatch):
         pol = _make(i, init, out_tanh, waves, monkeypatch)
         with torch.no_grad():                          # the path being replaced: torch float32 on the GPU
             x = _t(obs)
-            t_mean = _torch_tower(actor, out_tanh)(x)
+            t_mean = torch_tower(actor, out_tanh)(x)
             std = _t(log_std).exp()
             t_act = t_mean + std * _t(eps)
             t_lp = torch.distributions.Normal(t_mean, std).log_prob(t_act).sum(-1)
-            t_val = _torch_tower(critic, False)(x)[:, 0]
+            t_val = torch_tower(critic, False)(x)[:, 0]
         terr = {"mean": np.abs(t_mean.cpu().numpy() - refs["mean"]).max(), "log_prob": np.abs(t_lp.cpu().numpy() - refs["log_prob"]).max(),
                 "value": np.abs(t_val.cpu().numpy() - refs["value"]).max()}
-        mean, _, val = _run(pol, x, None, want_lp=False)
+        mean, _, val = run(pol, x, None, want_lp=False)
         _, lp, val2 = _sampled(pol, x, eps)
         assert np.array_equal(val, val2)
         ferr = {"mean": np.abs(mean - refs["mean"]).max(), "log_prob": np.abs(lp - refs["log_prob"]).max(),
                 "value": np.abs(val - refs["value"]).max()}
         bound = {k: _bound(terr[k], refs[k]) for k in ferr}
-        _record(f"{_id(i)} out_tanh={int(out_tanh)} waves={waves} blocks={pol.launch_shape(N, True)[1]} init={init}: " +
+        record(f"{_id(i)} out_tanh={int(out_tanh)} waves={waves} blocks={pol.launch_shape(N, True)[1]} init={init}: " +
                 "  ".join(f"{k}: fused {ferr[k]:.3e} torch {terr[k]:.3e} bound {bound[k]:.3e} ratio {ferr[k] / bound[k]:.2f}" for k in ferr))
         for k in ferr:
             assert np.isfinite(ferr[k]) and ferr[k] <= bound[k], (k, init, ferr[k], terr[k], bound[k])
@@ -241,7 +235,7 @@ def test_layout_with_exact_integers(obs_dim, hidden, waves, monkeypatch):
     I = obs.astype(np.float64) @ W1.T + b1
     assert np.abs(I).max() < 1024
     pol = FusedMlpPolicy(obs_dim, (hidden,), act_dim, out_tanh=False, value=False)
-    assert pol.launch_shape(N) == R.launch_shape((hidden,), N, 1, _simds(), force_waves=waves)
+    assert pol.launch_shape(N) == R.launch_shape((hidden,), N, 1, parity.simds(), force_waves=waves)
     obs_t = _t(obs)
     perm = rng.permutation(hidden)                      # which hidden unit each action of each round selects
     assert hidden % act_dim == 0
@@ -250,7 +244,7 @@ def test_layout_with_exact_integers(obs_dim, hidden, waves, monkeypatch):
         W2 = np.zeros((act_dim, hidden))
         W2[np.arange(act_dim), units] = 2.0 ** 16
         pol.load_layers([(W1 * 2.0 ** -16, b1 * 2.0 ** -16), (W2, np.arange(act_dim, dtype=np.float64))], np.zeros(act_dim))
-        act, _, _ = _run(pol, obs_t, None, want_lp=False)
+        act, _, _ = run(pol, obs_t, None, want_lp=False)
         want = I[:, units] + np.arange(act_dim)
         assert np.abs(act - want).max() < 0.2, (r, np.abs(act - want).max())
         assert np.array_equal(np.rint(act), want)

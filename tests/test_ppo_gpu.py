@@ -9,22 +9,20 @@ With QG_PPO_PARITY_OUT=<file> every case appends both paths' maxima to that file
 import collections
 import math
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import policy_reference as R  # noqa: E402
-import ppo_reference as G  # noqa: E402
-import ppo_torch as T  # noqa: E402
+import policy_reference as R
+import ppo_reference as G
+import ppo_torch as T
+from policy_checks import DEV
 
-from quadruped_gym_amd import _abi  # noqa: E402
-from quadruped_gym_amd.policy import FusedMlpPolicy  # noqa: E402
+from quadruped_gym_amd import _abi
+from quadruped_gym_amd.policy import FusedMlpPolicy
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 Samples = collections.namedtuple("Samples", G.Batch._fields)
 
 

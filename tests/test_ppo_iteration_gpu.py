@@ -3,7 +3,7 @@ FusedMlpPolicy.forward / reserve_grad / ppo_grad / update_from, DeviceRolloutBuf
 and audited by tests/ppo_iteration_reference.py: every stage in float64 against the recording's own inputs to that stage.
 
 No tolerance of its own: the normaliser's statistics and outputs by the rules of tests/test_normalize_gpu.py, the forward pass and the
-last values by the rule of tests/test_policy_gpu.py (its helper is imported), GAE within gae_bound, stored and gathered rows and the
+last values by the rule of tests/test_policy_gpu.py (``bound`` of tests/policy_checks.py), GAE within gae_bound, stored and gathered rows and the
 parameters bit for bit, the gradient and statistics by the rule of tests/test_ppo_gpu.py case 1 with torch float32 autograd on the
 GPU as the yardstick, the first minibatch of an iteration by test_first_epoch_has_no_clipped_row, the episode statistics by
 test_episode_statistics_equal_the_checker.
@@ -14,22 +14,20 @@ Streams: the module takes four from torch's pool, once, and uses all four (captu
 graph-form loop), which leaves the tests that run later in the process the hardware-queue assignment they had."""
 import functools
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import ppo_iteration_reference as P  # noqa: E402
-import ppo_torch as T  # noqa: E402
-from test_policy_gpu import DEV, _bound as forward_bound, _torch_tower  # noqa: E402
+import ppo_iteration_reference as P
+import ppo_torch as T
+from policy_checks import DEV, bound as forward_bound, torch_tower
 
-from quadruped_gym_amd import _abi  # noqa: E402
-from quadruped_gym_amd.normalize import RunningNormalizer  # noqa: E402
-from quadruped_gym_amd.policy import FusedMlpPolicy  # noqa: E402
-from quadruped_gym_amd.rollout import DeviceRolloutBuffer, RolloutBufferSamples  # noqa: E402
-from quadruped_gym_amd.sim import BatchedSim  # noqa: E402
+from quadruped_gym_amd import _abi
+from quadruped_gym_amd.normalize import RunningNormalizer
+from quadruped_gym_amd.policy import FusedMlpPolicy
+from quadruped_gym_amd.rollout import DeviceRolloutBuffer, RolloutBufferSamples
+from quadruped_gym_amd.sim import BatchedSim
 
 pytestmark = pytest.mark.gpu
 CASE_NAMES = list(P.CASES)
@@ -227,11 +225,11 @@ def _forward_baseline(actor, log_std, critic, obs, eps, out_tanh):
     """The path the forward pass replaces, as tests/test_policy_gpu.py forms it: torch float32 modules on the GPU."""
     with torch.no_grad():
         x = _t(np.asarray(obs, np.float32))
-        mean = _torch_tower([(np.array(W), np.array(b)) for W, b in actor], out_tanh)(x)
+        mean = torch_tower([(np.array(W), np.array(b)) for W, b in actor], out_tanh)(x)
         std = _t(log_std).exp()
         act = mean if eps is None else mean + std * _t(eps)
         lp = torch.distributions.Normal(mean, std).log_prob(act).sum(-1)
-        val = _torch_tower([(np.array(W), np.array(b)) for W, b in critic], False)(x)[:, 0]
+        val = torch_tower([(np.array(W), np.array(b)) for W, b in critic], False)(x)[:, 0]
     return _h(act), _h(lp), _h(val)
 
 

@@ -2,19 +2,16 @@
 float64 loop, the census of the committed seeds (conditions on the inputs, not measurements), and the auditor's sensitivity -- no
 finding on a clean float32 run, a finding at the right stage for every deliberate wiring error."""
 import functools
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import normalize_reference as NR  # noqa: E402
-import ppo_iteration_reference as P  # noqa: E402
-import ppo_reference as G  # noqa: E402
-import ppo_torch as T  # noqa: E402
-from test_policy_gpu import _bound as forward_bound  # noqa: E402  (the forward pass's tolerance rule; nothing there runs on import)
+import normalize_reference as NR
+import ppo_iteration_reference as P
+import ppo_reference as G
+import ppo_torch as T
+from policy_checks import bound as forward_bound         # the forward pass's tolerance rule
 
 CASE_NAMES = list(P.CASES)
 

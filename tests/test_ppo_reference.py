@@ -1,15 +1,12 @@
 """The float64 checker of the PPO loss and gradient pass (tests/ppo_reference.py) without a GPU: against torch float64 autograd of SB3's
 formulae, and the census of the batches tests/test_ppo_gpu.py runs -- every clipping class is populated and no row sits on a boundary."""
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import ppo_reference as G  # noqa: E402
-import ppo_torch as T  # noqa: E402
+import ppo_reference as G
+import ppo_torch as T
 
 
 @pytest.mark.parametrize("value", [False, True])

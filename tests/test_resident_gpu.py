@@ -2,8 +2,6 @@
 bits of the per-launch one-link-per-lane kernel -- they run the same substep code on state that stays in registers between env-steps
 (/root/reference keeps it in MjData across steps the same way, src/envs/quadruped.py:163-165) -- and the resident kernel must never
 be able to hang: it leaves by itself when nobody rings, and every entry point that needs the state in memory retires it first."""
-import os
-import sys
 import time
 
 import numpy as np
@@ -11,11 +9,10 @@ import pytest
 
 from quadruped_gym_amd import _abi
 
-pytestmark = pytest.mark.gpu
+from kernel_leaves import TWIN_PAIRS
+from parity import GOLD
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "step_vectors.npz")
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from kernel_leaves import TWIN_PAIRS  # noqa: E402
+pytestmark = pytest.mark.gpu
 
 
 def _task(frame_skip=4, imu=False, max_time=0.2, yaw=True):
@@ -111,7 +108,7 @@ def test_sequence_launch_matches_golden_vectors():
     torch.cuda.synchronize()
     assert torch.equal(pa[0], pb)
     _same_state(a, b)
-    # and against the fixture itself, within the stated one-step tolerances of tests/test_parity_gpu.py
+    # and against the fixture itself, within the stated one-step tolerances of tests/parity.py
     q1 = a.get_state()[0]
     assert np.abs(q1 - gold["A_qpos1"]).max() <= 5e-6 + 2e-6 * np.abs(gold["A_qpos1"]).max()
     a.close(); b.close()

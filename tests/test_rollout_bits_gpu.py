@@ -5,15 +5,10 @@ loop -- must leave every output as it was.  The compiler has contracted a sum di
 (quat_unit, reward_total, walk_reward_env), so this is checked, per instantiation, on 40 auto-resetting env-steps with resets on
 the way.  If a bit moves: find the expression in the two listings and pin its association in the source; the recordings are
 re-made only by a change that means to alter the numbers."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-import rollout_recordings as R  # noqa: E402
+import rollout_recordings as R
 
 pytestmark = pytest.mark.gpu
 

@@ -1,19 +1,16 @@
 """The rollout buffer without a GPU: the float64 checker of tests/rollout_buffer_reference.py against hand-worked cases, the host-only
 part of the C ABI (qg_rollout_* validate before the device check, no CPU backend) and DeviceRolloutBuffer's tensor checks."""
 import ctypes as C
-import os
-import sys
 import types
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import rollout_buffer_reference as R  # noqa: E402
+import rollout_buffer_reference as R
 
-from quadruped_gym_amd import _abi  # noqa: E402
-from quadruped_gym_amd import rollout as RB  # noqa: E402
+from quadruped_gym_amd import _abi
+from quadruped_gym_amd import rollout as RB
 
 QG_ERR_ARG, QG_ERR_DEVICE = -1, -2
 

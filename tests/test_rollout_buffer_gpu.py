@@ -10,19 +10,17 @@ its one stored value, 0.16), 0.12 or less on every other shape; an indexing or m
 With QG_ROLLOUT_PARITY_OUT=<file> every GAE case appends its largest ratio to that file."""
 import functools
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import rollout_buffer_reference as R  # noqa: E402
+import rollout_buffer_reference as R
+from policy_checks import DEV
 
-from quadruped_gym_amd.rollout import DeviceRolloutBuffer, RolloutBufferSamples  # noqa: E402
+from quadruped_gym_amd.rollout import DeviceRolloutBuffer, RolloutBufferSamples
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 IDS = ["x".join(str(v) for v in s) for s in R.SHAPES]
 STORED = ("observations", "actions", "log_probs", "values", "rewards", "dones", "advantages", "returns")
 

@@ -13,7 +13,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import contact_cells as CC  # noqa: E402
 from oracle import oracle as O  # noqa: E402
-from test_parity_gpu import TOL  # noqa: E402
+from parity import TOL  # noqa: E402
 
 
 def main():
