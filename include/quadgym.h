@@ -564,7 +564,8 @@ int qg_policy_launch_shape(const qg_policy *policy, int32_t n, int32_t with_valu
  *   entropy_loss = -sum_a(0.5 + log(2 pi) / 2 + log_std_a)          (state-independent)
  *   loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss
  * Without a critic (has_value == 0) value_loss = 0 and old_values / returns are not read.  Advantages are used as given (normalise
- * them beforehand); the optimiser and gradient-norm clipping are the caller's: grad is ONE flat vector.
+ * them beforehand: qg_policy_normalize_advantages_device); grad is ONE flat vector, which qg_policy_adam_update_device below or the
+ * caller's own optimiser takes.
  *
  * grad [qg_policy_param_count] is d loss / d parameters in the canonical order, every element overwritten (the caller need not clear
  * it).  The heads: d loss / d logp = -(adv r) / B, and 0 where (adv > 0 and r > 1 + c) or (adv < 0 and r < 1 - c);
@@ -608,6 +609,70 @@ typedef struct qg_ppo_batch {  /* device pointers: what qg_rollout_gather_device
 int qg_policy_reserve_grad(qg_policy *policy, int32_t max_batch);
 int qg_policy_ppo_grad_device(qg_policy *policy, const qg_ppo_params *params, int32_t B, const qg_ppo_batch *batch, float *grad,
                               float *stats, void *stream);
+
+/* ---- Adam, gradient-norm clipping and advantage normalisation on the device ------------------------------------------------------------
+ * What stands between the gradient and the next forward pass of SB3's PPO.train: torch.nn.utils.clip_grad_norm_ and torch.optim.Adam
+ * (amsgrad off, no weight decay) on the handle's own canonical parameters, and normalize_advantage for one minibatch.  One minibatch
+ * is then gather -> normalise -> ppo_grad -> adam_step: seven launches, no copy of the network, nothing of it on the host.
+ *
+ * qg_policy_adam_update_device, with g = grad, m and v the two moments (f32, zero after reserve) and t the step count (an integer in
+ * DEVICE memory, zero after reserve: a captured step replays as t = 1, 2, 3, ..), in exactly this order and with these roundings:
+ *   norm  = f32(sqrt(sum_i g_i^2))              the sum in f64 (every product is exact there) over a fixed partition, see below
+ *   coef  = max_grad_norm > 0 ? min(1, max_grad_norm / (norm + 1e-6)) : 1                    f32: one addition, one division
+ *   t     = t + 1;   lr = lr_device ? *lr_device : params.lr
+ *   step  = f32(lr / (1 - beta_one^t));   root = f32(sqrt(1 - beta_two^t));   a1 = f32(1 - beta_one);   a2 = f32(1 - beta_two)
+ *                                               each formed in f64 from the f32 arguments and rounded once
+ *   per element, in f32 (fl: one rounding; fma: one rounding for product and sum):
+ *   gc    = fl(coef g)
+ *   m     = fma(beta_one, m, fl(a1 gc));   v = fma(beta_two, v, fl(fl(a2 gc) gc))
+ *   p     = fl(p - fl(step fl(m / fl(fl(sqrt(v) / root) + eps))))                            square root and divisions correctly rounded
+ * grad is not modified (a data-parallel trainer all-reduces it between ppo_grad and this call).  lr_device (nullable) points to one
+ * f32 on the device that replaces params.lr: a schedule needs no re-capture; it must hold a finite value >= 0.  params_out (nullable,
+ * [qg_policy_param_count]) receives a copy of the new canonical vector.  stats (nullable, [4]): norm before clipping, coef, t after
+ * the step, the lr used.  The call also brings both operand images up to date -- the forward image including exp(log_std) (f64,
+ * rounded once), and the transposed image once qg_policy_reserve_grad has been called --, bit for bit what
+ * qg_policy_set_params_device would have produced from the new vector: the next forward / ppo_grad on the stream sees the new
+ * parameters.  qg_policy_set_params and qg_policy_set_params_device leave m, v and t alone, as loading weights leaves a torch optimiser.
+ *
+ * TWO launches per step.  The first writes one f64 sum of squares per slot of 2048 consecutive elements of grad (a thread its eight
+ * elements in ascending order, a fixed butterfly over the wave, the four waves in ascending order) and its first workgroup moves t;
+ * in the second every workgroup adds the slots in ascending order itself, forms the scalars and updates its 2048 elements, writing
+ * each new parameter to its places in the images.  No floating-point atomics; no workgroup waits for another; the partition depends on
+ * the parameter count alone; given the scalars, element i of p, m, v depends on element i of the inputs alone.  The same inputs give
+ * the same bits on every run, eagerly and under graph replay.  A zero gradient on m = 0 leaves p bit for bit; lr = 0 leaves p bit for
+ * bit while m, v, t move.  Image elements that are padding are never written: they stay zero.  Outputs for non-finite inputs are
+ * unspecified.  Calls on one handle must be ordered by the caller (one stream, or events).
+ *
+ * qg_policy_reserve_adam allocates m, v, t and the slots' sums.  Host call: it waits for the device and must not be called during a
+ * stream capture; a second call is a no-op that keeps the state; it does not need qg_policy_reserve_grad.  qg_policy_adam_get_state /
+ * _set_state copy m, v [qg_policy_param_count] and t (>= 0) from / to host arrays -- the round trip is exact --, wait for the device
+ * and must not be called during a capture; QG_ERR_ARG before qg_policy_reserve_adam.  qg_policy_adam_update_device follows the *_device
+ * contract: it enqueues on the caller's stream, returns at once, allocates nothing and can be captured into a hipGraph (params are
+ * taken by value at the call; what lr_device points to is read at each replay).  QG_ERR_ARG, before any device check: NULL policy /
+ * params / grad, a wrong struct_size, reserved != 0, a value outside the ranges below, params_out == grad, nothing reserved.
+ *
+ * qg_policy_normalize_advantages_device: out_i = f32((adv_i - mean) / (std + 1e-8)) with mean = sum(adv) / B and std =
+ * sqrt(sum((adv_i - mean)^2) / (B - 1)) (the unbiased one: torch's std()), both sums and the quotient in f64, the quotient rounded
+ * once.  ONE launch of one workgroup of 1024 threads: thread k adds the groups of four elements k, k + 1024, .. in ascending order,
+ * a fixed butterfly adds the threads of a wave, then the waves in ascending order: an order that depends on B alone.  A constant
+ * vector gives exact zeros.  out == adv (in place) is allowed; any other overlap is not.  It needs no reservation (the handle names
+ * the device), follows the *_device contract and is capturable.  QG_ERR_ARG: a NULL argument, B < 2 (SB3 skips the normalisation
+ * there) or B > 2^31 - 1 - 4096. */
+typedef struct qg_adam_params {
+    int32_t struct_size;       /* sizeof(qg_adam_params): checked */
+    int32_t reserved;          /* 0 */
+    float lr;                  /* finite, >= 0                       (SB3: 3e-4) */
+    float beta_one, beta_two;  /* in [0, 1)                          (0.9, 0.999) */
+    float eps;                 /* finite, > 0                        (1e-8; SB3's PPO passes 1e-5) */
+    float max_grad_norm;       /* finite; <= 0: clipping off         (SB3: 0.5) */
+} qg_adam_params;
+int qg_policy_reserve_adam(qg_policy *policy);
+/* (one optimiser step; "update" because every *step* entry point of this header advances the envs) */
+int qg_policy_adam_update_device(qg_policy *policy, const qg_adam_params *params, const float *grad, const float *lr_device,
+                               float *params_out, float *stats, void *stream);
+int qg_policy_adam_get_state(qg_policy *policy, float *exp_avg, float *exp_avg_sq, int64_t *step);
+int qg_policy_adam_set_state(qg_policy *policy, const float *exp_avg, const float *exp_avg_sq, int64_t step);
+int qg_policy_normalize_advantages_device(qg_policy *policy, int32_t B, const float *adv, float *out, void *stream);
 
 /* ---- running observation and reward normalisation (SB3's VecNormalize) on the device ---------------------------------------------------
  * A qg_norm keeps, in f64 on the device, a running mean and variance per observation column, a discounted return per env and the

@@ -184,6 +184,20 @@ class QgPpoBatch(C.Structure):
         return d
 
 
+class QgAdamParams(C.Structure):
+    """``qg_adam_params``: the constants of one optimiser step (``struct_size`` is filled in); ``max_grad_norm=None`` is off."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("lr", C.c_float), ("beta_one", C.c_float), ("beta_two", C.c_float),
+                ("eps", C.c_float), ("max_grad_norm", C.c_float)]
+
+    @classmethod
+    def make(cls, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.5):
+        d = cls()
+        d.struct_size = C.sizeof(cls)
+        d.lr, d.beta_one, d.beta_two, d.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
+        d.max_grad_norm = 0.0 if max_grad_norm is None else float(max_grad_norm)
+        return d
+
+
 class QgNormDesc(C.Structure):
     """``qg_norm_desc``: a running normaliser's shape and constants (``struct_size`` is filled in)."""
     _fields_ = [("struct_size", C.c_int32), ("obs_dim", C.c_int32), ("n_envs", C.c_int32), ("gamma", C.c_double),
@@ -379,6 +393,11 @@ def load_library():
     lib.qg_policy_launch_shape.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.qg_policy_reserve_grad.argtypes = [vp, C.c_int32]
     lib.qg_policy_ppo_grad_device.argtypes = [vp, C.POINTER(QgPpoParams), C.c_int32, C.POINTER(QgPpoBatch), vp, vp, vp]
+    lib.qg_policy_reserve_adam.argtypes = [vp]
+    lib.qg_policy_adam_update_device.argtypes = [vp, C.POINTER(QgAdamParams), vp, vp, vp, vp, vp]
+    lib.qg_policy_adam_get_state.argtypes = [vp, vp, vp, C.POINTER(C.c_int64)]
+    lib.qg_policy_adam_set_state.argtypes = [vp, vp, vp, C.c_int64]
+    lib.qg_policy_normalize_advantages_device.argtypes = [vp, C.c_int32, vp, vp, vp]
     i32, f64 = C.c_int32, C.c_double
     lib.qg_norm_create.argtypes = [i32, C.POINTER(QgNormDesc), C.POINTER(vp)]
     lib.qg_norm_destroy.argtypes = [vp]
@@ -424,6 +443,8 @@ EXPORTS = (
     "qg_policy_create", "qg_policy_destroy", "qg_policy_param_count", "qg_policy_set_params", "qg_policy_get_params",
     "qg_policy_set_params_device", "qg_policy_forward_device", "qg_policy_launch_shape",
     "qg_policy_reserve_grad", "qg_policy_ppo_grad_device",
+    "qg_policy_reserve_adam", "qg_policy_adam_update_device", "qg_policy_adam_get_state", "qg_policy_adam_set_state",
+    "qg_policy_normalize_advantages_device",
     "qg_norm_create", "qg_norm_destroy", "qg_norm_step_device", "qg_norm_update_obs_device", "qg_norm_apply_obs_device",
     "qg_norm_reset_returns_device", "qg_norm_get_state", "qg_norm_set_state",
     "qg_rollout_create", "qg_rollout_destroy", "qg_rollout_begin_device", "qg_rollout_add_device", "qg_rollout_compute_device",

@@ -1,5 +1,6 @@
-// qg_policy.h -- what the two translation units of the fused MLP policy share: the layer table both kernels read (qg_policy.hip: the
-// forward pass; qg_policy_grad.hip: the PPO loss and gradient pass) and the handle.  Internal: not installed, nothing in here is exported.
+// qg_policy.h -- what the translation units of the fused MLP policy share: the layer table their kernels read (qg_policy.hip: the
+// forward pass; qg_policy_grad.hip: the PPO loss and gradient pass; qg_policy_opt.hip: the optimiser step) and the handle.  Internal:
+// not installed, nothing in here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,6 +45,11 @@ struct KGrad {
     KGradLayer layer[2][QGP_MAX_LAYERS];
 };
 
+// ---- the optimiser step (qg_policy_opt.hip) -------------------------------------------------------------------------------
+#define QGA_THREADS 256           // threads per workgroup of both launches
+#define QGA_SLOT 2048             // canonical elements per workgroup: one f64 partial of the gradient norm (FusedMlpPolicy.ADAM_SLOT)
+#define QGN_THREADS 1024          // the advantage normaliser's one workgroup
+
 struct qg_policy {
     int32_t device;
     qg_policy_desc desc;
@@ -62,6 +68,12 @@ struct qg_policy {
     double *d_tile_misc;      // [tiles][QGG_MISC]
     double *d_slot_misc;      // [slots][QGG_MISC]
     float *d_partial;         // [slots][n_params]
+    // qg_policy_reserve_adam: all null / zero until then
+    int32_t adam_slots;       // ceil(n_params / QGA_SLOT)
+    float *d_adam_m;          // [n_params] first moment
+    float *d_adam_v;          // [n_params] second moment
+    long long *d_adam_t;      // the step count, in device memory: a captured step replays as t = 1, 2, 3, ..
+    double *d_adam_partial;   // [adam_slots] sums of squares of the gradient
 };
 
 // the transposed image from the canonical vector, on `st`; a no-op before qg_policy_reserve_grad (qg_policy_grad.hip)

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import QgPolicyDesc, QgPpoBatch, QgPpoParams, check
+from ._abi import QgAdamParams, QgPolicyDesc, QgPpoBatch, QgPpoParams, check
 from ._handle import Handle
 
 
@@ -67,6 +67,9 @@ class FusedMlpPolicy(Handle):
     # consecutive rows, the reduce launch adds the slots in ascending order (QGG_SLOT_TILES of csrc/qg_policy.h)
     GRAD_TILE_ROWS = 16
     GRAD_SLOT_ROWS = 512
+    # canonical elements per slot of ``adam_step``'s gradient norm: a workgroup sums the squares of that many consecutive elements in
+    # float64, every workgroup of the update launch adds the slots in ascending order (QGA_SLOT of csrc/qg_policy.h)
+    ADAM_SLOT = 2048
 
     def __init__(self, obs_dim: int, hidden, act_dim: int, out_tanh: bool = False, value: bool = True, device: int = 0):
         super().__init__(device)
@@ -242,3 +245,65 @@ class FusedMlpPolicy(Handle):
         check(self._lib.qg_policy_ppo_grad_device(self._h, C.byref(params), n, C.byref(desc), grad.data_ptr(),
                                                   stats.data_ptr() if stats is not None else None, self._stream_ptr(stream)),
               "qg_policy_ppo_grad_device")
+
+    # -- the optimiser ----------------------------------------------------------------------
+    def reserve_adam(self):
+        """Allocate the optimiser's state: both moments and the step count, zero, in device memory (waits for the device; not during
+        a graph capture; a second call keeps the state).  ``reserve_grad`` is not needed for it."""
+        check(self._lib.qg_policy_reserve_adam(self._h), "qg_policy_reserve_adam")
+
+    def adam_step(self, grad, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.5, lr_tensor=None, params_out=None, stats=None,
+                  stream=None):
+        """``torch.nn.utils.clip_grad_norm_`` (``max_grad_norm=None`` or ``<= 0``: off) and one ``torch.optim.Adam`` step on the
+        policy's own parameters, two launches on ``stream``; ``include/quadgym.h`` states the order of operations.  ``grad[n_params]``
+        is read, not changed.  The operand images follow: the next ``forward`` / ``ppo_grad`` on the stream uses the new parameters,
+        no ``update_from``.  ``lr_tensor`` (one float32 on the device) replaces ``lr`` and is read at every replay of a captured
+        step; ``params_out[n_params]`` receives the new canonical vector; ``stats[4]`` = norm before clipping, clip coefficient, the
+        step count after the step, the learning rate used."""
+        import torch
+        f32 = torch.float32
+        self._check_tensor(grad, (self.n_params,), f32, "grad")
+        if lr_tensor is not None:
+            self._check_tensor(lr_tensor, (1,) if lr_tensor.dim() else (), f32, "lr_tensor")
+        if params_out is not None:
+            self._check_tensor(params_out, (self.n_params,), f32, "params_out")
+            if params_out.data_ptr() == grad.data_ptr():
+                raise ValueError("params_out must not be grad")
+        if stats is not None:
+            self._check_tensor(stats, (4,), f32, "stats")
+        params = QgAdamParams.make(lr, betas, eps, max_grad_norm)
+        check(self._lib.qg_policy_adam_update_device(self._h, C.byref(params), grad.data_ptr(),
+                                                   lr_tensor.data_ptr() if lr_tensor is not None else None,
+                                                   params_out.data_ptr() if params_out is not None else None,
+                                                   stats.data_ptr() if stats is not None else None, self._stream_ptr(stream)),
+              "qg_policy_adam_update_device")
+
+    def adam_state(self):
+        """``{"step": int, "exp_avg": float32[n_params], "exp_avg_sq": float32[n_params]}`` (NumPy; waits for the device): with
+        ``params()`` what a checkpoint of the optimiser holds."""
+        m, v, t = np.empty(self.n_params, np.float32), np.empty(self.n_params, np.float32), C.c_int64()
+        check(self._lib.qg_policy_adam_get_state(self._h, m.ctypes.data, v.ctypes.data, C.byref(t)), "qg_policy_adam_get_state")
+        return {"step": int(t.value), "exp_avg": m, "exp_avg_sq": v}
+
+    def load_adam_state(self, state):
+        """What ``adam_state`` returned, bit for bit (synchronous; after ``reserve_adam``)."""
+        m, v = (np.ascontiguousarray(_np32(state[k])) for k in ("exp_avg", "exp_avg_sq"))
+        if m.shape != (self.n_params,) or v.shape != (self.n_params,):
+            raise ValueError(f"expected two moment vectors of {self.n_params} elements, got shapes {m.shape}, {v.shape}")
+        check(self._lib.qg_policy_adam_set_state(self._h, m.ctypes.data, v.ctypes.data, int(state["step"])), "qg_policy_adam_set_state")
+
+    def normalize_advantages(self, adv, out=None, stream=None):
+        """SB3's ``normalize_advantage`` for one minibatch, one launch: ``(adv - adv.mean()) / (adv.std() + 1e-8)`` with both moments
+        in float64 and one rounding.  ``out=None`` normalises ``adv`` in place; returns the tensor written."""
+        import torch
+        if adv.dim() != 1 or adv.shape[0] < 2:
+            raise ValueError(f"adv: expected a vector of at least 2 rows, got shape {tuple(adv.shape)}")
+        n = int(adv.shape[0])
+        self._check_tensor(adv, (n,), torch.float32, "adv")
+        if out is None:
+            out = adv
+        else:
+            self._check_tensor(out, (n,), torch.float32, "out")
+        check(self._lib.qg_policy_normalize_advantages_device(self._h, n, adv.data_ptr(), out.data_ptr(), self._stream_ptr(stream)),
+              "qg_policy_normalize_advantages_device")
+        return out

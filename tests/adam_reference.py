@@ -1,0 +1,162 @@
+"""The float64 definition of what FusedMlpPolicy.adam_step and .normalize_advantages compute (include/quadgym.h, "Adam, gradient-norm
+clipping and advantage normalisation"), in NumPy: torch.nn.utils.clip_grad_norm_ + torch.optim.Adam (amsgrad off, no weight decay) and
+SB3's normalize_advantage -- the formulae and nothing cleverer, in float64 or in float32 arithmetic --, the three nets and the gradient
+recipe the CPU and GPU tests share, and the error budget measured by tests/test_adam_reference.py.  No GPU, no torch."""
+import functools
+import math
+
+import numpy as np
+
+from quadruped_gym_amd.policy import FusedMlpPolicy
+
+F32 = np.float32
+# the arguments are float32 in the C ABI: every checker takes the float32 VALUES (as Python floats), never 0.9 or 3e-4 themselves
+LR, BETA1, BETA2, EPS, MAX_NORM = (float(F32(x)) for x in (3e-4, 0.9, 0.999, 1e-8, 0.5))
+
+# (obs_dim, hidden, act_dim, critic)
+NETS = {
+    "A": (1, (16,), 1, False),                    # 50 parameters: less than one wave
+    "B": (33, (64, 64), 12, True),                # 13 529: padded columns 33 -> 48 and 12 -> 16
+    "C": (260, (256, 256, 128), 12, True),        # 332 697: many slots, ragged tail
+}
+# how the tests scale a gradient: clipping active (norm far above max_norm), inactive (below it: coef == 1 exactly), switched off
+MODES = {"active": (50.0, MAX_NORM), "inactive": (0.1, MAX_NORM), "off": (50.0, 0.0)}
+# step numbers at which the budget is measured (the state is the one after t - 1 float32 steps); the GPU test uses 1 and 8
+BUDGET_STEPS = (1, 2, 8, 10, 1000)
+GPU_STEPS = (1, 8)
+
+# ---- the measured error budget (tests/test_adam_reference.py prints a fresh measurement and fails if it exceeds these) ----------------
+# the largest deviation of the float32 evaluation of ONE step from the float64 evaluation of the same float32 inputs, over NETS x
+# BUDGET_STEPS x MODES: m and v in float32 ulps of the float64 result, p as |dp_32 - dp_64| / lr (dp: the update subtracted from p)
+# measured: m 77620.4 ulp (net C, t = 2, clipping active: b1 m and (1 - b1) g cancel, so an ulp of the RESULT is far smaller than an ulp
+# of either term -- without cancellation, at t = 1, it is 2.7 ulp), v 5.94 ulp, p 7.26e-7; rounded up by about 3 %
+BUDGET_M_ULP = 80000.0
+BUDGET_V_ULP = 6.1
+BUDGET_P = 7.5e-7
+# the figure for m is loose wherever the two terms do not cancel, so the GPU test also holds m to a bound that follows from the stated
+# order of operations: m = fma(b1, m, fl(a1 fl(coef g))) carries half an ulp of the result, and relative to the term a1 coef g two
+# roundings (2^-24 each) and the error of coef (three: the norm, the sum, the quotient) -- 5 x 2^-24 |term| <= 5 ulp of the term (a
+# relative 2^-24 is up to one ulp at the top of a binade), 5.5 ulp of the largest of the result and the two terms in all
+DERIVED_M_TERM_ULP = 5.5
+
+
+def derived_m_tolerance(m_old, g, coef64, m64):
+    """The bound above per element, from the float32 inputs and the float64 results of a step."""
+    term = (1.0 - BETA1) * coef64 * np.asarray(g, np.float64)
+    return DERIVED_M_TERM_ULP * ulp32(np.maximum(np.maximum(np.abs(BETA1 * np.asarray(m_old, np.float64)), np.abs(term)), np.abs(m64)))
+MARGIN = 4.0          # a different but equally valid rounding order: contraction into fma, rsqrt against sqrt and divide
+
+
+def n_params(name):
+    obs_dim, hidden, act_dim, critic = NETS[name]
+    layout = FusedMlpPolicy.param_layout(obs_dim, hidden, act_dim, critic)
+    off, shape = list(layout.values())[-1]
+    return off + math.prod(shape)
+
+
+def clip_and_adam(p, m, v, t, g, lr, b1, b2, eps, max_norm, dtype):
+    """One step from the state ``(p, m, v)`` after ``t`` steps: ``(p, m, v, t + 1, info)`` in ``dtype`` arithmetic; ``info`` holds the
+    norm before clipping, the clip coefficient and ``dp``, the update that was subtracted from ``p``.  Scalars that depend on the step
+    count are formed in float64 and rounded once."""
+    dt = np.dtype(dtype).type
+    p, m, v, g = (np.asarray(a).astype(dtype) for a in (p, m, v, g))
+    norm = np.sqrt(np.sum(g * g))
+    coef = min(dt(1.0), dt(max_norm) / (norm + dt(1e-6))) if max_norm > 0 else dt(1.0)
+    gc = g * coef
+    t = t + 1
+    m = dt(b1) * m + dt(1.0 - b1) * gc
+    v = dt(b2) * v + dt(1.0 - b2) * gc * gc
+    denom = np.sqrt(v) / dt(math.sqrt(1.0 - b2 ** t)) + dt(eps)
+    dp = dt(lr / (1.0 - b1 ** t)) * (m / denom)
+    return p - dp, m, v, t, dict(norm=norm, coef=coef, dp=dp)
+
+
+def normalize_advantages(adv, dtype):
+    """SB3's normalize_advantage: torch's ``std()`` is the unbiased one."""
+    adv = np.asarray(adv).astype(dtype)
+    return (adv - adv.mean()) / (adv.std(ddof=1) + np.dtype(dtype).type(1e-8))
+
+
+def ulp32(x):
+    """The float32 spacing at ``|x|`` (``x`` float64)."""
+    return np.spacing(np.abs(np.asarray(x, np.float64)).astype(F32)).astype(np.float64)
+
+
+# ---- inputs ---------------------------------------------------------------------------------------------------------------------------
+def _seed(name, *more):
+    return [ord(name)] + [int(x) for x in more]
+
+
+def initial_params(name):
+    """Random parameters, torch.nn.Linear-like per tensor; ``log_std`` around -1."""
+    obs_dim, hidden, act_dim, critic = NETS[name]
+    rng = np.random.default_rng(_seed(name, 1))
+    flat = np.empty(n_params(name), F32)
+    for key, (off, shape) in FusedMlpPolicy.param_layout(obs_dim, hidden, act_dim, critic).items():
+        n = math.prod(shape)
+        bound = 1.0 / math.sqrt(shape[-1] if key.endswith("weight") else 16.0)
+        flat[off:off + n] = rng.uniform(-bound, bound, n) if key != "log_std" else rng.normal(-1.0, 0.3, n)
+    return flat
+
+
+def make_gradient(name, seed, norm):
+    """Normal draws with a scale per tensor (three decades) and a block of exact zeros, scaled to the Euclidean ``norm``; then a
+    block of magnitude 1e-12; float32."""
+    obs_dim, hidden, act_dim, critic = NETS[name]
+    rng = np.random.default_rng(_seed(name, 2, seed))
+    n = n_params(name)
+    g = np.empty(n, np.float64)
+    for off, shape in FusedMlpPolicy.param_layout(obs_dim, hidden, act_dim, critic).values():
+        k = math.prod(shape)
+        g[off:off + k] = rng.standard_normal(k) * 10.0 ** rng.uniform(-3.0, 0.0)
+    block = max(2, n // 16)
+    z0 = int(rng.integers(0, n - 2 * block + 1))
+    g[z0:z0 + 2 * block] = 0.0
+    tiny = rng.choice([-1.0, 1.0], block) * 1e-12
+    g *= norm / math.sqrt(float(np.sum(g * g)))
+    g[z0 + block:z0 + 2 * block] = tiny
+    return g.astype(F32)
+
+
+@functools.lru_cache(maxsize=None)
+def state_after(name, steps):
+    """``(p, m, v)`` after ``steps`` float32 steps (clipping at MAX_NORM, the default constants) from ``initial_params`` and zero
+    moments, on gradients drawn from a pool of eight with a random scale per step.  Read-only arrays."""
+    p = initial_params(name)
+    m, v = np.zeros_like(p), np.zeros_like(p)
+    rng = np.random.default_rng(_seed(name, 3))
+    pool = [make_gradient(name, 100 + k, 1.0) for k in range(8)] if steps else []
+    for t in range(steps):
+        g = pool[t % 8] * F32(10.0 ** rng.uniform(-1.0, 1.0))
+        p, m, v, _, _ = clip_and_adam(p, m, v, t, g, LR, BETA1, BETA2, EPS, MAX_NORM, F32)
+    for a in (p, m, v):
+        a.setflags(write=False)
+    return p, m, v
+
+
+@functools.lru_cache(maxsize=None)
+def one_step_case(name, t, mode):
+    """The inputs of step number ``t`` in ``mode`` and its float64 result: ``(p, m, v, g, max_norm, (p64, m64, v64, info64))``."""
+    norm, max_norm = MODES[mode]
+    p, m, v = state_after(name, t - 1)
+    g = make_gradient(name, 1000 + t, norm)
+    p64, m64, v64, _, info = clip_and_adam(*(a.astype(np.float64) for a in (p, m, v)), t - 1, g.astype(np.float64), LR, BETA1, BETA2, EPS,
+                                           max_norm, np.float64)
+    return p, m, v, g, max_norm, (p64, m64, v64, info)
+
+
+def deviations(m_got, v_got, dp_got, ref):
+    """``(m in ulp, v in ulp, |dp - dp64| / lr)``, each the largest over the elements, of one step's results against ``ref`` (the last
+    entry of ``one_step_case``)."""
+    _, m64, v64, info = ref
+    return (float(np.max(np.abs(m_got.astype(np.float64) - m64) / ulp32(m64))),
+            float(np.max(np.abs(v_got.astype(np.float64) - v64) / ulp32(v64))),
+            float(np.max(np.abs(np.asarray(dp_got, np.float64) - info["dp"])) / LR))
+
+
+def gpu_tolerances(p64, m64, v64, lr=LR, steps=1):
+    """Per-element absolute bounds ``(p, m, v)`` for ``steps`` consecutive steps on the device against their float64 replay: the
+    measured budget times MARGIN (at least one ulp for the moments), and for ``p`` half an ulp of ``p`` for its own rounding."""
+    return (steps * (MARGIN * BUDGET_P * lr + 0.5 * ulp32(p64)),
+            steps * max(MARGIN * BUDGET_M_ULP, 1.0) * ulp32(m64),
+            steps * max(MARGIN * BUDGET_V_ULP, 1.0) * ulp32(v64))
