@@ -870,6 +870,100 @@ int qg_rollout_get_info(qg_rollout *rollout, qg_rollout_info *info);
  * zeroes them; running episodes (cur_return, cur_length) continue. */
 int qg_rollout_episode_stats(qg_rollout *rollout, double *return_sum, int64_t *length_sum, int64_t *count, int32_t clear);
 
+/* ---- sensor noise, sensor bias and actuation latency on the device ---------------------------------------------------------------------
+ * A qg_perturb stands between a policy and an env: one launch before the env delays the actions by a per-episode number of env-steps
+ * and adds Gaussian noise to them, one launch behind the env adds Gaussian noise and a per-episode constant bias to chosen columns of
+ * the observation frames.  Like qg_norm it is independent of qg_sim and touches no step kernel; all of its state is in device memory.
+ *
+ * Keys.  Every draw is a pure function of (seed, env_index_base + i, episode_i, stream): shards reproduce the rows of one big handle,
+ * a replayed graph draws fresh noise at every replay (age and episode advance on the device), and a frame keeps its noise while it
+ * travels through the window of a stacked observation.
+ *   seed_p = seed + 0x51474E4F49534531                                        (mod 2^64: a key space apart from the simulator's streams)
+ *   k(s)   = the 24-bit integer of the simulator's stream hash:  x = seed_p + 0xA0761D6478BD642F * s + 0x9E3779B97F4A7C15 * (env + 1)
+ *            + 0xD1B54A32D192ED03 * (episode + 1);  k = mix64(mix64(x)) >> 40  (splitmix64's finaliser, twice; s as a 64-bit integer)
+ *   z(s)   = sqrt(-2 ln u1) * cos(2 pi u2),  u1 = (k(s) + 1) / 2^24,  u2 = k(s + 1) / 2^24;   |z| <= sqrt(48 ln 2) = 5.77
+ *            evaluated in f32 in this order: u1 and 2 * u2 are exact; L = logf(u1); r = sqrtf(-2 * L); c = cospif(2 * u2); z = r * c.
+ * Streams: 0 the delay; 2 + 2c the bias of column c (c < 64); S(f, q) = 4096 + 2 * (128 * f + q) the draws of frame f: q = c is
+ * observation column c, q = 64 + j the action noise of joint j for the env-step taken at age f.  Frame 0 is the reset frame, the frame
+ * the step taken at age a produces is frame a + 1.  f < 2^23.
+ *
+ * State per env: age (env-steps since the episode began), episode (this handle's own counter, 0 in a new handle; NOT the
+ * simulator's) and an action ring [max_delay + 1][n][12].
+ *   d_i = delay_lo + ((k(0) * (delay_hi - delay_lo + 1)) >> 24)              computed from the key of the running episode, not stored
+ *
+ * actions (before the env; reads age, does not advance it), M = max_delay + 1:
+ *   ring[age mod M][i] = actions_in[i];   v = age - d_i >= 0 ? ring[(age - d_i) mod M][i] : reset_action
+ *   actions_out[i][j] = v_j                                                 action_std == 0: a bit copy
+ *                     = v_j + action_std * z(S(age, 64 + j))                else: one product, one add, both rounded (no fma)
+ *   No clipping (the env clips).  actions_out may be actions_in.
+ *
+ * observe (behind the env); a row is [window][frame_dim], newest frame last; a' = age + 1.  The row of episode E with top frame t:
+ *   slot k holds frame f = max(t - (window - 1 - k), 0);    out = in + e(f, c)                                     ONE f32 add
+ *   e(f, c) = bias_std[c] * z(2 + 2c) + obs_std[c] * z(S(f, c))      two f32 products and their f32 sum, no fma; a term whose std is
+ *   0 is left out.  A column with obs_std[c] == 0 and bias_std[c] == 0 is copied bit for bit and never touches the hash.
+ *   live env:      obs row = (episode, a');  then age = a'
+ *   finished env, QG_PERTURB_DONE_ROW_RESET (the partially observable env: the row already holds the new episode's reset stack):
+ *                  obs row = (episode + 1, 0): frame 0 in every slot;  terminal_obs row, when given, = (episode, a')
+ *   finished env, QG_PERTURB_DONE_ROW_TERMINAL (the plain and the walking env: the row is the terminal observation):
+ *                  obs row = (episode, a')
+ *   finished env, both: then episode += 1, age = 0.   Rows of terminal_obs that belong to live envs are not touched.
+ *
+ * begin (an explicit reset): for the envs of the mask (all, when NULL): episode += 1, age = 0, and, when rows are given, their row =
+ * (episode + 1, 0).  Other envs' rows are not touched.
+ *
+ * One wave owns an env in observe and begin: it alone reads and writes that env's age and episode, so rows may be perturbed in
+ * place.  No atomics; no workgroup waits for another.  Results are bit-identical between runs, between eager calls and graph replay and
+ * between a handle and shards of it.  Outputs for non-finite inputs are unspecified (the device code is compiled with finite-math
+ * assumptions), except that columns copied through keep their bits.
+ *
+ * Ordering: qg_perturb_actions_device, _observe_device and _begin_device follow the contract of the other *_device entry points (they
+ * enqueue on the caller's stream, return at once, are ONE kernel launch each and may be captured into a hipGraph).  Calls on one handle
+ * must be ordered by the caller.  qg_perturb_create, _destroy, _get_delays, _get_state and _set_state wait for the device and must not
+ * be called during a capture. */
+typedef struct qg_perturb qg_perturb;
+typedef struct qg_perturb_desc {
+    int32_t struct_size;       /* sizeof(qg_perturb_desc): checked */
+    int32_t n_envs;            /* >= 1 */
+    int32_t frame_dim;         /* 1 .. 64 */
+    int32_t window;            /* 1 .. 64: an observation row is window * frame_dim floats */
+    int32_t max_delay;         /* 0 .. 16 env-steps: the ring holds max_delay + 1 action rows per env */
+    int32_t delay_lo;          /* 0 <= delay_lo <= delay_hi <= max_delay */
+    int32_t delay_hi;
+    int32_t done_row;          /* QG_PERTURB_DONE_ROW_RESET or _TERMINAL */
+    float action_std;          /* finite, >= 0 */
+    float obs_std[64];         /* per frame column, finite, >= 0; columns >= frame_dim are ignored */
+    float bias_std[64];
+    float reset_action[12];    /* what the servos hold until the first delayed action arrives (the task's default_ctrl); finite */
+    int32_t reserved;          /* 0 */
+    uint64_t seed;
+    uint64_t env_index_base;   /* env i of this handle is env env_index_base + i of the run */
+} qg_perturb_desc;
+#define QG_PERTURB_DONE_ROW_RESET 0
+#define QG_PERTURB_DONE_ROW_TERMINAL 1
+#define QG_PERTURB_DONE_U8 0   /* = QG_NORM_DONE_U8 */
+#define QG_PERTURB_DONE_F32 1  /* = QG_NORM_DONE_F32: the last column of the plain env's packed row */
+#define QG_PERTURB_MAX_DELAY 16
+/* Validation (QG_ERR_ARG) comes before the device check (QG_ERR_DEVICE: there is no CPU backend).  A new handle has age = 0,
+ * episode = 0 and a ring of zeros. */
+int qg_perturb_create(int32_t device_id, const qg_perturb_desc *desc, qg_perturb **out);
+int qg_perturb_destroy(qg_perturb *perturb);
+/* n must equal n_envs.  Device pointers, [n][12] f32, contiguous. */
+int qg_perturb_actions_device(qg_perturb *perturb, int32_t n, const float *actions_in, float *actions_out, void *stream);
+/* Rows of window * frame_dim floats at in_stride / out_stride (elements, >= the row length); obs_out may be obs_in.  terminal_obs
+ * (nullable, in place, its own stride) only with QG_PERTURB_DONE_ROW_RESET.  done nullable (no env finished), of the type done_kind
+ * names, at done_stride elements. */
+int qg_perturb_observe_device(qg_perturb *perturb, int32_t n, const float *obs_in, int32_t in_stride, float *obs_out, int32_t out_stride,
+                              float *terminal_obs, int32_t terminal_stride, const void *done, int32_t done_kind, int32_t done_stride,
+                              void *stream);
+/* mask: nullable device [n] u8 (non-zero selects); rows: nullable device rows at row_stride, perturbed in place. */
+int qg_perturb_begin_device(qg_perturb *perturb, int32_t n, const uint8_t *mask, float *rows, int32_t row_stride, void *stream);
+/* Host: delays[n_envs] = d_i of the running episodes. */
+int qg_perturb_get_delays(qg_perturb *perturb, int32_t *delays);
+/* Host arrays: age [n] i32, episode [n] i64 (0 <= episode < 2^62, 0 <= age < 2^23), ring [max_delay + 1][n][12] f32.  The round trip
+ * is exact. */
+int qg_perturb_get_state(qg_perturb *perturb, int32_t *age, int64_t *episode, float *ring);
+int qg_perturb_set_state(qg_perturb *perturb, const int32_t *age, const int64_t *episode, const float *ring);
+
 #ifdef __cplusplus
 }
 #endif

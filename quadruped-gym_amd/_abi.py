@@ -270,6 +270,44 @@ class QgRolloutInfo(C.Structure):
 ROLLOUT_DONE_U8, ROLLOUT_DONE_F32 = NORM_DONE_U8, NORM_DONE_F32
 
 
+class QgPerturbDesc(C.Structure):
+    """``qg_perturb_desc``: the shape, the standard deviations and the key of a perturbation layer (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_envs", C.c_int32), ("frame_dim", C.c_int32), ("window", C.c_int32),
+                ("max_delay", C.c_int32), ("delay_lo", C.c_int32), ("delay_hi", C.c_int32), ("done_row", C.c_int32),
+                ("action_std", C.c_float), ("obs_std", C.c_float * 64), ("bias_std", C.c_float * 64), ("reset_action", C.c_float * NU),
+                ("reserved", C.c_int32), ("seed", C.c_uint64), ("env_index_base", C.c_uint64)]
+
+    @classmethod
+    def make(cls, n_envs, frame_dim, window=1, max_delay=0, delays=(0, 0), action_std=0.0, obs_std=(), bias_std=(), reset_action=None,
+             done_row=0, seed=0, env_index_base=0):
+        """``obs_std`` / ``bias_std``: up to ``frame_dim`` values, missing columns are 0.  ``reset_action=None``: the default task's
+        ``default_ctrl``."""
+        d = cls()
+        d.struct_size = C.sizeof(cls)
+        d.n_envs, d.frame_dim, d.window, d.max_delay = int(n_envs), int(frame_dim), int(window), int(max_delay)
+        d.delay_lo, d.delay_hi, d.done_row = int(delays[0]), int(delays[1]), int(done_row)
+        d.action_std = float(action_std)
+        for name, vals in (("obs_std", obs_std), ("bias_std", bias_std)):
+            vals = [float(v) for v in vals]
+            if len(vals) > 64:
+                raise ValueError(f"{name}: at most 64 columns, got {len(vals)}")
+            for c, v in enumerate(vals):
+                getattr(d, name)[c] = v
+        if reset_action is None:
+            reset_action = (0.0, 0.0, -0.5) * 4             # qg_default_task's default_ctrl (quadruped.py:124)
+        if len(reset_action) != NU:
+            raise ValueError(f"reset_action: {NU} values, got {len(reset_action)}")
+        for j, v in enumerate(reset_action):
+            d.reset_action[j] = float(v)
+        d.seed, d.env_index_base = int(seed) % (1 << 64), int(env_index_base)
+        return d
+
+
+PERTURB_DONE_ROW_RESET, PERTURB_DONE_ROW_TERMINAL = 0, 1
+PERTURB_DONE_U8, PERTURB_DONE_F32 = NORM_DONE_U8, NORM_DONE_F32
+PERTURB_MAX_DELAY = 16
+
+
 def package_dir() -> str:
     return os.path.dirname(os.path.abspath(__file__))
 
@@ -415,6 +453,14 @@ def load_library():
     lib.qg_rollout_gather_device.argtypes = [vp, vp, i32, C.POINTER(QgRolloutBatch), vp]
     lib.qg_rollout_get_info.argtypes = [vp, C.POINTER(QgRolloutInfo)]
     lib.qg_rollout_episode_stats.argtypes = [vp, C.POINTER(f64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32]
+    lib.qg_perturb_create.argtypes = [i32, C.POINTER(QgPerturbDesc), C.POINTER(vp)]
+    lib.qg_perturb_destroy.argtypes = [vp]
+    lib.qg_perturb_actions_device.argtypes = [vp, i32, vp, vp, vp]
+    lib.qg_perturb_observe_device.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp]
+    lib.qg_perturb_begin_device.argtypes = [vp, i32, vp, vp, i32, vp]
+    lib.qg_perturb_get_delays.argtypes = [vp, vp]
+    lib.qg_perturb_get_state.argtypes = [vp, vp, vp, vp]
+    lib.qg_perturb_set_state.argtypes = [vp, vp, vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("qg_version", "qg_build_id", "qg_last_error", "qg_time_limit_substeps", "qg_walk_state_bytes", "qg_po_state_bytes",
@@ -449,6 +495,8 @@ EXPORTS = (
     "qg_norm_reset_returns_device", "qg_norm_get_state", "qg_norm_set_state",
     "qg_rollout_create", "qg_rollout_destroy", "qg_rollout_begin_device", "qg_rollout_add_device", "qg_rollout_compute_device",
     "qg_rollout_gather_device", "qg_rollout_get_info", "qg_rollout_episode_stats",
+    "qg_perturb_create", "qg_perturb_destroy", "qg_perturb_actions_device", "qg_perturb_observe_device", "qg_perturb_begin_device",
+    "qg_perturb_get_delays", "qg_perturb_get_state", "qg_perturb_set_state",
 )
 
 
