@@ -964,6 +964,79 @@ int qg_perturb_get_delays(qg_perturb *perturb, int32_t *delays);
 int qg_perturb_get_state(qg_perturb *perturb, int32_t *age, int64_t *episode, float *ring);
 int qg_perturb_set_state(qg_perturb *perturb, const int32_t *age, const int64_t *episode, const float *ring);
 
+/* ---- foot-contact sensing on the device: ground reaction forces, foot kinematics, gait timers --------------------------------------
+ * A qg_contact is bound to a simulator and only READS its state arrays: it adds no step kernel and changes none.  One launch
+ * (qg_contact_read_device) evaluates, for every env, at the state (qpos, qvel) AS IT STANDS IN MEMORY:
+ *
+ * Body poses and velocities, world frame (body 0 = FRAME, body 1 + 3k + i = link i of leg k; hinge j drives body j + 1 about its z):
+ *   x_0 = qpos[0:3], R_0 = R(qpos[3:7] / |qpos[3:7]|);   x_b = x_p + R_p pos_b,  R_b = R_p Q_b Rz(qpos[7 + j] - ref_j)   (p: parent)
+ *   v_0 = qvel[0:3], w_0 = R_0 qvel[3:6];   v_b = v_p + w_p x (x_b - x_p),  w_b = w_p + (third column of R_b) qvel[6 + j]
+ *
+ * Ground reaction force of body b (plane z = 0, the contact law of the step kernels), over its sample points cp_i:
+ *   r_i = R_b cp_i,  pen_i = max(0, contact_margin - (x_b.z + r_i.z)),  S = sum_i pen_i,  W = contact_stiffness * S
+ *   P = x_b + (sum_i pen_i r_i) / S                      centre of pressure;   vP = v_b + w_b x (P - x_b)
+ *   c = contact_damping * min(1, S / contact_ramp)       the damper ramps in with the summed penetration
+ *   F_n = max(0, W - c vP.z)                             no adhesion
+ *   c_t = c, or mu F_n / |vP.xy| where c |vP.xy| > mu F_n    viscous, Coulomb-limited
+ *   F[b] = (-c_t vP.x, -c_t vP.y, F_n);  F[b] = 0 where no point is below the margin.
+ * This is the force the NEXT substep would apply from the velocity before its update -- not the force of the substep that produced
+ * the state.  After an auto-reset the row describes the new episode's first state.  A qg_step_device_seq launch shows only the state
+ * after its last env-step.  The contact constants are those of the handle's model (any model); while per-env dynamics are on, friction
+ * and the contact stiffness and damping scales come from the env's row.  External wrenches and pushes do not enter.
+ *
+ * Feet are bodies 3, 6, 9, 12 (foot f = leg f).  contact_f = F[foot].z > force_threshold.  Gait timers, per foot, in whole env-steps
+ * (exact integers in device memory: prev_contact, phase_steps, last_air_steps, last_stance_steps; and one `armed` flag per env),
+ * updated by a read with advance != 0:
+ *   not armed, or done[env] != 0:  phase_steps = 1, last_air_steps = last_stance_steps = 0, no event, prev = contact; the env is armed
+ *   armed, contact == prev:        phase_steps += 1
+ *   armed, contact != prev:        touchdown (contact now): last_air_steps = phase_steps; liftoff: last_stance_steps = phase_steps;
+ *                                  the event's column is 1 in this row; phase_steps = 1, prev = contact
+ * With advance == 0 nothing is written: the row shows contact from the state, the timers as they stand, and no event.  Times are
+ * f32(steps) * f32(dt), dt = model.timestep * task.frame_skip of the simulator's task at the call.
+ *
+ * Outputs (device, f32, env-major, each nullable but not both): body_force [n][13][3]; feet [n][4][12] in the columns below (48 bytes
+ * per foot; `feet` must be 16-byte aligned).  Rows depend on their env alone: a handle of any size computes the same bits for a state.
+ * Outputs for non-finite states are unspecified (the device code is compiled with finite-math assumptions).
+ *
+ * Ordering: qg_contact_read_device follows the contract of the other *_device entry points: ONE kernel launch on the caller's stream,
+ * no allocation and no wait, may be captured into a hipGraph (the timers live in device memory, so a replay advances them).  The
+ * caller orders it behind the step whose state it is to see.  While the resident step mode is on the state lives in registers:
+ * reads are refused (qg_resident_stop first).  Every refusal is QG_ERR_ARG and comes before anything is launched.  qg_contact_create,
+ * _destroy, _reset, _read, _get_state and _set_state wait for the device and must not be called during a capture; destroy the
+ * qg_contact before its simulator. */
+typedef struct qg_contact qg_contact;
+typedef struct qg_contact_desc {
+    int32_t struct_size;       /* sizeof(qg_contact_desc): checked */
+    int32_t reserved;          /* 0 */
+    float force_threshold;     /* N; finite, >= 0 */
+} qg_contact_desc;
+#define QG_CONTACT_FORCE_DIM 39    /* floats per env of body_force */
+#define QG_CONTACT_FEET_DIM 48     /* floats per env of feet */
+#define QG_FOOT_DIM 12             /* floats per foot */
+#define QG_FOOT_POS 0              /* world position of the foot body's frame origin (3) */
+#define QG_FOOT_VEL 3              /* world velocity of that origin (3) */
+#define QG_FOOT_CONTACT 6          /* 0.0 or 1.0 */
+#define QG_FOOT_TOUCHDOWN 7        /* 0.0 or 1.0 */
+#define QG_FOOT_LIFTOFF 8          /* 0.0 or 1.0 */
+#define QG_FOOT_PHASE_TIME 9       /* s in the current phase (stance or swing), this sample included */
+#define QG_FOOT_LAST_AIR_TIME 10   /* s of the last completed swing (0: none yet in this episode) */
+#define QG_FOOT_LAST_STANCE_TIME 11
+#define QG_CONTACT_DONE_U8 0       /* = QG_NORM_DONE_U8 */
+#define QG_CONTACT_DONE_F32 1      /* = QG_NORM_DONE_F32: the last column of the plain env's packed row */
+int qg_contact_create(qg_sim *sim, const qg_contact_desc *desc, qg_contact **out);
+int qg_contact_destroy(qg_contact *contact);
+/* Disarms the envs of the host mask [n] (non-zero selects; NULL: every env): their next advancing read starts an episode. */
+int qg_contact_reset(qg_contact *contact, const uint8_t *mask);
+/* done: nullable device [n] at done_stride elements, of the type done_kind names; read only when advance != 0. */
+int qg_contact_read_device(qg_contact *contact, const void *done, int32_t done_kind, int32_t done_stride, int32_t advance,
+                           float *body_force, float *feet, void *stream);
+/* The same rows into host arrays (each nullable but not both), synchronously, without advancing the timers. */
+int qg_contact_read(qg_contact *contact, float *body_force, float *feet);
+/* The timers and armed flags as one opaque blob (the round trip is exact; a blob fits a handle of the same n_envs). */
+int64_t qg_contact_state_bytes(const qg_contact *contact);
+int qg_contact_get_state(qg_contact *contact, void *blob);
+int qg_contact_set_state(qg_contact *contact, const void *blob);
+
 #ifdef __cplusplus
 }
 #endif

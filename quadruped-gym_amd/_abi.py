@@ -308,6 +308,26 @@ PERTURB_DONE_U8, PERTURB_DONE_F32 = NORM_DONE_U8, NORM_DONE_F32
 PERTURB_MAX_DELAY = 16
 
 
+class QgContactDesc(C.Structure):
+    """``qg_contact_desc``: a contact sensor's constants (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("force_threshold", C.c_float)]
+
+    @classmethod
+    def make(cls, force_threshold=0.0):
+        d = cls()
+        d.struct_size = C.sizeof(cls)
+        d.force_threshold = float(force_threshold)
+        return d
+
+
+CONTACT_DONE_U8, CONTACT_DONE_F32 = NORM_DONE_U8, NORM_DONE_F32
+NFOOT, FOOT_DIM = 4, 12
+# the columns of a foot's row (QG_FOOT_* of include/quadgym.h)
+FOOT_COLUMNS = ("pos_x", "pos_y", "pos_z", "vel_x", "vel_y", "vel_z", "contact", "touchdown", "liftoff", "phase_time", "last_air_time",
+                "last_stance_time")
+FOOT_BODIES = (3, 6, 9, 12)
+
+
 def package_dir() -> str:
     return os.path.dirname(os.path.abspath(__file__))
 
@@ -461,10 +481,19 @@ def load_library():
     lib.qg_perturb_get_delays.argtypes = [vp, vp]
     lib.qg_perturb_get_state.argtypes = [vp, vp, vp, vp]
     lib.qg_perturb_set_state.argtypes = [vp, vp, vp, vp]
+    lib.qg_contact_create.argtypes = [vp, C.POINTER(QgContactDesc), C.POINTER(vp)]
+    lib.qg_contact_destroy.argtypes = [vp]
+    lib.qg_contact_reset.argtypes = [vp, vp]
+    lib.qg_contact_read_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.qg_contact_read.argtypes = [vp, vp, vp]
+    lib.qg_contact_state_bytes.restype = C.c_int64
+    lib.qg_contact_state_bytes.argtypes = [vp]
+    lib.qg_contact_get_state.argtypes = [vp, vp]
+    lib.qg_contact_set_state.argtypes = [vp, vp]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("qg_version", "qg_build_id", "qg_last_error", "qg_time_limit_substeps", "qg_walk_state_bytes", "qg_po_state_bytes",
-                        "qg_recommended_batch"):
+                        "qg_recommended_batch", "qg_contact_state_bytes"):
             fn.restype = C.c_int
     _lib = lib
     return lib
@@ -497,6 +526,8 @@ EXPORTS = (
     "qg_rollout_gather_device", "qg_rollout_get_info", "qg_rollout_episode_stats",
     "qg_perturb_create", "qg_perturb_destroy", "qg_perturb_actions_device", "qg_perturb_observe_device", "qg_perturb_begin_device",
     "qg_perturb_get_delays", "qg_perturb_get_state", "qg_perturb_set_state",
+    "qg_contact_create", "qg_contact_destroy", "qg_contact_reset", "qg_contact_read_device", "qg_contact_read",
+    "qg_contact_state_bytes", "qg_contact_get_state", "qg_contact_set_state",
 )
 
 

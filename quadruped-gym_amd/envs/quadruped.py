@@ -45,7 +45,24 @@ class ModelView:
 
 
 class DataView:
-    """Host mirror of ``mujoco.MjData``: ``qpos, qvel, act, ctrl, time, sensordata, xfrc_applied`` as float64 arrays."""
+    """Host mirror of ``mujoco.MjData``: ``qpos, qvel, act, ctrl, time, sensordata, xfrc_applied`` as float64 arrays.  On an env's
+    ``data``, ``contact_force [13, 3]`` (world-frame ground reaction force per body, the one the next substep applies) and
+    ``foot_contact [4]`` (bool) are evaluated on the device when they are read, and cost nothing otherwise."""
+
+    _contact_reader = None                  # the env's: () -> (contact_force, foot_contact)
+
+    @property
+    def contact_force(self):
+        return self._read_contact()[0]
+
+    @property
+    def foot_contact(self):
+        return self._read_contact()[1]
+
+    def _read_contact(self):
+        if self._contact_reader is None:
+            raise AttributeError("contact_force / foot_contact belong to an env's data")
+        return self._contact_reader()
 
     def __init__(self):
         self.qpos = np.zeros(19)
@@ -79,6 +96,8 @@ class QuadrupedEnv(EnvBase):
         qg_model, layout = load_model(model_path)          # FileNotFoundError for a bad path (quadruped.py:55-56)
         self.model = ModelView(qg_model, layout)
         self.data = DataView()
+        self.data._contact_reader = self._read_contact
+        self._contact = None                # the ContactSensor, created by the first read of data.contact_force / foot_contact
         self.max_time = max_time
         self.frame_skip = frame_skip
         if render_mode is not None or save_video:
@@ -160,8 +179,19 @@ class QuadrupedEnv(EnvBase):
 
     def close(self):
         if getattr(self, "_sim", None) is not None:
-            self._sim.close()
+            self._sim.close()                               # and, before it, the contact sensor bound to it
             self._sim = None
+            self._contact = None
+
+    def _read_contact(self):
+        """``(contact_force [13, 3] float64, foot_contact [4] bool)`` of the state ``data`` shows (edits of it are pushed first)."""
+        if self._contact is None:
+            from ..contact import ContactSensor
+            self._contact = ContactSensor(self._sim)
+        if self._synced is not None:
+            self._push_if_edited()
+        force, feet = self._contact.read_host()
+        return force[0].astype(np.float64), feet[0, :, _abi.FOOT_COLUMNS.index("contact")] > 0.5
 
     # -- host mirror <-> device state -----------------------------------------------------------------
     def _pull(self, state=None):

@@ -192,6 +192,24 @@ class BatchedEnvBase:
         """``[num_envs, 13, 6]`` f32: the external wrench rows (without the pushes of ``push_randomization``)."""
         return self._sim.get_external_wrench()
 
+    # -- foot-contact sensing (contact.py; include/quadgym.h: qg_contact_*) ----------------------------------------------------------
+    _contact = None
+
+    def contact_sensor(self, force_threshold: float = 0.0):
+        """The env's ``ContactSensor`` (created at the first call): ground forces, foot kinematics and gait timers of every robot in
+        one launch, ``sensor.read(done=...)`` behind a ``step_tensor``.  The env's ``reset`` restarts its timers, ``snapshot`` /
+        ``restore`` (where the env has them) carry them, ``close`` destroys it.  An env that never asks launches nothing."""
+        if self._contact is None:
+            from ..contact import ContactSensor
+            self._contact = ContactSensor(self._sim, force_threshold)
+        elif float(force_threshold) != self._contact.force_threshold:
+            raise ValueError(f"this env's contact sensor has force_threshold {self._contact.force_threshold}, not {float(force_threshold)}")
+        return self._contact
+
+    def _reset_contact(self, mask=None):
+        if self._contact is not None:
+            self._contact.reset(mask)
+
     def step_async(self, actions):
         self._actions = np.ascontiguousarray(actions, dtype=np.float32)
 
@@ -204,6 +222,7 @@ class BatchedEnvBase:
         if getattr(self, "_sim", None) is not None:
             self._sim.close()
             self._sim = None
+            self._contact = None
 
     def seed(self, seed=None):
         self._seed = 0 if seed is None else int(seed)
@@ -323,6 +342,7 @@ class QuadrupedVecEnv(BatchedEnvBase, _VecEnvBase):
     def reset(self):
         self._sync_task()
         self._sim.reset(seed=self._seed, flags=self._reset_flags)
+        self._reset_contact()
         return np.zeros((self.num_envs, self.obs_dim), np.float32)      # the reference's first obs is all zeros
 
     def _eval_callables(self, obs, state=None):
@@ -390,6 +410,7 @@ class QuadrupedVecEnv(BatchedEnvBase, _VecEnvBase):
                  else LazyInfos(self.num_envs, make))
         if host and finished.size:
             self._sim.reset(mask=done.astype(np.uint8), flags=self._reset_flags)    # draws from the batch's own streams
+            self._reset_contact(done)
         if finished.size:
             obs = obs.copy()
             obs[done] = 0.0                                 # envs that finished were reset: their next obs is the reset obs
