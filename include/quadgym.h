@@ -66,6 +66,11 @@ extern "C" {
 #define QG_ERR_ALLOC (-3)
 #define QG_ERR_LAUNCH (-4)
 
+/* The done vector of the device-side layers (qg_norm, qg_rollout, qg_perturb, qg_contact): a device [n] at done_stride elements
+ * (>= 1), of the type done_kind names, nullable where the entry point says so.  Non-zero is done. */
+#define QG_DONE_U8 0     /* uint8 (the walking and partially observable envs' buffer; torch.bool as well) */
+#define QG_DONE_F32 1    /* f32 (the last column of the plain env's packed row) */
+
 /* observation packs (qg_task.obs_mode) */
 #define QG_OBS_FULL 0    /* the 33-value sensordata of quadruped.py:141-143 */
 #define QG_OBS_IMU 1     /* jointpos 12 + accel 3 + gyro 3 + velocimeter 3 = 21 (BASELINE config 5) */
@@ -716,14 +721,14 @@ typedef struct qg_norm_desc {
     int32_t norm_obs;          /* 0 or 1 */
     int32_t norm_reward;       /* 0 or 1 */
 } qg_norm_desc;
-#define QG_NORM_DONE_U8 0      /* done is uint8 (the walking and partially observable envs' buffer) */
-#define QG_NORM_DONE_F32 1     /* done is f32 (the last column of the plain env's packed row) */
+#define QG_NORM_DONE_U8 QG_DONE_U8      /* the older names of the pair */
+#define QG_NORM_DONE_F32 QG_DONE_F32
 /* Validation (QG_ERR_ARG) comes before the device check (QG_ERR_DEVICE: there is no CPU backend). */
 int qg_norm_create(int32_t device_id, const qg_norm_desc *desc, qg_norm **out);
 int qg_norm_destroy(qg_norm *norm);
 /* One step as above; n must equal n_envs.  Device pointers; strides in elements.  obs rows of obs_dim floats at in_stride /
  * out_stride >= obs_dim; obs_out == obs_in (in place) is allowed, and so is reward_out == reward_in.  reward_in nullable: NULL is an
- * observation-only step (steps 1 and 2).  done nullable (no return is ever cleared), of the type done_kind names.  With the strides
+ * observation-only step (steps 1 and 2).  done: a done vector (QG_DONE_*), nullable (no return is ever cleared).  With the strides
  * one call normalises a packed [n][obs_dim + 2] row in place: obs at column 0, reward at column obs_dim, done at obs_dim + 1, every
  * stride obs_dim + 2.  Loads and stores are 16 bytes per lane where obs_dim and both strides are multiples of 4 and both bases are
  * 16-byte aligned, 4 bytes otherwise (the packed stride of 35). */
@@ -818,14 +823,14 @@ typedef struct qg_rollout_storage {
     float *returns;
     uint8_t *dones;            /* [K][n] */
 } qg_rollout_storage;
-#define QG_ROLLOUT_DONE_U8 0   /* = QG_NORM_DONE_U8 */
-#define QG_ROLLOUT_DONE_F32 1  /* = QG_NORM_DONE_F32: the last column of the plain env's packed row */
+#define QG_ROLLOUT_DONE_U8 QG_DONE_U8
+#define QG_ROLLOUT_DONE_F32 QG_DONE_F32
 /* The rows of one env-step (device pointers; strides in elements). */
 typedef struct qg_rollout_step {
     int32_t struct_size;       /* sizeof(qg_rollout_step): checked */
     int32_t next_obs_stride;   /* >= obs_dim */
     int32_t reward_stride;     /* >= 1 */
-    int32_t done_kind;         /* QG_ROLLOUT_DONE_U8 or _F32 */
+    int32_t done_kind;         /* QG_DONE_U8 or QG_DONE_F32 */
     int32_t done_stride;       /* >= 1 */
     int32_t episode_reward_stride; /* >= 1 where episode_reward is given */
     const float *next_obs;     /* [n] rows of obs_dim floats: the observation after the step */
@@ -833,7 +838,7 @@ typedef struct qg_rollout_step {
     const float *log_prob;     /* [n] */
     const float *value;        /* [n] */
     const float *reward;       /* [n] at reward_stride */
-    const void *done;          /* [n] at done_stride, of the type done_kind names */
+    const void *done;          /* a done vector (QG_DONE_*), not NULL */
     const float *trunc_value;  /* nullable [n] */
     const float *episode_reward; /* nullable [n] at episode_reward_stride */
 } qg_rollout_step;
@@ -940,8 +945,8 @@ typedef struct qg_perturb_desc {
 } qg_perturb_desc;
 #define QG_PERTURB_DONE_ROW_RESET 0
 #define QG_PERTURB_DONE_ROW_TERMINAL 1
-#define QG_PERTURB_DONE_U8 0   /* = QG_NORM_DONE_U8 */
-#define QG_PERTURB_DONE_F32 1  /* = QG_NORM_DONE_F32: the last column of the plain env's packed row */
+#define QG_PERTURB_DONE_U8 QG_DONE_U8
+#define QG_PERTURB_DONE_F32 QG_DONE_F32
 #define QG_PERTURB_MAX_DELAY 16
 /* Validation (QG_ERR_ARG) comes before the device check (QG_ERR_DEVICE: there is no CPU backend).  A new handle has age = 0,
  * episode = 0 and a ring of zeros. */
@@ -950,8 +955,8 @@ int qg_perturb_destroy(qg_perturb *perturb);
 /* n must equal n_envs.  Device pointers, [n][12] f32, contiguous. */
 int qg_perturb_actions_device(qg_perturb *perturb, int32_t n, const float *actions_in, float *actions_out, void *stream);
 /* Rows of window * frame_dim floats at in_stride / out_stride (elements, >= the row length); obs_out may be obs_in.  terminal_obs
- * (nullable, in place, its own stride) only with QG_PERTURB_DONE_ROW_RESET.  done nullable (no env finished), of the type done_kind
- * names, at done_stride elements. */
+ * (nullable, in place, its own stride) only with QG_PERTURB_DONE_ROW_RESET.  done: a done vector (QG_DONE_*), nullable (no env
+ * finished). */
 int qg_perturb_observe_device(qg_perturb *perturb, int32_t n, const float *obs_in, int32_t in_stride, float *obs_out, int32_t out_stride,
                               float *terminal_obs, int32_t terminal_stride, const void *done, int32_t done_kind, int32_t done_stride,
                               void *stream);
@@ -1021,13 +1026,13 @@ typedef struct qg_contact_desc {
 #define QG_FOOT_PHASE_TIME 9       /* s in the current phase (stance or swing), this sample included */
 #define QG_FOOT_LAST_AIR_TIME 10   /* s of the last completed swing (0: none yet in this episode) */
 #define QG_FOOT_LAST_STANCE_TIME 11
-#define QG_CONTACT_DONE_U8 0       /* = QG_NORM_DONE_U8 */
-#define QG_CONTACT_DONE_F32 1      /* = QG_NORM_DONE_F32: the last column of the plain env's packed row */
+#define QG_CONTACT_DONE_U8 QG_DONE_U8
+#define QG_CONTACT_DONE_F32 QG_DONE_F32
 int qg_contact_create(qg_sim *sim, const qg_contact_desc *desc, qg_contact **out);
 int qg_contact_destroy(qg_contact *contact);
 /* Disarms the envs of the host mask [n] (non-zero selects; NULL: every env): their next advancing read starts an episode. */
 int qg_contact_reset(qg_contact *contact, const uint8_t *mask);
-/* done: nullable device [n] at done_stride elements, of the type done_kind names; read only when advance != 0. */
+/* done: a done vector (QG_DONE_*), nullable; read only when advance != 0. */
 int qg_contact_read_device(qg_contact *contact, const void *done, int32_t done_kind, int32_t done_stride, int32_t advance,
                            float *body_force, float *feet, void *stream);
 /* The same rows into host arrays (each nullable but not both), synchronously, without advancing the timers. */

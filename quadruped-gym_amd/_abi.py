@@ -21,6 +21,8 @@ DYN_COLUMNS = ("friction", "payload_mass", "payload_x", "payload_y", "payload_z"
 CMD_FIXED_HEADING, CMD_FIXED_VELOCITY_ANGLE, CMD_FIXED_SPEED = 1, 2, 4
 MAP_AUTO, MAP_LANE, MAP_QUAD, MAP_PAIR, MAP_LINK = 0, 1, 2, 3, 4
 OBS_DIM = {OBS_FULL: 33, OBS_IMU: 21}
+# the done vector's two element types (QG_DONE_* of include/quadgym.h); the four layers' older names of the pair follow their structs
+DONE_U8, DONE_F32 = 0, 1
 
 
 class QgModel(C.Structure):
@@ -139,98 +141,6 @@ class QgWalkParams(C.Structure):
 NWALKREWARD = 11
 
 
-class QgPolicyDesc(C.Structure):
-    """``qg_policy_desc``: the shape of a fused MLP policy (``struct_size`` is filled in)."""
-    _fields_ = [("struct_size", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("n_hidden", C.c_int32),
-                ("hidden", C.c_int32 * 3), ("out_tanh", C.c_int32), ("has_value", C.c_int32)]
-
-    @classmethod
-    def make(cls, obs_dim, hidden, act_dim, out_tanh=False, value=True):
-        hidden = [int(h) for h in hidden]
-        d = cls()
-        d.struct_size = C.sizeof(cls)
-        d.obs_dim, d.act_dim, d.n_hidden = int(obs_dim), int(act_dim), len(hidden)
-        for i, h in enumerate(hidden[:3]):
-            d.hidden[i] = h
-        d.out_tanh, d.has_value = int(bool(out_tanh)), int(bool(value))
-        return d
-
-
-class QgPpoParams(C.Structure):
-    """``qg_ppo_params``: the coefficients of one PPO loss call (``struct_size`` is filled in); ``clip_range_vf=None`` is off."""
-    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("clip_range", C.c_float), ("clip_range_vf", C.c_float),
-                ("ent_coef", C.c_float), ("vf_coef", C.c_float)]
-
-    @classmethod
-    def make(cls, clip_range=0.2, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5):
-        d = cls()
-        d.struct_size = C.sizeof(cls)
-        d.clip_range, d.clip_range_vf = float(clip_range), 0.0 if clip_range_vf is None else float(clip_range_vf)
-        d.ent_coef, d.vf_coef = float(ent_coef), float(vf_coef)
-        return d
-
-
-class QgPpoBatch(C.Structure):
-    """``qg_ppo_batch``: device pointers of one minibatch (``struct_size`` is filled in)."""
-    _fields_ = [("struct_size", C.c_int32), ("obs_stride", C.c_int32), ("obs", C.c_void_p), ("actions", C.c_void_p),
-                ("old_log_prob", C.c_void_p), ("advantages", C.c_void_p), ("old_values", C.c_void_p), ("returns", C.c_void_p)]
-
-    @classmethod
-    def make(cls, obs_stride, **ptrs):
-        d = cls()
-        d.struct_size, d.obs_stride = C.sizeof(cls), int(obs_stride)
-        for name, ptr in ptrs.items():
-            setattr(d, name, ptr)
-        return d
-
-
-class QgAdamParams(C.Structure):
-    """``qg_adam_params``: the constants of one optimiser step (``struct_size`` is filled in); ``max_grad_norm=None`` is off."""
-    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("lr", C.c_float), ("beta_one", C.c_float), ("beta_two", C.c_float),
-                ("eps", C.c_float), ("max_grad_norm", C.c_float)]
-
-    @classmethod
-    def make(cls, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.5):
-        d = cls()
-        d.struct_size = C.sizeof(cls)
-        d.lr, d.beta_one, d.beta_two, d.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
-        d.max_grad_norm = 0.0 if max_grad_norm is None else float(max_grad_norm)
-        return d
-
-
-class QgNormDesc(C.Structure):
-    """``qg_norm_desc``: a running normaliser's shape and constants (``struct_size`` is filled in)."""
-    _fields_ = [("struct_size", C.c_int32), ("obs_dim", C.c_int32), ("n_envs", C.c_int32), ("gamma", C.c_double),
-                ("epsilon", C.c_double), ("clip_obs", C.c_double), ("clip_reward", C.c_double), ("norm_obs", C.c_int32),
-                ("norm_reward", C.c_int32)]
-
-    @classmethod
-    def make(cls, obs_dim, n_envs, gamma=0.99, epsilon=1e-8, clip_obs=10.0, clip_reward=10.0, norm_obs=True, norm_reward=True):
-        d = cls()
-        d.struct_size = C.sizeof(cls)
-        d.obs_dim, d.n_envs = int(obs_dim), int(n_envs)
-        d.gamma, d.epsilon, d.clip_obs, d.clip_reward = float(gamma), float(epsilon), float(clip_obs), float(clip_reward)
-        d.norm_obs, d.norm_reward = int(bool(norm_obs)), int(bool(norm_reward))
-        return d
-
-
-NORM_DONE_U8, NORM_DONE_F32 = 0, 1
-
-
-class QgRolloutDesc(C.Structure):
-    """``qg_rollout_desc``: a rollout buffer's shape and constants (``struct_size`` is filled in)."""
-    _fields_ = [("struct_size", C.c_int32), ("n_envs", C.c_int32), ("n_steps", C.c_int32), ("obs_dim", C.c_int32),
-                ("act_dim", C.c_int32), ("reserved", C.c_int32), ("gamma", C.c_double), ("gae_lambda", C.c_double)]
-
-    @classmethod
-    def make(cls, n_envs, n_steps, obs_dim, act_dim, gamma=0.99, gae_lambda=0.95):
-        d = cls()
-        d.struct_size = C.sizeof(cls)
-        d.n_envs, d.n_steps, d.obs_dim, d.act_dim = int(n_envs), int(n_steps), int(obs_dim), int(act_dim)
-        d.gamma, d.gae_lambda = float(gamma), float(gae_lambda)
-        return d
-
-
 class _Sized(C.Structure):
     """A struct whose first field is its own size: ``make(**fields)`` fills it in."""
 
@@ -239,6 +149,89 @@ class _Sized(C.Structure):
         s = cls(**fields)
         s.struct_size = C.sizeof(cls)
         return s
+
+
+class QgPolicyDesc(_Sized):
+    """``qg_policy_desc``: the shape of a fused MLP policy (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("n_hidden", C.c_int32),
+                ("hidden", C.c_int32 * 3), ("out_tanh", C.c_int32), ("has_value", C.c_int32)]
+
+    @classmethod
+    def make(cls, obs_dim, hidden, act_dim, out_tanh=False, value=True):
+        hidden = [int(h) for h in hidden]
+        d = super().make()
+        d.obs_dim, d.act_dim, d.n_hidden = int(obs_dim), int(act_dim), len(hidden)
+        for i, h in enumerate(hidden[:3]):
+            d.hidden[i] = h
+        d.out_tanh, d.has_value = int(bool(out_tanh)), int(bool(value))
+        return d
+
+
+class QgPpoParams(_Sized):
+    """``qg_ppo_params``: the coefficients of one PPO loss call (``struct_size`` is filled in); ``clip_range_vf=None`` is off."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("clip_range", C.c_float), ("clip_range_vf", C.c_float),
+                ("ent_coef", C.c_float), ("vf_coef", C.c_float)]
+
+    @classmethod
+    def make(cls, clip_range=0.2, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5):
+        d = super().make()
+        d.clip_range, d.clip_range_vf = float(clip_range), 0.0 if clip_range_vf is None else float(clip_range_vf)
+        d.ent_coef, d.vf_coef = float(ent_coef), float(vf_coef)
+        return d
+
+
+class QgPpoBatch(_Sized):
+    """``qg_ppo_batch``: device pointers of one minibatch (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("obs_stride", C.c_int32), ("obs", C.c_void_p), ("actions", C.c_void_p),
+                ("old_log_prob", C.c_void_p), ("advantages", C.c_void_p), ("old_values", C.c_void_p), ("returns", C.c_void_p)]
+
+    @classmethod
+    def make(cls, obs_stride, **ptrs):
+        return super().make(obs_stride=int(obs_stride), **ptrs)
+
+
+class QgAdamParams(_Sized):
+    """``qg_adam_params``: the constants of one optimiser step (``struct_size`` is filled in); ``max_grad_norm=None`` is off."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("lr", C.c_float), ("beta_one", C.c_float), ("beta_two", C.c_float),
+                ("eps", C.c_float), ("max_grad_norm", C.c_float)]
+
+    @classmethod
+    def make(cls, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.5):
+        d = super().make()
+        d.lr, d.beta_one, d.beta_two, d.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
+        d.max_grad_norm = 0.0 if max_grad_norm is None else float(max_grad_norm)
+        return d
+
+
+class QgNormDesc(_Sized):
+    """``qg_norm_desc``: a running normaliser's shape and constants (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("obs_dim", C.c_int32), ("n_envs", C.c_int32), ("gamma", C.c_double),
+                ("epsilon", C.c_double), ("clip_obs", C.c_double), ("clip_reward", C.c_double), ("norm_obs", C.c_int32),
+                ("norm_reward", C.c_int32)]
+
+    @classmethod
+    def make(cls, obs_dim, n_envs, gamma=0.99, epsilon=1e-8, clip_obs=10.0, clip_reward=10.0, norm_obs=True, norm_reward=True):
+        d = super().make()
+        d.obs_dim, d.n_envs = int(obs_dim), int(n_envs)
+        d.gamma, d.epsilon, d.clip_obs, d.clip_reward = float(gamma), float(epsilon), float(clip_obs), float(clip_reward)
+        d.norm_obs, d.norm_reward = int(bool(norm_obs)), int(bool(norm_reward))
+        return d
+
+
+NORM_DONE_U8, NORM_DONE_F32 = DONE_U8, DONE_F32
+
+
+class QgRolloutDesc(_Sized):
+    """``qg_rollout_desc``: a rollout buffer's shape and constants (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_envs", C.c_int32), ("n_steps", C.c_int32), ("obs_dim", C.c_int32),
+                ("act_dim", C.c_int32), ("reserved", C.c_int32), ("gamma", C.c_double), ("gae_lambda", C.c_double)]
+
+    @classmethod
+    def make(cls, n_envs, n_steps, obs_dim, act_dim, gamma=0.99, gae_lambda=0.95):
+        d = super().make()
+        d.n_envs, d.n_steps, d.obs_dim, d.act_dim = int(n_envs), int(n_steps), int(obs_dim), int(act_dim)
+        d.gamma, d.gae_lambda = float(gamma), float(gae_lambda)
+        return d
 
 
 class QgRolloutStorage(_Sized):
@@ -267,10 +260,10 @@ class QgRolloutInfo(C.Structure):
     _fields_ = [("pos", C.c_int32), ("reserved", C.c_int32), ("overflow", C.c_int64), ("bad_index", C.c_int64)]
 
 
-ROLLOUT_DONE_U8, ROLLOUT_DONE_F32 = NORM_DONE_U8, NORM_DONE_F32
+ROLLOUT_DONE_U8, ROLLOUT_DONE_F32 = DONE_U8, DONE_F32
 
 
-class QgPerturbDesc(C.Structure):
+class QgPerturbDesc(_Sized):
     """``qg_perturb_desc``: the shape, the standard deviations and the key of a perturbation layer (``struct_size`` is filled in)."""
     _fields_ = [("struct_size", C.c_int32), ("n_envs", C.c_int32), ("frame_dim", C.c_int32), ("window", C.c_int32),
                 ("max_delay", C.c_int32), ("delay_lo", C.c_int32), ("delay_hi", C.c_int32), ("done_row", C.c_int32),
@@ -282,8 +275,7 @@ class QgPerturbDesc(C.Structure):
              done_row=0, seed=0, env_index_base=0):
         """``obs_std`` / ``bias_std``: up to ``frame_dim`` values, missing columns are 0.  ``reset_action=None``: the default task's
         ``default_ctrl``."""
-        d = cls()
-        d.struct_size = C.sizeof(cls)
+        d = super().make()
         d.n_envs, d.frame_dim, d.window, d.max_delay = int(n_envs), int(frame_dim), int(window), int(max_delay)
         d.delay_lo, d.delay_hi, d.done_row = int(delays[0]), int(delays[1]), int(done_row)
         d.action_std = float(action_std)
@@ -304,23 +296,22 @@ class QgPerturbDesc(C.Structure):
 
 
 PERTURB_DONE_ROW_RESET, PERTURB_DONE_ROW_TERMINAL = 0, 1
-PERTURB_DONE_U8, PERTURB_DONE_F32 = NORM_DONE_U8, NORM_DONE_F32
+PERTURB_DONE_U8, PERTURB_DONE_F32 = DONE_U8, DONE_F32
 PERTURB_MAX_DELAY = 16
 
 
-class QgContactDesc(C.Structure):
+class QgContactDesc(_Sized):
     """``qg_contact_desc``: a contact sensor's constants (``struct_size`` is filled in)."""
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("force_threshold", C.c_float)]
 
     @classmethod
     def make(cls, force_threshold=0.0):
-        d = cls()
-        d.struct_size = C.sizeof(cls)
+        d = super().make()
         d.force_threshold = float(force_threshold)
         return d
 
 
-CONTACT_DONE_U8, CONTACT_DONE_F32 = NORM_DONE_U8, NORM_DONE_F32
+CONTACT_DONE_U8, CONTACT_DONE_F32 = DONE_U8, DONE_F32
 NFOOT, FOOT_DIM = 4, 12
 # the columns of a foot's row (QG_FOOT_* of include/quadgym.h)
 FOOT_COLUMNS = ("pos_x", "pos_y", "pos_z", "vel_x", "vel_y", "vel_z", "contact", "touchdown", "liftoff", "phase_time", "last_air_time",
@@ -335,6 +326,146 @@ def package_dir() -> str:
 def library_path() -> str:
     # QUADGYM_LIB selects another build of the same library (A/B timing of kernel variants on one box)
     return os.environ.get("QUADGYM_LIB") or os.path.join(package_dir(), "csrc", "libquadgym.so")
+
+
+_vp, _i32, _f64, _P = C.c_void_p, C.c_int32, C.c_double, C.POINTER
+# Every entry point include/quadgym.h declares, in its order: name -> argtypes, or (argtypes, restype) where the result is not the int
+# status.  The one list: load_library() applies it, EXPORTS is its keys.
+PROTOTYPES = {
+    # the library, the default robot and task
+    "qg_version": ([], C.c_char_p),
+    "qg_build_id": ([], C.c_char_p),
+    "qg_last_error": ([], C.c_char_p),
+    "qg_device_pci_bus_id": [_i32, C.c_char_p, _i32],
+    "qg_recommended_batch": ([_i32, _i32], _i32),
+    "qg_default_model": [_P(QgModel)],
+    "qg_default_task": [_P(QgTask)],
+    "qg_time_limit_substeps": ([_f64, _f64], C.c_int64),
+    # the simulator handle
+    "qg_create": [_i32, _i32, _P(QgModel), _P(QgTask), C.c_uint64, _P(_vp)],
+    "qg_destroy": [_vp],
+    "qg_num_envs": [_vp],
+    "qg_obs_dim": [_vp],
+    "qg_reset": [_vp, _vp, C.c_uint64, C.c_uint32],
+    "qg_step": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "qg_step_device": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "qg_step_device_packed": [_vp, _vp, _vp, _vp],
+    "qg_get_state": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "qg_step_mirror": [_vp] * 11,
+    "qg_set_state": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "qg_time_step_kernel": [_vp, _vp, _vp, _i32, _P(C.c_float)],
+    "qg_set_track_ctrl": [_vp, _i32],
+    "qg_debug_phase_times": [_vp],
+    "qg_debug_last_step_kernel": [_vp, C.c_char_p, _i32],
+    "qg_set_task": [_vp, _P(QgTask)],
+    "qg_get_task": [_vp, _P(QgTask)],
+    "qg_uses_baked_model": [_vp],
+    "qg_set_mapping": [_vp, _i32],
+    "qg_get_mapping": [_vp],
+    # the per-step exchange between GPUs
+    "qg_comm_unique_id": [_vp],
+    "qg_comm_create": [_vp, _i32, _i32, _vp, _P(_vp)],
+    "qg_comm_destroy": [_vp],
+    "qg_comm_rollout": [_vp, _vp, _i32, _vp, _vp, _i32, _i32],
+    "qg_comm_synchronize": [_vp],
+    # the walking task and the partially observable pack
+    "qg_walk_default_params": [_P(QgWalkParams)],
+    "qg_walk_create": [_vp, _P(QgWalkParams), _P(_vp)],
+    "qg_walk_destroy": [_vp],
+    "qg_walk_set_commands": [_vp, _vp, _vp],
+    "qg_walk_reset": [_vp, _vp, C.c_uint64, C.c_uint32],
+    "qg_walk_step": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "qg_walk_step_device": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "qg_walk_get_estimates": [_vp, _vp, _vp, _vp],
+    "qg_walk_set_command_sampler": [_vp, _vp],
+    "qg_walk_get_commands": [_vp, _vp, _vp],
+    "qg_po_create": [_vp, _i32, _P(_vp)],
+    "qg_po_destroy": [_vp],
+    "qg_po_obs_dim": [_vp],
+    "qg_po_reset": [_vp, _vp, C.c_uint64, C.c_uint32, _vp],
+    "qg_po_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "qg_po_step_device": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # snapshots of the task layers and the reset streams
+    "qg_walk_state_bytes": ([_vp], C.c_int64),
+    "qg_walk_get_state": [_vp, _vp],
+    "qg_walk_set_state": [_vp, _vp],
+    "qg_po_state_bytes": ([_vp], C.c_int64),
+    "qg_po_get_state": [_vp, _vp],
+    "qg_po_set_state": [_vp, _vp],
+    "qg_get_reset_streams": [_vp, _vp, _P(C.c_uint64)],
+    "qg_set_reset_streams": [_vp, _vp, C.c_uint64],
+    # many env-steps per launch; the resident mode
+    "qg_step_device_seq": [_vp, _vp, _vp, _i32, _vp],
+    "qg_resident_start": [_vp, _i32, _i32, _vp, _vp],
+    "qg_resident_stop": [_vp],
+    "qg_resident_buffers": [_vp, _P(_vp), _P(_vp), _P(_i32)],
+    "qg_resident_step_device": [_vp, _i32, _vp],
+    "qg_resident_ensure": [_vp],
+    "qg_resident_status": [_vp, _P(C.c_int64), _P(_i32), _P(C.c_int64), _P(C.c_int64)],
+    # per-env dynamics, external wrenches, pushes
+    "qg_set_dynamics_range": [_vp, _P(QgDynamicsRange)],
+    "qg_set_dynamics": [_vp, _vp, _vp],
+    "qg_get_dynamics": [_vp, _vp],
+    "qg_clear_dynamics": [_vp],
+    "qg_set_xfrc": [_vp, _vp, _vp],
+    "qg_set_xfrc_device": [_vp, _vp, _vp],
+    "qg_get_xfrc": [_vp, _vp],
+    "qg_set_push": [_vp, _P(QgPushParams)],
+    "qg_clear_xfrc": [_vp],
+    # the fused MLP policy: forward, PPO gradient, Adam
+    "qg_policy_create": [_i32, _P(QgPolicyDesc), _P(_vp)],
+    "qg_policy_destroy": [_vp],
+    "qg_policy_param_count": [_P(QgPolicyDesc)],
+    "qg_policy_set_params": [_vp, _vp],
+    "qg_policy_get_params": [_vp, _vp],
+    "qg_policy_set_params_device": [_vp, _vp, _vp],
+    "qg_policy_forward_device": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    "qg_policy_launch_shape": [_vp, _i32, _i32, _P(_i32), _P(_i32)],
+    "qg_policy_reserve_grad": [_vp, _i32],
+    "qg_policy_ppo_grad_device": [_vp, _P(QgPpoParams), _i32, _P(QgPpoBatch), _vp, _vp, _vp],
+    "qg_policy_reserve_adam": [_vp],
+    "qg_policy_adam_update_device": [_vp, _P(QgAdamParams), _vp, _vp, _vp, _vp, _vp],
+    "qg_policy_adam_get_state": [_vp, _vp, _vp, _P(C.c_int64)],
+    "qg_policy_adam_set_state": [_vp, _vp, _vp, C.c_int64],
+    "qg_policy_normalize_advantages_device": [_vp, _i32, _vp, _vp, _vp],
+    # running normalisation
+    "qg_norm_create": [_i32, _P(QgNormDesc), _P(_vp)],
+    "qg_norm_destroy": [_vp],
+    "qg_norm_step_device": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp],
+    "qg_norm_update_obs_device": [_vp, _i32, _vp, _i32, _vp],
+    "qg_norm_apply_obs_device": [_vp, _i32, _vp, _i32, _vp, _i32, _vp],
+    "qg_norm_reset_returns_device": [_vp, _vp],
+    "qg_norm_get_state": [_vp] * 8,
+    "qg_norm_set_state": [_vp, _vp, _vp, _f64, _f64, _f64, _f64, _vp],
+    # the rollout buffer
+    "qg_rollout_create": [_i32, _P(QgRolloutDesc), _P(QgRolloutStorage), _P(_vp)],
+    "qg_rollout_destroy": [_vp],
+    "qg_rollout_begin_device": [_vp, _vp, _i32, _vp],
+    "qg_rollout_add_device": [_vp, _P(QgRolloutStep), _vp],
+    "qg_rollout_compute_device": [_vp, _vp, _vp],
+    "qg_rollout_gather_device": [_vp, _vp, _i32, _P(QgRolloutBatch), _vp],
+    "qg_rollout_get_info": [_vp, _P(QgRolloutInfo)],
+    "qg_rollout_episode_stats": [_vp, _P(_f64), _P(C.c_int64), _P(C.c_int64), _i32],
+    # sensor noise, bias and actuation latency
+    "qg_perturb_create": [_i32, _P(QgPerturbDesc), _P(_vp)],
+    "qg_perturb_destroy": [_vp],
+    "qg_perturb_actions_device": [_vp, _i32, _vp, _vp, _vp],
+    "qg_perturb_observe_device": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp],
+    "qg_perturb_begin_device": [_vp, _i32, _vp, _vp, _i32, _vp],
+    "qg_perturb_get_delays": [_vp, _vp],
+    "qg_perturb_get_state": [_vp, _vp, _vp, _vp],
+    "qg_perturb_set_state": [_vp, _vp, _vp, _vp],
+    # the contact sensor
+    "qg_contact_create": [_vp, _P(QgContactDesc), _P(_vp)],
+    "qg_contact_destroy": [_vp],
+    "qg_contact_reset": [_vp, _vp],
+    "qg_contact_read_device": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "qg_contact_read": [_vp, _vp, _vp],
+    "qg_contact_state_bytes": ([_vp], C.c_int64),
+    "qg_contact_get_state": [_vp, _vp],
+    "qg_contact_set_state": [_vp, _vp],
+}
+EXPORTS = tuple(PROTOTYPES)
 
 
 _lib = None
@@ -360,175 +491,11 @@ def load_library():
     except Exception:
         pass
     lib = C.CDLL(path)
-    vp, u8p, fp, i32p = C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int32)
-    lib.qg_version.restype = C.c_char_p
-    lib.qg_version.argtypes = []
-    lib.qg_build_id.restype = C.c_char_p
-    lib.qg_build_id.argtypes = []
-    lib.qg_last_error.restype = C.c_char_p
-    lib.qg_last_error.argtypes = []
-    lib.qg_device_pci_bus_id.argtypes = [C.c_int32, C.c_char_p, C.c_int32]
-    lib.qg_recommended_batch.restype = C.c_int32
-    lib.qg_recommended_batch.argtypes = [C.c_int32, C.c_int32]
-    lib.qg_default_model.argtypes = [C.POINTER(QgModel)]
-    lib.qg_default_task.argtypes = [C.POINTER(QgTask)]
-    lib.qg_time_limit_substeps.restype = C.c_int64
-    lib.qg_time_limit_substeps.argtypes = [C.c_double, C.c_double]
-    lib.qg_create.argtypes = [C.c_int32, C.c_int32, C.POINTER(QgModel), C.POINTER(QgTask), C.c_uint64, C.POINTER(vp)]
-    lib.qg_destroy.argtypes = [vp]
-    lib.qg_num_envs.argtypes = [vp]
-    lib.qg_obs_dim.argtypes = [vp]
-    lib.qg_reset.argtypes = [vp, vp, C.c_uint64, C.c_uint32]
-    lib.qg_step.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.qg_step_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.qg_step_device_packed.argtypes = [vp, vp, vp, vp]
-    lib.qg_get_state.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.qg_step_mirror.argtypes = [vp] * 11
-    lib.qg_set_state.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.qg_time_step_kernel.argtypes = [vp, vp, vp, C.c_int32, C.POINTER(C.c_float)]
-    lib.qg_set_track_ctrl.argtypes = [vp, C.c_int32]
-    lib.qg_debug_phase_times.argtypes = [vp]
-    lib.qg_debug_last_step_kernel.argtypes = [vp, C.c_char_p, C.c_int32]
-    lib.qg_set_task.argtypes = [vp, C.POINTER(QgTask)]
-    lib.qg_get_task.argtypes = [vp, C.POINTER(QgTask)]
-    lib.qg_uses_baked_model.argtypes = [vp]
-    lib.qg_set_mapping.argtypes = [vp, C.c_int32]
-    lib.qg_get_mapping.argtypes = [vp]
-    lib.qg_comm_unique_id.argtypes = [vp]
-    lib.qg_comm_create.argtypes = [vp, C.c_int32, C.c_int32, vp, C.POINTER(vp)]
-    lib.qg_comm_destroy.argtypes = [vp]
-    lib.qg_comm_rollout.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32]
-    lib.qg_comm_synchronize.argtypes = [vp]
-    lib.qg_walk_default_params.argtypes = [C.POINTER(QgWalkParams)]
-    lib.qg_walk_create.argtypes = [vp, C.POINTER(QgWalkParams), C.POINTER(vp)]
-    lib.qg_walk_destroy.argtypes = [vp]
-    lib.qg_walk_set_commands.argtypes = [vp, vp, vp]
-    lib.qg_walk_reset.argtypes = [vp, vp, C.c_uint64, C.c_uint32]
-    lib.qg_walk_step.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.qg_walk_step_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.qg_walk_get_estimates.argtypes = [vp, vp, vp, vp]
-    lib.qg_walk_set_command_sampler.argtypes = [vp, vp]
-    lib.qg_walk_get_commands.argtypes = [vp, vp, vp]
-    lib.qg_po_create.argtypes = [vp, C.c_int32, C.POINTER(vp)]
-    lib.qg_po_destroy.argtypes = [vp]
-    lib.qg_po_obs_dim.argtypes = [vp]
-    lib.qg_po_reset.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp]
-    lib.qg_po_step.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.qg_walk_state_bytes.restype = C.c_int64
-    lib.qg_walk_state_bytes.argtypes = [vp]
-    lib.qg_walk_get_state.argtypes = [vp, vp]
-    lib.qg_walk_set_state.argtypes = [vp, vp]
-    lib.qg_po_state_bytes.restype = C.c_int64
-    lib.qg_po_state_bytes.argtypes = [vp]
-    lib.qg_po_get_state.argtypes = [vp, vp]
-    lib.qg_po_set_state.argtypes = [vp, vp]
-    lib.qg_get_reset_streams.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
-    lib.qg_set_reset_streams.argtypes = [vp, vp, C.c_uint64]
-    lib.qg_po_step_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.qg_step_device_seq.argtypes = [vp, vp, vp, C.c_int32, vp]
-    lib.qg_resident_start.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
-    lib.qg_resident_stop.argtypes = [vp]
-    lib.qg_resident_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int32)]
-    lib.qg_resident_step_device.argtypes = [vp, C.c_int32, vp]
-    lib.qg_resident_ensure.argtypes = [vp]
-    lib.qg_resident_status.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.qg_set_dynamics_range.argtypes = [vp, C.POINTER(QgDynamicsRange)]
-    lib.qg_set_dynamics.argtypes = [vp, vp, vp]
-    lib.qg_get_dynamics.argtypes = [vp, vp]
-    lib.qg_clear_dynamics.argtypes = [vp]
-    lib.qg_set_xfrc.argtypes = [vp, vp, vp]
-    lib.qg_set_xfrc_device.argtypes = [vp, vp, vp]
-    lib.qg_get_xfrc.argtypes = [vp, vp]
-    lib.qg_set_push.argtypes = [vp, C.POINTER(QgPushParams)]
-    lib.qg_clear_xfrc.argtypes = [vp]
-    lib.qg_policy_create.argtypes = [C.c_int32, C.POINTER(QgPolicyDesc), C.POINTER(vp)]
-    lib.qg_policy_destroy.argtypes = [vp]
-    lib.qg_policy_param_count.argtypes = [C.POINTER(QgPolicyDesc)]
-    lib.qg_policy_set_params.argtypes = [vp, vp]
-    lib.qg_policy_get_params.argtypes = [vp, vp]
-    lib.qg_policy_set_params_device.argtypes = [vp, vp, vp]
-    lib.qg_policy_forward_device.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
-    lib.qg_policy_launch_shape.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    lib.qg_policy_reserve_grad.argtypes = [vp, C.c_int32]
-    lib.qg_policy_ppo_grad_device.argtypes = [vp, C.POINTER(QgPpoParams), C.c_int32, C.POINTER(QgPpoBatch), vp, vp, vp]
-    lib.qg_policy_reserve_adam.argtypes = [vp]
-    lib.qg_policy_adam_update_device.argtypes = [vp, C.POINTER(QgAdamParams), vp, vp, vp, vp, vp]
-    lib.qg_policy_adam_get_state.argtypes = [vp, vp, vp, C.POINTER(C.c_int64)]
-    lib.qg_policy_adam_set_state.argtypes = [vp, vp, vp, C.c_int64]
-    lib.qg_policy_normalize_advantages_device.argtypes = [vp, C.c_int32, vp, vp, vp]
-    i32, f64 = C.c_int32, C.c_double
-    lib.qg_norm_create.argtypes = [i32, C.POINTER(QgNormDesc), C.POINTER(vp)]
-    lib.qg_norm_destroy.argtypes = [vp]
-    lib.qg_norm_step_device.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp]
-    lib.qg_norm_update_obs_device.argtypes = [vp, i32, vp, i32, vp]
-    lib.qg_norm_apply_obs_device.argtypes = [vp, i32, vp, i32, vp, i32, vp]
-    lib.qg_norm_reset_returns_device.argtypes = [vp, vp]
-    lib.qg_norm_get_state.argtypes = [vp] * 8
-    lib.qg_norm_set_state.argtypes = [vp, vp, vp, f64, f64, f64, f64, vp]
-    lib.qg_rollout_create.argtypes = [i32, C.POINTER(QgRolloutDesc), C.POINTER(QgRolloutStorage), C.POINTER(vp)]
-    lib.qg_rollout_destroy.argtypes = [vp]
-    lib.qg_rollout_begin_device.argtypes = [vp, vp, i32, vp]
-    lib.qg_rollout_add_device.argtypes = [vp, C.POINTER(QgRolloutStep), vp]
-    lib.qg_rollout_compute_device.argtypes = [vp, vp, vp]
-    lib.qg_rollout_gather_device.argtypes = [vp, vp, i32, C.POINTER(QgRolloutBatch), vp]
-    lib.qg_rollout_get_info.argtypes = [vp, C.POINTER(QgRolloutInfo)]
-    lib.qg_rollout_episode_stats.argtypes = [vp, C.POINTER(f64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32]
-    lib.qg_perturb_create.argtypes = [i32, C.POINTER(QgPerturbDesc), C.POINTER(vp)]
-    lib.qg_perturb_destroy.argtypes = [vp]
-    lib.qg_perturb_actions_device.argtypes = [vp, i32, vp, vp, vp]
-    lib.qg_perturb_observe_device.argtypes = [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp]
-    lib.qg_perturb_begin_device.argtypes = [vp, i32, vp, vp, i32, vp]
-    lib.qg_perturb_get_delays.argtypes = [vp, vp]
-    lib.qg_perturb_get_state.argtypes = [vp, vp, vp, vp]
-    lib.qg_perturb_set_state.argtypes = [vp, vp, vp, vp]
-    lib.qg_contact_create.argtypes = [vp, C.POINTER(QgContactDesc), C.POINTER(vp)]
-    lib.qg_contact_destroy.argtypes = [vp]
-    lib.qg_contact_reset.argtypes = [vp, vp]
-    lib.qg_contact_read_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
-    lib.qg_contact_read.argtypes = [vp, vp, vp]
-    lib.qg_contact_state_bytes.restype = C.c_int64
-    lib.qg_contact_state_bytes.argtypes = [vp]
-    lib.qg_contact_get_state.argtypes = [vp, vp]
-    lib.qg_contact_set_state.argtypes = [vp, vp]
-    for name in EXPORTS:
+    for name, proto in PROTOTYPES.items():
         fn = getattr(lib, name)
-        if name not in ("qg_version", "qg_build_id", "qg_last_error", "qg_time_limit_substeps", "qg_walk_state_bytes", "qg_po_state_bytes",
-                        "qg_recommended_batch", "qg_contact_state_bytes"):
-            fn.restype = C.c_int
+        fn.argtypes, fn.restype = proto if isinstance(proto, tuple) else (proto, C.c_int)
     _lib = lib
     return lib
-
-
-# every symbol include/quadgym.h declares
-EXPORTS = (
-    "qg_version", "qg_build_id", "qg_last_error", "qg_device_pci_bus_id", "qg_recommended_batch", "qg_default_model", "qg_default_task", "qg_time_limit_substeps",
-    "qg_create", "qg_destroy", "qg_num_envs", "qg_obs_dim", "qg_reset", "qg_step", "qg_step_device",
-    "qg_step_device_packed", "qg_get_state", "qg_step_mirror", "qg_set_state", "qg_time_step_kernel", "qg_set_track_ctrl", "qg_debug_phase_times", "qg_debug_last_step_kernel", "qg_set_task", "qg_get_task",
-    "qg_uses_baked_model", "qg_set_mapping", "qg_get_mapping",
-    "qg_comm_unique_id", "qg_comm_create", "qg_comm_destroy", "qg_comm_rollout", "qg_comm_synchronize",
-    "qg_walk_default_params", "qg_walk_create", "qg_walk_destroy", "qg_walk_set_commands", "qg_walk_reset", "qg_walk_step",
-    "qg_walk_step_device", "qg_walk_get_estimates", "qg_walk_set_command_sampler", "qg_walk_get_commands",
-    "qg_po_create", "qg_po_destroy", "qg_po_obs_dim", "qg_po_reset", "qg_po_step", "qg_po_step_device",
-    "qg_walk_state_bytes", "qg_walk_get_state", "qg_walk_set_state", "qg_po_state_bytes", "qg_po_get_state", "qg_po_set_state",
-    "qg_get_reset_streams", "qg_set_reset_streams",
-    "qg_step_device_seq", "qg_resident_start", "qg_resident_stop", "qg_resident_buffers", "qg_resident_step_device",
-    "qg_resident_ensure", "qg_resident_status",
-    "qg_set_dynamics_range", "qg_set_dynamics", "qg_get_dynamics", "qg_clear_dynamics",
-    "qg_set_xfrc", "qg_set_xfrc_device", "qg_get_xfrc", "qg_set_push", "qg_clear_xfrc",
-    "qg_policy_create", "qg_policy_destroy", "qg_policy_param_count", "qg_policy_set_params", "qg_policy_get_params",
-    "qg_policy_set_params_device", "qg_policy_forward_device", "qg_policy_launch_shape",
-    "qg_policy_reserve_grad", "qg_policy_ppo_grad_device",
-    "qg_policy_reserve_adam", "qg_policy_adam_update_device", "qg_policy_adam_get_state", "qg_policy_adam_set_state",
-    "qg_policy_normalize_advantages_device",
-    "qg_norm_create", "qg_norm_destroy", "qg_norm_step_device", "qg_norm_update_obs_device", "qg_norm_apply_obs_device",
-    "qg_norm_reset_returns_device", "qg_norm_get_state", "qg_norm_set_state",
-    "qg_rollout_create", "qg_rollout_destroy", "qg_rollout_begin_device", "qg_rollout_add_device", "qg_rollout_compute_device",
-    "qg_rollout_gather_device", "qg_rollout_get_info", "qg_rollout_episode_stats",
-    "qg_perturb_create", "qg_perturb_destroy", "qg_perturb_actions_device", "qg_perturb_observe_device", "qg_perturb_begin_device",
-    "qg_perturb_get_delays", "qg_perturb_get_state", "qg_perturb_set_state",
-    "qg_contact_create", "qg_contact_destroy", "qg_contact_reset", "qg_contact_read_device", "qg_contact_read",
-    "qg_contact_state_bytes", "qg_contact_get_state", "qg_contact_set_state",
-)
 
 
 class QuadGymError(RuntimeError):

@@ -9,8 +9,8 @@ from . import _abi
 
 
 class Handle:
-    """A subclass names the ABI's destroy function in ``_destroy``, sets ``device`` and stores what its create call returned in
-    ``_h``.  A handle bound to another one (a task layer to its simulator) passes it as ``parent``: the C side's destroy of the child
+    """A subclass names the ABI's destroy function in ``_destroy``, sets ``device`` and opens its handle with ``_create``
+    (into ``_h``).  A handle bound to another one (a task layer to its simulator) passes it as ``parent``: the C side's destroy of the child
     dereferences the parent, so a parent is never destroyed while a child is open.  The child holds the parent (dropping references
     destroys the child first), the parent knows its children weakly (``close()`` closes them first) and counts the open ones."""
 
@@ -32,6 +32,12 @@ class Handle:
             self._parent = parent
 
     # -- lifetime ---------------------------------------------------------------------------
+    def _create(self, fn_name, *args):
+        """The ABI's create call ``fn_name(*args, &handle)``; the handle it returns becomes ``_h``."""
+        h = C.c_void_p()
+        _abi.check(getattr(self._lib, fn_name)(*args, C.byref(h)), fn_name)
+        self._h = h
+
     def close(self):
         children, self._children = self._children, ()
         for ref in reversed(children):                      # most recently bound first
@@ -65,6 +71,10 @@ class Handle:
             stream = torch.cuda.current_stream(self.device)
         return C.c_void_p(stream.cuda_stream)
 
+    def _torch_device(self):
+        import torch
+        return torch.device("cuda", self.device)
+
     def _check_tensor(self, t, shape, dtype, what=None):
         if not t.is_cuda or t.device.index != self.device:
             raise ValueError(f"{what or 'tensor'} must live on cuda:{self.device}")
@@ -81,6 +91,20 @@ class Handle:
         if self.num_envs > 1 and t.stride(0) < 1:
             raise ValueError(f"{what}: the element stride must be >= 1, got {t.stride(0)}")
         return max(int(t.stride(0)), 1)
+
+    def _done_arg(self, done):
+        """The done vector of ``include/quadgym.h`` -- uint8, bool or float32 ``[self.num_envs]`` at any positive stride, or None --
+        as the ``(pointer, done_kind, done_stride)`` an entry point takes."""
+        import torch
+        if done is None:
+            return None, _abi.DONE_U8, 1
+        stride = self._check_vec(done, (torch.uint8, torch.bool, torch.float32), "done")
+        return done.data_ptr(), (_abi.DONE_F32 if done.dtype == torch.float32 else _abi.DONE_U8), stride
+
+    def _check_packed(self, t, what):
+        """The plain env's packed rows: contiguous float32 ``[self.num_envs, self.obs_dim + 2]`` (obs, reward, done)."""
+        import torch
+        self._check_tensor(t, (self.num_envs, self.obs_dim + 2), torch.float32, what)
 
     def _check_obs(self, t, n=None, what="obs"):
         """``[n, self.obs_dim]`` float32 whose rows are contiguous; the row stride is free (a column slice of a wider buffer).

@@ -29,9 +29,7 @@ class ContactSensor(_TaskLayer):
         super().__init__(sim.device, parent=sim)
         self.num_envs = sim.n
         self.force_threshold = force_threshold
-        h = C.c_void_p()
-        check(self._lib.qg_contact_create(sim._h, C.byref(QgContactDesc.make(force_threshold)), C.byref(h)), "qg_contact_create")
-        self._h = h
+        self._create("qg_contact_create", sim._h, C.byref(QgContactDesc.make(force_threshold)))
 
     def read(self, done=None, advance: bool = True, body_force=None, feet=None, stream=None):
         """One launch on ``stream`` (torch's current stream by default): ``(body_force [N, 13, 3], feet [N, 4, 12])`` float32 CUDA
@@ -40,7 +38,7 @@ class ContactSensor(_TaskLayer):
         event.  A bad argument raises ``ValueError`` before any launch."""
         import torch
         n = self.num_envs
-        dev = torch.device("cuda", self.device)
+        dev = self._torch_device()
         if body_force is None:
             body_force = torch.empty((n, NBODY, 3), device=dev, dtype=torch.float32)
         else:
@@ -51,11 +49,7 @@ class ContactSensor(_TaskLayer):
             self._check_tensor(feet, (n, NFOOT, FOOT_DIM), torch.float32, "feet")
             if feet.data_ptr() % 16:
                 raise ValueError("feet: the rows are written with 16-byte stores; the tensor must be 16-byte aligned")
-        dp, kind, stride = None, _abi.CONTACT_DONE_U8, 1
-        if done is not None:
-            stride = self._check_vec(done, (torch.uint8, torch.bool, torch.float32), "done")
-            kind = _abi.CONTACT_DONE_F32 if done.dtype == torch.float32 else _abi.CONTACT_DONE_U8
-            dp = done.data_ptr()
+        dp, kind, stride = self._done_arg(done)
         check(self._lib.qg_contact_read_device(self._h, dp, kind, stride, 1 if advance else 0, body_force.data_ptr(), feet.data_ptr(),
                                                self._stream_ptr(stream)), "qg_contact_read_device")
         return body_force, feet

@@ -100,9 +100,8 @@ extern "C" int qg_comm_create(qg_sim *s, int32_t rank, int32_t world, const uint
     *out = nullptr;
     QG_TRY(qg_rccl_load());
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    qg_comm *c = new (std::nothrow) qg_comm();
-    if (!c) return fail(QG_ERR_ALLOC, "out of host memory");
-    memset(c, 0, sizeof *c);
+    qg_comm *c = qg_new_handle<qg_comm>();
+    if (!c) return QG_ERR_ALLOC;
     c->sim = s;
     c->rank = rank;
     c->world = world;

@@ -142,9 +142,7 @@ __global__ __launch_bounds__(QGC_ENVS * 16) void qg_contact_kernel(KContact A, c
     int touchdown = 0, liftoff = 0;
     if (A.advance) {
         bool fresh = armed[e] == 0;
-        if (done)
-            fresh |= A.done_kind == QG_CONTACT_DONE_F32 ? ((const float *)done)[e * (size_t)A.done_stride] != 0.f
-                                                        : ((const uint8_t *)done)[e * (size_t)A.done_stride] != 0;
+        if (done) fresh |= qg_done_at(done, A.done_kind, A.done_stride, e);
         if (fresh) {
             t.y = 1, t.z = 0, t.w = 0;
         } else if (contact == t.x) {
@@ -181,11 +179,7 @@ struct qg_contact {
 };
 
 extern "C" int qg_contact_destroy(qg_contact *c) {
-    if (!c) return QG_OK;
-    (void)hipSetDevice(c->sim->device);
-    (void)hipDeviceSynchronize();                  // reads may still be in flight on a caller's stream
-    c->mem.free_all();
-    delete c;
+    if (c) qg_free_handle(c, c->sim->device);      // reads may still be in flight on a caller's stream
     return QG_OK;
 }
 
@@ -193,16 +187,14 @@ extern "C" int qg_contact_create(qg_sim *s, const qg_contact_desc *desc, qg_cont
     if (!out) return fail(QG_ERR_ARG, "qg_contact_create: null output");
     *out = nullptr;
     if (!desc) return fail(QG_ERR_ARG, "qg_contact_create: null description");
-    if (desc->struct_size != (int32_t)sizeof(qg_contact_desc))
-        return fail(QG_ERR_ARG, "qg_contact_desc.struct_size is %d, this library's is %d", desc->struct_size, (int)sizeof(qg_contact_desc));
+    QG_CHECK_STRUCT(desc, qg_contact_desc);
     if (desc->reserved != 0) return fail(QG_ERR_ARG, "qg_contact: reserved must be 0");
     if (!qg_finite32(desc->force_threshold) || desc->force_threshold < 0.f)
         return fail(QG_ERR_ARG, "qg_contact: force_threshold %g must be finite and >= 0", desc->force_threshold);
     if (!s) return fail(QG_ERR_ARG, "qg_contact_create: null simulator");
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    qg_contact *c = new (std::nothrow) qg_contact();
-    if (!c) return fail(QG_ERR_ALLOC, "out of host memory");
-    memset(c, 0, sizeof *c);
+    qg_contact *c = qg_new_handle<qg_contact>();
+    if (!c) return QG_ERR_ALLOC;
     c->sim = s;
     c->desc = *desc;
     const size_t n = (size_t)s->n;
@@ -246,11 +238,7 @@ static int contact_check(const qg_contact *c, const void *done, int32_t done_kin
                          const char *who) {
     if (!body_force && !feet) return fail(QG_ERR_ARG, "%s: body_force and feet are both NULL", who);
     if (!c) return fail(QG_ERR_ARG, "%s: null handle", who);
-    if (done) {
-        if (done_kind != QG_CONTACT_DONE_U8 && done_kind != QG_CONTACT_DONE_F32)
-            return fail(QG_ERR_ARG, "%s: done_kind %d is neither QG_CONTACT_DONE_U8 nor QG_CONTACT_DONE_F32", who, done_kind);
-        if (done_stride < 1) return fail(QG_ERR_ARG, "%s: done_stride must be >= 1", who);
-    }
+    QG_TRY(qg_check_done(who, done, done_kind, done_stride));
     if (c->sim->res.active) return fail(QG_ERR_ARG, "%s: the resident step mode is on, the state lives in registers (qg_resident_stop first)", who);
     return QG_OK;
 }

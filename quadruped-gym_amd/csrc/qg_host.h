@@ -1,9 +1,11 @@
 // qg_host.h -- what every host translation unit of the library shares: the error record and the two status-forwarding macros, the
-// finite test, opening a device, and the owner of a handle's device allocations.  Internal: not installed, and nothing in here is exported (libquadgym.map).
+// struct_size refusal, the done vector's check and read, the finite test, opening a device, the owner of a handle's device allocations
+// and a handle's birth and death.  Internal: not installed, and nothing in here is exported (libquadgym.map).
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <new>
 
 #include "../../include/quadgym.h"
 
@@ -11,6 +13,20 @@ int qg_fail(int code, const char *fmt, ...);   // records the message for qg_las
 #define fail qg_fail
 // a status of the library's own that is only forwarded (the message is the callee's)
 #define QG_TRY(expr) do { int rc_ = (expr); if (rc_ != QG_OK) return rc_; } while (0)
+// the refusal of a struct of the ABI whose struct_size is not this library's (`type` is spelled into the message)
+#define QG_CHECK_STRUCT(ptr, type)                                                                                          \
+    do {                                                                                                                    \
+        if ((ptr)->struct_size != (int32_t)sizeof(type))                                                                    \
+            return fail(QG_ERR_ARG, #type ".struct_size is %d, this library's is %d", (ptr)->struct_size, (int)sizeof(type)); \
+    } while (0)
+
+// the done vector of include/quadgym.h as an entry point `who` received it: NULL passes, whatever kind and stride say
+static inline int qg_check_done(const char *who, const void *done, int32_t kind, int32_t stride) {
+    if (!done) return QG_OK;
+    if (kind != QG_DONE_U8 && kind != QG_DONE_F32) return fail(QG_ERR_ARG, "%s: done_kind %d is neither QG_DONE_U8 nor QG_DONE_F32", who, kind);
+    if (stride < 1) return fail(QG_ERR_ARG, "%s: done_stride %d must be >= 1", who, stride);
+    return QG_OK;
+}
 
 // (exponent bits, not std::isfinite: the device pass, which parses the host code too, is compiled with finite-math assumptions and
 // warns about the latter)
@@ -22,6 +38,11 @@ static inline bool qg_finite32(float x) {
 
 #ifdef __HIPCC__   // (qg_tables.h, which the plain-C++ generator of the baked table includes, needs the line above only)
 #include <hip/hip_runtime.h>
+
+// element i of a done vector that passed qg_check_done (not NULL; kind is one of the two, so one compare tells them apart)
+__device__ __forceinline__ bool qg_done_at(const void *done, int32_t kind, int32_t stride, size_t i) {
+    return kind != QG_DONE_U8 ? ((const float *)done)[i * (size_t)stride] != 0.f : ((const uint8_t *)done)[i * (size_t)stride] != 0;
+}
 
 #define HIP_TRY(expr, code)                                                                         \
     do {                                                                                            \
@@ -71,4 +92,19 @@ struct QgDevMem {
         while (count > 0) (void)hipFree(ptr[--count]);
     }
 };
+
+// A handle is born zero-filled (NULL, with the message recorded, where the host is out of memory) ...
+template <class T> T *qg_new_handle() {
+    T *h = new (std::nothrow) T();
+    if (h) memset((void *)h, 0, sizeof *h);
+    else fail(QG_ERR_ALLOC, "out of host memory");
+    return h;
+}
+// ... and dies after what is in flight on its device: the caller's comment says what that may be
+template <class T> void qg_free_handle(T *h, int device) {
+    (void)hipSetDevice(device);
+    (void)hipDeviceSynchronize();
+    h->mem.free_all();
+    delete h;
+}
 #endif

@@ -231,8 +231,7 @@ __global__ __launch_bounds__(256) void qg_norm_apply_kernel(KNormApply A, const 
         if (A.norm_reward) r = qgn_norm1(r, 0.0, stats[3 * A.Dp + A.D], A.clip_reward);
         reward_out[i * A.rout_stride] = r;
         if (A.zero_returns) {
-            const bool d = A.done_kind ? ((const float *)done)[i * A.done_stride] != 0.f : ((const uint8_t *)done)[i * A.done_stride] != 0;
-            if (d) returns[i] = 0.0;
+            if (qg_done_at(done, A.done_kind, A.done_stride, i)) returns[i] = 0.0;
         }
     }
 }
@@ -259,8 +258,7 @@ static bool norm_finite(double x) {
 
 static int norm_validate(const qg_norm_desc *d) {
     if (!d) return fail(QG_ERR_ARG, "qg_norm: null description");
-    if (d->struct_size != (int32_t)sizeof(qg_norm_desc))
-        return fail(QG_ERR_ARG, "qg_norm_desc.struct_size is %d, this library's is %d", d->struct_size, (int)sizeof(qg_norm_desc));
+    QG_CHECK_STRUCT(d, qg_norm_desc);
     if (d->obs_dim < 1 || d->obs_dim > 512) return fail(QG_ERR_ARG, "qg_norm: obs_dim %d outside 1 .. 512", d->obs_dim);
     if (d->n_envs < 1) return fail(QG_ERR_ARG, "qg_norm: n_envs %d must be >= 1", d->n_envs);
     if (!norm_finite(d->gamma) || d->gamma < 0.0) return fail(QG_ERR_ARG, "qg_norm: gamma %g must be finite and >= 0", d->gamma);
@@ -274,11 +272,7 @@ static int norm_validate(const qg_norm_desc *d) {
 }
 
 extern "C" int qg_norm_destroy(qg_norm *p) {
-    if (!p) return QG_OK;
-    (void)hipSetDevice(p->device);
-    (void)hipDeviceSynchronize();                  // steps may still be in flight on a caller's stream
-    p->mem.free_all();
-    delete p;
+    if (p) qg_free_handle(p, p->device);           // steps may still be in flight on a caller's stream
     return QG_OK;
 }
 
@@ -308,9 +302,8 @@ extern "C" int qg_norm_create(int32_t device_id, const qg_norm_desc *desc, qg_no
     *out = nullptr;
     QG_TRY(norm_validate(desc));
     QG_TRY(qg_open_device(device_id, nullptr));
-    qg_norm *p = new (std::nothrow) qg_norm();
-    if (!p) return fail(QG_ERR_ALLOC, "out of host memory");
-    memset(p, 0, sizeof *p);
+    qg_norm *p = qg_new_handle<qg_norm>();
+    if (!p) return QG_ERR_ALLOC;
     p->device = device_id;
     p->desc = *desc;
     p->Dp = desc->obs_dim + 1;
@@ -387,9 +380,7 @@ extern "C" int qg_norm_step_device(qg_norm *p, int32_t n, const float *obs_in, i
     if (reward_in) {
         if (!reward_out) return fail(QG_ERR_ARG, "qg_norm_step_device: reward_in without reward_out");
         if (reward_in_stride < 1 || reward_out_stride < 1) return fail(QG_ERR_ARG, "qg_norm_step_device: reward strides must be >= 1");
-        if (done && (done_kind != QG_NORM_DONE_U8 && done_kind != QG_NORM_DONE_F32))
-            return fail(QG_ERR_ARG, "qg_norm_step_device: done_kind %d is neither QG_NORM_DONE_U8 nor QG_NORM_DONE_F32", done_kind);
-        if (done && done_stride < 1) return fail(QG_ERR_ARG, "qg_norm_step_device: done_stride must be >= 1");
+        QG_TRY(qg_check_done("qg_norm_step_device", done, done_kind, done_stride));
     }
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     const hipStream_t st = (hipStream_t)stream;

@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void qg_perturb_rows_kernel(KPerturb A, const 
     bool fin = BEGIN;
     if (done) {
         if (BEGIN) fin = ((const uint8_t *)done)[i] != 0;
-        else fin = done_kind == QG_PERTURB_DONE_F32 ? ((const float *)done)[i * done_stride] != 0.f : ((const uint8_t *)done)[i * done_stride] != 0;
+        else fin = qg_done_at(done, done_kind, done_stride, i);
     }
     if (BEGIN && !fin) return;
     const float ostd = consts[lane], bstd = consts[64 + lane];   // zeros from frame_dim on
@@ -170,8 +170,7 @@ struct qg_perturb {
 
 static int perturb_validate(const qg_perturb_desc *d) {
     if (!d) return fail(QG_ERR_ARG, "qg_perturb: null description");
-    if (d->struct_size != (int32_t)sizeof(qg_perturb_desc))
-        return fail(QG_ERR_ARG, "qg_perturb_desc.struct_size is %d, this library's is %d", d->struct_size, (int)sizeof(qg_perturb_desc));
+    QG_CHECK_STRUCT(d, qg_perturb_desc);
     if (d->n_envs < 1 || (int64_t)d->n_envs * QGP_NJ * (QG_PERTURB_MAX_DELAY + 1) > INT32_MAX)
         return fail(QG_ERR_ARG, "qg_perturb: n_envs %d outside 1 .. %d", d->n_envs, INT32_MAX / (QGP_NJ * (QG_PERTURB_MAX_DELAY + 1)));
     if (d->frame_dim < 1 || d->frame_dim > 64) return fail(QG_ERR_ARG, "qg_perturb: frame_dim %d outside 1 .. 64", d->frame_dim);
@@ -194,11 +193,7 @@ static int perturb_validate(const qg_perturb_desc *d) {
 }
 
 extern "C" int qg_perturb_destroy(qg_perturb *p) {
-    if (!p) return QG_OK;
-    (void)hipSetDevice(p->device);
-    (void)hipDeviceSynchronize();                  // launches may still be in flight on a caller's stream
-    p->mem.free_all();
-    delete p;
+    if (p) qg_free_handle(p, p->device);           // launches may still be in flight on a caller's stream
     return QG_OK;
 }
 
@@ -207,9 +202,8 @@ extern "C" int qg_perturb_create(int32_t device_id, const qg_perturb_desc *desc,
     *out = nullptr;
     QG_TRY(perturb_validate(desc));
     QG_TRY(qg_open_device(device_id, nullptr));
-    qg_perturb *p = new (std::nothrow) qg_perturb();
-    if (!p) return fail(QG_ERR_ALLOC, "out of host memory");
-    memset(p, 0, sizeof *p);
+    qg_perturb *p = qg_new_handle<qg_perturb>();
+    if (!p) return QG_ERR_ALLOC;
     p->device = device_id;
     p->desc = *desc;
     KPerturb &k = p->k;
@@ -261,11 +255,7 @@ extern "C" int qg_perturb_observe_device(qg_perturb *p, int32_t n, const float *
             return fail(QG_ERR_ARG, "qg_perturb_observe_device: terminal_obs goes with QG_PERTURB_DONE_ROW_RESET (the row is the terminal observation)");
         if (terminal_stride < row) return fail(QG_ERR_ARG, "qg_perturb_observe_device: terminal_stride %d < window * frame_dim = %d", terminal_stride, row);
     }
-    if (done) {
-        if (done_kind != QG_PERTURB_DONE_U8 && done_kind != QG_PERTURB_DONE_F32)
-            return fail(QG_ERR_ARG, "qg_perturb_observe_device: done_kind %d is neither QG_PERTURB_DONE_U8 nor QG_PERTURB_DONE_F32", done_kind);
-        if (done_stride < 1) return fail(QG_ERR_ARG, "qg_perturb_observe_device: done_stride must be >= 1");
-    }
+    QG_TRY(qg_check_done("qg_perturb_observe_device", done, done_kind, done_stride));
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     qg_perturb_rows_kernel<false><<<(unsigned)((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(p->k, obs_in, in_stride, obs_out, out_stride, terminal_obs,
                                                                                           terminal_stride, done, done_kind, done_stride, p->d_age,
@@ -281,7 +271,7 @@ extern "C" int qg_perturb_begin_device(qg_perturb *p, int32_t n, const uint8_t *
         return fail(QG_ERR_ARG, "qg_perturb_begin_device: row_stride %d < window * frame_dim = %d", row_stride, p->k.F * p->k.W);
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     qg_perturb_rows_kernel<true><<<(unsigned)((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(p->k, rows, row_stride, rows, row_stride, nullptr, 0, mask,
-                                                                                         QG_PERTURB_DONE_U8, 1, p->d_age, p->d_episode, p->d_consts);
+                                                                                         QG_DONE_U8, 1, p->d_age, p->d_episode, p->d_consts);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
     return QG_OK;
 }

@@ -81,11 +81,7 @@ struct qg_po {
 };
 
 extern "C" int qg_po_destroy(qg_po *p) {
-    if (!p) return QG_OK;
-    (void)hipSetDevice(p->walk->sim->device);
-    (void)hipDeviceSynchronize();                  // steps that read or write the frame ring may still be in flight on a caller's stream
-    p->mem.free_all();
-    delete p;
+    if (p) qg_free_handle(p, p->walk->sim->device);   // steps that read or write the frame ring may still be in flight on a caller's stream
     return QG_OK;
 }
 
@@ -107,9 +103,8 @@ extern "C" int qg_po_create(qg_walk *w, int32_t obs_window, qg_po **out) {
     if (obs_window < 1 || obs_window > 64) return fail(QG_ERR_ARG, "qg_po_create: obs_window must be in 1..64");
     qg_sim *s = w->sim;
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    qg_po *p = new (std::nothrow) qg_po();
-    if (!p) return fail(QG_ERR_ALLOC, "out of host memory");
-    memset(p, 0, sizeof *p);
+    qg_po *p = qg_new_handle<qg_po>();
+    if (!p) return QG_ERR_ALLOC;
     p->walk = w;
     KPoParams &k = p->kp;
     k.dt = (float)(s->model.timestep * s->task.frame_skip);          // po_walking_quad.py:18

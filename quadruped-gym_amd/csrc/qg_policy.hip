@@ -227,8 +227,7 @@ __global__ __launch_bounds__(64 * WAVES) void qg_policy_forward_kernel(KPolicy P
 // the description is valid: fills the kernel's layer table (offsets into both parameter images) and returns the canonical length
 static int policy_layout(const qg_policy_desc *d, KPolicy *k) {
     if (!d) return fail(QG_ERR_ARG, "qg_policy: null description");
-    if (d->struct_size != (int32_t)sizeof(qg_policy_desc))
-        return fail(QG_ERR_ARG, "qg_policy_desc.struct_size is %d, this library's is %d", d->struct_size, (int)sizeof(qg_policy_desc));
+    QG_CHECK_STRUCT(d, qg_policy_desc);
     if (d->obs_dim < 1 || d->obs_dim > 512) return fail(QG_ERR_ARG, "qg_policy: obs_dim %d outside 1 .. 512", d->obs_dim);
     if (d->act_dim < 1 || d->act_dim > 16) return fail(QG_ERR_ARG, "qg_policy: act_dim %d outside 1 .. 16", d->act_dim);
     if (d->n_hidden < 1 || d->n_hidden > 3) return fail(QG_ERR_ARG, "qg_policy: n_hidden %d outside 1 .. 3", d->n_hidden);
@@ -282,11 +281,7 @@ static int policy_layout(const qg_policy_desc *d, KPolicy *k) {
 extern "C" int qg_policy_param_count(const qg_policy_desc *desc) { return policy_layout(desc, nullptr); }
 
 extern "C" int qg_policy_destroy(qg_policy *p) {
-    if (!p) return QG_OK;
-    (void)hipSetDevice(p->device);
-    (void)hipDeviceSynchronize();                  // forward passes may still be in flight on a caller's stream
-    p->mem.free_all();
-    delete p;
+    if (p) qg_free_handle(p, p->device);           // forward passes may still be in flight on a caller's stream
     return QG_OK;
 }
 
@@ -305,9 +300,8 @@ extern "C" int qg_policy_create(int32_t device_id, const qg_policy_desc *desc, q
     if (count < 0) return count;
     int simds;
     QG_TRY(qg_open_device(device_id, &simds));
-    qg_policy *p = new (std::nothrow) qg_policy();
-    if (!p) return fail(QG_ERR_ALLOC, "out of host memory");
-    memset(p, 0, sizeof *p);
+    qg_policy *p = qg_new_handle<qg_policy>();
+    if (!p) return QG_ERR_ALLOC;
     p->device = device_id;
     p->desc = *desc;
     p->k = k;

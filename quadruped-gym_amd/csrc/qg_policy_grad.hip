@@ -413,10 +413,8 @@ extern "C" int qg_policy_reserve_grad(qg_policy *p, int32_t max_batch) {
 extern "C" int qg_policy_ppo_grad_device(qg_policy *p, const qg_ppo_params *pp, int32_t B, const qg_ppo_batch *bt, float *grad, float *stats,
                                          void *stream) {
     if (!p || !pp || !bt || !grad) return fail(QG_ERR_ARG, "qg_policy_ppo_grad_device: null argument");
-    if (pp->struct_size != (int32_t)sizeof(qg_ppo_params))
-        return fail(QG_ERR_ARG, "qg_ppo_params.struct_size is %d, this library's is %d", pp->struct_size, (int)sizeof(qg_ppo_params));
-    if (bt->struct_size != (int32_t)sizeof(qg_ppo_batch))
-        return fail(QG_ERR_ARG, "qg_ppo_batch.struct_size is %d, this library's is %d", bt->struct_size, (int)sizeof(qg_ppo_batch));
+    QG_CHECK_STRUCT(pp, qg_ppo_params);
+    QG_CHECK_STRUCT(bt, qg_ppo_batch);
     if (pp->reserved != 0) return fail(QG_ERR_ARG, "qg_ppo_params.reserved must be 0");
     if (!qg_finite32(pp->clip_range) || !(pp->clip_range > 0.f)) return fail(QG_ERR_ARG, "qg_ppo_params.clip_range must be finite and > 0");
     if (!qg_finite32(pp->clip_range_vf) || !qg_finite32(pp->ent_coef) || !qg_finite32(pp->vf_coef))

@@ -267,8 +267,7 @@ static bool unit_interval(float x) { return qg_finite32(x) && x >= 0.f && x < 1.
 extern "C" int qg_policy_adam_update_device(qg_policy *p, const qg_adam_params *ap, const float *grad, const float *lr_device, float *params_out,
                                           float *stats, void *stream) {
     if (!p || !ap || !grad) return fail(QG_ERR_ARG, "qg_policy_adam_update_device: null argument");
-    if (ap->struct_size != (int32_t)sizeof(qg_adam_params))
-        return fail(QG_ERR_ARG, "qg_adam_params.struct_size is %d, this library's is %d", ap->struct_size, (int)sizeof(qg_adam_params));
+    QG_CHECK_STRUCT(ap, qg_adam_params);
     if (ap->reserved != 0) return fail(QG_ERR_ARG, "qg_adam_params.reserved must be 0");
     if (!qg_finite32(ap->lr) || !(ap->lr >= 0.f)) return fail(QG_ERR_ARG, "qg_adam_params.lr must be finite and >= 0");
     if (!unit_interval(ap->beta_one) || !unit_interval(ap->beta_two)) return fail(QG_ERR_ARG, "qg_adam_params: beta_one and beta_two must lie in [0, 1)");

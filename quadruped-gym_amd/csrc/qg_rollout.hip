@@ -155,7 +155,7 @@ __global__ __launch_bounds__(QGR_BLOCK) void qg_rollout_add_kernel(KRolloutAdd a
     const uint64_t i = (uint64_t)b * QGR_BLOCK + threadIdx.x;
     if (i >= (uint64_t)a.n) return;
     const float r = a.reward[i * a.reward_stride];
-    const bool d = a.done_kind ? ((const float *)a.done)[i * a.done_stride] != 0.f : ((const uint8_t *)a.done)[i * a.done_stride] != 0;
+    const bool d = qg_done_at(a.done, a.done_kind, a.done_stride, i);
     a.log_probs[slot + i] = a.log_prob[i];
     a.values[slot + i] = a.value[i];
     a.dones[slot + i] = d ? 1 : 0;
@@ -287,8 +287,7 @@ static bool rollout_aligned(const void *p, size_t a) { return ((uintptr_t)p) % a
 
 static int rollout_validate(const qg_rollout_desc *d, const qg_rollout_storage *s) {
     if (!d) return fail(QG_ERR_ARG, "qg_rollout: null description");
-    if (d->struct_size != (int32_t)sizeof(qg_rollout_desc))
-        return fail(QG_ERR_ARG, "qg_rollout_desc.struct_size is %d, this library's is %d", d->struct_size, (int)sizeof(qg_rollout_desc));
+    QG_CHECK_STRUCT(d, qg_rollout_desc);
     if (d->n_envs < 1) return fail(QG_ERR_ARG, "qg_rollout: n_envs %d must be >= 1", d->n_envs);
     if (d->n_steps < 1) return fail(QG_ERR_ARG, "qg_rollout: n_steps %d must be >= 1", d->n_steps);
     if (d->obs_dim < 1 || d->obs_dim > 512) return fail(QG_ERR_ARG, "qg_rollout: obs_dim %d outside 1 .. 512", d->obs_dim);
@@ -301,8 +300,7 @@ static int rollout_validate(const qg_rollout_desc *d, const qg_rollout_storage *
         return fail(QG_ERR_ARG, "qg_rollout: (n_steps + 1) * n_envs = %lld rows are more than 2^31 - 1",
                     (long long)(((int64_t)d->n_steps + 1) * d->n_envs));
     if (!s) return fail(QG_ERR_ARG, "qg_rollout: null storage");
-    if (s->struct_size != (int32_t)sizeof(qg_rollout_storage))
-        return fail(QG_ERR_ARG, "qg_rollout_storage.struct_size is %d, this library's is %d", s->struct_size, (int)sizeof(qg_rollout_storage));
+    QG_CHECK_STRUCT(s, qg_rollout_storage);
     const void *f32s[] = {s->obs, s->actions, s->log_prob, s->values, s->rewards, s->advantages, s->returns};
     const char *names[] = {"obs", "actions", "log_prob", "values", "rewards", "advantages", "returns"};
     for (int k = 0; k < 7; k++) {
@@ -314,11 +312,7 @@ static int rollout_validate(const qg_rollout_desc *d, const qg_rollout_storage *
 }
 
 extern "C" int qg_rollout_destroy(qg_rollout *p) {
-    if (!p) return QG_OK;
-    (void)hipSetDevice(p->device);
-    (void)hipDeviceSynchronize();                  // launches may still be in flight on a caller's stream
-    p->mem.free_all();
-    delete p;
+    if (p) qg_free_handle(p, p->device);           // launches may still be in flight on a caller's stream
     return QG_OK;
 }
 
@@ -327,9 +321,8 @@ extern "C" int qg_rollout_create(int32_t device_id, const qg_rollout_desc *desc,
     *out = nullptr;
     QG_TRY(rollout_validate(desc, storage));
     QG_TRY(qg_open_device(device_id, nullptr));
-    qg_rollout *p = new (std::nothrow) qg_rollout();
-    if (!p) return fail(QG_ERR_ALLOC, "out of host memory");
-    memset(p, 0, sizeof *p);
+    qg_rollout *p = qg_new_handle<qg_rollout>();
+    if (!p) return QG_ERR_ALLOC;
     p->device = device_id;
     p->desc = *desc;
     p->st = *storage;
@@ -376,20 +369,20 @@ extern "C" int qg_rollout_begin_device(qg_rollout *p, const float *obs, int32_t 
 
 extern "C" int qg_rollout_add_device(qg_rollout *p, const qg_rollout_step *s, void *stream) {
     if (!s) return fail(QG_ERR_ARG, "qg_rollout_add_device: null step");
-    if (s->struct_size != (int32_t)sizeof(qg_rollout_step))
-        return fail(QG_ERR_ARG, "qg_rollout_step.struct_size is %d, this library's is %d", s->struct_size, (int)sizeof(qg_rollout_step));
+    QG_CHECK_STRUCT(s, qg_rollout_step);
     if (!p) return fail(QG_ERR_ARG, "qg_rollout_add_device: null handle");
     if (!s->next_obs || !s->actions || !s->log_prob || !s->value || !s->reward || !s->done)
         return fail(QG_ERR_ARG, "qg_rollout_add_device: next_obs, actions, log_prob, value, reward and done must not be NULL");
     const int D = p->desc.obs_dim, n = p->desc.n_envs, A = p->desc.act_dim;
     if (s->next_obs_stride < D) return fail(QG_ERR_ARG, "qg_rollout_add_device: next_obs_stride %d < obs_dim %d", s->next_obs_stride, D);
-    if (s->reward_stride < 1 || s->done_stride < 1) return fail(QG_ERR_ARG, "qg_rollout_add_device: reward and done strides must be >= 1");
-    if (s->done_kind != QG_ROLLOUT_DONE_U8 && s->done_kind != QG_ROLLOUT_DONE_F32)
-        return fail(QG_ERR_ARG, "qg_rollout_add_device: done_kind %d is neither QG_ROLLOUT_DONE_U8 nor QG_ROLLOUT_DONE_F32", s->done_kind);
+    // (both strides ahead of done_kind, as ever: qg_check_done alone would look at done_kind first)
+    if (s->reward_stride < 1 || s->done_stride < 1)
+        return fail(QG_ERR_ARG, "qg_rollout_add_device: reward_stride %d and done_stride %d must be >= 1", s->reward_stride, s->done_stride);
+    QG_TRY(qg_check_done("qg_rollout_add_device", s->done, s->done_kind, s->done_stride));
     if (s->episode_reward && s->episode_reward_stride < 1)
         return fail(QG_ERR_ARG, "qg_rollout_add_device: episode_reward_stride must be >= 1");
     const void *f32s[] = {s->next_obs, s->actions, s->log_prob, s->value, s->reward, s->trunc_value, s->episode_reward,
-                          s->done_kind == QG_ROLLOUT_DONE_F32 ? s->done : nullptr};
+                          s->done_kind == QG_DONE_F32 ? s->done : nullptr};
     for (const void *q : f32s)
         if (!rollout_aligned(q, sizeof(float))) return fail(QG_ERR_ARG, "qg_rollout_add_device: a float pointer is not aligned to 4 bytes");
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
@@ -432,8 +425,7 @@ extern "C" int qg_rollout_compute_device(qg_rollout *p, const float *last_values
 
 extern "C" int qg_rollout_gather_device(qg_rollout *p, const int64_t *idx, int32_t B, const qg_rollout_batch *out, void *stream) {
     if (!out) return fail(QG_ERR_ARG, "qg_rollout_gather_device: null batch");
-    if (out->struct_size != (int32_t)sizeof(qg_rollout_batch))
-        return fail(QG_ERR_ARG, "qg_rollout_batch.struct_size is %d, this library's is %d", out->struct_size, (int)sizeof(qg_rollout_batch));
+    QG_CHECK_STRUCT(out, qg_rollout_batch);
     if (B < 1) return fail(QG_ERR_ARG, "qg_rollout_gather_device: B is %d, a batch has at least one row", B);
     if (!p || !idx) return fail(QG_ERR_ARG, "qg_rollout_gather_device: null argument");
     if (!rollout_aligned(idx, sizeof(int64_t))) return fail(QG_ERR_ARG, "qg_rollout_gather_device: idx is not aligned to 8 bytes");

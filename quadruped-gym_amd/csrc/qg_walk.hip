@@ -149,9 +149,8 @@ extern "C" int qg_walk_create(qg_sim *s, const qg_walk_params *params, qg_walk *
     if (!params) { qg_walk_default_params(&dp); params = &dp; }
     if (!(params->min_freq > 0) || !(params->ema_alpha >= 0 && params->ema_alpha <= 1)) return fail(QG_ERR_ARG, "qg_walk_create: bad estimator parameters");
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
-    qg_walk *w = new (std::nothrow) qg_walk();
-    if (!w) return fail(QG_ERR_ALLOC, "out of host memory");
-    memset(w, 0, sizeof *w);
+    qg_walk *w = qg_new_handle<qg_walk>();
+    if (!w) return QG_ERR_ALLOC;
     w->sim = s;
     w->params = *params;
     const double dt = s->model.timestep * s->task.frame_skip;        // walking_quad.py:56,93

@@ -198,7 +198,7 @@ class BatchedEnvBase:
     def contact_sensor(self, force_threshold: float = 0.0):
         """The env's ``ContactSensor`` (created at the first call): ground forces, foot kinematics and gait timers of every robot in
         one launch, ``sensor.read(done=...)`` behind a ``step_tensor``.  The env's ``reset`` restarts its timers, ``snapshot`` /
-        ``restore`` (where the env has them) carry them, ``close`` destroys it.  An env that never asks launches nothing."""
+        ``restore`` carry them, ``close`` destroys it.  An env that never asks launches nothing."""
         if self._contact is None:
             from ..contact import ContactSensor
             self._contact = ContactSensor(self._sim, force_threshold)
@@ -209,6 +209,32 @@ class BatchedEnvBase:
     def _reset_contact(self, mask=None):
         if self._contact is not None:
             self._contact.reset(mask)
+
+    # -- checkpoint / resume ----------------------------------------------------------------------------------------------------------
+    def snapshot(self):
+        """What every batched env keeps per robot, as a ``dict`` of NumPy arrays: the simulator's snapshot under ``"sim"`` and, where
+        the env has a contact sensor, its gait timers under ``"contact"``.  The task envs add their layers' state."""
+        snap = {"sim": self._sim.snapshot()}
+        if self._contact is not None:
+            snap["contact"] = self._contact.state()
+        return snap
+
+    def _check_snapshot(self, snap):
+        """Raises unless every part of ``snap`` fits this env; writes nothing."""
+        sim = snap["sim"]
+        if np.asarray(sim["qpos"]).shape != (self.num_envs, 19) or np.asarray(sim["episode"]).shape != (self.num_envs,):
+            raise ValueError("the snapshot was taken from an env of another size")
+        if self._contact is not None:             # (a snapshot's timers are ignored by an env without a sensor)
+            if "contact" not in snap:
+                raise ValueError("the snapshot holds no contact-sensor timers (it was taken from an env without a sensor)")
+            self._contact.check_state(snap["contact"])
+
+    def restore(self, snap):
+        """All-or-nothing: every part of the snapshot is checked against this env BEFORE anything is written."""
+        self._check_snapshot(snap)
+        self._sim.restore(snap["sim"])
+        if self._contact is not None:
+            self._contact.load_state(snap["contact"])
 
     def step_async(self, actions):
         self._actions = np.ascontiguousarray(actions, dtype=np.float32)

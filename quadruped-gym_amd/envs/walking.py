@@ -118,34 +118,22 @@ class WalkingQuadrupedVecEnv(BatchedEnvBase, _VecEnvBase):      # SB3's VecEnv w
         """Everything this env keeps per robot -- physics state, reset streams, the walking layer's task state (estimator included)
         and, for the partially observable env, the filter estimate and the frame ring -- as a ``dict`` of NumPy arrays.
         ``restore(snapshot)`` on an env of the same shape continues bit for bit."""
-        snap = {"sim": self._sim.snapshot(), "walk": self._walk.state(), "velocity": self.velocity.copy(), "heading": self.heading.copy()}
-        if self._contact is not None:             # the contact sensor's gait timers, where the env has one (contact_sensor())
-            snap["contact"] = self._contact.state()
-        return snap
+        return dict(super().snapshot(), walk=self._walk.state(), velocity=self.velocity.copy(), heading=self.heading.copy())
 
     def _check_snapshot(self, snap):
         """Raises unless every part of ``snap`` fits this env; writes nothing."""
         self._walk.check_state(snap["walk"])
-        sim = snap["sim"]
-        if np.asarray(sim["qpos"]).shape != (self.num_envs, 19) or np.asarray(sim["episode"]).shape != (self.num_envs,):
-            raise ValueError("the snapshot was taken from an env of another size")
+        super()._check_snapshot(snap)
         if np.asarray(snap["velocity"]).shape != self.velocity.shape or np.asarray(snap["heading"]).shape != self.heading.shape:
             raise ValueError("the snapshot's commands do not fit this env")
-        if self._contact is not None:             # (a snapshot's timers are ignored by an env without a sensor)
-            if "contact" not in snap:
-                raise ValueError("the snapshot holds no contact-sensor timers (it was taken from an env without a sensor)")
-            self._contact.check_state(snap["contact"])
 
     def restore(self, snap):
         """All-or-nothing: every part of the snapshot is checked against this env BEFORE anything is written.  Continues bit for
         bit with ``device_commands=True`` (or fixed commands); with host-side command sampling the commands an auto-reset re-draws
         come from NumPy's global generator, which a snapshot does not hold."""
-        self._check_snapshot(snap)
-        self._sim.restore(snap["sim"])
+        super().restore(snap)             # checks every part, the subclasses' too, before it writes
         self._walk.load_state(snap["walk"])
         self.velocity[:], self.heading[:] = snap["velocity"], snap["heading"]
-        if self._contact is not None:
-            self._contact.load_state(snap["contact"])
 
     def _resample(self, idx):
         if self.device_commands:          # already redrawn on the device by the reset / auto-reset itself

@@ -11,9 +11,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi
 from ._abi import QgNormDesc, check
 from ._handle import Handle
+from .envs.device_wrapper import DeviceVecEnvWrapper
 
 
 class RunningNormalizer(Handle):
@@ -34,9 +34,7 @@ class RunningNormalizer(Handle):
         self.norm_obs, self.norm_reward = bool(norm_obs), bool(norm_reward)
         self.training = True
         self.desc = QgNormDesc.make(self.obs_dim, self.num_envs, gamma, epsilon, clip_obs, clip_reward, norm_obs, norm_reward)
-        h = C.c_void_p()
-        check(self._lib.qg_norm_create(self.device, C.byref(self.desc), C.byref(h)), "qg_norm_create")
-        self._h = h
+        self._create("qg_norm_create", self.device, C.byref(self.desc))
 
     # -- device path ------------------------------------------------------------------------
     def step(self, obs, reward=None, done=None, obs_out=None, reward_out=None, stream=None):
@@ -47,18 +45,15 @@ class RunningNormalizer(Handle):
         _, in_stride = self._check_obs(obs, self.num_envs)
         obs_out = obs if obs_out is None else obs_out
         _, out_stride = self._check_obs(obs_out, self.num_envs, "obs_out")
-        r_ptr = ro_ptr = d_ptr = None
-        r_stride = ro_stride = d_stride = 1
-        kind = _abi.NORM_DONE_U8
+        r_ptr = ro_ptr = None
+        r_stride = ro_stride = 1
+        d_ptr, kind, d_stride = self._done_arg(None)
         if reward is not None:
             r_stride = self._check_vec(reward, (torch.float32,), "reward")
             reward_out = reward if reward_out is None else reward_out
             ro_stride = self._check_vec(reward_out, (torch.float32,), "reward_out")
             r_ptr, ro_ptr = reward.data_ptr(), reward_out.data_ptr()
-            if done is not None:
-                d_stride = self._check_vec(done, (torch.uint8, torch.bool, torch.float32), "done")
-                kind = _abi.NORM_DONE_F32 if done.dtype == torch.float32 else _abi.NORM_DONE_U8
-                d_ptr = done.data_ptr()
+            d_ptr, kind, d_stride = self._done_arg(done)
         elif done is not None or reward_out is not None:
             raise ValueError("done and reward_out need a reward")
         check(self._lib.qg_norm_step_device(self._h, self.num_envs, obs.data_ptr(), in_stride, obs_out.data_ptr(), out_stride, r_ptr,
@@ -71,11 +66,9 @@ class RunningNormalizer(Handle):
         given (its done column is then copied over).  Returns the normalised packed tensor."""
         import torch
         D = self.obs_dim
-        for t, what in ((packed, "packed"),) + (((out, "out"),) if out is not None else ()):
-            if not t.is_cuda or t.device.index != self.device:
-                raise ValueError(f"{what} must live on cuda:{self.device}")
-            if tuple(t.shape) != (self.num_envs, D + 2) or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{what}: expected a contiguous float32 tensor of shape ({self.num_envs}, {D + 2}), got {t.dtype} {tuple(t.shape)}")
+        self._check_packed(packed, "packed")
+        if out is not None:
+            self._check_packed(out, "out")
         dst = packed if out is None else out
         self.step(packed[:, :D], packed[:, D], packed[:, D + 1], obs_out=dst[:, :D], reward_out=dst[:, D], stream=stream)
         if out is not None:
@@ -122,23 +115,19 @@ class RunningNormalizer(Handle):
                                           float(sd["ret_rms.var"]), float(sd["ret_rms.count"]), returns.ctypes.data), "qg_norm_set_state")
 
 
-class DeviceVecNormalize:
+class DeviceVecNormalize(DeviceVecEnvWrapper):
     """``VecNormalize`` around ``QuadrupedVecEnv``, ``WalkingQuadrupedVecEnv`` or ``POWalkingQuadrupedVecEnv`` whose ``step_tensor``
     stays on the device: the env's launch, then the normaliser's on the same stream.  Keyword options are ``RunningNormalizer``'s.
     The NumPy ``reset()`` / ``step()`` are a cold path built for correctness only (they upload the rows and run the same device
     calls).  Every other attribute passes through to the wrapped env."""
 
+    _snapshot_key = "normalizer"
+
     def __init__(self, venv, **options):
-        self.venv = venv
-        self._packed = venv.packed_step                     # the plain env steps into packed [N, obs_dim + 2] rows
         device = options.pop("device", venv.device)
         self.normalizer = RunningNormalizer(venv.num_envs, venv.obs_dim, device=device, **options)
+        super().__init__(venv, self.normalizer)
         self.old_obs = self.old_reward = None
-
-    def __getattr__(self, name):                            # only reached for what this class does not define
-        if name == "venv":
-            raise AttributeError(name)
-        return getattr(self.venv, name)
 
     @property
     def training(self):
@@ -155,9 +144,7 @@ class DeviceVecNormalize:
         if self._packed:
             packed = self.venv.step_tensor(actions, *args, **kwargs)
             return self.normalizer.step_packed(packed, stream=stream)
-        names = ("obs", "reward", "done", "components", "terminal_obs")
-        bound = dict(zip(names, args))
-        bound.update({k: v for k, v in kwargs.items() if k in names})
+        bound = self._step_buffers(args, kwargs)
         self.venv.step_tensor(actions, *args, **kwargs)
         self.normalizer.step(bound["obs"], bound["reward"], bound["done"], stream=stream)
         if bound.get("terminal_obs") is not None:
@@ -165,20 +152,10 @@ class DeviceVecNormalize:
         return None
 
     # -- NumPy cold path --------------------------------------------------------------------
-    def _dev(self):
-        import torch
-        return torch.device("cuda", self.normalizer.device)
-
-    def _normalize_rows(self, rows):
-        import torch
-        t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.float32)).to(self._dev())
-        return self.normalizer.normalize_obs(t).cpu().numpy()
-
     def reset(self):
-        import torch
         obs = np.ascontiguousarray(self.venv.reset(), dtype=np.float32)
         self.old_obs = obs.copy()
-        t = torch.from_numpy(obs).to(self._dev())
+        t = self._upload(obs)
         self.normalizer.reset_returns()
         if self.normalizer.training and self.normalizer.norm_obs:
             self.normalizer.update_obs(t)
@@ -188,28 +165,20 @@ class DeviceVecNormalize:
         self.venv.step_async(actions)
 
     def step_wait(self):
-        import torch
         obs, rew, done, infos = self.venv.step_wait()
         obs, rew = np.ascontiguousarray(obs, dtype=np.float32), np.ascontiguousarray(rew, dtype=np.float32)
         self.old_obs, self.old_reward = obs.copy(), rew.copy()
-        dev = self._dev()
-        t_obs, t_rew = torch.from_numpy(obs).to(dev), torch.from_numpy(rew).to(dev)
-        t_done = torch.from_numpy(np.ascontiguousarray(done, dtype=np.uint8)).to(dev)
-        self.normalizer.step(t_obs, t_rew, t_done)
-        finished = np.nonzero(done)[0]
-        rows = [(int(i), infos[int(i)]) for i in finished]
-        rows = [(i, info) for i, info in rows if isinstance(info, dict) and info.get("terminal_observation") is not None]
+        t_obs, t_rew = self._upload(obs), self._upload(rew)
+        self.normalizer.step(t_obs, t_rew, self._upload(done, np.uint8))
+        rows = self._finished_with_terminal(done, infos)
         if rows:
-            term = self._normalize_rows(np.stack([info["terminal_observation"] for _, info in rows]))
+            term = self._upload(np.stack([info["terminal_observation"] for _, info in rows]))
+            term = self.normalizer.normalize_obs(term).cpu().numpy()
             for k, (i, info) in enumerate(rows):
                 info = dict(info)
                 info["terminal_observation"] = term[k]
                 infos[i] = info
         return t_obs.cpu().numpy(), t_rew.cpu().numpy(), done, infos
-
-    def step(self, actions):
-        self.step_async(actions)
-        return self.step_wait()
 
     def get_original_obs(self):
         return None if self.old_obs is None else self.old_obs.copy()
@@ -218,19 +187,15 @@ class DeviceVecNormalize:
         return None if self.old_reward is None else self.old_reward.copy()
 
     # -- checkpoint / resume ----------------------------------------------------------------
+    def _layer_state(self):
+        return self.normalizer.state_dict()
+
+    def _load_layer_state(self, state):
+        self.normalizer.load_state_dict(state)
+
     def snapshot(self):
-        """The wrapped env's snapshot (its own, or the simulator's for the plain env) with the normaliser's state beside it."""
-        env = self.venv.snapshot() if hasattr(self.venv, "snapshot") else {"sim": self.venv._sim.snapshot()}
-        return {"env": env, "normalizer": self.normalizer.state_dict(), "training": self.normalizer.training}
+        return dict(super().snapshot(), training=self.normalizer.training)
 
     def restore(self, snap):
-        if hasattr(self.venv, "restore"):
-            self.venv.restore(snap["env"])
-        else:
-            self.venv._sim.restore(snap["env"]["sim"])
-        self.normalizer.load_state_dict(snap["normalizer"])
+        super().restore(snap)
         self.normalizer.training = bool(snap.get("training", True))
-
-    def close(self):
-        self.normalizer.close()
-        self.venv.close()

@@ -19,6 +19,7 @@ import numpy as np
 from . import _abi
 from ._abi import QgPerturbDesc, check
 from ._handle import Handle
+from .envs.device_wrapper import DeviceVecEnvWrapper
 
 # frame columns by name, per layout (width -> {group: slice}): the partially observable frame (po_walking_quad.py:48-56) and the
 # 33- and 21-value sensor packs (QG_OBS_FULL, QG_OBS_IMU)
@@ -72,9 +73,7 @@ class Perturbation(Handle):
         self.desc = QgPerturbDesc.make(self.num_envs, self.frame_dim, self.window, self.max_delay, self.delay_range, action_std,
                                        column_stds(obs_std, frame_dim), column_stds(bias_std, frame_dim), reset_action,
                                        self._DONE_ROWS[done_row], seed, env_index_base)
-        h = C.c_void_p()
-        check(self._lib.qg_perturb_create(self.device, C.byref(self.desc), C.byref(h)), "qg_perturb_create")
-        self._h = h
+        self._create("qg_perturb_create", self.device, C.byref(self.desc))
 
     # -- device path ------------------------------------------------------------------------
     def perturb_actions(self, actions, out=None, stream=None):
@@ -87,13 +86,6 @@ class Perturbation(Handle):
               "qg_perturb_actions_device")
         return out
 
-    def _done(self, done):
-        import torch
-        if done is None:
-            return None, _abi.PERTURB_DONE_U8, 1
-        stride = self._check_vec(done, (torch.uint8, torch.bool, torch.float32), "done")
-        return done.data_ptr(), (_abi.PERTURB_DONE_F32 if done.dtype == torch.float32 else _abi.PERTURB_DONE_U8), stride
-
     def observe(self, obs, done=None, terminal_obs=None, out=None, stream=None):
         """``obs`` float32 ``[N, window * frame_dim]`` (strided rows allowed) as the env left it, ``done`` uint8 / bool / float32
         ``[N]`` at any stride or None, ``terminal_obs`` (``done_row="reset"`` only) perturbed in place.  ``out`` defaults to in
@@ -105,16 +97,15 @@ class Perturbation(Handle):
         if terminal_obs is not None:
             _, t_stride = self._check_obs(terminal_obs, self.num_envs, "terminal_obs")
             t_ptr = terminal_obs.data_ptr()
-        d_ptr, kind, d_stride = self._done(done)
+        d_ptr, kind, d_stride = self._done_arg(done)
         check(self._lib.qg_perturb_observe_device(self._h, self.num_envs, obs.data_ptr(), in_stride, out.data_ptr(), out_stride, t_ptr,
                                                   t_stride, d_ptr, kind, d_stride, self._stream_ptr(stream)), "qg_perturb_observe_device")
         return out
 
     def observe_packed(self, packed, stream=None):
         """The plain env's packed rows ``[N, obs_dim + 2]`` (obs, reward, done as float32) in place; reward and done are not touched."""
-        import torch
         D = self.obs_dim
-        self._check_tensor(packed, (self.num_envs, D + 2), torch.float32, "packed")
+        self._check_packed(packed, "packed")
         self.observe(packed[:, :D], packed[:, D + 1], stream=stream)
         return packed
 
@@ -158,7 +149,7 @@ class Perturbation(Handle):
         check(self._lib.qg_perturb_set_state(self._h, age.ctypes.data, episode.ctypes.data, ring.ctypes.data), "qg_perturb_set_state")
 
 
-class DevicePerturbedVecEnv:
+class DevicePerturbedVecEnv(DeviceVecEnvWrapper):
     """Sensor noise, sensor bias and actuation latency around ``QuadrupedVecEnv``, ``WalkingQuadrupedVecEnv`` or
     ``POWalkingQuadrupedVecEnv``; ``step_tensor`` stays on the device: ``perturb_actions``, the env's launch with the delayed actions,
     ``observe``, all on one stream.  ``obs_noise`` / ``obs_bias``: standard deviations per frame column -- a scalar, a sequence, or a
@@ -168,11 +159,11 @@ class DevicePerturbedVecEnv:
     what a rollout buffer stores).  The NumPy ``reset()`` / ``step()`` are a cold path built for correctness only.  Every other
     attribute passes through to the wrapped env."""
 
+    _snapshot_key = "perturbation"
+
     def __init__(self, venv, obs_noise=None, obs_bias=None, action_noise: float = 0.0, action_latency=(0.0, 0.0), seed: int = 0,
                  env_index_base: int | None = None, device: int | None = None):
         import torch
-        self.venv = venv
-        self._packed = venv.packed_step
         po = hasattr(venv, "obs_window")                    # the stacked frames; its finished rows hold the reset stack
         frame = venv.FRAME if po else venv.obs_dim
         window = venv.obs_window if po else 1
@@ -186,12 +177,8 @@ class DevicePerturbedVecEnv:
         self.perturbation = Perturbation(venv.num_envs, frame, window, obs_noise, obs_bias, action_noise, (lo, hi),
                                          reset_action=list(sim.task.default_ctrl), done_row="reset" if po else "terminal", seed=seed,
                                          env_index_base=base, device=venv.device if device is None else device)
-        self._delayed = torch.empty((venv.num_envs, _abi.NU), dtype=torch.float32, device=torch.device("cuda", self.perturbation.device))
-
-    def __getattr__(self, name):                            # only reached for what this class does not define
-        if name == "venv":
-            raise AttributeError(name)
-        return getattr(self.venv, name)
+        super().__init__(venv, self.perturbation)
+        self._delayed = torch.empty((venv.num_envs, _abi.NU), dtype=torch.float32, device=self.perturbation._torch_device())
 
     # -- device path ------------------------------------------------------------------------
     def step_tensor(self, actions, *args, **kwargs):
@@ -201,25 +188,19 @@ class DevicePerturbedVecEnv:
         if self._packed:
             packed = self.venv.step_tensor(self._delayed, *args, **kwargs)
             return self.perturbation.observe_packed(packed, stream=stream)
-        names = ("obs", "reward", "done", "components", "terminal_obs")
-        bound = dict(zip(names, args))
-        bound.update({k: v for k, v in kwargs.items() if k in names})
+        bound = self._step_buffers(args, kwargs)
         self.venv.step_tensor(self._delayed, *args, **kwargs)
         self.perturbation.observe(bound["obs"], bound["done"], terminal_obs=bound.get("terminal_obs"), stream=stream)
         return None
 
     # -- NumPy cold path --------------------------------------------------------------------
-    def _to_device(self, a, dtype=np.float32):
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self._delayed.device)
-
     def reset(self):
-        rows = self._to_device(self.venv.reset())
+        rows = self._upload(self.venv.reset())
         self.perturbation.begin(rows=rows)
         return rows.cpu().numpy()
 
     def step_async(self, actions):
-        self.perturbation.perturb_actions(self._to_device(actions), out=self._delayed)
+        self.perturbation.perturb_actions(self._upload(actions), out=self._delayed)
         self.venv.step_async(self._delayed.cpu().numpy())
 
     def step_wait(self):
@@ -229,8 +210,7 @@ class DevicePerturbedVecEnv:
         comes back as the env returned it."""
         obs, rew, done, infos = self.venv.step_wait()
         obs = np.array(obs, dtype=np.float32)
-        finished = [int(i) for i in np.nonzero(done)[0]
-                    if isinstance(infos[int(i)], dict) and infos[int(i)].get("terminal_observation") is not None]
+        finished = [i for i, _ in self._finished_with_terminal(done, infos)]
         reset_rows = self.perturbation.done_row == "reset"
         term = np.zeros_like(obs)
         for i in finished:
@@ -238,9 +218,9 @@ class DevicePerturbedVecEnv:
         rows = obs.copy()
         if not reset_rows:
             rows[finished] = term[finished]
-        t_rows = self._to_device(rows)
-        t_term = self._to_device(term) if reset_rows and finished else None
-        self.perturbation.observe(t_rows, self._to_device(done, np.uint8), terminal_obs=t_term)
+        t_rows = self._upload(rows)
+        t_term = self._upload(term) if reset_rows and finished else None
+        self.perturbation.observe(t_rows, self._upload(done, np.uint8), terminal_obs=t_term)
         rows = t_rows.cpu().numpy()
         term = t_term.cpu().numpy() if t_term is not None else rows
         for i in finished:
@@ -251,23 +231,9 @@ class DevicePerturbedVecEnv:
             rows[finished] = obs[finished]
         return rows, rew, done, infos
 
-    def step(self, actions):
-        self.step_async(actions)
-        return self.step_wait()
-
     # -- checkpoint / resume ----------------------------------------------------------------
-    def snapshot(self):
-        """The wrapped env's snapshot (its own, or the simulator's for the plain env) with the layer's state beside it."""
-        env = self.venv.snapshot() if hasattr(self.venv, "snapshot") else {"sim": self.venv._sim.snapshot()}
-        return {"env": env, "perturbation": self.perturbation.state()}
+    def _layer_state(self):
+        return self.perturbation.state()
 
-    def restore(self, snap):
-        if hasattr(self.venv, "restore"):
-            self.venv.restore(snap["env"])
-        else:
-            self.venv._sim.restore(snap["env"]["sim"])
-        self.perturbation.load_state(snap["perturbation"])
-
-    def close(self):
-        self.perturbation.close()
-        self.venv.close()
+    def _load_layer_state(self, state):
+        self.perturbation.load_state(state)

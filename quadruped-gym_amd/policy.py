@@ -78,9 +78,7 @@ class FusedMlpPolicy(Handle):
         if len(self.hidden) > 3:
             raise ValueError("at most three hidden layers")
         self.desc = QgPolicyDesc.make(self.obs_dim, self.hidden, self.act_dim, self.out_tanh, self.has_value)
-        h = C.c_void_p()
-        check(self._lib.qg_policy_create(self.device, C.byref(self.desc), C.byref(h)), "qg_policy_create")
-        self._h = h
+        self._create("qg_policy_create", self.device, C.byref(self.desc))
         self.n_params = int(self._lib.qg_policy_param_count(C.byref(self.desc)))
 
     # -- parameters -------------------------------------------------------------------------

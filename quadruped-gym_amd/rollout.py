@@ -9,7 +9,6 @@ from __future__ import annotations
 import collections
 import ctypes as C
 
-from . import _abi
 from ._abi import QgRolloutBatch, QgRolloutDesc, QgRolloutInfo, QgRolloutStep, QgRolloutStorage, check
 from ._handle import Handle
 
@@ -36,7 +35,7 @@ class DeviceRolloutBuffer(Handle):
         if min(self.num_envs, self.n_steps, self.obs_dim, self.act_dim) < 1:
             raise ValueError("num_envs, n_steps, obs_dim and act_dim must be >= 1")
         K, n = self.n_steps, self.num_envs
-        dev = torch.device("cuda", self.device)
+        dev = self._torch_device()
         f32 = dict(device=dev, dtype=torch.float32)
         self.observations = torch.zeros((K + 1, n, self.obs_dim), **f32)
         self.actions = torch.zeros((K, n, self.act_dim), **f32)
@@ -47,9 +46,7 @@ class DeviceRolloutBuffer(Handle):
                                              log_prob=self.log_probs.data_ptr(), values=self.values.data_ptr(),
                                              rewards=self.rewards.data_ptr(), advantages=self.advantages.data_ptr(),
                                              returns=self.returns.data_ptr(), dones=self.dones.data_ptr())
-        h = C.c_void_p()
-        check(self._lib.qg_rollout_create(self.device, C.byref(self.desc), C.byref(self.storage), C.byref(h)), "qg_rollout_create")
-        self._h = h
+        self._create("qg_rollout_create", self.device, C.byref(self.desc), C.byref(self.storage))
         self._count = 0                                     # calls of add() since begin(), capped at K: the CALLER's count
         self._batch = {}                                    # batch size -> reusable output tensors of get()
 
@@ -76,11 +73,10 @@ class DeviceRolloutBuffer(Handle):
         self._check_tensor(log_prob, (self.num_envs,), torch.float32, "log_prob")
         self._check_tensor(value, (self.num_envs,), torch.float32, "value")
         r_stride = self._check_vec(reward, f32, "reward")
-        d_stride = self._check_vec(done, (torch.uint8, torch.bool, torch.float32), "done")
+        d_ptr, d_kind, d_stride = self._done_arg(done)
         s = QgRolloutStep.make(next_obs=next_obs.data_ptr(), next_obs_stride=o_stride, actions=actions.data_ptr(),
                                log_prob=log_prob.data_ptr(), value=value.data_ptr(), reward=reward.data_ptr(), reward_stride=r_stride,
-                               done=done.data_ptr(), done_stride=d_stride,
-                               done_kind=_abi.ROLLOUT_DONE_F32 if done.dtype == torch.float32 else _abi.ROLLOUT_DONE_U8)
+                               done=d_ptr, done_stride=d_stride, done_kind=d_kind)
         if trunc_value is not None:
             self._check_tensor(trunc_value, (self.num_envs,), torch.float32, "trunc_value")
             s.trunc_value = trunc_value.data_ptr()
@@ -92,9 +88,8 @@ class DeviceRolloutBuffer(Handle):
 
     def add_packed(self, rows, actions, log_prob, value, trunc_value=None, episode_reward=None, stream=None):
         """``add`` for the plain env's packed rows ``[N, obs_dim + 2]`` (obs, reward, done as float32) where the step left them."""
-        import torch
         D = self.obs_dim
-        self._check_tensor(rows, (self.num_envs, D + 2), torch.float32, "rows")
+        self._check_packed(rows, "rows")
         self.add(rows[:, :D], actions, log_prob, value, rows[:, D], rows[:, D + 1], trunc_value=trunc_value,
                  episode_reward=episode_reward, stream=stream)
 
@@ -115,7 +110,7 @@ class DeviceRolloutBuffer(Handle):
     def _outputs(self, B):
         import torch
         if B not in self._batch:
-            f32 = dict(device=torch.device("cuda", self.device), dtype=torch.float32)
+            f32 = dict(device=self._torch_device(), dtype=torch.float32)
             self._batch[B] = RolloutBufferSamples(torch.empty((B, self.obs_dim), **f32), torch.empty((B, self.act_dim), **f32),
                                                   *[torch.empty(B, **f32) for _ in range(4)])
         return self._batch[B]
@@ -154,7 +149,7 @@ class DeviceRolloutBuffer(Handle):
         if total < 1:
             raise ValueError("the buffer is empty: nothing has been added since begin()")
         batch_size = total if batch_size is None else int(batch_size)
-        perm = torch.randperm(total, device=torch.device("cuda", self.device), generator=generator)
+        perm = torch.randperm(total, device=self._torch_device(), generator=generator)
         for start in range(0, total, batch_size):
             yield self.sample(perm[start:start + batch_size])
 

@@ -31,10 +31,7 @@ class BatchedSim(Handle):
         self.task = task if task is not None else _abi.default_task()
         self.n = int(n_envs)
         self.env_index_base = int(env_index_base)
-        h = C.c_void_p()
-        check(self._lib.qg_create(self.n, self.device, C.byref(self.model), C.byref(self.task), self.env_index_base,
-                                  C.byref(h)), "qg_create")
-        self._h = h
+        self._create("qg_create", self.n, self.device, C.byref(self.model), C.byref(self.task), self.env_index_base)
         # the step time is a staircase in the batch size: just past a stair's top a batch is SLOWER in absolute
         # terms than the top itself -- say so once, where it is worst (4097 .. ~6500 envs on an MI355X run below 4096 envs' env-steps/s)
         top = _abi.recommended_batch(1, self.device)          # the first stair: one wave of the one-link-per-lane kernel per SIMD

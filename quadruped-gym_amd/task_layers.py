@@ -91,9 +91,7 @@ class WalkLayer(_TaskLayer):
         super().__init__(sim.device, parent=sim)
         self.num_envs = sim.n
         self.params = params if params is not None else default_walk_params()
-        h = C.c_void_p()
-        check(self._lib.qg_walk_create(sim._h, C.byref(self.params), C.byref(h)), "qg_walk_create")
-        self._h = h
+        self._create("qg_walk_create", sim._h, C.byref(self.params))
 
     def reset(self, seed: int = 0, flags: int = 0, mask=None):
         mask, mp = _mask_ptr(mask, self.num_envs)
@@ -140,9 +138,7 @@ class ObsPack(_TaskLayer):
     def __init__(self, walk: WalkLayer, obs_window: int = 1):
         super().__init__(walk.device, parent=walk)
         self.num_envs, self.obs_window = walk.num_envs, int(obs_window)
-        h = C.c_void_p()
-        check(self._lib.qg_po_create(walk._h, self.obs_window, C.byref(h)), "qg_po_create")
-        self._h = h
+        self._create("qg_po_create", walk._h, self.obs_window)
         self.obs_dim = int(self._lib.qg_po_obs_dim(self._h))
         self._terminal = None             # scratch for the library's terminal stacks of step()
 

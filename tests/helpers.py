@@ -3,6 +3,7 @@ import ctypes as C
 import json
 import lzma
 import os
+import re
 import shutil
 
 import numpy as np
@@ -11,6 +12,16 @@ import pytest
 NQ, NV, NU, NBODY = 19, 18, 12, 13
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def header_text():
+    return open(os.path.join(ROOT, "include", "quadgym.h")).read()
+
+
+def header_define(header, name):
+    """The integer a `#define name ...` of the header stands for: a literal, or another macro's name (an alias), followed."""
+    value = re.search(r"#define %s (\w+)" % name, header).group(1)
+    return int(value) if value.isdigit() else header_define(header, value)
 
 
 def reference_model(tmp_dir):

@@ -4,7 +4,6 @@ header's; bad Python arguments raise ValueError before the library is reached.""
 import ctypes as C
 import math
 import os
-import re
 import shutil
 import subprocess
 
@@ -16,6 +15,7 @@ from quadruped_gym_amd.envs.quadruped import DataView
 from quadruped_gym_amd.envs.vec_env import BatchedEnvBase
 
 import contact_sensor_reference as R
+from helpers import header_define
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QG_ERR_ARG = -1
@@ -44,7 +44,7 @@ def test_symbols_are_exported_declared_and_bound():
 
 def test_foot_columns_are_the_headers():
     header = _header()
-    define = lambda name: int(re.search(r"#define %s (\d+)" % name, header).group(1))
+    define = lambda name: header_define(header, name)                  # (QG_CONTACT_DONE_* are aliases of QG_DONE_*)
     cols = ContactSensor.FOOT_COLUMNS
     assert cols == _abi.FOOT_COLUMNS == R.FOOT_COLUMNS and len(cols) == define("QG_FOOT_DIM") == _abi.FOOT_DIM == 12
     assert cols[define("QG_FOOT_POS"):define("QG_FOOT_POS") + 3] == ("pos_x", "pos_y", "pos_z")

@@ -12,6 +12,8 @@ import pytest
 from quadruped_gym_amd import _abi
 from quadruped_gym_amd import perturb as P
 
+from helpers import header_define
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QG_ERR_ARG = -1
 NEW = ("qg_perturb_create", "qg_perturb_destroy", "qg_perturb_actions_device", "qg_perturb_observe_device", "qg_perturb_begin_device",
@@ -35,7 +37,7 @@ def test_symbols_are_exported_declared_and_bound():
     for name, value in (("QG_PERTURB_DONE_ROW_RESET", _abi.PERTURB_DONE_ROW_RESET), ("QG_PERTURB_DONE_ROW_TERMINAL", _abi.PERTURB_DONE_ROW_TERMINAL),
                         ("QG_PERTURB_DONE_U8", _abi.PERTURB_DONE_U8), ("QG_PERTURB_DONE_F32", _abi.PERTURB_DONE_F32),
                         ("QG_PERTURB_MAX_DELAY", _abi.PERTURB_MAX_DELAY)):
-        assert int(re.search(r"#define %s (\d+)" % name, header).group(1)) == value
+        assert header_define(header, name) == value                     # (QG_PERTURB_DONE_* are aliases of QG_DONE_*)
     assert "qg_perturb" in open(os.path.join(ROOT, "quadruped-gym_amd", "csrc", "Makefile")).read()
 
 
