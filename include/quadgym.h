@@ -1042,6 +1042,62 @@ int64_t qg_contact_state_bytes(const qg_contact *contact);
 int qg_contact_get_state(qg_contact *contact, void *blob);
 int qg_contact_set_state(qg_contact *contact, const void *blob);
 
+/* ---- reward-term monitoring on the device: the step log and per-term episode sums -----------------------------------------------------
+ * A qg_monitor consumes the reward components the step kernels leave on the device (qg_walk_step_device's `components`,
+ * qg_step_device's `reward_components`): what the reference's training script logs at every env-step (train_quadruped.py:86-110: the
+ * mean of every reward key over the envs, the reward's mean and np.std) goes into a ring the caller owns, and every term is summed over
+ * each env's episode, the finished episodes' sums over each other.  Like qg_norm and qg_rollout it is independent of qg_sim, takes
+ * pointers and touches no step kernel.  With n = n_envs, C = n_terms, x[i][c] for c < C env i's term c and x[i][C] its reward, ONE
+ * record does, in this order:
+ *
+ *   1. the log row.  row = records % capacity, records as the launch finds it in device memory.  For c <= C
+ *        log[row][c] = fl(S[c] / n),  S[c] the f64 sum of f64(x[i][c]) over ALL n envs -- a finished env counts with its terminal
+ *        step's terms, as the reference's infos do -- added in a fixed order: per env chunk of 256 by a butterfly over the lanes (32, 16,
+ *        .. 1), ((w0 + w1) + w2) + w3 over a workgroup's waves, a tile's chunks one after the other per thread, the tiles in 4 runs
+ *        and ((r0 + r1) + r2) + r3 over the runs.
+ *        log[row][C + 1] = sqrt(M2 / n): the population standard deviation of the reward (np.std, ddof = 0).  M2 comes from a thread's
+ *        sum(x - K) and sum((x - K)^2) with K its first reward (exact in f64), then Chan's merge over lanes, waves and tiles (the tiles in
+ *        64 runs, then a butterfly) -- never E[x^2] - E[x]^2.  A constant reward and n = 1 give exactly 0.
+ *        log[row][C + 2] = the number of envs whose done is set, exact.
+ *   2. the episode accumulators, per env by one thread: acc[i][c] = acc[i][c] + f64(x[i][c]) -- ONE IEEE add per step and term --,
+ *        len[i] += 1.
+ *   3. the fold.  For the envs with done[i] != 0: totals[c] = totals[c] + F[c], F[c] the sum of their acc[i][c] in the order of S (an
+ *        env that did not finish adds an exact zero: the order depends on (n, C) alone, and a step where nobody finishes leaves totals
+ *        bit for bit); length_sum += len[i], episodes += 1; then acc[i][.] = 0, len[i] = 0.
+ *   4. records += 1, in device memory: nothing the host bakes into a launch depends on the step number, so the hipGraph of one
+ *        closed-loop step, replayed K times, fills K rows.
+ *
+ * Two launches, a tile pass and a combine pass of one workgroup across a kernel boundary.  No floating-point atomics, no integer ones
+ * either; no workgroup reads what another workgroup of its own launch wrote.  The same inputs give the same bits on every run,
+ * eagerly and under graph replay, whatever the strides and alignment of the caller's tensors; bits may differ between different n.
+ * Only log[row] and the handle's own state are written.  Calls on one monitor must be ordered by the caller on one stream.  Outputs
+ * for non-finite inputs are unspecified (the device code is compiled with finite-math assumptions: run the walking envs with
+ * nan_direction off).  qg_monitor_record_device follows the contract of the other *_device entry points (it enqueues on the caller's
+ * stream, returns at once and may be captured); every other entry point waits for the device and must not be called during a capture.
+ * Validation (QG_ERR_ARG: a NULL handle or pointer, a size or stride out of range, a bad done vector) comes before any device call. */
+#define QG_MONITOR_MAX_TERMS 32
+typedef struct qg_monitor qg_monitor;
+/* 1 <= n_terms <= QG_MONITOR_MAX_TERMS (the walking layers have 11, the plain env 3), n_envs >= 1, capacity >= 1 rows of the ring.  A
+ * new handle has empty accumulators and totals and records = 0. */
+int qg_monitor_create(int32_t device_id, int32_t n_envs, int32_t n_terms, int32_t capacity, qg_monitor **out);
+int qg_monitor_destroy(qg_monitor *monitor);
+/* components: [n] rows of n_terms floats at comp_stride >= n_terms; reward: [n] at reward_stride >= 1; done: a done vector
+ * (QG_DONE_*), NULL: nobody finished; log: f64 [capacity][n_terms + 3] on the device, the caller's. */
+int qg_monitor_record_device(qg_monitor *monitor, const float *components, int32_t comp_stride, const float *reward, int32_t reward_stride,
+                             const void *done, int32_t done_kind, int32_t done_stride, double *log, void *stream);
+/* Empties the running accumulators (acc, len) of the envs of the host mask [n] (non-zero selects; NULL: every env).  clear_totals != 0
+ * also zeroes totals, episodes and length_sum; clear_log != 0 sets records = 0 (the ring itself is the caller's). */
+int qg_monitor_reset(qg_monitor *monitor, const uint8_t *host_mask, int32_t clear_totals, int32_t clear_log);
+/* The cursor, the finished episodes' number and lengths and totals [n_terms + 1] (the reward last).  clear != 0 then zeroes totals,
+ * episodes and length_sum; the running episodes and the cursor continue. */
+int qg_monitor_get_info(qg_monitor *monitor, int64_t *records, int64_t *episodes, int64_t *length_sum, double *totals, int32_t clear);
+/* The whole state from / to host arrays: acc [n][n_terms + 1], len [n], totals [n_terms + 1] and the three integers.  The round trip
+ * is exact: a restored monitor continues bit for bit. */
+int qg_monitor_get_state(qg_monitor *monitor, double *acc, int32_t *len, double *totals, int64_t *episodes, int64_t *length_sum,
+                         int64_t *records);
+int qg_monitor_set_state(qg_monitor *monitor, const double *acc, const int32_t *len, const double *totals, int64_t episodes,
+                         int64_t length_sum, int64_t records);
+
 #ifdef __cplusplus
 }
 #endif

@@ -317,6 +317,7 @@ NFOOT, FOOT_DIM = 4, 12
 FOOT_COLUMNS = ("pos_x", "pos_y", "pos_z", "vel_x", "vel_y", "vel_z", "contact", "touchdown", "liftoff", "phase_time", "last_air_time",
                 "last_stance_time")
 FOOT_BODIES = (3, 6, 9, 12)
+MONITOR_MAX_TERMS = 32          # QG_MONITOR_MAX_TERMS
 
 
 def package_dir() -> str:
@@ -464,6 +465,14 @@ PROTOTYPES = {
     "qg_contact_state_bytes": ([_vp], C.c_int64),
     "qg_contact_get_state": [_vp, _vp],
     "qg_contact_set_state": [_vp, _vp],
+    # the reward monitor
+    "qg_monitor_create": [_i32, _i32, _i32, _i32, _P(_vp)],
+    "qg_monitor_destroy": [_vp],
+    "qg_monitor_record_device": [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp],
+    "qg_monitor_reset": [_vp, _vp, _i32, _i32],
+    "qg_monitor_get_info": [_vp, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64), _vp, _i32],
+    "qg_monitor_get_state": [_vp, _vp, _vp, _vp, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)],
+    "qg_monitor_set_state": [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64],
 }
 EXPORTS = tuple(PROTOTYPES)
 
