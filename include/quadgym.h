@@ -66,7 +66,7 @@ extern "C" {
 #define QG_ERR_ALLOC (-3)
 #define QG_ERR_LAUNCH (-4)
 
-/* The done vector of the device-side layers (qg_norm, qg_rollout, qg_perturb, qg_contact): a device [n] at done_stride elements
+/* The done vector of the device-side layers (qg_norm, qg_rollout, qg_perturb, qg_contact, qg_gait): a device [n] at done_stride elements
  * (>= 1), of the type done_kind names, nullable where the entry point says so.  Non-zero is done. */
 #define QG_DONE_U8 0     /* uint8 (the walking and partially observable envs' buffer; torch.bool as well) */
 #define QG_DONE_F32 1    /* f32 (the last column of the plain env's packed row) */
@@ -1097,6 +1097,71 @@ int qg_monitor_get_state(qg_monitor *monitor, double *acc, int32_t *len, double 
                          int64_t *records);
 int qg_monitor_set_state(qg_monitor *monitor, const double *acc, const int32_t *len, const double *totals, int64_t episodes,
                          int64_t length_sum, int64_t records);
+
+/* ---- gait-shaped reward terms from the foot-contact sensor ---------------------------------------------------------------------------------
+ * A qg_gait is bound to a qg_contact.  Its launch (qg_gait_reward_device) IS that sensor's read of the env-step -- forces, foot rows,
+ * timers, advance / done semantics and bits exactly as qg_contact_read_device, body_force and feet being optional outputs of it -- and
+ * in the same kernel reduces seven reward terms per env, weights them and adds them to the reward.  It is the ADVANCING READ of its
+ * env-step: a caller does not also call qg_contact_read_device(advance = 1) in that env-step (the timers would move twice).
+ *
+ * For env i and foot f = 0..3 (bodies 3, 6, 9, 12), with r = feet[i][f][.] in the QG_FOOT_* columns as this launch reports them,
+ * c_f = r[CONTACT], td_f = r[TOUCHDOWN] (0.0 or 1.0 each) and Fz_b = body_force[i][b][2], the unweighted terms, in this order:
+ *   0 feet_air_time       g_i * sum_f td_f (r[LAST_AIR_TIME] - air_time_target)
+ *   1 feet_slip           sum_f c_f (r[VEL_X]^2 + r[VEL_Y]^2)
+ *   2 feet_clearance      sum_f (1 - c_f) (r[POS_Z] - clearance_target)^2 sqrt(r[VEL_X]^2 + r[VEL_Y]^2)
+ *   3 touchdown_speed     sum_f td_f r[VEL_Z]^2
+ *   4 feet_contact_force  sum_f max(Fz_foot(f) - max_contact_force, 0)
+ *   5 body_contact        the number of the 9 non-foot bodies with Fz_b > force_threshold (the sensor's threshold, the foot flag's
+ *                         exact f32 comparison)
+ *   6 flight              1 where sum_f c_f == 0, else 0
+ * The gate: g_i = 1 without a command; with command [n] rows (cmd_x, cmd_y), g_i = 1 where max(|cmd_x|, |cmd_y|) > min_command_speed,
+ * else 0 (the max-norm: the comparison is exact in every precision).  Sums over feet run in ascending f, in f32.
+ *   components[i][base_terms + k] = f32(w_k * term_k);   shaped_i = the f32 sum of the seven in ascending k;
+ *   reward_out[i] = reward[i] + shaped_i  (shaped_i alone where reward is NULL; reward_out may be reward).
+ * Where done names env i, the sensor's row already describes the new episode's first state: its seven components are exact zeros and
+ * its reward passes through bit for bit (done is read for this whatever `advance` says).  A launch with advance == 0 shows no
+ * touchdown, so terms 0 and 3 are zero there.  Outputs for non-finite inputs are unspecified.
+ *
+ * base_components (nullable; f32 [n] rows of base_terms <= 25 columns): the launch copies them to components[i][0 : base_terms] and
+ * writes its seven behind them, so that one [n][base_terms + 7] buffer feeds a qg_monitor (QG_MONITOR_MAX_TERMS columns).  The rows of
+ * base_components and components may not overlap -- unless base_components == components at the same stride: the base columns are in
+ * place already and nothing is copied.
+ *
+ * ONE kernel launch on the caller's stream behind the step whose state it is to see, no allocation, no wait, no LDS, no atomics;
+ * capturable, and bit-reproducible eagerly and under graph replay; rows depend on their env alone.  Only the caller's outputs and
+ * the sensor's timers are written.  Refused while the resident step mode is on (qg_resident_stop first); every refusal is QG_ERR_ARG
+ * and comes before anything is launched.  The handle has no per-env state of its own (nothing to snapshot: the timers are the
+ * sensor's); destroy the qg_gait before its qg_contact. */
+#define QG_GAIT_NTERMS 7
+#define QG_GAIT_FEET_AIR_TIME 0
+#define QG_GAIT_FEET_SLIP 1
+#define QG_GAIT_FEET_CLEARANCE 2
+#define QG_GAIT_TOUCHDOWN_SPEED 3
+#define QG_GAIT_FEET_CONTACT_FORCE 4
+#define QG_GAIT_BODY_CONTACT 5
+#define QG_GAIT_FLIGHT 6
+typedef struct qg_gait qg_gait;
+typedef struct qg_gait_desc {
+    int32_t struct_size;               /* sizeof(qg_gait_desc): checked */
+    int32_t reserved;                  /* 0 */
+    float weights[QG_GAIT_NTERMS];     /* w_k, any sign; finite */
+    float air_time_target;             /* s; this and the three thresholds below: finite, >= 0 */
+    float clearance_target;            /* m */
+    float max_contact_force;           /* N */
+    float min_command_speed;           /* the command's units */
+} qg_gait_desc;
+int qg_gait_create(qg_contact *contact, const qg_gait_desc *desc, qg_gait **out);
+int qg_gait_destroy(qg_gait *gait);
+/* weights [QG_GAIT_NTERMS], host, finite: read by the launches that follow; a captured graph keeps the weights it was captured with. */
+int qg_gait_set_weights(qg_gait *gait, const float *weights);
+/* done: a done vector (QG_DONE_*), nullable.  reward (nullable), reward_out: f32 [n] at their strides >= 1.  components: [n] rows of
+ * base_terms + 7 floats at components_stride >= base_terms + 7; components and reward_out are each nullable but not both.
+ * base_components: see above (base_stride >= base_terms; NULL with base_terms = 0).  command: nullable, [n] rows of 2 floats at
+ * command_stride >= 2.  body_force [n][13][3] and feet [n][4][12] (16-byte aligned): the sensor's outputs, each nullable. */
+int qg_gait_reward_device(qg_gait *gait, const void *done, int32_t done_kind, int32_t done_stride, int32_t advance, const float *reward,
+                        int32_t reward_stride, float *reward_out, int32_t reward_out_stride, float *components, int32_t components_stride,
+                        const float *base_components, int32_t base_stride, int32_t base_terms, const float *command,
+                        int32_t command_stride, float *body_force, float *feet, void *stream);
 
 #ifdef __cplusplus
 }

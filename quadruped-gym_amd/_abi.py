@@ -318,6 +318,9 @@ FOOT_COLUMNS = ("pos_x", "pos_y", "pos_z", "vel_x", "vel_y", "vel_z", "contact",
                 "last_stance_time")
 FOOT_BODIES = (3, 6, 9, 12)
 MONITOR_MAX_TERMS = 32          # QG_MONITOR_MAX_TERMS
+# the gait-shaped reward terms in the order of their columns (QG_GAIT_* of include/quadgym.h)
+GAIT_TERMS = ("feet_air_time", "feet_slip", "feet_clearance", "touchdown_speed", "feet_contact_force", "body_contact", "flight")
+GAIT_MAX_BASE_TERMS = MONITOR_MAX_TERMS - len(GAIT_TERMS)
 
 
 def package_dir() -> str:
@@ -473,6 +476,11 @@ PROTOTYPES = {
     "qg_monitor_get_info": [_vp, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64), _vp, _i32],
     "qg_monitor_get_state": [_vp, _vp, _vp, _vp, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)],
     "qg_monitor_set_state": [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64],
+    # the gait-shaped reward terms (the descriptor's mirror, QgGaitDesc, is gait.py's)
+    "qg_gait_create": [_vp, _vp, _P(_vp)],
+    "qg_gait_destroy": [_vp],
+    "qg_gait_set_weights": [_vp, _P(C.c_float)],
+    "qg_gait_reward_device": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp],
 }
 EXPORTS = tuple(PROTOTYPES)
 
