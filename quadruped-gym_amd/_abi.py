@@ -323,6 +323,23 @@ GAIT_TERMS = ("feet_air_time", "feet_slip", "feet_clearance", "touchdown_speed",
 GAIT_MAX_BASE_TERMS = MONITOR_MAX_TERMS - len(GAIT_TERMS)
 
 
+class QgGaitDesc(_Sized):
+    """``qg_gait_desc``: the weights and thresholds of a gait reward (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("weights", C.c_float * len(GAIT_TERMS)),
+                ("air_time_target", C.c_float), ("clearance_target", C.c_float), ("max_contact_force", C.c_float),
+                ("min_command_speed", C.c_float)]
+
+    @classmethod
+    def make(cls, weights=(0.0,) * len(GAIT_TERMS), air_time_target=0.0, clearance_target=0.0, max_contact_force=0.0,
+             min_command_speed=0.0):
+        d = super().make()
+        for k, w in enumerate(weights):
+            d.weights[k] = float(w)
+        d.air_time_target, d.clearance_target = float(air_time_target), float(clearance_target)
+        d.max_contact_force, d.min_command_speed = float(max_contact_force), float(min_command_speed)
+        return d
+
+
 def package_dir() -> str:
     return os.path.dirname(os.path.abspath(__file__))
 
@@ -476,8 +493,8 @@ PROTOTYPES = {
     "qg_monitor_get_info": [_vp, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64), _vp, _i32],
     "qg_monitor_get_state": [_vp, _vp, _vp, _vp, _P(C.c_int64), _P(C.c_int64), _P(C.c_int64)],
     "qg_monitor_set_state": [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int64],
-    # the gait-shaped reward terms (the descriptor's mirror, QgGaitDesc, is gait.py's)
-    "qg_gait_create": [_vp, _vp, _P(_vp)],
+    # the gait-shaped reward terms
+    "qg_gait_create": [_vp, _P(QgGaitDesc), _P(_vp)],
     "qg_gait_destroy": [_vp],
     "qg_gait_set_weights": [_vp, _P(C.c_float)],
     "qg_gait_reward_device": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp],

@@ -106,16 +106,24 @@ class Handle:
         import torch
         self._check_tensor(t, (self.num_envs, self.obs_dim + 2), torch.float32, what)
 
-    def _check_obs(self, t, n=None, what="obs"):
-        """``[n, self.obs_dim]`` float32 whose rows are contiguous; the row stride is free (a column slice of a wider buffer).
-        Returns ``(n, row stride in floats)``."""
+    ANY_ROWS = "n"          # `_check_rows(rows=ANY_ROWS)`: any number of rows >= 1 (spelled into the refusal's shape)
+
+    def _check_rows(self, t, width, what, rows=None):
+        """The one strided-rows check: float32 ``[rows, width]`` on this device (``rows`` defaults to ``self.num_envs``) whose rows are
+        contiguous; the row stride is free (a column slice of a wider buffer).  A single column has no inner stride to violate and a
+        single row no row stride.  Returns the row stride in floats, at least ``width``."""
         import torch
-        width = self.obs_dim
+        rows = self.num_envs if rows is None else rows
         if not t.is_cuda or t.device.index != self.device:
             raise ValueError(f"{what} must live on cuda:{self.device}")
-        if t.dim() != 2 or t.shape[1] != width or t.dtype != torch.float32 or t.shape[0] < 1 or (n is not None and t.shape[0] != n):
-            rows = "n" if n is None else n
+        if (t.dim() != 2 or t.shape[1] != width or t.dtype != torch.float32 or t.shape[0] < 1
+                or (rows is not self.ANY_ROWS and t.shape[0] != rows)):
             raise ValueError(f"{what}: expected a float32 tensor of shape ({rows}, {width}), got {t.dtype} {tuple(t.shape)}")
-        if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < width):
+        if (width > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < width):
             raise ValueError(f"{what}: rows must be contiguous, at a row stride >= {width}; got strides {tuple(t.stride())}")
-        return int(t.shape[0]), int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), width)
+        return max(int(t.stride(0)), width)
+
+    def _check_obs(self, t, n=None, what="obs"):
+        """``_check_rows`` at the width ``self.obs_dim``, of ``n`` rows (None: any number >= 1).  Returns ``(rows, row stride)``."""
+        stride = self._check_rows(t, self.obs_dim, what, self.ANY_ROWS if n is None else n)
+        return int(t.shape[0]), stride

@@ -31,6 +31,17 @@ class ContactSensor(_TaskLayer):
         self.force_threshold = force_threshold
         self._create("qg_contact_create", sim._h, C.byref(QgContactDesc.make(force_threshold)))
 
+    def _check_outputs(self, body_force, feet):
+        """The optional outputs of a read (``read`` and ``GaitReward.step``): contiguous float32 ``[N, 13, 3]`` and ``[N, 4, 12]`` on
+        this device, ``feet`` at a 16-byte boundary.  None passes; nothing is allocated."""
+        import torch
+        if body_force is not None:
+            self._check_tensor(body_force, (self.num_envs, NBODY, 3), torch.float32, "body_force")
+        if feet is not None:
+            self._check_tensor(feet, (self.num_envs, NFOOT, FOOT_DIM), torch.float32, "feet")
+            if feet.data_ptr() % 16:
+                raise ValueError("feet: the rows are written with 16-byte stores; the tensor must be 16-byte aligned")
+
     def read(self, done=None, advance: bool = True, body_force=None, feet=None, stream=None):
         """One launch on ``stream`` (torch's current stream by default): ``(body_force [N, 13, 3], feet [N, 4, 12])`` float32 CUDA
         tensors, allocated unless passed.  ``advance=True`` moves the gait timers on by one env-step; ``done`` (uint8, bool or
@@ -39,17 +50,12 @@ class ContactSensor(_TaskLayer):
         import torch
         n = self.num_envs
         dev = self._torch_device()
+        self._check_outputs(body_force, feet)
+        dp, kind, stride = self._done_arg(done)
         if body_force is None:
             body_force = torch.empty((n, NBODY, 3), device=dev, dtype=torch.float32)
-        else:
-            self._check_tensor(body_force, (n, NBODY, 3), torch.float32, "body_force")
         if feet is None:
             feet = torch.empty((n, NFOOT, FOOT_DIM), device=dev, dtype=torch.float32)
-        else:
-            self._check_tensor(feet, (n, NFOOT, FOOT_DIM), torch.float32, "feet")
-            if feet.data_ptr() % 16:
-                raise ValueError("feet: the rows are written with 16-byte stores; the tensor must be 16-byte aligned")
-        dp, kind, stride = self._done_arg(done)
         check(self._lib.qg_contact_read_device(self._h, dp, kind, stride, 1 if advance else 0, body_force.data_ptr(), feet.data_ptr(),
                                                self._stream_ptr(stream)), "qg_contact_read_device")
         return body_force, feet

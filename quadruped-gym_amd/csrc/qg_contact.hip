@@ -7,7 +7,6 @@
 #include <stdint.h>
 
 #include <cstring>
-#include <new>
 
 #include "qg_contact_dev.h"
 
@@ -85,14 +84,12 @@ extern "C" int qg_contact_reset(qg_contact *c, const uint8_t *mask) {
     if (!mask) {
         HIP_TRY(hipMemset(c->d_armed, 0, n * sizeof(int32_t)), QG_ERR_DEVICE);
     } else {
-        int32_t *h = new (std::nothrow) int32_t[n];
-        if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
-        hipError_t e = hipMemcpy(h, c->d_armed, n * sizeof(int32_t), hipMemcpyDeviceToHost);
-        for (size_t i = 0; i < n && e == hipSuccess; i++)
+        QgHostBuf<int32_t> h(n);
+        QG_TRY(h.oom());
+        HIP_TRY(hipMemcpy(h, c->d_armed, n * sizeof(int32_t), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+        for (size_t i = 0; i < n; i++)
             if (mask[i]) h[i] = 0;
-        if (e == hipSuccess) e = hipMemcpy(c->d_armed, h, n * sizeof(int32_t), hipMemcpyHostToDevice);
-        delete[] h;
-        if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_contact_reset: %s", hipGetErrorString(e));
+        HIP_TRY(hipMemcpy(c->d_armed, h, n * sizeof(int32_t), hipMemcpyHostToDevice), QG_ERR_DEVICE);
     }
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
     return QG_OK;
@@ -126,7 +123,7 @@ static int contact_launch(qg_contact *c, const void *done, int32_t done_kind, in
 extern "C" int qg_contact_read_device(qg_contact *c, const void *done, int32_t done_kind, int32_t done_stride, int32_t advance, float *body_force,
                                       float *feet, void *stream) {
     QG_TRY(contact_check(c, done, done_kind, done_stride, body_force, feet, "qg_contact_read_device"));
-    if ((uintptr_t)feet & 15) return fail(QG_ERR_ARG, "qg_contact_read_device: feet must be 16-byte aligned");
+    if (!qg_aligned(feet, 16)) return fail(QG_ERR_ARG, "qg_contact_read_device: feet must be 16-byte aligned");
     HIP_TRY(hipSetDevice(c->sim->device), QG_ERR_DEVICE);
     qg_note_caller_stream(c->sim, (hipStream_t)stream);          // a later host-pointer call of the simulator waits for this read
     return contact_launch(c, done, done_kind, done_stride, advance, body_force, feet, (hipStream_t)stream);

@@ -190,7 +190,7 @@ extern "C" int qg_gait_reward_device(qg_gait *g, const void *done, int32_t done_
                     base_terms + QG_GAIT_NTERMS);
     if (base_components && base_stride < base_terms) return fail(QG_ERR_ARG, "%s: base_stride %d must be >= base_terms %d", who, base_stride, base_terms);
     if (command && command_stride < 2) return fail(QG_ERR_ARG, "%s: command_stride %d must be >= 2", who, command_stride);
-    if ((uintptr_t)feet & 15) return fail(QG_ERR_ARG, "%s: feet must be 16-byte aligned", who);
+    if (!qg_aligned(feet, 16)) return fail(QG_ERR_ARG, "%s: feet must be 16-byte aligned", who);
     qg_contact *c = g->contact;
     qg_sim *s = c->sim;
     // the base columns already at the front of the wide buffer: nothing to copy.  Any other overlap of the two would let a lane read what

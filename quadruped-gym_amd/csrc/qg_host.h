@@ -1,6 +1,6 @@
 // qg_host.h -- what every host translation unit of the library shares: the error record and the two status-forwarding macros, the
-// struct_size refusal, the done vector's check and read, the finite test, opening a device, the owner of a handle's device allocations
-// and a handle's birth and death.  Internal: not installed, and nothing in here is exported (libquadgym.map).
+// struct_size refusal, the done vector's check and read, the finite and alignment tests, a host staging buffer, opening a device, the
+// owner of a handle's device allocations and a handle's birth and death.  Internal: not installed, and nothing in here is exported (libquadgym.map).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -35,9 +35,29 @@ static inline bool qg_finite32(float x) {
     memcpy(&u, &x, sizeof u);
     return (u & 0x7f800000u) != 0x7f800000u;
 }
+static inline bool qg_finite64(double x) {
+    uint64_t u;
+    memcpy(&u, &x, sizeof u);
+    return ((u >> 52) & 0x7ff) != 0x7ff;
+}
 
-#ifdef __HIPCC__   // (qg_tables.h, which the plain-C++ generator of the baked table includes, needs the line above only)
+#ifdef __HIPCC__   // (qg_tables.h, which the plain-C++ generator of the baked table includes, needs the lines above only)
 #include <hip/hip_runtime.h>
+
+// `p` sits at a multiple of `a` bytes (NULL does)
+__host__ __device__ static inline bool qg_aligned(const void *p, size_t a) { return ((uintptr_t)p) % a == 0; }
+
+// A host staging buffer of `count` elements that frees itself on every return path.  Nothing throws: a failed allocation leaves NULL,
+// which oom() turns into the library's status.
+template <class T> struct QgHostBuf {
+    T *p;
+    explicit QgHostBuf(size_t count) : p(new (std::nothrow) T[count]) {}
+    ~QgHostBuf() { delete[] p; }
+    QgHostBuf(const QgHostBuf &) = delete;
+    QgHostBuf &operator=(const QgHostBuf &) = delete;
+    operator T *() const { return p; }
+    int oom() const { return p ? QG_OK : fail(QG_ERR_ALLOC, "out of host memory"); }
+};
 
 // element i of a done vector that passed qg_check_done (not NULL; kind is one of the two, so one compare tells them apart)
 __device__ __forceinline__ bool qg_done_at(const void *done, int32_t kind, int32_t stride, size_t i) {

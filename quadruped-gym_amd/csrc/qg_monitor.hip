@@ -20,15 +20,14 @@
 // memory (term-major: a wave's access to one term is 512 contiguous bytes).
 //
 // Numerics.  Column sums are plain f64 sums in a fixed order (f32 inputs: the unit of the error is eps64 x sum |x|).  The standard
-// deviation comes from sum(x - K) and sum((x - K)^2) in f64 with K the thread's first reward (exact differences, a constant reward
-// gives M2 = 0 exactly), merged by Chan's formula: never E[x^2] - E[x]^2.
+// deviation comes from the reward's f64 moments, K the thread's first reward (qg_moments_dev.h).
 
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <new>
 
 #include "qg_host.h"
+#include "qg_moments_dev.h"
 
 #define QGM_TILE 256              // envs per chunk = threads per workgroup of the tile pass (one env per thread)
 #define QGM_WAVES (QGM_TILE / 64)
@@ -37,57 +36,11 @@
 #define QGM_CHAN_RUNS 64          // ... and merges the tiles' reward moments in 64 runs (one per lane), then a butterfly over the lanes
 #define QGM_MAX_PITCH (QG_MONITOR_MAX_TERMS | 1)
 
-// (na, ma, Ma) <- merge with (nb, mb, Mb): Chan et al.  Either side may be empty.  (A private copy of qg_norm.hip's: sharing a header
-// would have to leave that unit's listing unchanged.)
-__device__ __forceinline__ void qgm_merge(double &na, double &ma, double &Ma, double nb, double mb, double Mb) {
-    if (nb == 0.0) return;
-    if (na == 0.0) {
-        na = nb, ma = mb, Ma = Mb;
-        return;
-    }
-    const double n = na + nb, d = mb - ma, f = nb / n;
-    ma = ma + d * f;
-    Ma = Ma + Mb + d * d * na * f;
-    na = n;
-}
-
-// shifted sums -> (mean, M2)
-__device__ __forceinline__ void qgm_finish(double cnt, double K, double s1, double s2, double &mean, double &M2) {
-    if (cnt == 0.0) {
-        mean = 0.0, M2 = 0.0;
-        return;
-    }
-    mean = K + s1 / cnt;
-    M2 = fmax(s2 - s1 * s1 / cnt, 0.0);
-}
-
 // the sum over the 64 lanes in the order of the butterfly (32, 16, .. 1): the same bits in every lane, on every run
-__device__ __forceinline__ double qgm_wave_sum(double v) {
+template <class T> __device__ __forceinline__ T qgm_wave_sum(T v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
-}
-
-__device__ __forceinline__ long long qgm_wave_sum_i64(long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// Chan's merge over the 64 lanes: lane l takes lane l ^ off as the right-hand side where l < l ^ off, and is the right-hand side
-// otherwise -- both lanes of a pair compute merge(lower, upper), so every lane ends with the same bits
-__device__ __forceinline__ void qgm_wave_merge(int lane, double &cnt, double &mean, double &M2) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double oc = __shfl_xor(cnt, off, 64), om = __shfl_xor(mean, off, 64), oM = __shfl_xor(M2, off, 64);
-        if (lane & off) {
-            double a = oc, b = om, c = oM;
-            qgm_merge(a, b, c, cnt, mean, M2);
-            cnt = a, mean = b, M2 = c;
-        } else {
-            qgm_merge(cnt, mean, M2, oc, om, oM);
-        }
-    }
 }
 
 // A slab row: W = 2 * (C + 1) + 2 doubles -- the column sums [C + 1], the finished envs' sums [C + 1], the reward's mean and M2 (its
@@ -167,9 +120,9 @@ __global__ __launch_bounds__(QGM_TILE) void qg_monitor_tile_kernel(KMonitor A, c
         }
     }
     double mean, M2;
-    qgm_finish(cnt, K, s1, s2, mean, M2);
-    qgm_wave_merge(lane, cnt, mean, M2);
-    flen = qgm_wave_sum_i64(flen), fcount = qgm_wave_sum_i64(fcount);
+    qg_moments_finish(cnt, K, s1, s2, mean, M2);
+    qg_moments_wave_merge(lane, cnt, mean, M2);
+    flen = qgm_wave_sum(flen), fcount = qgm_wave_sum(fcount);
     if (lane == 0) {
         shc[wave][0] = cnt, shc[wave][1] = mean, shc[wave][2] = M2;
         shi[wave][0] = flen, shi[wave][1] = fcount;
@@ -183,7 +136,7 @@ __global__ __launch_bounds__(QGM_TILE) void qg_monitor_tile_kernel(KMonitor A, c
     }
     if (t == 64) {                                          // (another wave than the sums' first)
         double na = shc[0][0], ma = shc[0][1], Ma = shc[0][2];
-        for (int w = 1; w < QGM_WAVES; w++) qgm_merge(na, ma, Ma, shc[w][0], shc[w][1], shc[w][2]);
+        for (int w = 1; w < QGM_WAVES; w++) qg_moments_merge(na, ma, Ma, shc[w][0], shc[w][1], shc[w][2]);
         row[2 * Cp] = ma, row[2 * Cp + 1] = Ma;
         long long fl = 0, fc = 0;
         for (int w = 0; w < QGM_WAVES; w++) fl += shi[w][0], fc += shi[w][1];
@@ -226,11 +179,11 @@ __global__ __launch_bounds__(64 * QGM_SUM_RUNS) void qg_monitor_combine_kernel(K
         double na = 0.0, ma = 0.0, Ma = 0.0;
         long long fl = 0, fc = 0;
         for (int g = lane * GC; g < h1; g++) {
-            qgm_merge(na, ma, Ma, (double)min((long long)A.R, n - (long long)g * A.R), part[(size_t)g * W + 2 * Cp], part[(size_t)g * W + 2 * Cp + 1]);
+            qg_moments_merge(na, ma, Ma, (double)min((long long)A.R, n - (long long)g * A.R), part[(size_t)g * W + 2 * Cp], part[(size_t)g * W + 2 * Cp + 1]);
             fl += parti[2 * g], fc += parti[2 * g + 1];
         }
-        qgm_wave_merge(lane, na, ma, Ma);
-        fl = qgm_wave_sum_i64(fl), fc = qgm_wave_sum_i64(fc);
+        qg_moments_wave_merge(lane, na, ma, Ma);
+        fl = qgm_wave_sum(fl), fc = qgm_wave_sum(fc);
         if (lane == 0) {
             out[Cp] = sqrt(Ma / (double)n);                          // population standard deviation (ddof = 0)
             out[Cp + 1] = (double)fc;
@@ -329,22 +282,19 @@ extern "C" int qg_monitor_reset(qg_monitor *p, const uint8_t *host_mask, int32_t
         HIP_TRY(hipMemset(p->d_acc, 0, (size_t)Cp * n * sizeof(double)), QG_ERR_DEVICE);
         HIP_TRY(hipMemset(p->d_len, 0, (size_t)n * sizeof(int32_t)), QG_ERR_DEVICE);
     } else {
-        double *acc = new (std::nothrow) double[(size_t)Cp * n];
-        int32_t *len = new (std::nothrow) int32_t[n];
-        hipError_t e = acc && len ? hipMemcpy(acc, p->d_acc, (size_t)Cp * n * sizeof(double), hipMemcpyDeviceToHost) : hipErrorOutOfMemory;
-        if (e == hipSuccess) e = hipMemcpy(len, p->d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
-        if (e == hipSuccess) {
-            for (int i = 0; i < n; i++)
-                if (host_mask[i]) {
-                    for (int c = 0; c < Cp; c++) acc[(size_t)c * n + i] = 0.0;
-                    len[i] = 0;
-                }
-            e = hipMemcpy(p->d_acc, acc, (size_t)Cp * n * sizeof(double), hipMemcpyHostToDevice);
-        }
-        if (e == hipSuccess) e = hipMemcpy(p->d_len, len, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
-        delete[] acc;
-        delete[] len;
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? QG_ERR_ALLOC : QG_ERR_DEVICE, "qg_monitor_reset: %s", hipGetErrorString(e));
+        QgHostBuf<double> acc((size_t)Cp * n);
+        QgHostBuf<int32_t> len(n);
+        QG_TRY(acc.oom());
+        QG_TRY(len.oom());
+        HIP_TRY(hipMemcpy(acc, p->d_acc, (size_t)Cp * n * sizeof(double), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+        HIP_TRY(hipMemcpy(len, p->d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+        for (int i = 0; i < n; i++)
+            if (host_mask[i]) {
+                for (int c = 0; c < Cp; c++) acc[(size_t)c * n + i] = 0.0;
+                len[i] = 0;
+            }
+        HIP_TRY(hipMemcpy(p->d_acc, acc, (size_t)Cp * n * sizeof(double), hipMemcpyHostToDevice), QG_ERR_DEVICE);
+        HIP_TRY(hipMemcpy(p->d_len, len, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice), QG_ERR_DEVICE);
     }
     if (clear_totals) {
         HIP_TRY(hipMemset(p->d_totals, 0, (size_t)Cp * sizeof(double)), QG_ERR_DEVICE);
@@ -376,13 +326,11 @@ extern "C" int qg_monitor_get_state(qg_monitor *p, double *acc, int32_t *len, do
     if (!p || !acc || !len) return fail(QG_ERR_ARG, "qg_monitor_get_state: null argument");
     QG_TRY(qg_monitor_get_info(p, records, episodes, length_sum, totals, 0));
     const int n = p->n, Cp = p->Cp;
-    double *h = new (std::nothrow) double[(size_t)Cp * n];
-    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
-    hipError_t e = hipMemcpy(h, p->d_acc, (size_t)Cp * n * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(len, p->d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) monitor_transpose(h, acc, Cp, n);
-    delete[] h;
-    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_monitor_get_state: %s", hipGetErrorString(e));
+    QgHostBuf<double> h((size_t)Cp * n);
+    QG_TRY(h.oom());
+    HIP_TRY(hipMemcpy(h, p->d_acc, (size_t)Cp * n * sizeof(double), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    HIP_TRY(hipMemcpy(len, p->d_len, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    monitor_transpose(h, acc, Cp, n);
     return QG_OK;
 }
 
@@ -396,16 +344,14 @@ extern "C" int qg_monitor_set_state(qg_monitor *p, const double *acc, const int3
         if (len[i] < 0) return fail(QG_ERR_ARG, "qg_monitor_set_state: len[%d] is %d (>= 0)", i, len[i]);
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
-    double *h = new (std::nothrow) double[(size_t)Cp * n];
-    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
+    QgHostBuf<double> h((size_t)Cp * n);
+    QG_TRY(h.oom());
     monitor_transpose(acc, h, n, Cp);
     const long long counts[3] = {episodes, length_sum, records};
-    hipError_t e = hipMemcpy(p->d_acc, h, (size_t)Cp * n * sizeof(double), hipMemcpyHostToDevice);
-    delete[] h;
-    if (e == hipSuccess) e = hipMemcpy(p->d_len, len, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_totals, totals, (size_t)Cp * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(p->d_counts, counts, sizeof counts, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_monitor_set_state: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(p->d_acc, h, (size_t)Cp * n * sizeof(double), hipMemcpyHostToDevice), QG_ERR_DEVICE);
+    HIP_TRY(hipMemcpy(p->d_len, len, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice), QG_ERR_DEVICE);
+    HIP_TRY(hipMemcpy(p->d_totals, totals, (size_t)Cp * sizeof(double), hipMemcpyHostToDevice), QG_ERR_DEVICE);
+    HIP_TRY(hipMemcpy(p->d_counts, counts, sizeof counts, hipMemcpyHostToDevice), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
     return QG_OK;
 }

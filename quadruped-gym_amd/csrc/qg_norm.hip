@@ -16,17 +16,16 @@
 // the rows of a tile in turn.  Statistics: f64 [4][obs_dim + 1] = mean | var | count | inv_std, the count kept per column so that a
 // column's thread owns every word it updates.
 //
-// Numerics.  Within a tile a thread accumulates sum(x - K) and sum((x - K)^2) in f64 with K its first element (x - K is exact in
-// f64 for f32 inputs; a constant column gives M2 = 0 exactly), never E[x^2] - E[x]^2; everything above is Chan's pairwise merge.
+// Numerics.  f64 moments, K a thread's first element of its tile; everything above a thread is Chan's merge (qg_moments_dev.h).
 
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 
 #include "qg_host.h"
+#include "qg_moments_dev.h"
 
 #define QGN_COLS 64               // columns per workgroup of the moments pass (one per lane)
 #define QGN_WAVES 4
@@ -34,29 +33,6 @@
 #define QGN_SLICES 16             // the combine pass merges the tiles in 16 runs per column, then a tree over the runs
 
 typedef float qgn_f32x4 __attribute__((ext_vector_type(4)));
-
-// (na, ma, Ma) <- merge with (nb, mb, Mb): Chan et al.  Either side may be empty.
-__device__ __forceinline__ void qgn_merge(double &na, double &ma, double &Ma, double nb, double mb, double Mb) {
-    if (nb == 0.0) return;
-    if (na == 0.0) {
-        na = nb, ma = mb, Ma = Mb;
-        return;
-    }
-    const double n = na + nb, d = mb - ma, f = nb / n;
-    ma = ma + d * f;
-    Ma = Ma + Mb + d * d * na * f;
-    na = n;
-}
-
-// shifted sums -> (mean, M2)
-__device__ __forceinline__ void qgn_finish(double cnt, double K, double s1, double s2, double &mean, double &M2) {
-    if (cnt == 0.0) {
-        mean = 0.0, M2 = 0.0;
-        return;
-    }
-    mean = K + s1 / cnt;
-    M2 = fmax(s2 - s1 * s1 / cnt, 0.0);
-}
 
 // the one expression of the reciprocal standard deviation (the combine pass and qg_norm_set_state both go through it, so a
 // restored state normalises with the bits the original did)
@@ -102,11 +78,11 @@ __global__ __launch_bounds__(64 * QGN_WAVES) void qg_norm_moments_kernel(int n, 
                 }
         }
         double mean, M2;
-        qgn_finish(cnt, K, s1, s2, mean, M2);
+        qg_moments_finish(cnt, K, s1, s2, mean, M2);
         sh[0][t] = cnt, sh[1][t] = mean, sh[2][t] = M2;
         __syncthreads();
         if (wave == 0) {
-            for (int w = 1; w < QGN_WAVES; w++) qgn_merge(cnt, mean, M2, sh[0][64 * w + lane], sh[1][64 * w + lane], sh[2][64 * w + lane]);
+            for (int w = 1; w < QGN_WAVES; w++) qg_moments_merge(cnt, mean, M2, sh[0][64 * w + lane], sh[1][64 * w + lane], sh[2][64 * w + lane]);
             if (c < D) part[(size_t)g * Dp + c] = make_double2(mean, M2);
         }
     } else {
@@ -122,12 +98,12 @@ __global__ __launch_bounds__(64 * QGN_WAVES) void qg_norm_moments_kernel(int n, 
             cnt += 1.0;
         }
         double mean, M2;
-        qgn_finish(cnt, K, s1, s2, mean, M2);
+        qg_moments_finish(cnt, K, s1, s2, mean, M2);
         sh[0][t] = cnt, sh[1][t] = mean, sh[2][t] = M2;
         __syncthreads();
         for (int off = 32 * QGN_WAVES; off >= 1; off >>= 1) {
             if (t < off) {
-                qgn_merge(cnt, mean, M2, sh[0][t + off], sh[1][t + off], sh[2][t + off]);
+                qg_moments_merge(cnt, mean, M2, sh[0][t + off], sh[1][t + off], sh[2][t + off]);
                 sh[0][t] = cnt, sh[1][t] = mean, sh[2][t] = M2;
             }
             __syncthreads();
@@ -150,13 +126,13 @@ __global__ __launch_bounds__(16 * QGN_SLICES) void qg_norm_combine_kernel(int n,
     double na = 0.0, ma = 0.0, Ma = 0.0;
     for (int g = s * GS; g < g1; g++) {
         const double2 p = part[(size_t)g * Dp + cr];
-        qgn_merge(na, ma, Ma, (double)min(R, n - g * R), p.x, p.y);
+        qg_moments_merge(na, ma, Ma, (double)min(R, n - g * R), p.x, p.y);
     }
     sh[0][t] = na, sh[1][t] = ma, sh[2][t] = Ma;
     __syncthreads();
     for (int off = QGN_SLICES / 2; off >= 1; off >>= 1) {
         if (s < off) {
-            qgn_merge(na, ma, Ma, sh[0][t + 16 * off], sh[1][t + 16 * off], sh[2][t + 16 * off]);
+            qg_moments_merge(na, ma, Ma, sh[0][t + 16 * off], sh[1][t + 16 * off], sh[2][t + 16 * off]);
             sh[0][t] = na, sh[1][t] = ma, sh[2][t] = Ma;
         }
         __syncthreads();
@@ -249,22 +225,15 @@ struct qg_norm {
     double2 *d_part;          // [QGN_MAX_TILES][Dp]: the moments pass's (mean, M2) per tile and column
 };
 
-// by the bit pattern: the device pass of this file is compiled with finite-math assumptions and warns at isfinite()
-static bool norm_finite(double x) {
-    uint64_t u;
-    memcpy(&u, &x, sizeof u);
-    return ((u >> 52) & 0x7ff) != 0x7ff;
-}
-
 static int norm_validate(const qg_norm_desc *d) {
     if (!d) return fail(QG_ERR_ARG, "qg_norm: null description");
     QG_CHECK_STRUCT(d, qg_norm_desc);
     if (d->obs_dim < 1 || d->obs_dim > 512) return fail(QG_ERR_ARG, "qg_norm: obs_dim %d outside 1 .. 512", d->obs_dim);
     if (d->n_envs < 1) return fail(QG_ERR_ARG, "qg_norm: n_envs %d must be >= 1", d->n_envs);
-    if (!norm_finite(d->gamma) || d->gamma < 0.0) return fail(QG_ERR_ARG, "qg_norm: gamma %g must be finite and >= 0", d->gamma);
-    if (!norm_finite(d->epsilon) || d->epsilon < 0.0) return fail(QG_ERR_ARG, "qg_norm: epsilon %g must be finite and >= 0", d->epsilon);
-    if (!norm_finite(d->clip_obs) || d->clip_obs <= 0.0) return fail(QG_ERR_ARG, "qg_norm: clip_obs %g must be finite and > 0", d->clip_obs);
-    if (!norm_finite(d->clip_reward) || d->clip_reward <= 0.0)
+    if (!qg_finite64(d->gamma) || d->gamma < 0.0) return fail(QG_ERR_ARG, "qg_norm: gamma %g must be finite and >= 0", d->gamma);
+    if (!qg_finite64(d->epsilon) || d->epsilon < 0.0) return fail(QG_ERR_ARG, "qg_norm: epsilon %g must be finite and >= 0", d->epsilon);
+    if (!qg_finite64(d->clip_obs) || d->clip_obs <= 0.0) return fail(QG_ERR_ARG, "qg_norm: clip_obs %g must be finite and > 0", d->clip_obs);
+    if (!qg_finite64(d->clip_reward) || d->clip_reward <= 0.0)
         return fail(QG_ERR_ARG, "qg_norm: clip_reward %g must be finite and > 0", d->clip_reward);
     if ((d->norm_obs != 0 && d->norm_obs != 1) || (d->norm_reward != 0 && d->norm_reward != 1))
         return fail(QG_ERR_ARG, "qg_norm: norm_obs and norm_reward are 0 or 1");
@@ -280,17 +249,14 @@ extern "C" int qg_norm_destroy(qg_norm *p) {
 static int norm_upload(qg_norm *p, const double *mean, const double *var, const double *count, double ret_mean, double ret_var,
                        double ret_count, const double *returns) {
     const int D = p->desc.obs_dim, Dp = p->Dp;
-    double *h = new (std::nothrow) double[(size_t)4 * Dp];
-    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
+    QgHostBuf<double> h((size_t)4 * Dp);
+    QG_TRY(h.oom());
     for (int c = 0; c < D; c++) h[c] = mean ? mean[c] : 0.0, h[Dp + c] = var ? var[c] : 1.0, h[2 * Dp + c] = count ? *count : 1e-4;
     h[D] = ret_mean, h[Dp + D] = ret_var, h[2 * Dp + D] = ret_count;
     for (int c = 0; c < Dp; c++) h[3 * Dp + c] = 0.0;
-    hipError_t e = hipMemcpy(p->d_stats, h, (size_t)4 * Dp * sizeof(double), hipMemcpyHostToDevice);
-    delete[] h;
-    if (e == hipSuccess)
-        e = returns ? hipMemcpy(p->d_returns, returns, (size_t)p->desc.n_envs * sizeof(double), hipMemcpyHostToDevice)
-                    : hipMemset(p->d_returns, 0, (size_t)p->desc.n_envs * sizeof(double));
-    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_norm: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(p->d_stats, h, (size_t)4 * Dp * sizeof(double), hipMemcpyHostToDevice), QG_ERR_DEVICE);
+    if (returns) HIP_TRY(hipMemcpy(p->d_returns, returns, (size_t)p->desc.n_envs * sizeof(double), hipMemcpyHostToDevice), QG_ERR_DEVICE);
+    else HIP_TRY(hipMemset(p->d_returns, 0, (size_t)p->desc.n_envs * sizeof(double)), QG_ERR_DEVICE);
     qg_norm_inv_kernel<<<1, 64, 0, nullptr>>>(Dp, p->d_stats, p->desc.epsilon);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
@@ -356,7 +322,7 @@ static int norm_apply(qg_norm *p, int32_t n, const float *obs_in, int32_t in_str
     A.done_kind = done_kind, A.done_stride = done_stride;
     A.zero_returns = zero_returns && done;
     A.clip_obs = (float)p->desc.clip_obs, A.clip_reward = (float)p->desc.clip_reward;
-    const bool vec = D % 4 == 0 && in_stride % 4 == 0 && out_stride % 4 == 0 && ((uintptr_t)obs_in | (uintptr_t)obs_out) % 16 == 0;
+    const bool vec = D % 4 == 0 && in_stride % 4 == 0 && out_stride % 4 == 0 && qg_aligned(obs_in, 16) && qg_aligned(obs_out, 16);
     const bool obs_work = obs_in && (A.norm_obs || obs_in != obs_out);          // switched off and in place: nothing to copy
     const bool rew_work = reward_in && (A.norm_reward || reward_in != reward_out || A.zero_returns);
     const int64_t obs_items = obs_work ? (int64_t)n * (D / (vec ? 4 : 1)) : 0;
@@ -421,18 +387,14 @@ extern "C" int qg_norm_get_state(qg_norm *p, double *mean, double *var, double *
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);         // a step may be in flight on a caller's stream
     const int D = p->desc.obs_dim, Dp = p->Dp;
-    double *h = new (std::nothrow) double[(size_t)3 * Dp];
-    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
-    hipError_t e = hipMemcpy(h, p->d_stats, (size_t)3 * Dp * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(returns, p->d_returns, (size_t)p->desc.n_envs * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) {
-        memcpy(mean, h, (size_t)D * sizeof(double));
-        memcpy(var, h + Dp, (size_t)D * sizeof(double));
-        *count = h[2 * Dp];
-        *ret_mean = h[D], *ret_var = h[Dp + D], *ret_count = h[2 * Dp + D];
-    }
-    delete[] h;
-    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_norm_get_state: %s", hipGetErrorString(e));
+    QgHostBuf<double> h((size_t)3 * Dp);
+    QG_TRY(h.oom());
+    HIP_TRY(hipMemcpy(h, p->d_stats, (size_t)3 * Dp * sizeof(double), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    HIP_TRY(hipMemcpy(returns, p->d_returns, (size_t)p->desc.n_envs * sizeof(double), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    memcpy(mean, h, (size_t)D * sizeof(double));
+    memcpy(var, h + Dp, (size_t)D * sizeof(double));
+    *count = h[2 * Dp];
+    *ret_mean = h[D], *ret_var = h[Dp + D], *ret_count = h[2 * Dp + D];
     return QG_OK;
 }
 
@@ -440,10 +402,10 @@ extern "C" int qg_norm_set_state(qg_norm *p, const double *mean, const double *v
                                  double ret_count, const double *returns) {
     if (!p || !mean || !var || !returns) return fail(QG_ERR_ARG, "qg_norm_set_state: null argument");
     for (int c = 0; c < p->desc.obs_dim; c++)
-        if (!norm_finite(mean[c]) || !norm_finite(var[c]) || var[c] < 0.0)
+        if (!qg_finite64(mean[c]) || !qg_finite64(var[c]) || var[c] < 0.0)
             return fail(QG_ERR_ARG, "qg_norm_set_state: column %d: mean %g, var %g (finite, var >= 0)", c, mean[c], var[c]);
-    if (!norm_finite(count) || count <= 0.0 || !norm_finite(ret_count) || ret_count <= 0.0 || !norm_finite(ret_mean) ||
-        !norm_finite(ret_var) || ret_var < 0.0)
+    if (!qg_finite64(count) || count <= 0.0 || !qg_finite64(ret_count) || ret_count <= 0.0 || !qg_finite64(ret_mean) ||
+        !qg_finite64(ret_var) || ret_var < 0.0)
         return fail(QG_ERR_ARG, "qg_norm_set_state: counts must be > 0, the return statistic finite with var >= 0");
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);

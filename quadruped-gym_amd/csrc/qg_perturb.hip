@@ -22,7 +22,6 @@
 #include <climits>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 
 #include "qg_host.h"
 
@@ -281,13 +280,10 @@ extern "C" int qg_perturb_get_delays(qg_perturb *p, int32_t *delays) {
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
     const size_t n = (size_t)p->k.n;
-    int64_t *ep = new (std::nothrow) int64_t[n];
-    if (!ep) return fail(QG_ERR_ALLOC, "out of host memory");
-    const hipError_t e = hipMemcpy(ep, p->d_episode, n * sizeof(int64_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess)
-        for (size_t i = 0; i < n; i++) delays[i] = qgp_delay(qgp_key(p->k.seed_p, p->k.base + i, (uint64_t)ep[i]), p->k.delay_lo, p->k.delay_hi);
-    delete[] ep;
-    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_perturb_get_delays: %s", hipGetErrorString(e));
+    QgHostBuf<int64_t> ep(n);
+    QG_TRY(ep.oom());
+    HIP_TRY(hipMemcpy(ep, p->d_episode, n * sizeof(int64_t), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    for (size_t i = 0; i < n; i++) delays[i] = qgp_delay(qgp_key(p->k.seed_p, p->k.base + i, (uint64_t)ep[i]), p->k.delay_lo, p->k.delay_hi);
     return QG_OK;
 }
 

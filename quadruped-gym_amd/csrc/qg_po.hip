@@ -5,7 +5,6 @@
 
 #include <climits>
 #include <cstring>
-#include <new>
 
 #include "qg_sim.h"          // qg_sim, qg_walk; through it qg_po_dev.h
 
@@ -130,10 +129,13 @@ extern "C" int qg_po_create(qg_walk *w, int32_t obs_window, qg_po **out) {
         qg_po_destroy(p);
         return QG_ERR_ALLOC;
     }
-    float *h = new float[4 * n];                                     // computed_orientation = [1, 0, 0, 0] (:19)
+    QgHostBuf<float> h(4 * n);                                       // computed_orientation = [1, 0, 0, 0] (:19)
+    if (h.oom()) {
+        qg_po_destroy(p);
+        return QG_ERR_ALLOC;
+    }
     for (size_t i = 0; i < n; i++) { h[i] = 1.f; h[n + i] = h[2 * n + i] = h[3 * n + i] = 0.f; }
     const hipError_t e = hipMemcpy(p->st.orient, h, 4 * n * 4, hipMemcpyHostToDevice);
-    delete[] h;
     if (e != hipSuccess) {
         qg_po_destroy(p);
         return fail(QG_ERR_ALLOC, "qg_po_create: %s", hipGetErrorString(e));

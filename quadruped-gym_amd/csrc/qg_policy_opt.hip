@@ -48,8 +48,6 @@ __device__ __forceinline__ void qga_store4(float *__restrict__ dst, int i, int n
     }
 }
 
-__device__ __forceinline__ bool qga_aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 // the sum over a workgroup: a fixed butterfly within the wave, then the waves in ascending order; the same value in every thread
 template <int WAVES>
 __device__ __forceinline__ double qga_block_sum(double s, double *ws) {
@@ -68,7 +66,7 @@ constexpr int QGA_GROUPS = QGA_SLOT / (4 * QGA_THREADS);          // groups of f
 __global__ __launch_bounds__(QGA_THREADS) void qg_policy_adam_norm_kernel(int n, const float *__restrict__ grad, double *__restrict__ partial,
                                                                           long long *t) {
     __shared__ double ws[QGA_THREADS / 64];
-    const bool wide = qga_aligned16(grad);
+    const bool wide = qg_aligned(grad, 16);
     double s = 0.0;
 #pragma unroll
     for (int k = 0; k < QGA_GROUPS; k++) {
@@ -166,7 +164,7 @@ __global__ __launch_bounds__(QGA_THREADS) void qg_policy_adam_update_kernel(KPol
         table.layer[threadIdx.x] = P.layer[t][l];
         table.wt_off[threadIdx.x] = (packed_t && l > 0) ? G.layer[t][l].wt_off : -1;
     }
-    const bool wide_g = qga_aligned16(grad), wide_o = qga_aligned16(params_out);
+    const bool wide_g = qg_aligned(grad, 16), wide_o = qg_aligned(params_out, 16);
     float g[QGA_GROUPS][4], p[QGA_GROUPS][4], m[QGA_GROUPS][4], v[QGA_GROUPS][4];
 #pragma unroll
     for (int k = 0; k < QGA_GROUPS; k++) {
@@ -215,7 +213,7 @@ __global__ __launch_bounds__(QGA_THREADS) void qg_policy_adam_update_kernel(KPol
 // SB3's normalize_advantage.  Thread t owns the groups of four elements t, t + QGN_THREADS, .. whatever the width of its loads.
 __global__ __launch_bounds__(QGN_THREADS) void qg_policy_normalize_advantages_kernel(int n, const float *adv, float *out) {
     __shared__ double ws[QGN_THREADS / 64];
-    const bool wide_in = qga_aligned16(adv), wide_out = qga_aligned16(out);
+    const bool wide_in = qg_aligned(adv, 16), wide_out = qg_aligned(out, 16);
     double s = 0.0;
     for (int i = 4 * (int)threadIdx.x; i < n; i += 4 * QGN_THREADS) {
         float x[4];

@@ -25,7 +25,6 @@
 #include <climits>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 
 #include "qg_host.h"
 
@@ -276,15 +275,6 @@ struct qg_rollout {
     long long *d_cur_length, *d_fin_length, *d_fin_count;
 };
 
-// by the bit pattern: the device pass of this file is compiled with finite-math assumptions and warns at isfinite()
-static bool rollout_finite(double x) {
-    uint64_t u;
-    memcpy(&u, &x, sizeof u);
-    return ((u >> 52) & 0x7ff) != 0x7ff;
-}
-
-static bool rollout_aligned(const void *p, size_t a) { return ((uintptr_t)p) % a == 0; }
-
 static int rollout_validate(const qg_rollout_desc *d, const qg_rollout_storage *s) {
     if (!d) return fail(QG_ERR_ARG, "qg_rollout: null description");
     QG_CHECK_STRUCT(d, qg_rollout_desc);
@@ -292,9 +282,9 @@ static int rollout_validate(const qg_rollout_desc *d, const qg_rollout_storage *
     if (d->n_steps < 1) return fail(QG_ERR_ARG, "qg_rollout: n_steps %d must be >= 1", d->n_steps);
     if (d->obs_dim < 1 || d->obs_dim > 512) return fail(QG_ERR_ARG, "qg_rollout: obs_dim %d outside 1 .. 512", d->obs_dim);
     if (d->act_dim < 1 || d->act_dim > 16) return fail(QG_ERR_ARG, "qg_rollout: act_dim %d outside 1 .. 16", d->act_dim);
-    if (!rollout_finite(d->gamma) || d->gamma < 0.0 || d->gamma > 1.0)
+    if (!qg_finite64(d->gamma) || d->gamma < 0.0 || d->gamma > 1.0)
         return fail(QG_ERR_ARG, "qg_rollout: gamma %g must be finite and in [0, 1]", d->gamma);
-    if (!rollout_finite(d->gae_lambda) || d->gae_lambda < 0.0 || d->gae_lambda > 1.0)
+    if (!qg_finite64(d->gae_lambda) || d->gae_lambda < 0.0 || d->gae_lambda > 1.0)
         return fail(QG_ERR_ARG, "qg_rollout: gae_lambda %g must be finite and in [0, 1]", d->gae_lambda);
     if (((int64_t)d->n_steps + 1) * d->n_envs > INT32_MAX)
         return fail(QG_ERR_ARG, "qg_rollout: (n_steps + 1) * n_envs = %lld rows are more than 2^31 - 1",
@@ -305,7 +295,7 @@ static int rollout_validate(const qg_rollout_desc *d, const qg_rollout_storage *
     const char *names[] = {"obs", "actions", "log_prob", "values", "rewards", "advantages", "returns"};
     for (int k = 0; k < 7; k++) {
         if (!f32s[k]) return fail(QG_ERR_ARG, "qg_rollout_storage.%s is NULL", names[k]);
-        if (!rollout_aligned(f32s[k], sizeof(float))) return fail(QG_ERR_ARG, "qg_rollout_storage.%s is not aligned to 4 bytes", names[k]);
+        if (!qg_aligned(f32s[k], sizeof(float))) return fail(QG_ERR_ARG, "qg_rollout_storage.%s is not aligned to 4 bytes", names[k]);
     }
     if (!s->dones) return fail(QG_ERR_ARG, "qg_rollout_storage.dones is NULL");
     return QG_OK;
@@ -355,9 +345,9 @@ extern "C" int qg_rollout_begin_device(qg_rollout *p, const float *obs, int32_t 
     if (!p) return fail(QG_ERR_ARG, "qg_rollout_begin_device: null handle");
     const int D = p->desc.obs_dim, n = p->desc.n_envs;
     if (obs && obs_stride < D) return fail(QG_ERR_ARG, "qg_rollout_begin_device: obs_stride %d < obs_dim %d", obs_stride, D);
-    if (obs && !rollout_aligned(obs, sizeof(float))) return fail(QG_ERR_ARG, "qg_rollout_begin_device: obs is not aligned to 4 bytes");
+    if (obs && !qg_aligned(obs, sizeof(float))) return fail(QG_ERR_ARG, "qg_rollout_begin_device: obs is not aligned to 4 bytes");
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
-    const bool vec = D % 4 == 0 && rollout_aligned(p->st.obs, 16) && (!obs || (obs_stride % 4 == 0 && rollout_aligned(obs, 16)));
+    const bool vec = D % 4 == 0 && qg_aligned(p->st.obs, 16) && (!obs || (obs_stride % 4 == 0 && qg_aligned(obs, 16)));
     int64_t blocks;
     QG_TRY(rollout_blocks(n, D / (vec ? 4 : 1), &blocks));
     const hipStream_t st = (hipStream_t)stream;
@@ -384,7 +374,7 @@ extern "C" int qg_rollout_add_device(qg_rollout *p, const qg_rollout_step *s, vo
     const void *f32s[] = {s->next_obs, s->actions, s->log_prob, s->value, s->reward, s->trunc_value, s->episode_reward,
                           s->done_kind == QG_DONE_F32 ? s->done : nullptr};
     for (const void *q : f32s)
-        if (!rollout_aligned(q, sizeof(float))) return fail(QG_ERR_ARG, "qg_rollout_add_device: a float pointer is not aligned to 4 bytes");
+        if (!qg_aligned(q, sizeof(float))) return fail(QG_ERR_ARG, "qg_rollout_add_device: a float pointer is not aligned to 4 bytes");
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     KRolloutAdd a;
     memset(&a, 0, sizeof a);
@@ -398,7 +388,7 @@ extern "C" int qg_rollout_add_device(qg_rollout *p, const qg_rollout_step *s, vo
     a.dones = p->st.dones;
     a.cur_return = p->d_cur_return, a.fin_return = p->d_fin_return;
     a.cur_length = p->d_cur_length, a.fin_length = p->d_fin_length, a.fin_count = p->d_fin_count;
-    const bool vec = D % 4 == 0 && s->next_obs_stride % 4 == 0 && rollout_aligned(s->next_obs, 16) && rollout_aligned(p->st.obs, 16);
+    const bool vec = D % 4 == 0 && s->next_obs_stride % 4 == 0 && qg_aligned(s->next_obs, 16) && qg_aligned(p->st.obs, 16);
     int64_t ob, ab;
     QG_TRY(rollout_blocks(n, D / (vec ? 4 : 1), &ob));
     QG_TRY(rollout_blocks(n, A, &ab));
@@ -414,7 +404,7 @@ extern "C" int qg_rollout_add_device(qg_rollout *p, const qg_rollout_step *s, vo
 
 extern "C" int qg_rollout_compute_device(qg_rollout *p, const float *last_values, void *stream) {
     if (!p || !last_values) return fail(QG_ERR_ARG, "qg_rollout_compute_device: null argument");
-    if (!rollout_aligned(last_values, sizeof(float))) return fail(QG_ERR_ARG, "qg_rollout_compute_device: last_values is not aligned to 4 bytes");
+    if (!qg_aligned(last_values, sizeof(float))) return fail(QG_ERR_ARG, "qg_rollout_compute_device: last_values is not aligned to 4 bytes");
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     const int n = p->desc.n_envs;
     qg_rollout_gae_kernel<<<(unsigned)((n + QGR_GAE_BLOCK - 1) / QGR_GAE_BLOCK), QGR_GAE_BLOCK, 0, (hipStream_t)stream>>>(
@@ -428,10 +418,10 @@ extern "C" int qg_rollout_gather_device(qg_rollout *p, const int64_t *idx, int32
     QG_CHECK_STRUCT(out, qg_rollout_batch);
     if (B < 1) return fail(QG_ERR_ARG, "qg_rollout_gather_device: B is %d, a batch has at least one row", B);
     if (!p || !idx) return fail(QG_ERR_ARG, "qg_rollout_gather_device: null argument");
-    if (!rollout_aligned(idx, sizeof(int64_t))) return fail(QG_ERR_ARG, "qg_rollout_gather_device: idx is not aligned to 8 bytes");
+    if (!qg_aligned(idx, sizeof(int64_t))) return fail(QG_ERR_ARG, "qg_rollout_gather_device: idx is not aligned to 8 bytes");
     const void *f32s[] = {out->obs, out->actions, out->old_log_prob, out->old_values, out->advantages, out->returns};
     for (const void *q : f32s)
-        if (!rollout_aligned(q, sizeof(float))) return fail(QG_ERR_ARG, "qg_rollout_gather_device: an output is not aligned to 4 bytes");
+        if (!qg_aligned(q, sizeof(float))) return fail(QG_ERR_ARG, "qg_rollout_gather_device: an output is not aligned to 4 bytes");
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     const int D = p->desc.obs_dim, A = p->desc.act_dim;
     KRolloutGather a;
@@ -441,7 +431,7 @@ extern "C" int qg_rollout_gather_device(qg_rollout *p, const int64_t *idx, int32
     a.advantages = p->st.advantages, a.returns = p->st.returns;
     a.o_obs = out->obs, a.o_actions = out->actions, a.o_log_prob = out->old_log_prob, a.o_values = out->old_values;
     a.o_advantages = out->advantages, a.o_returns = out->returns;
-    const bool vec = D % 4 == 0 && rollout_aligned(p->st.obs, 16) && rollout_aligned(out->obs, 16);
+    const bool vec = D % 4 == 0 && qg_aligned(p->st.obs, 16) && qg_aligned(out->obs, 16);
     int64_t ob = 0, ab = 0;
     if (out->obs) QG_TRY(rollout_blocks(B, D / (vec ? 4 : 1), &ob));
     if (out->actions) QG_TRY(rollout_blocks(B, A, &ab));
@@ -473,30 +463,22 @@ extern "C" int qg_rollout_episode_stats(qg_rollout *p, double *return_sum, int64
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
     const size_t n = (size_t)p->desc.n_envs;
-    double *hr = new (std::nothrow) double[n];
-    long long *hl = new (std::nothrow) long long[2 * n];
-    if (!hr || !hl) {
-        delete[] hr;
-        delete[] hl;
-        return fail(QG_ERR_ALLOC, "out of host memory");
+    QgHostBuf<double> hr(n);
+    QgHostBuf<long long> hl(2 * n);
+    QG_TRY(hr.oom());
+    QG_TRY(hl.oom());
+    HIP_TRY(hipMemcpy(hr, p->d_fin_return, n * sizeof(double), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    HIP_TRY(hipMemcpy(hl, p->d_fin_length, n * sizeof(long long), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    HIP_TRY(hipMemcpy(hl + n, p->d_fin_count, n * sizeof(long long), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    if (clear) {
+        HIP_TRY(hipMemset(p->d_fin_return, 0, n * sizeof(double)), QG_ERR_DEVICE);
+        HIP_TRY(hipMemset(p->d_fin_length, 0, n * sizeof(long long)), QG_ERR_DEVICE);
+        HIP_TRY(hipMemset(p->d_fin_count, 0, n * sizeof(long long)), QG_ERR_DEVICE);
+        HIP_TRY(hipDeviceSynchronize(), QG_ERR_DEVICE);
     }
-    hipError_t e = hipMemcpy(hr, p->d_fin_return, n * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(hl, p->d_fin_length, n * sizeof(long long), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(hl + n, p->d_fin_count, n * sizeof(long long), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && clear) {
-        e = hipMemset(p->d_fin_return, 0, n * sizeof(double));
-        if (e == hipSuccess) e = hipMemset(p->d_fin_length, 0, n * sizeof(long long));
-        if (e == hipSuccess) e = hipMemset(p->d_fin_count, 0, n * sizeof(long long));
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    }
-    if (e == hipSuccess) {
-        double rs = 0.0;
-        int64_t ls = 0, cs = 0;
-        for (size_t i = 0; i < n; i++) rs += hr[i], ls += hl[i], cs += hl[n + i];          // in env order
-        *return_sum = rs, *length_sum = ls, *count = cs;
-    }
-    delete[] hr;
-    delete[] hl;
-    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_rollout_episode_stats: %s", hipGetErrorString(e));
+    double rs = 0.0;
+    int64_t ls = 0, cs = 0;
+    for (size_t i = 0; i < n; i++) rs += hr[i], ls += hl[i], cs += hl[n + i];          // in env order
+    *return_sum = rs, *length_sum = ls, *count = cs;
     return QG_OK;
 }

@@ -52,29 +52,27 @@ static int dyn_check_row(const qg_sim *s, const float *row, const char *who, con
 }
 // The dynamics rows through a host buffer, transposed: [QG_NDYN][n] on the device, [n][QG_NDYN] at the ABI.  `out`: the device's rows;
 // `in`: the rows of the envs in `mask` (NULL: all), `in_stride` floats apart (0: the same row for every env, which needs no fetch).
-static int dyn_rows_transfer(qg_sim *s, const char *who, float *out, const float *in, size_t in_stride, const uint8_t *mask) {
+static int dyn_rows_transfer(qg_sim *s, float *out, const float *in, size_t in_stride, const uint8_t *mask) {
     const size_t n = (size_t)s->n, bytes = n * QG_NDYN * sizeof(float);
-    float *h = (float *)malloc(bytes);
-    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
-    hipError_t e = (in && !in_stride) ? hipSuccess : hipMemcpy(h, s->d_dyn, bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out)
+    QgHostBuf<float> h(n * QG_NDYN);
+    QG_TRY(h.oom());
+    if (!in || in_stride) HIP_TRY(hipMemcpy(h, s->d_dyn, bytes, hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    if (out)
         for (int c = 0; c < QG_NDYN; c++)
             for (size_t i = 0; i < n; i++) out[i * QG_NDYN + c] = h[c * n + i];
-    if (e == hipSuccess && in) {
+    if (in) {
         for (size_t i = 0; i < n; i++)
             if (!mask || mask[i])
                 for (int c = 0; c < QG_NDYN; c++) h[c * n + i] = in[i * in_stride + c];
-        e = hipMemcpy(s->d_dyn, h, bytes, hipMemcpyHostToDevice);
+        HIP_TRY(hipMemcpy(s->d_dyn, h, bytes, hipMemcpyHostToDevice), QG_ERR_DEVICE);
     }
-    free(h);
-    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
     return QG_OK;
 }
 // identity rows into the dynamics buffer (with them the per-env kernels compute the shared model's bits)
-static int dyn_fill_identity(qg_sim *s, const char *who) {
+static int dyn_fill_identity(qg_sim *s) {
     float id[QG_NDYN];
     dyn_identity_row(s, id);
-    return dyn_rows_transfer(s, who, nullptr, id, 0, nullptr);
+    return dyn_rows_transfer(s, nullptr, id, 0, nullptr);
 }
 // what the per-env kernels read behind the model tables: the dynamics rows' address, the wrench rows' address (NULL while wrench mode
 // is off: the kernels' wave-uniform branch), the FRAME's centre of mass and the push schedule.  Callers have waited for the device.
@@ -99,7 +97,7 @@ static int per_env_enable(qg_sim *s, const char *who, const char *what) {
     if (!s->d_dyn && s->mem.alloc(s->d_dyn, n * QG_NDYN * sizeof(float))) return QG_ERR_ALLOC;
     if (!s->d_model_dyn && s->mem.alloc(s->d_model_dyn, sizeof(KModelDyn))) return QG_ERR_ALLOC;
     HIP_TRY(hipMemcpy(&s->d_model_dyn->m, s->d_model, sizeof(KModel), hipMemcpyDeviceToDevice), QG_ERR_DEVICE);
-    QG_TRY(dyn_fill_identity(s, who));
+    QG_TRY(dyn_fill_identity(s));
     return model_dyn_upload(s);
 }
 // switch the mode on: the row buffer (identity rows) and the per-env kernels' model pointer, the table-driven kernels
@@ -144,7 +142,7 @@ extern "C" int qg_get_dynamics(qg_sim *s, float *rows) {
     }
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     QG_TRY(qg_retire_and_sync(s));
-    return dyn_rows_transfer(s, "qg_get_dynamics", rows, nullptr, 0, nullptr);
+    return dyn_rows_transfer(s, rows, nullptr, 0, nullptr);
 }
 
 extern "C" int qg_set_dynamics(qg_sim *s, const uint8_t *mask, const float *rows) {
@@ -161,7 +159,7 @@ extern "C" int qg_set_dynamics(qg_sim *s, const uint8_t *mask, const float *rows
     // read-modify-write of the rows: steps (and their auto-reset draws) may be in flight on a caller's stream even when the mode was
     // already on (dyn_enable then returns at once) -- the header's ordering contract
     QG_TRY(qg_retire_and_sync(s));
-    return dyn_rows_transfer(s, "qg_set_dynamics", nullptr, rows, QG_NDYN, mask);
+    return dyn_rows_transfer(s, nullptr, rows, QG_NDYN, mask);
 }
 
 extern "C" int qg_clear_dynamics(qg_sim *s) {
@@ -169,7 +167,7 @@ extern "C" int qg_clear_dynamics(qg_sim *s) {
     if (!s->dyn) return QG_OK;
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);        // per-env steps may be in flight on a caller's stream
-    if (s->xfrc) QG_TRY(dyn_fill_identity(s, "qg_clear_dynamics"));       // wrench mode keeps the per-env kernels: identity rows
+    if (s->xfrc) QG_TRY(dyn_fill_identity(s));       // wrench mode keeps the per-env kernels: identity rows
     s->dyn = 0;
     s->dyn_range_set = 0;
     return QG_OK;
@@ -211,16 +209,12 @@ extern "C" int qg_set_xfrc(qg_sim *s, const uint8_t *mask, const float *rows) {
         HIP_TRY(hipMemcpy(s->d_xfrc, rows, xfrc_bytes(s), hipMemcpyHostToDevice), QG_ERR_DEVICE);
         return QG_OK;
     }
-    float *h = (float *)malloc(xfrc_bytes(s));
-    if (!h) return fail(QG_ERR_ALLOC, "out of host memory");
-    hipError_t e = hipMemcpy(h, s->d_xfrc, xfrc_bytes(s), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) {
-        for (size_t i = 0; i < n; i++)
-            if (mask[i]) memcpy(h + i * w, rows + i * w, w * sizeof(float));
-        e = hipMemcpy(s->d_xfrc, h, xfrc_bytes(s), hipMemcpyHostToDevice);
-    }
-    free(h);
-    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_set_xfrc: %s", hipGetErrorString(e));
+    QgHostBuf<float> h(n * w);
+    QG_TRY(h.oom());
+    HIP_TRY(hipMemcpy(h, s->d_xfrc, xfrc_bytes(s), hipMemcpyDeviceToHost), QG_ERR_DEVICE);
+    for (size_t i = 0; i < n; i++)
+        if (mask[i]) memcpy(h + i * w, rows + i * w, w * sizeof(float));
+    HIP_TRY(hipMemcpy(s->d_xfrc, h, xfrc_bytes(s), hipMemcpyHostToDevice), QG_ERR_DEVICE);
     return QG_OK;
 }
 

@@ -28,7 +28,6 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
-#include <new>
 
 #include "qg_sim.h"          // qg_sim, qg_walk; through it qg_walk_dev.h: KWalkParams / KWalkState and the per-env device functions
                              // (shared with the fused step kernels)
@@ -230,8 +229,8 @@ extern "C" int qg_walk_set_commands(qg_walk *w, const float *velocity_xy, const 
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
     size_t n = (size_t)s->n;
-    float *host = new (std::nothrow) float[6 * n];
-    if (!host) return fail(QG_ERR_ALLOC, "out of host memory");
+    QgHostBuf<float> host(6 * n);
+    QG_TRY(host.oom());
     float *vel = host, *head = host + 2 * n, *gv = host + 4 * n;
     for (size_t i = 0; i < n; i++) {
         float v0 = velocity_xy[2 * i], v1 = velocity_xy[2 * i + 1], h0 = heading_xy[2 * i], h1 = heading_xy[2 * i + 1];
@@ -239,11 +238,9 @@ extern "C" int qg_walk_set_commands(qg_walk *w, const float *velocity_xy, const 
         gv[i] = h0 * v0 - h1 * v1;                    // control_inputs.py:14-27
         gv[n + i] = h1 * v0 + h0 * v1;
     }
-    hipError_t e = hipMemcpy(w->st.vel, vel, 2 * n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(w->st.head, head, 2 * n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(w->st.gvel, gv, 2 * n * 4, hipMemcpyHostToDevice);
-    delete[] host;
-    if (e != hipSuccess) return fail(QG_ERR_DEVICE, "qg_walk_set_commands: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(w->st.vel, vel, 2 * n * 4, hipMemcpyHostToDevice), QG_ERR_DEVICE);
+    HIP_TRY(hipMemcpy(w->st.head, head, 2 * n * 4, hipMemcpyHostToDevice), QG_ERR_DEVICE);
+    HIP_TRY(hipMemcpy(w->st.gvel, gv, 2 * n * 4, hipMemcpyHostToDevice), QG_ERR_DEVICE);
     return QG_OK;
 }
 
@@ -284,17 +281,15 @@ extern "C" int qg_walk_get_commands(qg_walk *w, float *velocity_xy, float *headi
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
     size_t n = (size_t)s->n;
-    float *host = new (std::nothrow) float[2 * n];
-    if (!host) return fail(QG_ERR_ALLOC, "out of host memory");
+    QgHostBuf<float> host(2 * n);
+    QG_TRY(host.oom());
     float *dsts[2] = {velocity_xy, heading_xy};
     const float *srcs[2] = {w->st.vel, w->st.head};
     for (int a = 0; a < 2; a++) {
         if (!dsts[a]) continue;
-        hipError_t e = hipMemcpy(host, srcs[a], 2 * n * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { delete[] host; return fail(QG_ERR_DEVICE, "qg_walk_get_commands: %s", hipGetErrorString(e)); }
+        HIP_TRY(hipMemcpy(host, srcs[a], 2 * n * 4, hipMemcpyDeviceToHost), QG_ERR_DEVICE);
         for (size_t i = 0; i < n; i++) { dsts[a][2 * i] = host[i]; dsts[a][2 * i + 1] = host[n + i]; }
     }
-    delete[] host;
     return QG_OK;
 }
 

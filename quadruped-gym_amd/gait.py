@@ -14,28 +14,12 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import FOOT_DIM, GAIT_MAX_BASE_TERMS, GAIT_TERMS, NBODY, NFOOT, check
+from ._abi import GAIT_MAX_BASE_TERMS, GAIT_TERMS, QgGaitDesc, check          # (QgGaitDesc: re-exported)
 from ._handle import Handle
 from .envs.device_wrapper import STEP_BUFFERS, DeviceVecEnvWrapper
 
 NTERMS = len(GAIT_TERMS)
 THRESHOLDS = ("air_time_target", "clearance_target", "max_contact_force", "min_command_speed")
-
-
-class QgGaitDesc(C.Structure):
-    """``qg_gait_desc``: the weights and thresholds of a gait reward (``make`` fills ``struct_size`` in)."""
-    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("weights", C.c_float * NTERMS), ("air_time_target", C.c_float),
-                ("clearance_target", C.c_float), ("max_contact_force", C.c_float), ("min_command_speed", C.c_float)]
-
-    @classmethod
-    def make(cls, weights=(0.0,) * NTERMS, air_time_target=0.0, clearance_target=0.0, max_contact_force=0.0, min_command_speed=0.0):
-        d = cls()
-        d.struct_size = C.sizeof(cls)
-        for k, w in enumerate(weights):
-            d.weights[k] = float(w)
-        d.air_time_target, d.clearance_target = float(air_time_target), float(clearance_target)
-        d.max_contact_force, d.min_command_speed = float(max_contact_force), float(min_command_speed)
-        return d
 
 
 def term_weights(weights) -> list:
@@ -83,17 +67,6 @@ class GaitReward(Handle):
         self.weights = dict(zip(GAIT_TERMS, w))
 
     # -- device path ------------------------------------------------------------------------
-    def _check_rows(self, t, width, what):
-        """Float32 ``[N, width]`` on this device with contiguous rows at a row stride >= width.  Returns the row stride."""
-        import torch
-        if not t.is_cuda or t.device.index != self.device:
-            raise ValueError(f"{what} must live on cuda:{self.device}")
-        if t.dim() != 2 or tuple(t.shape) != (self.num_envs, width) or t.dtype != torch.float32:
-            raise ValueError(f"{what}: expected a float32 tensor of shape ({self.num_envs}, {width}), got {t.dtype} {tuple(t.shape)}")
-        if (width > 1 and t.stride(1) != 1) or (self.num_envs > 1 and t.stride(0) < width):
-            raise ValueError(f"{what}: rows must be contiguous, at a row stride >= {width}; got strides {tuple(t.stride())}")
-        return max(int(t.stride(0)), width)
-
     @staticmethod
     def _span(t, width, stride):
         lo = t.data_ptr()
@@ -135,12 +108,7 @@ class GaitReward(Handle):
         m_ptr, m_stride = None, 2
         if command is not None:
             m_stride, m_ptr = self._check_rows(command, 2, "command"), command.data_ptr()
-        if body_force is not None:
-            self._check_tensor(body_force, (n, NBODY, 3), torch.float32, "body_force")
-        if feet is not None:
-            self._check_tensor(feet, (n, NFOOT, FOOT_DIM), torch.float32, "feet")
-            if feet.data_ptr() % 16:
-                raise ValueError("feet: the rows are written with 16-byte stores; the tensor must be 16-byte aligned")
+        self.sensor._check_outputs(body_force, feet)
         if reward_out is None:
             reward_out = torch.empty(n, device=dev, dtype=torch.float32)
         if components is None:

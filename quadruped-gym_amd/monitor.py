@@ -53,21 +53,11 @@ class RewardMonitor(Handle):
         return cls(env.num_envs, list(env.reward_keys), capacity=capacity, device=getattr(env, "device", 0))
 
     # -- device path ------------------------------------------------------------------------
-    def _check_components(self, t):
-        import torch
-        if not t.is_cuda or t.device.index != self.device:
-            raise ValueError(f"components must live on cuda:{self.device}")
-        if t.dim() != 2 or tuple(t.shape) != (self.num_envs, self.n_terms) or t.dtype != torch.float32:
-            raise ValueError(f"components: expected a float32 tensor of shape ({self.num_envs}, {self.n_terms}), got {t.dtype} {tuple(t.shape)}")
-        if (self.n_terms > 1 and t.stride(1) != 1) or (self.num_envs > 1 and t.stride(0) < self.n_terms):
-            raise ValueError(f"components: rows must be contiguous, at a row stride >= {self.n_terms}; got strides {tuple(t.stride())}")
-        return max(int(t.stride(0)), self.n_terms)
-
     def record(self, components, reward, done=None, stream=None):
         """One env-step: ``components`` float32 ``[N, len(keys)]`` (strided rows allowed), ``reward`` float32 ``[N]`` at any positive
         stride, ``done`` uint8 / bool / float32 ``[N]`` or None (nobody finished)."""
         import torch
-        c_stride = self._check_components(components)
+        c_stride = self._check_rows(components, self.n_terms, "components")
         r_stride = self._check_vec(reward, (torch.float32,), "reward")
         d_ptr, kind, d_stride = self._done_arg(done)
         check(self._lib.qg_monitor_record_device(self._h, components.data_ptr(), c_stride, reward.data_ptr(), r_stride, d_ptr, kind, d_stride,

@@ -196,6 +196,29 @@ def test_switched_off_flags_copy_through_and_state_round_trips():
     a.close(), b.close()
 
 
+def test_a_single_column_at_an_inner_stride_equals_its_contiguous_copy():
+    """obs_dim 1: the [5, 1] view x[:, ::2] of a [5, 2] tensor (strides (2, 2)) has no inner stride to violate -- the library takes
+    the row stride alone -- and so does an output of the same kind."""
+    n = 5
+    rng = np.random.default_rng(7)
+    x = _t(rng.normal(2.0, 3.0, (3, n, 2)).astype(np.float32))
+    rew, done = _t(rng.normal(0.0, 1.0, (3, n)).astype(np.float32)), _t((rng.random((3, n)) < 0.4).astype(np.uint8))
+    x0 = x.clone()
+    a, b = _new(n, 1), _new(n, 1)
+    for k in range(3):
+        wide = torch.full((n, 2), -7.0, device=DEV)
+        view, out = x[k][:, ::2], wide[:, ::2]
+        assert tuple(view.shape) == (n, 1) and view.stride() == (2, 2) == out.stride()
+        ra, rb = torch.empty(n, device=DEV), torch.empty(n, device=DEV)
+        a.step(view, rew[k], done[k], obs_out=out, reward_out=ra)
+        ob, _ = b.step(view.contiguous(), rew[k], done[k], obs_out=torch.empty((n, 1), device=DEV), reward_out=rb)
+        assert torch.equal(out, ob) and torch.equal(ra, rb)
+        assert torch.equal(wide[:, 1], torch.full((n,), -7.0, device=DEV))          # the column between the output's rows
+        assert _state_bytes(a) == _state_bytes(b)
+    assert torch.equal(x, x0)                                                       # the inputs, the odd column included
+    a.close(), b.close()
+
+
 # ---- 3. bit-for-bit identity: run to run, eager against graph replay ---------------------------------------------------------------------
 @pytest.mark.parametrize("n,D", R.SHAPES, ids=IDS)
 def test_two_runs_and_both_graph_forms_leave_the_same_bits(n, D):

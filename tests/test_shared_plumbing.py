@@ -1,11 +1,15 @@
 """What the device-side layers share, without a GPU: one pair of done constants under five names, one prototype table behind the
-binding, one way to fill `struct_size`, and the VecEnv wrappers' base driven with a stub env."""
+binding, one way to fill `struct_size`, one strided-rows check, the ledger of what the layers' C code shares, and the VecEnv wrappers'
+base driven with a stub env."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
 import pytest
 
 from quadruped_gym_amd import _abi
+from quadruped_gym_amd._handle import Handle
 from quadruped_gym_amd.envs.device_wrapper import STEP_BUFFERS, DeviceVecEnvWrapper
 
 from helpers import header_define, header_text
@@ -57,7 +61,7 @@ def test_every_struct_with_a_struct_size_is_sized():
     sized = _sized_classes()
     with_field = [v for v in vars(_abi).values() if isinstance(v, type) and issubclass(v, C.Structure) and v is not _abi._Sized
                   and "struct_size" in [f[0] for f in getattr(v, "_fields_", [])]]
-    assert sorted(c.__name__ for c in with_field) == sorted(c.__name__ for c in sized) and len(sized) == 11
+    assert sorted(c.__name__ for c in with_field) == sorted(c.__name__ for c in sized) and len(sized) == 12
     for cls in sized:
         assert cls._fields_[0][0] == "struct_size"
 
@@ -66,9 +70,9 @@ def test_every_struct_with_a_struct_size_is_sized():
     lambda: _abi.QgPolicyDesc.make(33, (64, 64), 12), lambda: _abi.QgPpoParams.make(), lambda: _abi.QgPpoBatch.make(33, obs=16),
     lambda: _abi.QgAdamParams.make(), lambda: _abi.QgNormDesc.make(33, 8), lambda: _abi.QgRolloutDesc.make(8, 4, 33, 12),
     lambda: _abi.QgRolloutStorage.make(), lambda: _abi.QgRolloutStep.make(done_stride=1), lambda: _abi.QgRolloutBatch.make(),
-    lambda: _abi.QgPerturbDesc.make(8, 33), lambda: _abi.QgContactDesc.make(1.5)],
+    lambda: _abi.QgPerturbDesc.make(8, 33), lambda: _abi.QgContactDesc.make(1.5), lambda: _abi.QgGaitDesc.make()],
     ids=["policy_desc", "ppo_params", "ppo_batch", "adam_params", "norm_desc", "rollout_desc", "rollout_storage", "rollout_step",
-         "rollout_batch", "perturb_desc", "contact_desc"])
+         "rollout_batch", "perturb_desc", "contact_desc", "gait_desc"])
 def test_make_fills_struct_size(make):
     d = make()
     assert isinstance(d, _abi._Sized) and d.struct_size == C.sizeof(type(d)) > 0
@@ -83,6 +87,96 @@ def test_make_keeps_each_structs_own_conversions():
     p = _abi.QgPerturbDesc.make(8, 26, window=5, delays=(1, 3), max_delay=3, obs_std=[0.5], seed=-1)
     assert (p.n_envs, p.frame_dim, p.window, p.delay_lo, p.delay_hi, p.obs_std[0], p.obs_std[1], p.seed) == (8, 26, 5, 1, 3, 0.5, 0.0, 2**64 - 1)
     assert _abi.QgContactDesc.make(2).force_threshold == 2.0
+    g = _abi.QgGaitDesc.make(range(1, 8), 0.25, 0.5, 20, 0.125)              # weights in GAIT_TERMS order, the four thresholds
+    assert (list(g.weights), g.air_time_target, g.clearance_target, g.max_contact_force, g.min_command_speed, g.reserved) == (
+        [1, 2, 3, 4, 5, 6, 7], 0.25, 0.5, 20.0, 0.125, 0) and len(g.weights) == len(_abi.GAIT_TERMS)
+
+
+# -- the one strided-rows check with a stub tensor: no device ------------------------------------------------------------------------
+class _StubTensor:
+    def __init__(self, shape, strides, dtype="float32", cuda=True, index=0):
+        import torch
+        self.shape, self._strides, self.dtype, self.is_cuda = tuple(shape), tuple(strides), getattr(torch, dtype), cuda
+        self.device = type("_Device", (), {"index": index})()
+
+    def dim(self):
+        return len(self.shape)
+
+    def stride(self, k=None):
+        return self._strides if k is None else self._strides[k]
+
+
+def _stub_handle():
+    h = object.__new__(Handle)                          # no library handle: the checks read these three attributes only
+    h.device, h.num_envs, h.obs_dim = 0, 3, 5
+    return h
+
+
+@pytest.mark.parametrize("shape, strides, want", [((3, 5), (5, 1), 5), ((3, 5), (8, 1), 8), ((1, 5), (0, 1), 5), ((3, 1), (2, 2), 2)],
+                         ids=["contiguous", "column_slice", "one_row", "width_one_strided"])
+def test_check_rows_accepts_strided_rows_and_returns_the_stride(shape, strides, want):
+    h = _stub_handle()
+    t = _StubTensor(shape, strides)
+    assert h._check_rows(t, shape[1], "x", rows=shape[0]) == want
+    if shape[0] == h.num_envs:
+        assert h._check_rows(t, shape[1], "x") == want                     # rows defaults to num_envs
+    assert h._check_rows(t, shape[1], "x", rows=Handle.ANY_ROWS) == want
+
+
+@pytest.mark.parametrize("tensor, message", [
+    (_StubTensor((3, 5), (5, 1), cuda=False), "x must live on cuda:0"),
+    (_StubTensor((3, 5), (5, 1), index=1), "x must live on cuda:0"),
+    (_StubTensor((3, 5), (5, 1), dtype="float64"), "x: expected a float32 tensor of shape (3, 5), got torch.float64 (3, 5)"),
+    (_StubTensor((15,), (1,)), "x: expected a float32 tensor of shape (3, 5), got torch.float32 (15,)"),
+    (_StubTensor((3, 5, 1), (5, 1, 1)), "x: expected a float32 tensor of shape (3, 5), got torch.float32 (3, 5, 1)"),
+    (_StubTensor((4, 5), (5, 1)), "x: expected a float32 tensor of shape (3, 5), got torch.float32 (4, 5)"),
+    (_StubTensor((3, 4), (4, 1)), "x: expected a float32 tensor of shape (3, 5), got torch.float32 (3, 4)"),
+    (_StubTensor((3, 5), (4, 1)), "x: rows must be contiguous, at a row stride >= 5; got strides (4, 1)"),
+    (_StubTensor((3, 5), (1, 3)), "x: rows must be contiguous, at a row stride >= 5; got strides (1, 3)"),
+    (_StubTensor((3, 5), (0, 1)), "x: rows must be contiguous, at a row stride >= 5; got strides (0, 1)")],
+    ids=["not_cuda", "other_device", "float64", "one_dim", "three_dim", "row_count", "width", "rows_overlap", "transposed", "expanded"])
+def test_check_rows_refuses_with_the_three_message_shapes(tensor, message):
+    with pytest.raises(ValueError) as err:
+        _stub_handle()._check_rows(tensor, 5, "x")
+    assert str(err.value) == message
+
+
+def test_check_obs_is_check_rows_at_obs_dim():
+    h = _stub_handle()
+    assert h._check_obs(_StubTensor((3, 5), (8, 1))) == (3, 8) == h._check_obs(_StubTensor((3, 5), (8, 1)), 3)
+    assert h._check_obs(_StubTensor((7, 5), (5, 1))) == (7, 5) and h._check_obs(_StubTensor((1, 5), (0, 1))) == (1, 5)     # any n >= 1
+    for bad, n, message in ((_StubTensor((7, 5), (5, 1)), 3, "next_obs: expected a float32 tensor of shape (3, 5), got torch.float32 (7, 5)"),
+                            (_StubTensor((0, 5), (5, 1)), None, "next_obs: expected a float32 tensor of shape (n, 5), got torch.float32 (0, 5)"),
+                            (_StubTensor((3, 5), (5, 2)), None, "next_obs: rows must be contiguous, at a row stride >= 5; got strides (5, 2)")):
+        with pytest.raises(ValueError) as err:
+            h._check_obs(bad, n, "next_obs")
+        assert str(err.value) == message
+    h.obs_dim = 1                                       # the widened case: a single column has no inner stride to violate
+    assert h._check_obs(_StubTensor((3, 1), (2, 2))) == (3, 2)
+
+
+# -- the layers' C code -------------------------------------------------------------------------------------------------------------------
+def test_layer_helpers_exist_once():
+    """The f64 moments (Chan's merge, the shifted-sums finish), the finite test of a double and the lifetime of a host staging buffer
+    are text of qg_moments_dev.h and qg_host.h, not a copy per layer: each fragment occurs there only, among the .hip / .h / .inc files
+    of csrc/.  A copy that has to stay for its listing's sake (tools/asm_diff.py) would be named here with its reason: there is none."""
+    csrc = os.path.join(_abi.package_dir(), "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".inc"))}
+
+    def files(pattern):
+        return [f for f, t in text.items() if re.search(pattern, t)]
+
+    # Chan's merge and the finish of the shifted sums
+    assert files(re.escape("d * d * na * f")) == ["qg_moments_dev.h"] == files(re.escape("s2 - s1 * s1 / cnt"))
+    assert files(re.escape('#include "qg_moments_dev.h"')) == ["qg_monitor.hip", "qg_norm.hip"]
+    # the exponent test of a double
+    assert files(re.escape("0x7ff) != 0x7ff")) == ["qg_host.h"]
+    # host staging buffers are QgHostBuf's: no translation unit allocates or frees one by hand (qg_resident_free( is a function's name)
+    for pattern in (r"new \(std::nothrow\) [^;(]*\[", r"delete\s*\[\]", r"(?<![A-Za-z0-9_])malloc\(", r"(?<![A-Za-z0-9_])free\("):
+        assert [f for f in files(pattern) if f.endswith(".hip")] == [], pattern
+    assert files(r"new \(std::nothrow\) [^;(]*\[") == ["qg_host.h"] == files(r"delete\s*\[\]")
+    # one alignment test
+    assert files(r"rollout_aligned|qga_aligned16|\(uintptr_t\)feet & 15") == []
 
 
 # -- the wrappers' base with a stub env: no library call -------------------------------------------------------------------------------
