@@ -560,6 +560,23 @@ int qg_policy_forward_device(qg_policy *policy, int32_t n, const float *obs, int
  * and A/B timing read it to know which instantiation ran.  Host only, launches nothing. */
 int qg_policy_launch_shape(const qg_policy *policy, int32_t n, int32_t with_value, int32_t *waves, int32_t *blocks);
 
+/* ---- asymmetric actor-critic: a critic window ---------------------------------------------------------------------------------------------
+ * A handle of qg_policy_create_asym reads TWO windows of an observation row: the actor columns [0, obs_dim) as ever, the critic columns
+ * [critic_obs_offset, critic_obs_offset + critic_obs_dim) of the same row -- the joint row of qg_priv_read_device, for one:
+ * (0, O + 85) shows the critic everything, (O, 85) the clean privileged state alone.
+ *   value = critic(obs[i * obs_stride + critic_obs_offset .. + critic_obs_dim)),  and the v of qg_policy_ppo_grad_device likewise.
+ * The canonical vector keeps its order; the critic's first layer is W[hidden[0]][critic_obs_dim].  Every entry point that takes a
+ * qg_policy takes such a handle; the stride rule becomes obs_stride >= obs_dim where the critic is not launched (a forward pass without
+ * a value buffer) and obs_stride >= max(obs_dim, critic_obs_offset + critic_obs_dim) where it is (a forward pass with one, every
+ * qg_policy_ppo_grad_device).  A handle of qg_policy_create has the window (0, obs_dim) and computes what it always has, bit for bit.
+ * QG_ERR_ARG, before the device check: desc->has_value != 1; critic_obs_dim outside 1 .. 512; critic_obs_offset < 0 or
+ * critic_obs_offset + critic_obs_dim > 512; an invalid description. */
+int qg_policy_create_asym(int32_t device_id, const qg_policy_desc *desc, int32_t critic_obs_offset, int32_t critic_obs_dim, qg_policy **out);
+/* Length of the canonical flat vector of such a handle (the offset does not enter), or QG_ERR_ARG.  Host only. */
+int qg_policy_param_count_asym(const qg_policy_desc *desc, int32_t critic_obs_dim);
+/* The critic's window; (0, obs_dim) for the handles of qg_policy_create, with or without a critic tower.  Host only. */
+int qg_policy_critic_window(const qg_policy *policy, int32_t *offset, int32_t *dim);
+
 /* ---- the PPO loss and its gradient for a qg_policy (one minibatch of SB3 2.x PPO.train) ------------------------------------------------
  * With c = clip_range, cv = clip_range_vf, sigma = exp(log_std), per row of the batch:
  *   mean = actor(obs)  (tanh on it when out_tanh);  z_a = (action_a - mean_a) / sigma_a
@@ -1162,6 +1179,70 @@ int qg_gait_reward_device(qg_gait *gait, const void *done, int32_t done_kind, in
                         int32_t reward_stride, float *reward_out, int32_t reward_out_stride, float *components, int32_t components_stride,
                         const float *base_components, int32_t base_stride, int32_t base_terms, const float *command,
                         int32_t command_stride, float *body_force, float *feet, void *stream);
+
+/* ---- privileged state pack: the simulator's truth as the input row of an asymmetric critic -----------------------------------------------
+ * A qg_priv is bound to a simulator and only READS its state arrays: it adds no step kernel and changes none.  One launch
+ * (qg_priv_read_device) writes, for every env i, the joint row
+ *   out[i] = [ obs[i][0 : obs_dim]  |  QG_PRIV_DIM privileged columns ]
+ * the observation an actor sees (noisy, lagged, stacked: whatever the caller's obs rows hold) copied bit for bit in front, and behind
+ * it the state the sensors do not show, evaluated at (qpos, qvel, act, nstep, episode) AS THEY STAND IN MEMORY -- after an auto-reset
+ * the row describes the new episode's first state.  With R0 = R(qpos[3:7] / |qpos[3:7]|), formed as the contact sensor forms it:
+ *   cols   name          definition
+ *   0-2    base_lin_vel  R0^T qvel[0:3]                     (the unlagged velocimeter)
+ *   3-5    base_ang_vel  qvel[3:6], bit copy
+ *   6-8    gravity_dir   R0^T (0, 0, -1): the negated third row of R0
+ *   9      base_height   qpos[2], bit copy
+ *   10-21  joint_pos     qpos[7:19], bit copy
+ *   22-33  joint_vel     qvel[6:18], bit copy
+ *   34-45  act           the 12 servo activation states, bit copy
+ *   46-49  foot_contact  F[foot f].z > force_threshold as 0.0 / 1.0 (bodies 3, 6, 9, 12)
+ *   50-61  foot_force    F[foot f], world xyz, foot-major
+ *   62-65  foot_height   x_foot.z (the sensor's QG_FOOT_POS z)
+ *   66     body_contact  the number of the 9 non-foot bodies with F_b.z > force_threshold, as f32
+ *   67-77  dynamics      the env's QG_NDYN row, bit copy; the identity row while per-env dynamics are off
+ *   78-83  frame_wrench  the FRAME's xfrc row (force, torque) plus the push schedule's force for env-step s = nstep / frame_skip of the
+ *                        key (seed, env_index_base + i, episode): the wrench the NEXT env-step applies to the FRAME; zeros while wrench
+ *                        mode is off
+ *   84     episode_time  f32(nstep) * f32(model.timestep), one rounding
+ * F[b], x_b and the threshold comparison are the contact sensor's, computed by the same device code: columns 46-65 are bit for bit what
+ * qg_contact_read_device(advance = 0) with the same threshold reports for that state (and the force is the one the next substep
+ * applies).  The push is drawn by the device function the step kernels draw it with, from the schedule as it stands in device memory.
+ *
+ * ONE kernel launch on the caller's stream behind the step whose state it is to see, no allocation, no wait, no LDS, no atomics;
+ * capturable, and bit-reproducible eagerly and under graph replay; rows depend on their env alone, so a handle of any size computes
+ * the same bits for a state.  Only the caller's rows are written.  Refused while the resident step mode is on (qg_resident_stop
+ * first); every refusal is QG_ERR_ARG and comes before anything is launched.  The handle has no per-env state (nothing to snapshot);
+ * destroy the qg_priv before its simulator. */
+typedef struct qg_priv qg_priv;
+typedef struct qg_priv_desc {
+    int32_t struct_size;       /* sizeof(qg_priv_desc): checked */
+    int32_t reserved;          /* 0 */
+    float force_threshold;     /* N; finite, >= 0 */
+} qg_priv_desc;
+#define QG_PRIV_DIM 85
+#define QG_PRIV_BASE_LIN_VEL 0
+#define QG_PRIV_BASE_ANG_VEL 3
+#define QG_PRIV_GRAVITY_DIR 6
+#define QG_PRIV_BASE_HEIGHT 9
+#define QG_PRIV_JOINT_POS 10
+#define QG_PRIV_JOINT_VEL 22
+#define QG_PRIV_ACT 34
+#define QG_PRIV_FOOT_CONTACT 46
+#define QG_PRIV_FOOT_FORCE 50
+#define QG_PRIV_FOOT_HEIGHT 62
+#define QG_PRIV_BODY_CONTACT 66
+#define QG_PRIV_DYNAMICS 67
+#define QG_PRIV_FRAME_WRENCH 78
+#define QG_PRIV_EPISODE_TIME 84
+int qg_priv_create(qg_sim *sim, const qg_priv_desc *desc, qg_priv **out);
+int qg_priv_destroy(qg_priv *priv);
+/* obs: nullable [n] rows of obs_dim floats at obs_stride >= obs_dim, copied bit for bit to out[i][0 : obs_dim] (obs == NULL: obs_dim
+ * must be 0).  out: [n] rows at out_stride >= obs_dim + QG_PRIV_DIM; the 85 columns go to out[i][obs_dim : obs_dim + 85]; columns
+ * behind them are not written.  obs and out may not overlap.  The obs rows are copied with 16-byte accesses where obs_dim and both
+ * strides are multiples of 4 and both pointers are 16-byte aligned, element by element otherwise: the bits are the same. */
+int qg_priv_read_device(qg_priv *priv, const float *obs, int32_t obs_stride, int32_t obs_dim, float *out, int32_t out_stride, void *stream);
+/* Synchronous, into a host [n][QG_PRIV_DIM] array (no observation in front). */
+int qg_priv_read(qg_priv *priv, float *host_out);
 
 #ifdef __cplusplus
 }

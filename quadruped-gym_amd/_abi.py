@@ -340,6 +340,14 @@ class QgGaitDesc(_Sized):
         return d
 
 
+# the privileged state pack (qg_priv_*): ``qg_priv_desc`` has the fields of ``qg_contact_desc`` and shares its mirror, ``QgContactDesc``;
+# the privileged columns as (name, first column, width) in column order (QG_PRIV_* of include/quadgym.h)
+PRIV_COLUMNS = (("base_lin_vel", 0, 3), ("base_ang_vel", 3, 3), ("gravity_dir", 6, 3), ("base_height", 9, 1), ("joint_pos", 10, 12),
+                ("joint_vel", 22, 12), ("act", 34, 12), ("foot_contact", 46, 4), ("foot_force", 50, 12), ("foot_height", 62, 4),
+                ("body_contact", 66, 1), ("dynamics", 67, NDYN), ("frame_wrench", 78, 6), ("episode_time", 84, 1))
+PRIV_DIM = 85
+
+
 def package_dir() -> str:
     return os.path.dirname(os.path.abspath(__file__))
 
@@ -442,6 +450,9 @@ PROTOTYPES = {
     "qg_policy_set_params_device": [_vp, _vp, _vp],
     "qg_policy_forward_device": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "qg_policy_launch_shape": [_vp, _i32, _i32, _P(_i32), _P(_i32)],
+    "qg_policy_create_asym": [_i32, _P(QgPolicyDesc), _i32, _i32, _P(_vp)],
+    "qg_policy_param_count_asym": [_P(QgPolicyDesc), _i32],
+    "qg_policy_critic_window": [_vp, _P(_i32), _P(_i32)],
     "qg_policy_reserve_grad": [_vp, _i32],
     "qg_policy_ppo_grad_device": [_vp, _P(QgPpoParams), _i32, _P(QgPpoBatch), _vp, _vp, _vp],
     "qg_policy_reserve_adam": [_vp],
@@ -498,6 +509,11 @@ PROTOTYPES = {
     "qg_gait_destroy": [_vp],
     "qg_gait_set_weights": [_vp, _P(C.c_float)],
     "qg_gait_reward_device": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp],
+    # the privileged state pack
+    "qg_priv_create": [_vp, _P(QgContactDesc), _P(_vp)],       # (qg_priv_desc: the layout of qg_contact_desc)
+    "qg_priv_destroy": [_vp],
+    "qg_priv_read_device": [_vp, _vp, _i32, _i32, _vp, _i32, _vp],
+    "qg_priv_read": [_vp, _vp],
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -1,7 +1,8 @@
 // qg_contact_dev.h -- the device code of foot-contact sensing (include/quadgym.h: qg_contact_*) and the qg_contact handle,
-// shared by the two kernels that evaluate it: qg_contact_kernel (qg_contact.hip, the sensor's read) and qg_gait_kernel (qg_gait.hip, the
-// same read with the gait-shaped reward terms reduced behind it in the same launch).  Internal: not installed, nothing in here is
-// exported.  Same text, same arithmetic, same rounding in both kernels: the gait launch reports the sensor's bits.
+// shared by the kernels that evaluate it: qg_contact_kernel (qg_contact.hip, the sensor's read), qg_gait_kernel (qg_gait.hip, the same
+// read with the gait-shaped reward terms reduced behind it in the same launch) and qg_priv_kernel (qg_priv.hip, the forces and foot
+// heights of the privileged state pack).  Internal: not installed, nothing in here is
+// exported.  Same text, same arithmetic, same rounding in every kernel: the gait launch reports the sensor's bits.
 //
 // Layout of a wave.  The work is latency-bound (about 150 B in and 350 B out per env), so the launch is shaped like the headline
 // step's: one body per lane, 16 lanes per env (13 working, 3 idle), 4 envs per wave -- 4096 envs are 1024 waves, one per SIMD.  Every
@@ -61,6 +62,16 @@ __device__ __forceinline__ void qgc_cross(const float *a, const float *b, float 
     out[2] = a[0] * b[1] - a[1] * b[0];
 }
 
+// R0 = R(qpos[3:7] / |qpos[3:7]|) of env e, row-major: the FRAME's orientation (also what the privileged state pack rotates with)
+__device__ __forceinline__ void qgc_frame_rot(const float *__restrict__ sq /* [19][n] */, size_t n, size_t e, float *R) {
+    float qw = qgc_at(sq, 3, n, e), qx = qgc_at(sq, 4, n, e), qy = qgc_at(sq, 5, n, e), qz = qgc_at(sq, 6, n, e);
+    const float inv = 1.0f / sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+    qw *= inv, qx *= inv, qy *= inv, qz *= inv;
+    R[0] = 1.f - 2.f * (qy * qy + qz * qz); R[1] = 2.f * (qx * qy - qw * qz);       R[2] = 2.f * (qx * qz + qw * qy);
+    R[3] = 2.f * (qx * qy + qw * qz);       R[4] = 1.f - 2.f * (qx * qx + qz * qz); R[5] = 2.f * (qy * qz - qw * qx);
+    R[6] = 2.f * (qx * qz - qw * qy);       R[7] = 2.f * (qy * qz + qw * qx);       R[8] = 1.f - 2.f * (qx * qx + qy * qy);
+}
+
 // Body b (0 .. QG_NBODY - 1) of env e: the world position x and velocity v of its frame origin and the ground reaction force F on it.
 // DYN: friction and the contact stiffness / damping scales come from the env's dynamics row ([QG_NDYN][n]).  Reads only; crosses no lane.
 template <bool DYN>
@@ -69,12 +80,7 @@ __device__ __forceinline__ void qgc_body(const KModel *__restrict__ M, const flo
     // ---- the FRAME ------------------------------------------------------------------------------------------------------------------
     float R[9], w[3];
     {
-        float qw = qgc_at(sq, 3, n, e), qx = qgc_at(sq, 4, n, e), qy = qgc_at(sq, 5, n, e), qz = qgc_at(sq, 6, n, e);
-        const float inv = 1.0f / sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-        qw *= inv, qx *= inv, qy *= inv, qz *= inv;
-        R[0] = 1.f - 2.f * (qy * qy + qz * qz); R[1] = 2.f * (qx * qy - qw * qz);       R[2] = 2.f * (qx * qz + qw * qy);
-        R[3] = 2.f * (qx * qy + qw * qz);       R[4] = 1.f - 2.f * (qx * qx + qz * qz); R[5] = 2.f * (qy * qz - qw * qx);
-        R[6] = 2.f * (qx * qz - qw * qy);       R[7] = 2.f * (qy * qz + qw * qx);       R[8] = 1.f - 2.f * (qx * qx + qy * qy);
+        qgc_frame_rot(sq, n, e, R);
         const float wl[3] = {qgc_at(sv, 3, n, e), qgc_at(sv, 4, n, e), qgc_at(sv, 5, n, e)};
         qgc_rot(R, wl, w);
         for (int d = 0; d < 3; ++d) x[d] = qgc_at(sq, d, n, e), v[d] = qgc_at(sv, d, n, e);

@@ -164,13 +164,6 @@ extern "C" int qg_gait_set_weights(qg_gait *g, const float *weights) {
     return QG_OK;
 }
 
-// [n] rows of `width` floats at `stride`: the float range they span
-static inline bool gait_rows_overlap(const float *a, int64_t a_stride, int a_width, const float *b, int64_t b_stride, int b_width, int64_t n) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = (uintptr_t)(a + (n - 1) * a_stride + a_width);
-    const uintptr_t b0 = (uintptr_t)b, b1 = (uintptr_t)(b + (n - 1) * b_stride + b_width);
-    return a0 < b1 && b0 < a1;
-}
-
 extern "C" int qg_gait_reward_device(qg_gait *g, const void *done, int32_t done_kind, int32_t done_stride, int32_t advance, const float *reward,
                                    int32_t reward_stride, float *reward_out, int32_t reward_out_stride, float *components,
                                    int32_t components_stride, const float *base_components, int32_t base_stride, int32_t base_terms,
@@ -197,7 +190,7 @@ extern "C" int qg_gait_reward_device(qg_gait *g, const void *done, int32_t done_
     // another one writes
     const bool in_place = base_components && base_components == components && base_stride == components_stride;
     if (base_components && base_terms > 0 && !in_place &&
-        gait_rows_overlap(base_components, base_stride, base_terms, components, components_stride, base_terms + QG_GAIT_NTERMS, s->n))
+        qg_rows_overlap(base_components, base_stride, base_terms, components, components_stride, base_terms + QG_GAIT_NTERMS, s->n))
         return fail(QG_ERR_ARG, "%s: base_components and components overlap (allowed only as the first base_terms columns of the same rows)", who);
     if (s->res.active) return fail(QG_ERR_ARG, "%s: the resident step mode is on, the state lives in registers (qg_resident_stop first)", who);
 

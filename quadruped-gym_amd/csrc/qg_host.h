@@ -47,6 +47,13 @@ static inline bool qg_finite64(double x) {
 // `p` sits at a multiple of `a` bytes (NULL does)
 __host__ __device__ static inline bool qg_aligned(const void *p, size_t a) { return ((uintptr_t)p) % a == 0; }
 
+// [n] rows of `a_width` floats at `a_stride` and [n] rows of `b_width` floats at `b_stride`: the float ranges they span intersect
+static inline bool qg_rows_overlap(const float *a, int64_t a_stride, int a_width, const float *b, int64_t b_stride, int b_width, int64_t n) {
+    const uintptr_t a0 = (uintptr_t)a, a1 = (uintptr_t)(a + (n - 1) * a_stride + a_width);
+    const uintptr_t b0 = (uintptr_t)b, b1 = (uintptr_t)(b + (n - 1) * b_stride + b_width);
+    return a0 < b1 && b0 < a1;
+}
+
 // A host staging buffer of `count` elements that frees itself on every return path.  Nothing throws: a failed allocation leaves NULL,
 // which oom() turns into the library's status.
 template <class T> struct QgHostBuf {

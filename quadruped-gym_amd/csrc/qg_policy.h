@@ -24,6 +24,9 @@ struct KPolicy {
     int32_t packed_floats;
     int32_t lds0_floats, lds1_floats;   // the two activation buffers (layer l reads buffer l & 1, writes the other)
     KPolLayer layer[2][QGP_MAX_LAYERS];
+    int32_t critic_off;           // the critic's window: it reads columns [critic_off, critic_off + layer[1][0].in_dim) of a row (the
+                                  // actor [0, obs_dim)); 0 and obs_dim on a handle of qg_policy_create.  Behind the table: what the
+                                  // actor's launches read keeps its place in the kernel arguments
 };
 
 typedef float qgp_f32x4 __attribute__((ext_vector_type(4)));
@@ -75,6 +78,13 @@ struct qg_policy {
     long long *d_adam_t;      // the step count, in device memory: a captured step replays as t = 1, 2, 3, ..
     double *d_adam_partial;   // [adam_slots] sums of squares of the gradient
 };
+
+// the columns of an observation row the handle's launches read: obs_dim where the critic is not launched, else the farther end of
+// the two towers' windows
+static inline int32_t qg_policy_row_width(const qg_policy *p, bool with_critic) {
+    const int32_t end = (with_critic && p->k.n_towers == 2) ? p->k.critic_off + p->k.layer[1][0].in_dim : 0;
+    return end > p->desc.obs_dim ? end : p->desc.obs_dim;
+}
 
 // the transposed image from the canonical vector, on `st`; a no-op before qg_policy_reserve_grad (qg_policy_grad.hip)
 int qg_policy_pack_transposed(qg_policy *p, hipStream_t st);

@@ -135,6 +135,8 @@ __global__ __launch_bounds__(64 * WAVES) void qg_policy_forward_kernel(KPolicy P
         constexpr int R = QGP_TILE / WAVES;
         constexpr int JU = WAVES == 1 ? 1 : 4;
         const int width = 16 * P.layer[tower][0].nq;
+        // the tower's window of the row (wave-uniform): the actor's columns [0, obs_dim), the critic's [critic_off, .. + its input width)
+        const int in_dim = tower ? P.layer[1][0].in_dim : P.obs_dim, in_off = tower ? P.critic_off : 0;
         for (int c0 = lane; c0 < width + lane; c0 += 64 * JU) {
             float v[JU][R];
 #pragma unroll
@@ -142,14 +144,14 @@ __global__ __launch_bounds__(64 * WAVES) void qg_policy_forward_kernel(KPolicy P
 #pragma unroll
                 for (int r = 0; r < R; r++) {
                     const int env = env0 + wave + WAVES * r;
-                    v[ju][r] = obs[(size_t)min(env, n - 1) * obs_stride + min(c0 + 64 * ju, P.obs_dim - 1)];
+                    v[ju][r] = obs[(size_t)min(env, n - 1) * obs_stride + in_off + min(c0 + 64 * ju, in_dim - 1)];
                 }
 #pragma unroll
             for (int ju = 0; ju < JU; ju++)
 #pragma unroll
                 for (int r = 0; r < R; r++) {
                     const int c = c0 + 64 * ju, ee = wave + WAVES * r;
-                    if (c < width) x0[((c >> 2) * 16 + ee) * 4 + (c & 3)] = (c < P.obs_dim && env0 + ee < n) ? v[ju][r] : 0.f;
+                    if (c < width) x0[((c >> 2) * 16 + ee) * 4 + (c & 3)] = (c < in_dim && env0 + ee < n) ? v[ju][r] : 0.f;
                 }
         }
     }
@@ -224,8 +226,9 @@ __global__ __launch_bounds__(64 * WAVES) void qg_policy_forward_kernel(KPolicy P
 // ------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------
-// the description is valid: fills the kernel's layer table (offsets into both parameter images) and returns the canonical length
-static int policy_layout(const qg_policy_desc *d, KPolicy *k) {
+// the description is valid: fills the kernel's layer table (offsets into both parameter images) and returns the canonical length.
+// critic_dim < 0: the critic reads the actor's columns (qg_policy_create); else its window (qg_policy_create_asym)
+static int policy_layout(const qg_policy_desc *d, KPolicy *k, int32_t critic_off = 0, int32_t critic_dim = -1) {
     if (!d) return fail(QG_ERR_ARG, "qg_policy: null description");
     QG_CHECK_STRUCT(d, qg_policy_desc);
     if (d->obs_dim < 1 || d->obs_dim > 512) return fail(QG_ERR_ARG, "qg_policy: obs_dim %d outside 1 .. 512", d->obs_dim);
@@ -236,16 +239,26 @@ static int policy_layout(const qg_policy_desc *d, KPolicy *k) {
             return fail(QG_ERR_ARG, "qg_policy: hidden[%d] = %d (a multiple of 16, 16 .. 256; tanh layers only)", i, d->hidden[i]);
     if ((d->out_tanh != 0 && d->out_tanh != 1) || (d->has_value != 0 && d->has_value != 1))
         return fail(QG_ERR_ARG, "qg_policy: out_tanh and has_value are 0 or 1");
+    if (critic_dim >= 0) {
+        if (!d->has_value) return fail(QG_ERR_ARG, "qg_policy: a critic window, but has_value is 0");
+        if (critic_dim < 1 || critic_dim > 512) return fail(QG_ERR_ARG, "qg_policy: critic_obs_dim %d outside 1 .. 512", critic_dim);
+        if (critic_off < 0 || critic_off > 512 - critic_dim)
+            return fail(QG_ERR_ARG, "qg_policy: critic_obs_offset %d: the window must lie in columns 0 .. 512 (offset + dim = %lld)", critic_off,
+                        (long long)critic_off + critic_dim);
+    } else {
+        critic_off = 0, critic_dim = d->obs_dim;
+    }
     KPolicy p;
     memset(&p, 0, sizeof p);
     p.obs_dim = d->obs_dim;
+    p.critic_off = critic_off;
     p.act_dim = d->act_dim;
     p.n_layers = d->n_hidden + 1;
     p.out_tanh = d->out_tanh;
     p.n_towers = d->has_value ? 2 : 1;
     int src = 0, dst = 0;
     for (int t = 0; t < p.n_towers; t++) {
-        int in = d->obs_dim;
+        int in = t == 0 ? d->obs_dim : critic_dim;
         for (int l = 0; l < p.n_layers; l++) {
             const int out = l < d->n_hidden ? d->hidden[l] : (t == 0 ? d->act_dim : 1);
             KPolLayer &L = p.layer[t][l];
@@ -270,6 +283,7 @@ static int policy_layout(const qg_policy_desc *d, KPolicy *k) {
     p.packed_floats = dst + 32;
     // activation buffers, floats (16 envs per feature): layer l reads buffer l & 1 and writes the other
     int f0 = 16 * p.layer[0][0].nq, f1 = d->hidden[0];
+    if (p.n_towers == 2 && 16 * p.layer[1][0].nq > f0) f0 = 16 * p.layer[1][0].nq;      // the wider of the two towers' first layers
     if (d->n_hidden > 1 && d->hidden[1] > f0) f0 = d->hidden[1];
     if (d->n_hidden > 2 && d->hidden[2] > f1) f1 = d->hidden[2];
     p.lds0_floats = 16 * f0;
@@ -279,6 +293,10 @@ static int policy_layout(const qg_policy_desc *d, KPolicy *k) {
 }
 
 extern "C" int qg_policy_param_count(const qg_policy_desc *desc) { return policy_layout(desc, nullptr); }
+extern "C" int qg_policy_param_count_asym(const qg_policy_desc *desc, int32_t critic_obs_dim) {
+    if (critic_obs_dim < 0) return fail(QG_ERR_ARG, "qg_policy: critic_obs_dim %d outside 1 .. 512", critic_obs_dim);
+    return policy_layout(desc, nullptr, 0, critic_obs_dim);
+}
 
 extern "C" int qg_policy_destroy(qg_policy *p) {
     if (p) qg_free_handle(p, p->device);           // forward passes may still be in flight on a caller's stream
@@ -292,11 +310,11 @@ static int policy_pack(qg_policy *p, hipStream_t st) {
     return qg_policy_pack_transposed(p, st);       // the gradient pass's image, once qg_policy_reserve_grad has been called
 }
 
-extern "C" int qg_policy_create(int32_t device_id, const qg_policy_desc *desc, qg_policy **out) {
+static int policy_create(int32_t device_id, const qg_policy_desc *desc, int32_t critic_off, int32_t critic_dim, qg_policy **out) {
     if (!out) return fail(QG_ERR_ARG, "qg_policy_create: null output");
     *out = nullptr;
     KPolicy k;
-    const int count = policy_layout(desc, &k);
+    const int count = policy_layout(desc, &k, critic_off, critic_dim);
     if (count < 0) return count;
     int simds;
     QG_TRY(qg_open_device(device_id, &simds));
@@ -319,6 +337,26 @@ extern "C" int qg_policy_create(int32_t device_id, const qg_policy_desc *desc, q
         return rc;
     }
     *out = p;
+    return QG_OK;
+}
+
+extern "C" int qg_policy_create(int32_t device_id, const qg_policy_desc *desc, qg_policy **out) {
+    return policy_create(device_id, desc, 0, -1, out);
+}
+
+extern "C" int qg_policy_create_asym(int32_t device_id, const qg_policy_desc *desc, int32_t critic_obs_offset, int32_t critic_obs_dim,
+                                     qg_policy **out) {
+    if (critic_obs_dim < 0) {
+        if (out) *out = nullptr;
+        return fail(QG_ERR_ARG, "qg_policy: critic_obs_dim %d outside 1 .. 512", critic_obs_dim);
+    }
+    return policy_create(device_id, desc, critic_obs_offset, critic_obs_dim, out);
+}
+
+extern "C" int qg_policy_critic_window(const qg_policy *p, int32_t *offset, int32_t *dim) {
+    if (!p || !offset || !dim) return fail(QG_ERR_ARG, "qg_policy_critic_window: null argument");
+    *offset = p->k.critic_off;
+    *dim = p->k.n_towers == 2 ? p->k.layer[1][0].in_dim : p->desc.obs_dim;
     return QG_OK;
 }
 
@@ -382,6 +420,8 @@ extern "C" int qg_policy_forward_device(qg_policy *p, int32_t n, const float *ob
     if (n < 1) return fail(QG_ERR_ARG, "qg_policy_forward_device: n must be >= 1");
     if (obs_stride < p->desc.obs_dim) return fail(QG_ERR_ARG, "qg_policy_forward_device: obs_stride %d < obs_dim %d", obs_stride, p->desc.obs_dim);
     if (value && !p->desc.has_value) return fail(QG_ERR_ARG, "qg_policy_forward_device: a value buffer, but the policy has no critic tower");
+    if (obs_stride < qg_policy_row_width(p, value != nullptr))
+        return fail(QG_ERR_ARG, "qg_policy_forward_device: obs_stride %d < %d, the end of the critic's window", obs_stride, qg_policy_row_width(p, true));
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     const hipStream_t st = (hipStream_t)stream;
     int32_t waves, blocks;

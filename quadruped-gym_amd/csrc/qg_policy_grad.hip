@@ -103,10 +103,11 @@ __global__ __launch_bounds__(64 * QGG_WAVES) void qg_policy_grad_rows_kernel(KPo
     // the observation tile, zero padded, into buffer 0 in the operand image (as the forward pass) and into the records
     {
         const int width = 16 * P.layer[tower][0].nq;
+        const int in_dim = tower ? P.layer[1][0].in_dim : P.obs_dim, in_off = tower ? P.critic_off : 0;      // the tower's window of the row (wave-uniform)
         for (int idx = threadIdx.x; idx < QGP_TILE * width; idx += 64 * QGG_WAVES) {
             const int ee = idx / width, c = idx - ee * width;
             float v = 0.f;
-            if (c < P.obs_dim && row0 + ee < n) v = bt.obs[(size_t)(row0 + ee) * bt.obs_stride + c];
+            if (c < in_dim && row0 + ee < n) v = bt.obs[(size_t)(row0 + ee) * bt.obs_stride + in_off + c];
             x0[((c >> 2) * 16 + ee) * 4 + (c & 3)] = v;
             rec[(size_t)(row0 + ee) * G.rec + G.layer[tower][0].h_off + c] = v;
         }
@@ -424,6 +425,9 @@ extern "C" int qg_policy_ppo_grad_device(qg_policy *p, const qg_ppo_params *pp, 
         return fail(QG_ERR_ARG, "qg_policy_ppo_grad_device: B = %d, but qg_policy_reserve_grad has reserved %d rows", B, p->grad_max);
     if (bt->obs_stride < p->desc.obs_dim)
         return fail(QG_ERR_ARG, "qg_policy_ppo_grad_device: obs_stride %d < obs_dim %d", bt->obs_stride, p->desc.obs_dim);
+    if (bt->obs_stride < qg_policy_row_width(p, true))
+        return fail(QG_ERR_ARG, "qg_policy_ppo_grad_device: obs_stride %d < %d, the end of the critic's window", bt->obs_stride,
+                    qg_policy_row_width(p, true));
     if (!bt->obs || !bt->actions || !bt->old_log_prob || !bt->advantages) return fail(QG_ERR_ARG, "qg_ppo_batch: null obs, actions, old_log_prob or advantages");
     if (p->desc.has_value && (!bt->returns || (pp->clip_range_vf > 0.f && !bt->old_values)))
         return fail(QG_ERR_ARG, "qg_ppo_batch: the policy has a critic: returns (and old_values when clip_range_vf > 0) are required");

@@ -210,6 +210,20 @@ class BatchedEnvBase:
         if self._contact is not None:
             self._contact.reset(mask)
 
+    # -- the privileged state pack (privileged.py; include/quadgym.h: qg_priv_*) --------------------------------------------------------
+    _priv = None
+
+    def privileged_state(self, force_threshold: float = 0.0):
+        """The env's ``PrivilegedState`` (created at the first call): the joint row ``[observation | 85 privileged columns]`` of an
+        asymmetric critic in one launch, ``pack.read(out, obs)`` behind a ``step_tensor``.  It has no per-env state, so there is nothing
+        to reset or snapshot; ``close`` destroys it.  An env that never asks launches nothing."""
+        if self._priv is None:
+            from ..privileged import PrivilegedState
+            self._priv = PrivilegedState(self._sim, force_threshold)
+        elif float(force_threshold) != self._priv.force_threshold:
+            raise ValueError(f"this env's privileged state pack has force_threshold {self._priv.force_threshold}, not {float(force_threshold)}")
+        return self._priv
+
     # -- checkpoint / resume ----------------------------------------------------------------------------------------------------------
     def snapshot(self):
         """What every batched env keeps per robot, as a ``dict`` of NumPy arrays: the simulator's snapshot under ``"sim"`` and, where
@@ -249,6 +263,7 @@ class BatchedEnvBase:
             self._sim.close()
             self._sim = None
             self._contact = None
+            self._priv = None
 
     def seed(self, seed=None):
         self._seed = 0 if seed is None else int(seed)

@@ -57,6 +57,8 @@ def _sequential_layers(seq):
 class FusedMlpPolicy(Handle):
     """``obs_dim -> hidden[0] -> .. -> act_dim`` with tanh after every hidden layer; ``out_tanh`` puts a tanh on the action mean too
     (``False``: SB3's linear ``action_net``); ``value=True`` adds a critic tower with the same hidden sizes and one output.
+    ``critic_obs=(offset, dim)`` makes the pair asymmetric: the actor reads columns ``[0, obs_dim)`` of a row, the critic columns
+    ``[offset, offset + dim)`` of the same row (``privileged.py`` writes such rows), and its first layer is ``dim`` wide.
 
     Hidden widths are multiples of 16 up to 256, at most three of them; ``obs_dim <= 512``, ``act_dim <= 16``.  A new policy holds
     zeros; load parameters with ``load_layers`` / ``load_module`` / ``load_sb3_state_dict`` (host) or ``update_from`` (device,
@@ -70,32 +72,53 @@ class FusedMlpPolicy(Handle):
     # canonical elements per slot of ``adam_step``'s gradient norm: a workgroup sums the squares of that many consecutive elements in
     # float64, every workgroup of the update launch adds the slots in ascending order (QGA_SLOT of csrc/qg_policy.h)
     ADAM_SLOT = 2048
+    asymmetric = False          # the critic reads a window of its own (critic_obs=...)
+    _critic_obs = None
 
-    def __init__(self, obs_dim: int, hidden, act_dim: int, out_tanh: bool = False, value: bool = True, device: int = 0):
+    @property
+    def critic_obs(self):
+        """``(offset, dim)``: the columns of a row the critic reads; ``(0, obs_dim)`` unless the policy is asymmetric."""
+        return self._critic_obs if self._critic_obs is not None else (0, self.obs_dim)
+
+    def __init__(self, obs_dim: int, hidden, act_dim: int, out_tanh: bool = False, value: bool = True, device: int = 0, critic_obs=None):
         super().__init__(device)
         self.obs_dim, self.act_dim, self.hidden = int(obs_dim), int(act_dim), tuple(int(h) for h in hidden)
         self.out_tanh, self.has_value = bool(out_tanh), bool(value)
         if len(self.hidden) > 3:
             raise ValueError("at most three hidden layers")
         self.desc = QgPolicyDesc.make(self.obs_dim, self.hidden, self.act_dim, self.out_tanh, self.has_value)
-        self._create("qg_policy_create", self.device, C.byref(self.desc))
-        self.n_params = int(self._lib.qg_policy_param_count(C.byref(self.desc)))
+        if critic_obs is not None:
+            if not self.has_value:
+                raise ValueError("critic_obs: the policy was built with value=False")
+            off, dim = (int(x) for x in critic_obs)
+            self._create("qg_policy_create_asym", self.device, C.byref(self.desc), off, dim)
+            self.n_params = int(self._lib.qg_policy_param_count_asym(C.byref(self.desc), dim))
+        else:
+            self._create("qg_policy_create", self.device, C.byref(self.desc))
+            self.n_params = int(self._lib.qg_policy_param_count(C.byref(self.desc)))
+        off, dim = C.c_int32(), C.c_int32()
+        check(self._lib.qg_policy_critic_window(self._h, C.byref(off), C.byref(dim)), "qg_policy_critic_window")
+        self._critic_obs = (off.value, dim.value)
+        self.asymmetric = self._critic_obs != (0, self.obs_dim)     # the window (0, obs_dim) IS the symmetric policy, however it was asked for
 
     # -- parameters -------------------------------------------------------------------------
     def layer_shapes(self):
         """``(actor, critic)``: the ``(out, in)`` shapes of the weight matrices, in order."""
-        dims = (self.obs_dim,) + self.hidden
-        body = [(dims[i + 1], dims[i]) for i in range(len(self.hidden))]
-        return body + [(self.act_dim, dims[-1])], (body + [(1, dims[-1])] if self.has_value else [])
+        def body(first):
+            dims = (first,) + self.hidden
+            return [(dims[i + 1], dims[i]) for i in range(len(self.hidden))]
+        last = self.hidden[-1]
+        return body(self.obs_dim) + [(self.act_dim, last)], (body(self.critic_obs[1]) + [(1, last)] if self.has_value else [])
 
     @staticmethod
-    def param_layout(obs_dim, hidden, act_dim, value=True):
+    def param_layout(obs_dim, hidden, act_dim, value=True, critic_obs_dim=None):
         """``name -> (offset, shape)`` over the canonical flat vector of a policy of this description, in order: ``actor.0.weight``,
-        ``actor.0.bias``, .., ``log_std``, ``critic.0.weight``, ..  (``k`` counts the Linear layers of a tower).  Host arithmetic
-        only."""
-        dims = (int(obs_dim),) + tuple(int(h) for h in hidden)
+        ``actor.0.bias``, .., ``log_std``, ``critic.0.weight``, ..  (``k`` counts the Linear layers of a tower).  ``critic_obs_dim``:
+        the input width of an asymmetric critic (None: the actor's).  Host arithmetic only."""
+        hidden = tuple(int(h) for h in hidden)
         out, off = collections.OrderedDict(), 0
         for tower, last in (("actor", int(act_dim)), ("critic", 1))[:2 if value else 1]:
+            dims = (int(obs_dim if tower == "actor" or critic_obs_dim is None else critic_obs_dim),) + hidden
             for k, (i, o) in enumerate(zip(dims, dims[1:] + (last,))):
                 out[f"{tower}.{k}.weight"] = (off, (o, i))
                 out[f"{tower}.{k}.bias"] = (off + o * i, (o,))
@@ -108,7 +131,7 @@ class FusedMlpPolicy(Handle):
     def param_slices(self):
         """``param_layout`` of this policy: view ``params()``, a flat parameter tensor or the ``grad`` of ``ppo_grad`` per layer with
         ``flat[off:off + math.prod(shape)].view(shape)``."""
-        return self.param_layout(self.obs_dim, self.hidden, self.act_dim, self.has_value)
+        return self.param_layout(self.obs_dim, self.hidden, self.act_dim, self.has_value, self.critic_obs[1])
 
     def set_params(self, flat):
         """The canonical flat vector from the host (synchronous)."""
@@ -163,6 +186,8 @@ class FusedMlpPolicy(Handle):
         must be False."""
         if self.out_tanh:
             raise ValueError("SB3's action_net is linear: build the policy with out_tanh=False")
+        if self.asymmetric:
+            raise ValueError("SB3's ActorCriticPolicy has no asymmetric critic: load an asymmetric policy with load_layers / load_module")
 
         def tower(prefix, head):
             return [(sd[f"{prefix}.{2 * i}.weight"], sd[f"{prefix}.{2 * i}.bias"]) for i in range(len(self.hidden))] + \
@@ -172,6 +197,30 @@ class FusedMlpPolicy(Handle):
         self.load_layers(actor, sd["log_std"], critic)
 
     # -- device path ------------------------------------------------------------------------
+    def _check_obs(self, t, n=None, what="obs", with_critic=False):
+        """Rows of ``obs_dim`` columns at a row stride that reaches every column the launch reads: ``obs_dim`` where the critic is not
+        launched, else the farther end of the two windows (the same number on a symmetric policy).  The tensor itself may be the
+        actor's slice ``rows[:, :obs_dim]`` of wider rows, or the whole wide rows.  Returns ``(rows, row stride)``."""
+        need = max(self.obs_dim, sum(self.critic_obs)) if (with_critic and self.has_value) else self.obs_dim
+        shown = int(t.shape[1]) if t.dim() == 2 else 0      # the columns the caller's tensor itself vouches for
+        if t.dim() == 2 and t.shape[1] > self.obs_dim and self.asymmetric:
+            t = t[:, :self.obs_dim]                        # the wide rows: the same pointer and stride
+        n, stride = super()._check_obs(t, n, what)
+        if need > self.obs_dim:
+            # the critic reads behind the actor's columns.  Several rows show it by their stride (and the memory under the LAST row must
+            # be there too: a slice of wider rows shares their storage); a single row has no stride, so it must be the wide row itself
+            window = f"the critic reads columns {self.critic_obs[0]} .. {sum(self.critic_obs)} of a row"
+            if n == 1 and shown < need:
+                raise ValueError(f"{what}: {window}; one row of {shown} columns does not hold them: pass the wide row")
+            if n > 1 and stride < need:
+                raise ValueError(f"{what}: {window}; the row stride {stride} is shorter")
+            stride = max(stride, need)
+            have = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+            if have < (n - 1) * stride + need:
+                raise ValueError(f"{what}: {window}; the tensor's memory ends {(n - 1) * stride + need - have} floats before the last "
+                                 f"row's: pass the wide rows, or their slice [:, :{self.obs_dim}]")
+        return n, stride
+
     def update_from(self, params_tensor, stream=None):
         """The canonical flat vector from a device tensor, enqueued on ``stream`` (default: torch's current stream): forward passes
         enqueued later on that stream use it.  No host synchronisation."""
@@ -192,7 +241,7 @@ class FusedMlpPolicy(Handle):
         """One launch: ``actions[n, act_dim]`` (the mean, or ``mean + exp(log_std) * eps`` with standard-normal ``eps[n, act_dim]`` from
         the caller, not clipped), optionally ``log_prob[n]`` and ``value[n]``."""
         import torch
-        n, stride = self._check_obs(obs)
+        n, stride = self._check_obs(obs, with_critic=value is not None)
         self._check_tensor(actions, (n, self.act_dim), torch.float32)
         if eps is not None:
             self._check_tensor(eps, (n, self.act_dim), torch.float32)
@@ -220,7 +269,7 @@ class FusedMlpPolicy(Handle):
         attributes (``old_values`` / ``returns`` may be None without a critic; ``old_values`` also without value clipping);
         ``observations`` may be row-strided.  Advantages are used as given."""
         import torch
-        n, stride = self._check_obs(batch.observations, what="observations")
+        n, stride = self._check_obs(batch.observations, what="observations", with_critic=True)
         f32 = torch.float32
         self._check_tensor(batch.actions, (n, self.act_dim), f32, "actions")
         self._check_tensor(batch.old_log_prob, (n,), f32, "old_log_prob")
