@@ -632,6 +632,67 @@ int qg_policy_reserve_grad(qg_policy *policy, int32_t max_batch);
 int qg_policy_ppo_grad_device(qg_policy *policy, const qg_ppo_params *params, int32_t B, const qg_ppo_batch *batch, float *grad,
                               float *stats, void *stream);
 
+/* ---- teacher-student distillation: an imitation loss and its gradient for a qg_policy ---------------------------------------------------
+ * The student's action mean regressed onto given target means (a teacher's: what qg_policy_forward_device of the teacher's handle
+ * writes with eps = NULL), on rows the caller chooses -- in DAgger the rows the student itself visited.  Per row i of B rows, all in
+ * f64:
+ *   mu_i = actor(obs_i)  (tanh on it when out_tanh);  t_i = target_mean[i];  w_i = weights ? weights[i] : 1
+ *   QG_DISTILL_MSE:  l_i = sum_a (mu_i[a] - t_i[a])^2
+ *   QG_DISTILL_KL:   l_i = KL(N(t_i, exp(lt)) || N(mu_i, exp(ls)))
+ *                        = sum_a [ ls_a - lt_a + (exp(2 lt_a) + (t_i[a] - mu_i[a])^2) / (2 exp(2 ls_a)) - 1/2 ]
+ *                    ls the student's own log_std, lt = target_log_std [act_dim] in device memory (the teacher's log_std)
+ *   loss = coef / B sum_i w_i l_i
+ * The loss sums over the action dimensions (as the PPO log-probability does) and divides by B, NOT by sum_i w_i: a row of weight zero
+ * then contributes exact zeros to every sum, and no second pass over the rows is needed.
+ *
+ * grad [qg_policy_param_count] is d loss / d parameters in the canonical order, every element overwritten.  The heads:
+ *   d loss / d mu_i[a] = coef / B w_i 2 (mu - t)                     (MSE)       coef / B w_i (mu - t) / exp(2 ls_a)       (KL)
+ *   a factor 1 - mu^2 with out_tanh, each delta rounded to f32 once; then back through the tanh layers as qg_policy_ppo_grad_device.
+ *   d loss / d log_std_a = coef / B sum_i w_i (1 - (exp(2 lt_a) + (t - mu)^2) / exp(2 ls_a))   (KL);   exact +0.0   (MSE)
+ * The critic's entries of a handle that has a critic are exact +0.0 and the critic tower is not launched: handles with and without
+ * a critic and handles of qg_policy_create_asym are accepted alike, and only the actor's window [0, obs_dim) of a row is read
+ * (obs_stride >= obs_dim suffices).  stats (nullable, [8]): loss, sq_err = 1/B sum_i w_i sum_a (mu - t)^2 (both modes), kl = 1/B sum_i
+ * w_i l_i (KL mode; 0 in MSE mode), max_abs_err = max |mu - t| over the rows with w_i != 0 (0 when there is none), weight_sum =
+ * sum_i w_i (B without weights), 0, 0, 0 -- the sums in f64, each statistic rounded once.
+ *
+ * THREE launches, the pass of qg_policy_ppo_grad_device on the actor's tower with other heads, in the same scratch
+ * (qg_policy_reserve_grad; calls on one handle must be ordered by the caller).  Rounding order: the forward pass and the walk back
+ * as there (f32 products in chains of 16 on the matrix instruction, the chains, the bias and tanh in f64, rounded once).  A row's l_i:
+ * the actions 4g .. 4g + 3 in ascending order, then the four groups g by a fixed butterfly.  The scalar sums of a tile of 16 rows: the
+ * rows in ascending order.  dW and db: a tile's 16 rows are one f32 chain in ascending row order from zero, the 32 tiles of a slot
+ * of 512 rows are added in ascending order in f64 and rounded once, the slots in ascending order in f64 and rounded once.  No
+ * floating-point atomics, no workgroup waits for another, and the partition depends on B alone: the same inputs give the same bits
+ * on every run, eagerly and under graph replay, at any obs_stride.  A row of weight zero adds exact zeros to every chain (x + 0 is
+ * exact), so moving rows of weight zero about changes no bit as long as the other rows keep their order and their tiles (a single
+ * such row may sit anywhere); rows that move to another tile change the grouping of the sum, and with it, possibly, the last bit.
+ * Outputs for non-finite inputs are unspecified, in rows of weight zero too: the backward products multiply that row's zero deltas
+ * with its activations.  The parameters and the forward pass are not touched.
+ *
+ * It follows the *_device contract: enqueues on the caller's stream, returns at once, allocates nothing, can be captured into a
+ * hipGraph (params and the batch's pointers are taken by value at the call).  QG_ERR_ARG, before any device call: NULL params / batch
+ * / grad / policy, a wrong struct_size, reserved != 0, an unknown loss, a non-finite coef, B < 1, a NULL obs or target_mean, KL mode
+ * without target_log_std, B > the rows reserved (nothing reserved included), obs_stride < obs_dim.
+ * Not offered: distilling the value, recurrent students, mixing the executed action between teacher and student (torch.where does it),
+ * accumulating into grad (add two flat vectors, or all-reduce them), normalising by sum_i w_i (scale coef). */
+#define QG_DISTILL_MSE 0
+#define QG_DISTILL_KL 1
+typedef struct qg_distill_params {
+    int32_t struct_size;           /* sizeof(qg_distill_params): checked */
+    int32_t loss;                  /* QG_DISTILL_MSE or QG_DISTILL_KL */
+    float coef;                    /* finite */
+    int32_t reserved;              /* 0 */
+} qg_distill_params;
+typedef struct qg_distill_batch {  /* device pointers */
+    int32_t struct_size;           /* sizeof(qg_distill_batch): checked */
+    int32_t obs_stride;            /* floats, >= obs_dim */
+    const float *obs;              /* [B] rows */
+    const float *target_mean;      /* [B][act_dim] */
+    const float *target_log_std;   /* [act_dim]; required in KL mode, not read in MSE mode */
+    const float *weights;          /* [B], or NULL: every row has weight 1 */
+} qg_distill_batch;
+int qg_policy_distill_grad_device(qg_policy *policy, const qg_distill_params *params, int32_t B, const qg_distill_batch *batch,
+                                  float *grad, float *stats, void *stream);
+
 /* ---- Adam, gradient-norm clipping and advantage normalisation on the device ------------------------------------------------------------
  * What stands between the gradient and the next forward pass of SB3's PPO.train: torch.nn.utils.clip_grad_norm_ and torch.optim.Adam
  * (amsgrad off, no weight decay) on the handle's own canonical parameters, and normalize_advantage for one minibatch.  One minibatch

@@ -190,6 +190,12 @@ class QgPpoBatch(_Sized):
         return super().make(obs_stride=int(obs_stride), **ptrs)
 
 
+DISTILL_LOSSES = {"mse": 0, "kl": 1}      # QG_DISTILL_MSE, QG_DISTILL_KL
+
+
+# (the mirrors of qg_distill_params / qg_distill_batch live with their one user: policy.QgDistillParams, policy.QgDistillBatch)
+
+
 class QgAdamParams(_Sized):
     """``qg_adam_params``: the constants of one optimiser step (``struct_size`` is filled in); ``max_grad_norm=None`` is off."""
     _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("lr", C.c_float), ("beta_one", C.c_float), ("beta_two", C.c_float),
@@ -455,6 +461,7 @@ PROTOTYPES = {
     "qg_policy_critic_window": [_vp, _P(_i32), _P(_i32)],
     "qg_policy_reserve_grad": [_vp, _i32],
     "qg_policy_ppo_grad_device": [_vp, _P(QgPpoParams), _i32, _P(QgPpoBatch), _vp, _vp, _vp],
+    "qg_policy_distill_grad_device": [_vp, _vp, _i32, _vp, _vp, _vp, _vp],      # (params and batch: byref of policy.py's mirrors)
     "qg_policy_reserve_adam": [_vp],
     "qg_policy_adam_update_device": [_vp, _P(QgAdamParams), _vp, _vp, _vp, _vp, _vp],
     "qg_policy_adam_get_state": [_vp, _vp, _vp, _P(C.c_int64)],

@@ -1,5 +1,6 @@
 // qg_policy.h -- what the translation units of the fused MLP policy share: the layer table their kernels read (qg_policy.hip: the
-// forward pass; qg_policy_grad.hip: the PPO loss and gradient pass; qg_policy_opt.hip: the optimiser step) and the handle.  Internal:
+// forward pass; qg_policy_grad.hip: the PPO loss and gradient pass; qg_policy_distill.hip: the imitation loss and gradient pass;
+// qg_policy_opt.hip: the optimiser step) and the handle.  Internal:
 // not installed, nothing in here is exported.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -22,9 +22,8 @@
 #include <cmath>
 #include <cstring>
 
-#include "qg_policy.h"
+#include "qg_policy_grad_dev.h"
 
-#define QGG_WAVES 4
 #define QGG_HALF_LOG_2PI 0.91893853320467274178
 
 // canonical flat parameters -> the transposed image of the layers past the first (one thread per packed float)
@@ -46,48 +45,7 @@ __global__ void qg_policy_pack_t_kernel(KPolicy P, KGrad G, const float *__restr
         }
 }
 
-// sum += (operand image block row m, nk blocks of 16 along k) . (activations in the register image).  A block of 16 is one f32 chain of
-// the matrix instruction (16 exact products, as the forward pass); the blocks are added in f64 -- the pass differentiates sums with heavy
-// cancellation over the rows, and a pre-activation that is good to the last f32 bit keeps its error at that of torch's blocked sums.
-// Operands come in groups of four blocks, the next group's loads issued before this group's matrix instructions (indices past the end
-// are clamped and the instructions guarded, wave-uniformly): a wave waits for memory once per group, not once per block.
-__device__ __forceinline__ void qgg_load_group(qgp_f32x4 (&a)[4], qgp_f32x4 (&b)[4], const qgp_f32x4 *w, const qgp_f32x4 *xin, int q0, int nk, int lane) {
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const int q = min(q0 + u, nk - 1);
-        a[u] = w[q * 64];
-        b[u] = xin[q * 64 + lane];
-    }
-}
-
-__device__ __forceinline__ void qgg_product(const float *__restrict__ image, int nk, int m, const qgp_f32x4 *xin, double (&sum)[4], int lane) {
-    const qgp_f32x4 *w = (const qgp_f32x4 *)image + (size_t)m * nk * 64 + lane;
-    qgp_f32x4 a[4], b[4], an[4], bn[4];
-    qgg_load_group(a, b, w, xin, 0, nk, lane);
-    for (int q0 = 0; q0 < nk; q0 += 4) {
-        qgg_load_group(an, bn, w, xin, q0 + 4, nk, lane);
-#pragma unroll
-        for (int u = 0; u < 4; u++)
-            if (q0 + u < nk) {
-                qgp_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int s = 0; s < 4; s++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][s], b[u][s], acc, 0, 0, 0);
-#pragma unroll
-                for (int r = 0; r < 4; r++) sum[r] += (double)acc[r];
-            }
-#pragma unroll
-        for (int u = 0; u < 4; u++) a[u] = an[u], b[u] = bn[u];
-    }
-}
-
-// the sum over the 16 rows of a tile (lanes that differ in their low four bits): a fixed butterfly, the same value in every lane
-__device__ __forceinline__ double qgg_sum_rows(double v) {
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 8);
-    return v;
-}
+// (qgg_product, the product over an operand image, and qgg_sum_rows: qg_policy_grad_dev.h)
 
 __global__ __launch_bounds__(64 * QGG_WAVES) void qg_policy_grad_rows_kernel(KPolicy P, KGrad G, qg_ppo_params pp, const float *__restrict__ packed,
                                                                             const float *__restrict__ packed_t, int n, qg_ppo_batch bt,
@@ -411,6 +369,13 @@ extern "C" int qg_policy_reserve_grad(qg_policy *p, int32_t max_batch) {
     return QG_OK;
 }
 
+int qg_policy_grad_launch_weights(qg_policy *p, const KGrad &g, int tiles, int slots, hipStream_t st) {
+    qg_policy_grad_weights_kernel<<<dim3((unsigned)g.n_items, (unsigned)slots), 64, 0, st>>>(p->k, g, tiles, p->n_params, p->d_rec, p->d_tile_misc,
+                                                                                                p->d_partial, p->d_slot_misc);
+    HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
+    return QG_OK;
+}
+
 extern "C" int qg_policy_ppo_grad_device(qg_policy *p, const qg_ppo_params *pp, int32_t B, const qg_ppo_batch *bt, float *grad, float *stats,
                                          void *stream) {
     if (!p || !pp || !bt || !grad) return fail(QG_ERR_ARG, "qg_policy_ppo_grad_device: null argument");
@@ -438,9 +403,7 @@ extern "C" int qg_policy_ppo_grad_device(qg_policy *p, const qg_ppo_params *pp, 
     qg_policy_grad_rows_kernel<<<dim3((unsigned)tiles, (unsigned)p->k.n_towers), 64 * QGG_WAVES, lds, st>>>(
         p->k, p->g, *pp, p->d_packed, p->d_packed_t, B, *bt, p->d_rec, p->d_tile_misc);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
-    qg_policy_grad_weights_kernel<<<dim3((unsigned)p->g.n_items, (unsigned)slots), 64, 0, st>>>(p->k, p->g, tiles, p->n_params, p->d_rec,
-                                                                                                   p->d_tile_misc, p->d_partial, p->d_slot_misc);
-    HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
+    QG_TRY(qg_policy_grad_launch_weights(p, p->g, tiles, slots, st));
     const int threads = 256;
     qg_policy_grad_reduce_kernel<<<(p->n_params + 8 + threads - 1) / threads, threads, 0, st>>>(p->k, *pp, B, slots, p->n_params, p->d_params,
                                                                                                   p->d_partial, p->d_slot_misc, grad, stats);

@@ -9,12 +9,35 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import math
 
 import numpy as np
 
 from . import _abi
-from ._abi import QgAdamParams, QgPolicyDesc, QgPpoBatch, QgPpoParams, check
+from ._abi import DISTILL_LOSSES, QgAdamParams, QgPolicyDesc, QgPpoBatch, QgPpoParams, check
 from ._handle import Handle
+
+
+class QgDistillParams(C.Structure):
+    """``qg_distill_params``: the loss (``"mse"`` / ``"kl"`` or its number) and coefficient of one distillation call (``struct_size`` is
+    filled in, the way ``_abi._Sized`` fills it)."""
+    _fields_ = [("struct_size", C.c_int32), ("loss", C.c_int32), ("coef", C.c_float), ("reserved", C.c_int32)]
+
+    @classmethod
+    def make(cls, loss="mse", coef=1.0):
+        d = _abi._Sized.make.__func__(cls)
+        d.loss, d.coef = int(DISTILL_LOSSES.get(loss, loss)), float(coef)
+        return d
+
+
+class QgDistillBatch(C.Structure):
+    """``qg_distill_batch``: device pointers of one minibatch of rows and target means (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("obs_stride", C.c_int32), ("obs", C.c_void_p), ("target_mean", C.c_void_p),
+                ("target_log_std", C.c_void_p), ("weights", C.c_void_p)]
+
+    @classmethod
+    def make(cls, obs_stride, **ptrs):
+        return _abi._Sized.make.__func__(cls, obs_stride=int(obs_stride), **ptrs)
 
 
 def _np32(a):
@@ -292,6 +315,46 @@ class FusedMlpPolicy(Handle):
         check(self._lib.qg_policy_ppo_grad_device(self._h, C.byref(params), n, C.byref(desc), grad.data_ptr(),
                                                   stats.data_ptr() if stats is not None else None, self._stream_ptr(stream)),
               "qg_policy_ppo_grad_device")
+
+    # -- teacher-student distillation -------------------------------------------------------
+    DISTILL_STAT_NAMES = ("loss", "sq_err", "kl", "max_abs_err", "weight_sum")
+
+    def distill_grad(self, obs, target_mean, grad, stats=None, *, loss="mse", coef=1.0, target_log_std=None, weights=None, stream=None):
+        """The imitation loss of one minibatch (``include/quadgym.h`` states it) and its gradient, three launches on ``stream``, in the
+        scratch of ``reserve_grad``: the action mean of this policy (the student) on ``obs`` against ``target_mean[n, act_dim]`` --
+        what ``teacher.forward(rows, target_mean)`` wrote.  ``loss="mse"``: ``coef / n * sum_rows w * sum_a (mean - target)^2``;
+        ``loss="kl"``: ``coef / n * sum_rows w * KL(N(target, exp(target_log_std)) || N(mean, exp(log_std)))`` with the teacher's
+        ``target_log_std[act_dim]`` on the device.  ``weights[n]`` (optional) are the ``w``; the sum is divided by ``n``, not by their
+        sum.  ``grad[n_params]`` in the canonical order, every element overwritten (the critic's entries, and ``log_std`` in MSE
+        mode, with zeros); ``stats[8]`` (optional) = ``DISTILL_STAT_NAMES``, then zeros.  Only the actor's columns of a row are read:
+        ``obs`` may be row-strided -- the slice ``rows[:, :obs_dim]`` of wider rows -- or the wide rows themselves."""
+        import torch
+        if loss not in DISTILL_LOSSES:
+            raise ValueError(f"loss: expected one of {sorted(DISTILL_LOSSES)}, got {loss!r}")
+        if not math.isfinite(coef):
+            raise ValueError(f"coef must be finite, got {coef}")
+        if obs.dim() == 2 and obs.shape[1] > self.obs_dim:
+            obs = obs[:, :self.obs_dim]                    # the wide rows: the same pointer and stride
+        n, stride = self._check_obs(obs)
+        f32 = torch.float32
+        self._check_tensor(target_mean, (n, self.act_dim), f32, "target_mean")
+        ptrs = dict(obs=obs.data_ptr(), target_mean=target_mean.data_ptr())
+        if loss == "kl":
+            if target_log_std is None:
+                raise ValueError('loss="kl" needs target_log_std, the teacher\'s log_std on the device')
+            self._check_tensor(target_log_std, (self.act_dim,), f32, "target_log_std")
+            ptrs["target_log_std"] = target_log_std.data_ptr()
+        if weights is not None:
+            self._check_tensor(weights, (n,), f32, "weights")
+            ptrs["weights"] = weights.data_ptr()
+        self._check_tensor(grad, (self.n_params,), f32, "grad")
+        if stats is not None:
+            self._check_tensor(stats, (8,), f32, "stats")
+        params = QgDistillParams.make(loss, coef)
+        desc = QgDistillBatch.make(stride, **ptrs)
+        check(self._lib.qg_policy_distill_grad_device(self._h, C.byref(params), n, C.byref(desc), grad.data_ptr(),
+                                                      stats.data_ptr() if stats is not None else None, self._stream_ptr(stream)),
+              "qg_policy_distill_grad_device")
 
     # -- the optimiser ----------------------------------------------------------------------
     def reserve_adam(self):
