@@ -1,11 +1,37 @@
 """``DeviceVecEnvWrapper`` -- what the VecEnv wrappers around a device-side layer share (``DeviceVecNormalize``,
-``DevicePerturbedVecEnv``): the wrapped env and the pass-through to it, the buffers of a ``step_tensor`` call by name, the upload
-of the NumPy cold path, the finished envs whose info holds a terminal observation, and checkpoint / resume / close over the layer."""
+``DevicePerturbedVecEnv``, ``DeviceGaitRewardVecEnv``, ``DevicePrivilegedVecEnv``): the wrapped env and the pass-through to it, the
+buffers of a ``step_tensor`` call by name, the upload of the NumPy cold path, the finished envs whose info holds a terminal
+observation, checkpoint / resume / close over the layer, and the walk along a stack's ``.venv`` chain by which a wrapper refuses, at
+construction, an order of the stack that cannot work.
+
+The orders that work, inside to outside: ``DevicePerturbedVecEnv`` next to the env (never around ``DevicePrivilegedVecEnv``: its
+noise belongs on the actor's columns); ``DeviceGaitRewardVecEnv`` anywhere, but with ``gate_on_command=True`` inside any
+``DeviceVecNormalize`` that normalises observations (the gate reads the command in m/s); ``DeviceVecNormalize`` outside
+``DevicePrivilegedVecEnv`` around the walking envs, and inside it around the plain env, whose packed step keeps the wide rows apart."""
 from __future__ import annotations
 
 import numpy as np
 
 STEP_BUFFERS = ("obs", "reward", "done", "components", "terminal_obs")      # the walking envs' step_tensor, behind `actions`
+
+
+def stack_layers(venv):
+    """The wrappers of the stack ``venv``, outermost first, along the ``.venv`` chain; the env itself is not among them."""
+    while isinstance(venv, DeviceVecEnvWrapper):
+        yield venv
+        venv = venv.venv
+
+
+def stack_layer(venv, key):
+    """The outermost wrapper of the stack ``venv`` whose snapshot key is ``key`` (``"privileged"``, ``"normalizer"`` ...), or None."""
+    return next((layer for layer in stack_layers(venv) if layer._snapshot_key == key), None)
+
+
+def base_env(venv):
+    """The env at the bottom of the stack ``venv``."""
+    while isinstance(venv, DeviceVecEnvWrapper):
+        venv = venv.venv
+    return venv
 
 
 class DeviceVecEnvWrapper:

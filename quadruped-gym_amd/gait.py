@@ -16,7 +16,7 @@ import numpy as np
 
 from ._abi import GAIT_MAX_BASE_TERMS, GAIT_TERMS, QgGaitDesc, check          # (QgGaitDesc: re-exported)
 from ._handle import Handle
-from .envs.device_wrapper import STEP_BUFFERS, DeviceVecEnvWrapper
+from .envs.device_wrapper import STEP_BUFFERS, DeviceVecEnvWrapper, stack_layers
 
 NTERMS = len(GAIT_TERMS)
 THRESHOLDS = ("air_time_target", "clearance_target", "max_contact_force", "min_command_speed")
@@ -126,7 +126,9 @@ class DeviceGaitRewardVecEnv(DeviceVecEnvWrapper):
     The sensor is the env's (``venv.contact_sensor(force_threshold)``): the env's ``reset`` restarts its timers and the env's snapshot
     carries them, so this layer's own state is empty.  ``components``, if passed, is ``[N, len(venv.reward_keys) + 7]``: the env's
     columns, then the seven -- ``reward_keys`` lists them, so ``RewardMonitor.for_env(wrapper)`` works as it is.
-    ``gate_on_command=True`` (the partially observable env only) gates ``feet_air_time`` on the newest frame's command columns.  The
+    ``gate_on_command=True`` (the partially observable env only) gates ``feet_air_time`` on the newest frame's command columns, in
+    m/s: around a ``DeviceVecNormalize`` with ``norm_obs=True`` it is refused at construction, before any handle exists (the order
+    that works is ``DeviceVecNormalize(DeviceGaitRewardVecEnv(env, gate_on_command=True))``).  The
     NumPy ``step()`` is a cold path built for correctness: it returns shaped rewards and leaves ``last_gait_components [N, 7]``;
     ``infos`` stay the env's.  Every other attribute passes through to the wrapped env."""
 
@@ -136,6 +138,10 @@ class DeviceGaitRewardVecEnv(DeviceVecEnvWrapper):
     def __init__(self, venv, weights=None, force_threshold: float = 1.0, gate_on_command: bool = False, **options):
         if gate_on_command and not hasattr(venv, "obs_window"):
             raise ValueError("gate_on_command: only the partially observable env's observation holds the command")
+        if gate_on_command and any(layer._snapshot_key == "normalizer" and layer.normalizer.norm_obs for layer in stack_layers(venv)):
+            raise ValueError("gate_on_command around a DeviceVecNormalize that normalises observations: the gate would compare normalised "
+                             "command columns with min_command_speed in m/s; put the gait terms inside, "
+                             "DeviceVecNormalize(DeviceGaitRewardVecEnv(env, gate_on_command=True))")
         self.gait = GaitReward(venv.contact_sensor(force_threshold), weights, **options)
         super().__init__(venv, self.gait)
         self.gate_on_command = bool(gate_on_command)

@@ -13,7 +13,7 @@ import numpy as np
 
 from ._abi import QgNormDesc, check
 from ._handle import Handle
-from .envs.device_wrapper import DeviceVecEnvWrapper
+from .envs.device_wrapper import DeviceVecEnvWrapper, base_env
 
 
 class RunningNormalizer(Handle):
@@ -119,15 +119,35 @@ class DeviceVecNormalize(DeviceVecEnvWrapper):
     """``VecNormalize`` around ``QuadrupedVecEnv``, ``WalkingQuadrupedVecEnv`` or ``POWalkingQuadrupedVecEnv`` whose ``step_tensor``
     stays on the device: the env's launch, then the normaliser's on the same stream.  Keyword options are ``RunningNormalizer``'s.
     The NumPy ``reset()`` / ``step()`` are a cold path built for correctness only (they upload the rows and run the same device
-    calls).  Every other attribute passes through to the wrapped env."""
+    calls).  Every other attribute passes through to the wrapped env.
+
+    Terminal rows.  Where the wrapped stack reports an ``actor_obs_dim`` below its ``obs_dim`` (``DevicePrivilegedVecEnv`` inside:
+    the statistics are over the wide row, ``terminal_obs`` and ``infos["terminal_observation"]`` stay at the actor's width), the
+    terminal rows are normalised with the leading ``actor_obs_dim`` columns of the statistics: bit for bit what ``normalize_obs``
+    gives on a wide row that holds them in front.  They go through a wide scratch allocated here, so a step allocates nothing.  A
+    ``terminal_obs`` of any other width is refused before the env's launch.
+
+    Refused at construction, before any handle exists: this wrapper around ``DevicePrivilegedVecEnv`` around the plain env (a packed
+    step whose rows are not ``obs_dim`` wide: the wide rows travel beside the packed ones and would never be normalised).  There the
+    normaliser goes INSIDE: ``DevicePrivilegedVecEnv(DeviceVecNormalize(env))`` -- actor columns normalised, privileged columns raw."""
 
     _snapshot_key = "normalizer"
 
     def __init__(self, venv, **options):
+        if venv.packed_step and int(venv.obs_dim) != int(base_env(venv).obs_dim):
+            raise ValueError(f"DeviceVecNormalize around a packed step whose rows are {int(base_env(venv).obs_dim)} + 2 wide while the stack's "
+                             f"obs_dim is {int(venv.obs_dim)} (DevicePrivilegedVecEnv around the plain env): put the normaliser inside, "
+                             "DevicePrivilegedVecEnv(DeviceVecNormalize(env)) -- actor columns normalised, privileged columns raw")
         device = options.pop("device", venv.device)
         self.normalizer = RunningNormalizer(venv.num_envs, venv.obs_dim, device=device, **options)
         super().__init__(venv, self.normalizer)
         self.old_obs = self.old_reward = None
+        actor = getattr(venv, "actor_obs_dim", None)
+        self.terminal_dim = int(venv.obs_dim) if actor is None else int(actor)      # the width of the stack's terminal rows
+        self._term_wide = None
+        if self.terminal_dim < self.normalizer.obs_dim:
+            import torch
+            self._term_wide = torch.zeros((self.num_envs, self.normalizer.obs_dim), device=self.normalizer._torch_device(), dtype=torch.float32)
 
     @property
     def training(self):
@@ -145,11 +165,41 @@ class DeviceVecNormalize(DeviceVecEnvWrapper):
             packed = self.venv.step_tensor(actions, *args, **kwargs)
             return self.normalizer.step_packed(packed, stream=stream)
         bound = self._step_buffers(args, kwargs)
+        term = bound.get("terminal_obs")
+        narrow = term is not None and self._check_terminal(term)                # before the env's launch
+        if bound.get("obs") is not None:
+            self.normalizer._check_obs(bound["obs"], self.normalizer.num_envs)
         self.venv.step_tensor(actions, *args, **kwargs)
         self.normalizer.step(bound["obs"], bound["reward"], bound["done"], stream=stream)
-        if bound.get("terminal_obs") is not None:
-            self.normalizer.normalize_obs(bound["terminal_obs"], stream=stream)
+        if narrow:
+            self._normalize_narrow(term, stream)
+        elif term is not None:
+            self.normalizer.normalize_obs(term, stream=stream)
         return None
+
+    def _check_terminal(self, term):
+        """True where ``term`` holds the stack's narrow terminal rows ``[N, terminal_dim]``, False where it is ``obs_dim`` wide (any
+        number of rows, as ``normalize_obs`` takes them); any other tensor raises ``ValueError``."""
+        nz = self.normalizer
+        if self._term_wide is None or (term.dim() == 2 and term.shape[1] == nz.obs_dim):
+            nz._check_obs(term, None, "terminal_obs")
+            return False
+        if term.dim() != 2 or term.shape[1] != self.terminal_dim or term.shape[0] > nz.num_envs:
+            raise ValueError(f"terminal_obs: expected a float32 tensor of shape ({nz.num_envs}, {self.terminal_dim}) -- the stack's "
+                             f"terminal rows stay at the actor's width -- or ({nz.num_envs}, {nz.obs_dim}), got {tuple(term.shape)}")
+        nz._check_rows(term, self.terminal_dim, "terminal_obs", nz.ANY_ROWS)
+        return True
+
+    def _normalize_narrow(self, term, stream=None):
+        """``term [n <= N, terminal_dim]`` in place with the leading columns of the statistics, through the wide scratch."""
+        import torch
+        n, O = term.shape[0], self.terminal_dim
+        wide = self._term_wide[:n]
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.normalizer.device)):
+            wide[:, :O].copy_(term)
+            self.normalizer.normalize_obs(wide, stream=stream)
+            term.copy_(wide[:, :O])
+        return term
 
     # -- NumPy cold path --------------------------------------------------------------------
     def reset(self):
@@ -173,7 +223,10 @@ class DeviceVecNormalize(DeviceVecEnvWrapper):
         rows = self._finished_with_terminal(done, infos)
         if rows:
             term = self._upload(np.stack([info["terminal_observation"] for _, info in rows]))
-            term = self.normalizer.normalize_obs(term).cpu().numpy()
+            if self._term_wide is not None and self._check_terminal(term):
+                term = self._normalize_narrow(term).cpu().numpy()
+            else:
+                term = self.normalizer.normalize_obs(term).cpu().numpy()
             for k, (i, info) in enumerate(rows):
                 info = dict(info)
                 info["terminal_observation"] = term[k]

@@ -19,7 +19,7 @@ import numpy as np
 from . import _abi
 from ._abi import QgPerturbDesc, check
 from ._handle import Handle
-from .envs.device_wrapper import DeviceVecEnvWrapper
+from .envs.device_wrapper import DeviceVecEnvWrapper, stack_layer
 
 # frame columns by name, per layout (width -> {group: slice}): the partially observable frame (po_walking_quad.py:48-56) and the
 # 33- and 21-value sensor packs (QG_OBS_FULL, QG_OBS_IMU)
@@ -157,13 +157,20 @@ class DevicePerturbedVecEnv(DeviceVecEnvWrapper):
     sensor groups of the 33- and 21-value packs).  ``action_latency = (lo, hi)`` in seconds, converted with timestep x frame_skip
     (rounded to nearest) as ``push_randomization`` converts.  The caller's ``actions`` tensor is left as the policy wrote it (it is
     what a rollout buffer stores).  The NumPy ``reset()`` / ``step()`` are a cold path built for correctness only.  Every other
-    attribute passes through to the wrapped env."""
+    attribute passes through to the wrapped env.
+
+    Stacking order: next to the env.  Around a stack that holds ``DevicePrivilegedVecEnv`` it is refused at construction, before any
+    handle exists (the noise would land on the truth columns, or meet rows of another width after the launch): the order that works
+    is ``DevicePrivilegedVecEnv(DevicePerturbedVecEnv(env))``."""
 
     _snapshot_key = "perturbation"
 
     def __init__(self, venv, obs_noise=None, obs_bias=None, action_noise: float = 0.0, action_latency=(0.0, 0.0), seed: int = 0,
                  env_index_base: int | None = None, device: int | None = None):
         import torch
+        if stack_layer(venv, "privileged") is not None:     # before any handle: the noise would land on the truth columns
+            raise ValueError("DevicePerturbedVecEnv around DevicePrivilegedVecEnv: sensor noise, bias and latency belong on the actor's "
+                             "columns only; put it inside, DevicePrivilegedVecEnv(DevicePerturbedVecEnv(env))")
         po = hasattr(venv, "obs_window")                    # the stacked frames; its finished rows hold the reset stack
         frame = venv.FRAME if po else venv.obs_dim
         window = venv.obs_window if po else 1

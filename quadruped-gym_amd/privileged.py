@@ -83,8 +83,12 @@ class DevicePrivilegedVecEnv(DeviceVecEnvWrapper):
     state's privileged columns no longer exist when the step returns.
 
     Stacking order: ``DevicePerturbedVecEnv`` goes INSIDE this wrapper (noise, bias and latency on the actor's columns only; the
-    privileged columns stay clean), ``DeviceVecNormalize`` OUTSIDE (statistics over the wide row).  The NumPy ``reset()`` / ``step()``
-    are a cold path built for correctness: they return wide rows.  Every other attribute passes through to the wrapped env."""
+    privileged columns stay clean; around this wrapper it is refused at construction), ``DeviceVecNormalize`` OUTSIDE around the
+    walking envs (statistics over the wide row; it normalises the ``O``-wide terminal rows with the leading ``O`` columns of its
+    statistics).  Around the plain env, whose packed step keeps the wide rows apart, the normaliser goes inside --
+    ``DevicePrivilegedVecEnv(DeviceVecNormalize(env))``: actor columns normalised, privileged columns raw -- and is refused outside.
+    The NumPy ``reset()`` / ``step()`` are a cold path built for correctness: they return wide rows.  Every other attribute passes
+    through to the wrapped env."""
 
     _snapshot_key = "privileged"
     privileged_dim = PRIV_DIM
