@@ -193,7 +193,26 @@ class QgPpoBatch(_Sized):
 DISTILL_LOSSES = {"mse": 0, "kl": 1}      # QG_DISTILL_MSE, QG_DISTILL_KL
 
 
-# (the mirrors of qg_distill_params / qg_distill_batch live with their one user: policy.QgDistillParams, policy.QgDistillBatch)
+class QgDistillParams(_Sized):
+    """``qg_distill_params``: the loss (``"mse"`` / ``"kl"`` or its number) and coefficient of one distillation call (``struct_size`` is
+    filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("loss", C.c_int32), ("coef", C.c_float), ("reserved", C.c_int32)]
+
+    @classmethod
+    def make(cls, loss="mse", coef=1.0):
+        d = super().make()
+        d.loss, d.coef = int(DISTILL_LOSSES.get(loss, loss)), float(coef)
+        return d
+
+
+class QgDistillBatch(_Sized):
+    """``qg_distill_batch``: device pointers of one minibatch of rows and target means (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("obs_stride", C.c_int32), ("obs", C.c_void_p), ("target_mean", C.c_void_p),
+                ("target_log_std", C.c_void_p), ("weights", C.c_void_p)]
+
+    @classmethod
+    def make(cls, obs_stride, **ptrs):
+        return super().make(obs_stride=int(obs_stride), **ptrs)
 
 
 class QgAdamParams(_Sized):

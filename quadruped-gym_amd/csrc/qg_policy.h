@@ -34,7 +34,16 @@ typedef float qgp_f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- the gradient pass (qg_policy_grad.hip) ------------------------------------------------------------------------------
 #define QGG_SLOT_TILES 32         // 16-row tiles per partial-sum slot: a slot is 512 rows (FusedMlpPolicy.GRAD_SLOT_ROWS)
-#define QGG_MISC 24               // f64 per tile / per slot: log_std sums [16], policy, kl, clip count, value, 4 spare
+#define QGG_MISC 24               // f64 per tile / per slot: the log_std sums [0, 16), then the slots named below, 4 spare
+#define QGG_MISC_POLICY 16        // the PPO pass: sum_rows of the policy term, of the kl estimate, of the clip count, of the value term
+#define QGG_MISC_KL 17
+#define QGG_MISC_CLIP 18
+#define QGG_MISC_VALUE 19         // the last slot the weights launch adds, and only on a handle with a critic
+#define QGD_MISC_LOSS 16          // the distillation pass, over the same slots: sum_rows w l, sum_rows w sum_a (mu - t)^2, sum_rows w
+#define QGD_MISC_SQ 17
+#define QGD_MISC_W 18
+#define QGD_MISC_MAX 20           // tile_misc alone (the weights launch adds nothing past QGG_MISC_VALUE): max |mu - t| of the tile
+#define QGG_HALF_LOG_2PI 0.91893853320467274178
 
 struct KGradLayer {
     int32_t wt_off;               // offset (floats) into the transposed image: W^T' [nq][nb][64][4] (layers >= 1; layer 0 has none)

@@ -210,7 +210,7 @@ __global__ __launch_bounds__(64 * WAVES) void qg_policy_forward_kernel(KPolicy P
                             act = qgp_sample(mean, sd[a], ev);
                         }
                         if (live) actions[(size_t)env * P.act_dim + a] = act;
-                        lp += -0.5 * (double)ev * (double)ev - (double)sd[16 + a] - 0.91893853320467274178;
+                        lp += -0.5 * (double)ev * (double)ev - (double)sd[16 + a] - QGG_HALF_LOG_2PI;
                     }
                 }
                 if (log_prob) {   // the sum over the action components runs over the four lane groups (f64: rounded to f32 once)

@@ -20,75 +20,23 @@
 
 #include "qg_policy_grad_dev.h"
 
-#define QGD_MISC_LOSS 16          // tile_misc / slot_misc: sum_rows w l, sum_rows w sum_a (mu - t)^2, sum_rows w (behind the 16 log_std terms)
-#define QGD_MISC_SQ 17
-#define QGD_MISC_W 18
-#define QGD_MISC_MAX 20           // tile_misc alone (the weights launch does not add the entries past 19): max |mu - t| of the tile
-
-// the sum over the 16 rows of a tile in ascending row order, the same value in every lane: rows that add zero are then no-ops, whatever
-// their place in the tile
-__device__ __forceinline__ double qgd_sum_rows(double v, int lane) {
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < 16; j++) s += __shfl(v, (lane & 48) | j);
-    return s;
-}
+// (qgg_product, qgd_sum_rows and the QGG_ROWS_* shell of a rows kernel: qg_policy_grad_dev.h)
 
 __global__ __launch_bounds__(64 * QGG_WAVES) void qg_policy_distill_rows_kernel(KPolicy P, KGrad G, qg_distill_params dp, const float *__restrict__ packed,
                                                                                const float *__restrict__ packed_t, int n, qg_distill_batch bt,
                                                                                float *rec, double *__restrict__ tile_misc) {
-    extern __shared__ qgp_f32x4 qgd_lds[];
-    const int tile = blockIdx.x, row0 = tile * QGP_TILE;
-    const int lane = threadIdx.x & 63, e = lane & 15, g = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float *x0 = (float *)qgd_lds;
-    float *x1 = x0 + P.lds0_floats;
-    float *myrec = rec + (size_t)(row0 + e) * G.rec;          // the record of this lane's row (rows past n in the last tile have one too)
-
-    // the actor's window of the observation tile, zero padded, into buffer 0 in the operand image and into the records
-    {
-        const int width = 16 * P.layer[0][0].nq;
-        for (int idx = threadIdx.x; idx < QGP_TILE * width; idx += 64 * QGG_WAVES) {
-            const int ee = idx / width, c = idx - ee * width;
-            float v = 0.f;
-            if (c < P.obs_dim && row0 + ee < n) v = bt.obs[(size_t)(row0 + ee) * bt.obs_stride + c];
-            x0[((c >> 2) * 16 + ee) * 4 + (c & 3)] = v;
-            rec[(size_t)(row0 + ee) * G.rec + G.layer[0][0].h_off + c] = v;
-        }
-    }
-
-    const int nl = P.n_layers;
+    QGG_ROWS_ENTRY(0);          // the actor's tower alone, and its window of the row
+    QGG_ROWS_STAGE(P.obs_dim, 0, bt.obs, bt.obs_stride);
     for (int l = 0; l < nl; l++) {
-        const KPolLayer L = P.layer[0][l];
-        const qgp_f32x4 *xin = (const qgp_f32x4 *)((l & 1) ? x1 : x0);
-        qgp_f32x4 *xout = (qgp_f32x4 *)((l & 1) ? x0 : x1);
-        __syncthreads();          // the layer's input is complete (and the buffer it overwrites has been read by every wave)
+        QGG_ROWS_LAYER(l);
         if (l < nl - 1) {
-            const int h_next = G.layer[0][l + 1].h_off, d_own = G.layer[0][l].d_off;
-            for (int m = wave; m < L.nb; m += QGG_WAVES) {
-                const qgp_f32x4 bias = *(const qgp_f32x4 *)(packed + L.b_off + 16 * m + 4 * g);
-                double sum[4] = {(double)bias[0], (double)bias[1], (double)bias[2], (double)bias[3]};
-                qgg_product(packed + L.w_off, L.nq, m, xin, sum, lane);
-                qgp_f32x4 h, dh;
-#pragma unroll
-                for (int r = 0; r < 4; r++) {            // tanh and its derivative in f64, each rounded once
-                    const double t = tanh(sum[r]);
-                    h[r] = (float)t;
-                    dh[r] = (float)(1.0 - t * t);
-                }
-                xout[m * 64 + lane] = h;
-                *(qgp_f32x4 *)(myrec + h_next + 16 * m + 4 * g) = h;
-                *(qgp_f32x4 *)(myrec + d_own + 16 * m + 4 * g) = dh;      // kept where this thread will put the block's delta
-            }
+            QGG_ROWS_HIDDEN(l);
             continue;
         }
         if (wave != 0) continue;
         // ---- the heads of the tile's rows (f64), and the output layer's delta ----
-        const qgp_f32x4 bias = *(const qgp_f32x4 *)(packed + L.b_off + 4 * g);
-        double acc[4] = {(double)bias[0], (double)bias[1], (double)bias[2], (double)bias[3]};
-        qgg_product(packed + L.w_off, L.nq, 0, xin, acc, lane);
-        const int row = row0 + e;
-        const bool live = row < n, kl = dp.loss == QG_DISTILL_KL;
+        QGG_ROWS_OUTPUT(l);
+        const bool kl = dp.loss == QG_DISTILL_KL;
         const double w = live ? (bt.weights ? (double)bt.weights[row] : 1.0) : 0.0;
         const double scale = (double)dp.coef / (double)n * w;          // coef / B w_i
         const float *sd = packed + P.std_off;
@@ -133,29 +81,9 @@ __global__ __launch_bounds__(64 * QGG_WAVES) void qg_policy_distill_rows_kernel(
         }
         const double s_l = qgd_sum_rows(w * li, lane), s_sq = qgd_sum_rows(w * sq, lane), s_w = qgd_sum_rows(w, lane);
         if (lane == 0) misc[QGD_MISC_LOSS] = s_l, misc[QGD_MISC_SQ] = s_sq, misc[QGD_MISC_W] = s_w, misc[QGD_MISC_MAX] = mx;
-        xout[lane] = d;
-        *(qgp_f32x4 *)(myrec + G.layer[0][l].d_off + 4 * g) = d;
+        QGG_ROWS_DELTA(l, d);
     }
-
-    // ---- back through the layers: delta_l sits in the buffer layer l wrote its output to; delta_{l-1} goes to the other ----
-    for (int l = nl - 1; l >= 1; l--) {
-        const KPolLayer L = P.layer[0][l];
-        const KGradLayer GL = G.layer[0][l];
-        const int d_prev = G.layer[0][l - 1].d_off;
-        const qgp_f32x4 *din = (const qgp_f32x4 *)((l & 1) ? x0 : x1);
-        qgp_f32x4 *dout = (qgp_f32x4 *)((l & 1) ? x1 : x0);
-        __syncthreads();
-        for (int m = wave; m < L.nq; m += QGG_WAVES) {          // the blocks of layer l's input = of layer l - 1's output
-            double sum[4] = {0.0, 0.0, 0.0, 0.0};
-            qgg_product(packed_t + GL.wt_off, L.nb, m, din, sum, lane);
-            const qgp_f32x4 dh = *(const qgp_f32x4 *)(myrec + d_prev + 16 * m + 4 * g);      // this thread's own store of the forward part
-            qgp_f32x4 d;
-#pragma unroll
-            for (int r = 0; r < 4; r++) d[r] = (float)(sum[r] * (double)dh[r]);
-            dout[m * 64 + lane] = d;
-            *(qgp_f32x4 *)(myrec + d_prev + 16 * m + 4 * g) = d;
-        }
-    }
+    QGG_ROWS_WALK_BACK();
 }
 
 // grad from the slots' partial sums; the last workgroup's first wave writes stats
@@ -208,29 +136,26 @@ extern "C" int qg_policy_distill_grad_device(qg_policy *p, const qg_distill_para
     if (dp->loss != QG_DISTILL_MSE && dp->loss != QG_DISTILL_KL)
         return fail(QG_ERR_ARG, "qg_distill_params.loss is %d: QG_DISTILL_MSE (0) or QG_DISTILL_KL (1)", dp->loss);
     if (!qg_finite32(dp->coef)) return fail(QG_ERR_ARG, "qg_distill_params.coef must be finite");
+    // (params and batch are refused before the handle is looked at, so B < 1 is refused here; qg_policy_grad_check_rows needs the handle)
     if (B < 1) return fail(QG_ERR_ARG, "qg_policy_distill_grad_device: B must be >= 1");
     if (!bt->obs || !bt->target_mean) return fail(QG_ERR_ARG, "qg_distill_batch: null obs or target_mean");
     if (dp->loss == QG_DISTILL_KL && !bt->target_log_std) return fail(QG_ERR_ARG, "qg_distill_batch: QG_DISTILL_KL needs target_log_std");
     if (!p) return fail(QG_ERR_ARG, "qg_policy_distill_grad_device: null policy");
-    if (B > p->grad_max)
-        return fail(QG_ERR_ARG, "qg_policy_distill_grad_device: B = %d, but qg_policy_reserve_grad has reserved %d rows", B, p->grad_max);
-    if (bt->obs_stride < p->desc.obs_dim)
-        return fail(QG_ERR_ARG, "qg_policy_distill_grad_device: obs_stride %d < obs_dim %d", bt->obs_stride, p->desc.obs_dim);
+    QG_TRY(qg_policy_grad_check_rows(p, "qg_policy_distill_grad_device", B, bt->obs_stride, false));
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     const hipStream_t st = (hipStream_t)stream;
-    const int tiles = (B + QGP_TILE - 1) / QGP_TILE, slots = (tiles + QGG_SLOT_TILES - 1) / QGG_SLOT_TILES;
-    const size_t lds = (size_t)(p->k.lds0_floats + p->k.lds1_floats) * sizeof(float);
-    qg_policy_distill_rows_kernel<<<dim3((unsigned)tiles, 1u), 64 * QGG_WAVES, lds, st>>>(p->k, p->g, *dp, p->d_packed, p->d_packed_t, B, *bt,
+    const QgGradGeom geo = qg_policy_grad_geom(p, B);
+    qg_policy_distill_rows_kernel<<<dim3((unsigned)geo.tiles, 1u), 64 * QGG_WAVES, geo.lds, st>>>(p->k, p->g, *dp, p->d_packed, p->d_packed_t, B, *bt,
                                                                                              p->d_rec, p->d_tile_misc);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
     // the actor's work items alone: the weights kernel takes the item after the last as the one that adds the tiles' scalars, and an
     // item below the critic's first never selects a critic layer
     KGrad actor = p->g;
     if (p->k.n_towers == 2) actor.n_items = p->g.layer[1][0].item0 + 1;
-    QG_TRY(qg_policy_grad_launch_weights(p, actor, tiles, slots, st));
+    QG_TRY(qg_policy_grad_launch_weights(p, actor, geo.tiles, geo.slots, st));
     const int threads = 256;
     qg_policy_distill_reduce_kernel<<<(p->n_params + threads - 1) / threads + 1, threads, 0, st>>>(
-        p->k, *dp, B, tiles, slots, p->n_params, p->d_partial, p->d_slot_misc, p->d_tile_misc, grad, stats);
+        p->k, *dp, B, geo.tiles, geo.slots, p->n_params, p->d_partial, p->d_slot_misc, p->d_tile_misc, grad, stats);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
     return QG_OK;
 }

@@ -24,8 +24,6 @@
 
 #include "qg_policy_grad_dev.h"
 
-#define QGG_HALF_LOG_2PI 0.91893853320467274178
-
 // canonical flat parameters -> the transposed image of the layers past the first (one thread per packed float)
 __global__ void qg_policy_pack_t_kernel(KPolicy P, KGrad G, const float *__restrict__ src, float *__restrict__ packed_t) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -45,64 +43,23 @@ __global__ void qg_policy_pack_t_kernel(KPolicy P, KGrad G, const float *__restr
         }
 }
 
-// (qgg_product, the product over an operand image, and qgg_sum_rows: qg_policy_grad_dev.h)
+// (qgg_product, the product over an operand image, qgg_sum_rows and the QGG_ROWS_* shell of a rows kernel: qg_policy_grad_dev.h)
 
 __global__ __launch_bounds__(64 * QGG_WAVES) void qg_policy_grad_rows_kernel(KPolicy P, KGrad G, qg_ppo_params pp, const float *__restrict__ packed,
                                                                             const float *__restrict__ packed_t, int n, qg_ppo_batch bt,
                                                                             float *rec, double *__restrict__ tile_misc) {
-    extern __shared__ qgp_f32x4 qgg_lds[];
-    const int tower = blockIdx.y, tile = blockIdx.x, row0 = tile * QGP_TILE;
-    const int lane = threadIdx.x & 63, e = lane & 15, g = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float *x0 = (float *)qgg_lds;
-    float *x1 = x0 + P.lds0_floats;
-    float *myrec = rec + (size_t)(row0 + e) * G.rec;          // the record of this lane's row (rows past n in the last tile have one too)
-
-    // the observation tile, zero padded, into buffer 0 in the operand image (as the forward pass) and into the records
-    {
-        const int width = 16 * P.layer[tower][0].nq;
-        const int in_dim = tower ? P.layer[1][0].in_dim : P.obs_dim, in_off = tower ? P.critic_off : 0;      // the tower's window of the row (wave-uniform)
-        for (int idx = threadIdx.x; idx < QGP_TILE * width; idx += 64 * QGG_WAVES) {
-            const int ee = idx / width, c = idx - ee * width;
-            float v = 0.f;
-            if (c < in_dim && row0 + ee < n) v = bt.obs[(size_t)(row0 + ee) * bt.obs_stride + in_off + c];
-            x0[((c >> 2) * 16 + ee) * 4 + (c & 3)] = v;
-            rec[(size_t)(row0 + ee) * G.rec + G.layer[tower][0].h_off + c] = v;
-        }
-    }
-
-    const int nl = P.n_layers;
+    QGG_ROWS_ENTRY(blockIdx.y);
+    const int in_dim = tower ? P.layer[1][0].in_dim : P.obs_dim, in_off = tower ? P.critic_off : 0;      // the tower's window of the row (wave-uniform)
+    QGG_ROWS_STAGE(in_dim, in_off, bt.obs, bt.obs_stride);
     for (int l = 0; l < nl; l++) {
-        const KPolLayer L = P.layer[tower][l];
-        const qgp_f32x4 *xin = (const qgp_f32x4 *)((l & 1) ? x1 : x0);
-        qgp_f32x4 *xout = (qgp_f32x4 *)((l & 1) ? x0 : x1);
-        __syncthreads();          // the layer's input is complete (and the buffer it overwrites has been read by every wave)
+        QGG_ROWS_LAYER(l);
         if (l < nl - 1) {
-            const int h_next = G.layer[tower][l + 1].h_off, d_own = G.layer[tower][l].d_off;
-            for (int m = wave; m < L.nb; m += QGG_WAVES) {
-                const qgp_f32x4 bias = *(const qgp_f32x4 *)(packed + L.b_off + 16 * m + 4 * g);
-                double sum[4] = {(double)bias[0], (double)bias[1], (double)bias[2], (double)bias[3]};
-                qgg_product(packed + L.w_off, L.nq, m, xin, sum, lane);
-                qgp_f32x4 h, dh;
-#pragma unroll
-                for (int r = 0; r < 4; r++) {            // tanh and its derivative in f64, each rounded once
-                    const double t = tanh(sum[r]);
-                    h[r] = (float)t;
-                    dh[r] = (float)(1.0 - t * t);
-                }
-                xout[m * 64 + lane] = h;
-                *(qgp_f32x4 *)(myrec + h_next + 16 * m + 4 * g) = h;
-                *(qgp_f32x4 *)(myrec + d_own + 16 * m + 4 * g) = dh;      // kept where this thread will put the block's delta
-            }
+            QGG_ROWS_HIDDEN(l);
             continue;
         }
         if (wave != 0) continue;
         // ---- the loss heads of the tile's rows (f64), and the output layer's delta ----
-        const qgp_f32x4 bias = *(const qgp_f32x4 *)(packed + L.b_off + 4 * g);
-        double acc[4] = {(double)bias[0], (double)bias[1], (double)bias[2], (double)bias[3]};
-        qgg_product(packed + L.w_off, L.nq, 0, xin, acc, lane);
-        const int row = row0 + e;
-        const bool live = row < n;
+        QGG_ROWS_OUTPUT(l);
         const double inv_b = 1.0 / (double)n;
         double *misc = tile_misc + (size_t)tile * QGG_MISC;
         qgp_f32x4 d = {0.f, 0.f, 0.f, 0.f};
@@ -143,7 +100,7 @@ __global__ __launch_bounds__(64 * QGG_WAVES) void qg_policy_grad_rows_kernel(KPo
                 if (e == 0) misc[a] = dls;
             }
             pol = qgg_sum_rows(pol), kl = qgg_sum_rows(kl), cf = qgg_sum_rows(cf);
-            if (lane == 0) misc[16] = pol, misc[17] = kl, misc[18] = cf;
+            if (lane == 0) misc[QGG_MISC_POLICY] = pol, misc[QGG_MISC_KL] = kl, misc[QGG_MISC_CLIP] = cf;
         } else {
             double vl = 0.0, dv = 0.0;
             if (live && g == 0) {
@@ -160,31 +117,11 @@ __global__ __launch_bounds__(64 * QGG_WAVES) void qg_policy_grad_rows_kernel(KPo
             }
             d[0] = (float)dv;
             vl = qgg_sum_rows(vl);
-            if (lane == 0) misc[19] = vl;
+            if (lane == 0) misc[QGG_MISC_VALUE] = vl;
         }
-        xout[lane] = d;
-        *(qgp_f32x4 *)(myrec + G.layer[tower][l].d_off + 4 * g) = d;
+        QGG_ROWS_DELTA(l, d);
     }
-
-    // ---- back through the layers: delta_l sits in the buffer layer l wrote its output to; delta_{l-1} goes to the other ----
-    for (int l = nl - 1; l >= 1; l--) {
-        const KPolLayer L = P.layer[tower][l];
-        const KGradLayer GL = G.layer[tower][l];
-        const int d_prev = G.layer[tower][l - 1].d_off;
-        const qgp_f32x4 *din = (const qgp_f32x4 *)((l & 1) ? x0 : x1);
-        qgp_f32x4 *dout = (qgp_f32x4 *)((l & 1) ? x1 : x0);
-        __syncthreads();
-        for (int m = wave; m < L.nq; m += QGG_WAVES) {          // the blocks of layer l's input = of layer l - 1's output
-            double sum[4] = {0.0, 0.0, 0.0, 0.0};
-            qgg_product(packed_t + GL.wt_off, L.nb, m, din, sum, lane);
-            const qgp_f32x4 dh = *(const qgp_f32x4 *)(myrec + d_prev + 16 * m + 4 * g);      // this thread's own store of the forward part
-            qgp_f32x4 d;
-#pragma unroll
-            for (int r = 0; r < 4; r++) d[r] = (float)(sum[r] * (double)dh[r]);
-            dout[m * 64 + lane] = d;
-            *(qgp_f32x4 *)(myrec + d_prev + 16 * m + 4 * g) = d;
-        }
-    }
+    QGG_ROWS_WALK_BACK();
 }
 
 // dW (and db, on the items of input block 0) of one slot of tiles.  Matrix instruction: A[i][k] = delta[row 4s + k][16m + i],
@@ -197,7 +134,7 @@ __global__ __launch_bounds__(64) void qg_policy_grad_weights_kernel(KPolicy P, K
     if (item == G.n_items - 1) {
         if (lane < QGG_MISC) {
             double s = 0.0;
-            if (lane < 19 || (lane == 19 && P.n_towers == 2))
+            if (lane < QGG_MISC_VALUE || (lane == QGG_MISC_VALUE && P.n_towers == 2))
                 for (int t = t0; t < t1; t++) s += tile_misc[(size_t)t * QGG_MISC + lane];
             slot_misc[(size_t)slot * QGG_MISC + lane] = s;
         }
@@ -289,9 +226,9 @@ __global__ void qg_policy_grad_reduce_kernel(KPolicy P, qg_ppo_params pp, int n,
         }
         grad[i] = (float)s;
     } else if (stats && i < n_params + 8) {
-        double sum[4] = {0.0, 0.0, 0.0, 0.0};          // policy, kl, clip count, value
+        double sum[4] = {0.0, 0.0, 0.0, 0.0};          // QGG_MISC_POLICY .. QGG_MISC_VALUE: policy, kl, clip count, value
         for (int k = 0; k < n_slots; k++)
-            for (int c = 0; c < 4; c++) sum[c] += slot_misc[(size_t)k * QGG_MISC + 16 + c];
+            for (int c = 0; c < 4; c++) sum[c] += slot_misc[(size_t)k * QGG_MISC + QGG_MISC_POLICY + c];
         double ent = 0.0;
         for (int a = 0; a < P.act_dim; a++) ent -= 0.5 + QGG_HALF_LOG_2PI + (double)params[P.src_log_std + a];
         const double b = (double)n;
@@ -351,7 +288,8 @@ extern "C" int qg_policy_reserve_grad(qg_policy *p, int32_t max_batch) {
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);         // a pass on a caller's stream may be using what this replaces
     if (max_batch <= p->grad_max) return QG_OK;
     grad_layout(p->k, &p->g);
-    const size_t tiles = ((size_t)max_batch + QGP_TILE - 1) / QGP_TILE, slots = (tiles + QGG_SLOT_TILES - 1) / QGG_SLOT_TILES;
+    const QgGradGeom geo = qg_policy_grad_geom(p, max_batch);
+    const size_t tiles = geo.tiles, slots = geo.slots;
     p->grad_max = 0;
     grad_release(p, p->d_rec);
     grad_release(p, p->d_tile_misc);
@@ -366,6 +304,20 @@ extern "C" int qg_policy_reserve_grad(qg_policy *p, int32_t max_batch) {
     QG_TRY(qg_policy_pack_transposed(p, nullptr));
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);
     p->grad_max = max_batch;
+    return QG_OK;
+}
+
+QgGradGeom qg_policy_grad_geom(const qg_policy *p, int32_t B) {
+    const int tiles = (B - 1) / QGP_TILE + 1;          // B >= 1: ceil(B / QGP_TILE), whatever the size of B
+    return {tiles, (tiles + QGG_SLOT_TILES - 1) / QGG_SLOT_TILES, (size_t)(p->k.lds0_floats + p->k.lds1_floats) * sizeof(float)};
+}
+
+int qg_policy_grad_check_rows(const qg_policy *p, const char *who, int32_t B, int32_t obs_stride, bool with_critic) {
+    if (B < 1) return fail(QG_ERR_ARG, "%s: B must be >= 1", who);
+    if (B > p->grad_max) return fail(QG_ERR_ARG, "%s: B = %d, but qg_policy_reserve_grad has reserved %d rows", who, B, p->grad_max);
+    if (obs_stride < p->desc.obs_dim) return fail(QG_ERR_ARG, "%s: obs_stride %d < obs_dim %d", who, obs_stride, p->desc.obs_dim);
+    if (obs_stride < qg_policy_row_width(p, with_critic))
+        return fail(QG_ERR_ARG, "%s: obs_stride %d < %d, the end of the critic's window", who, obs_stride, qg_policy_row_width(p, with_critic));
     return QG_OK;
 }
 
@@ -385,27 +337,19 @@ extern "C" int qg_policy_ppo_grad_device(qg_policy *p, const qg_ppo_params *pp, 
     if (!qg_finite32(pp->clip_range) || !(pp->clip_range > 0.f)) return fail(QG_ERR_ARG, "qg_ppo_params.clip_range must be finite and > 0");
     if (!qg_finite32(pp->clip_range_vf) || !qg_finite32(pp->ent_coef) || !qg_finite32(pp->vf_coef))
         return fail(QG_ERR_ARG, "qg_ppo_params: clip_range_vf, ent_coef and vf_coef must be finite");
-    if (B < 1) return fail(QG_ERR_ARG, "qg_policy_ppo_grad_device: B must be >= 1");
-    if (B > p->grad_max)
-        return fail(QG_ERR_ARG, "qg_policy_ppo_grad_device: B = %d, but qg_policy_reserve_grad has reserved %d rows", B, p->grad_max);
-    if (bt->obs_stride < p->desc.obs_dim)
-        return fail(QG_ERR_ARG, "qg_policy_ppo_grad_device: obs_stride %d < obs_dim %d", bt->obs_stride, p->desc.obs_dim);
-    if (bt->obs_stride < qg_policy_row_width(p, true))
-        return fail(QG_ERR_ARG, "qg_policy_ppo_grad_device: obs_stride %d < %d, the end of the critic's window", bt->obs_stride,
-                    qg_policy_row_width(p, true));
+    QG_TRY(qg_policy_grad_check_rows(p, "qg_policy_ppo_grad_device", B, bt->obs_stride, true));
     if (!bt->obs || !bt->actions || !bt->old_log_prob || !bt->advantages) return fail(QG_ERR_ARG, "qg_ppo_batch: null obs, actions, old_log_prob or advantages");
     if (p->desc.has_value && (!bt->returns || (pp->clip_range_vf > 0.f && !bt->old_values)))
         return fail(QG_ERR_ARG, "qg_ppo_batch: the policy has a critic: returns (and old_values when clip_range_vf > 0) are required");
     HIP_TRY(hipSetDevice(p->device), QG_ERR_DEVICE);
     const hipStream_t st = (hipStream_t)stream;
-    const int tiles = (B + QGP_TILE - 1) / QGP_TILE, slots = (tiles + QGG_SLOT_TILES - 1) / QGG_SLOT_TILES;
-    const size_t lds = (size_t)(p->k.lds0_floats + p->k.lds1_floats) * sizeof(float);
-    qg_policy_grad_rows_kernel<<<dim3((unsigned)tiles, (unsigned)p->k.n_towers), 64 * QGG_WAVES, lds, st>>>(
+    const QgGradGeom geo = qg_policy_grad_geom(p, B);
+    qg_policy_grad_rows_kernel<<<dim3((unsigned)geo.tiles, (unsigned)p->k.n_towers), 64 * QGG_WAVES, geo.lds, st>>>(
         p->k, p->g, *pp, p->d_packed, p->d_packed_t, B, *bt, p->d_rec, p->d_tile_misc);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
-    QG_TRY(qg_policy_grad_launch_weights(p, p->g, tiles, slots, st));
+    QG_TRY(qg_policy_grad_launch_weights(p, p->g, geo.tiles, geo.slots, st));
     const int threads = 256;
-    qg_policy_grad_reduce_kernel<<<(p->n_params + 8 + threads - 1) / threads, threads, 0, st>>>(p->k, *pp, B, slots, p->n_params, p->d_params,
+    qg_policy_grad_reduce_kernel<<<(p->n_params + 8 + threads - 1) / threads, threads, 0, st>>>(p->k, *pp, B, geo.slots, p->n_params, p->d_params,
                                                                                                   p->d_partial, p->d_slot_misc, grad, stats);
     HIP_TRY(hipGetLastError(), QG_ERR_LAUNCH);
     return QG_OK;

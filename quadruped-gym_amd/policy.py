@@ -13,31 +13,8 @@ import math
 
 import numpy as np
 
-from . import _abi
-from ._abi import DISTILL_LOSSES, QgAdamParams, QgPolicyDesc, QgPpoBatch, QgPpoParams, check
+from ._abi import DISTILL_LOSSES, QgAdamParams, QgDistillBatch, QgDistillParams, QgPolicyDesc, QgPpoBatch, QgPpoParams, check
 from ._handle import Handle
-
-
-class QgDistillParams(C.Structure):
-    """``qg_distill_params``: the loss (``"mse"`` / ``"kl"`` or its number) and coefficient of one distillation call (``struct_size`` is
-    filled in, the way ``_abi._Sized`` fills it)."""
-    _fields_ = [("struct_size", C.c_int32), ("loss", C.c_int32), ("coef", C.c_float), ("reserved", C.c_int32)]
-
-    @classmethod
-    def make(cls, loss="mse", coef=1.0):
-        d = _abi._Sized.make.__func__(cls)
-        d.loss, d.coef = int(DISTILL_LOSSES.get(loss, loss)), float(coef)
-        return d
-
-
-class QgDistillBatch(C.Structure):
-    """``qg_distill_batch``: device pointers of one minibatch of rows and target means (``struct_size`` is filled in)."""
-    _fields_ = [("struct_size", C.c_int32), ("obs_stride", C.c_int32), ("obs", C.c_void_p), ("target_mean", C.c_void_p),
-                ("target_log_std", C.c_void_p), ("weights", C.c_void_p)]
-
-    @classmethod
-    def make(cls, obs_stride, **ptrs):
-        return _abi._Sized.make.__func__(cls, obs_stride=int(obs_stride), **ptrs)
 
 
 def _np32(a):

@@ -1,4 +1,5 @@
-"""Shared helpers for the test-suite (state sampling, model variants, one oracle model per env, body wrenches)."""
+"""Shared helpers for the test-suite (state sampling, model variants, one oracle model per env, body wrenches, hipGraph capture)."""
+import contextlib
 import ctypes as C
 import json
 import lzma
@@ -22,6 +23,30 @@ def header_define(header, name):
     """The integer a `#define name ...` of the header stands for: a literal, or another macro's name (an alias), followed."""
     value = re.search(r"#define %s (\w+)" % name, header).group(1)
     return int(value) if value.isdigit() else header_define(header, value)
+
+
+@contextlib.contextmanager
+def capture_graph(graph, device="cuda:0"):
+    """Captures the body into ``graph`` and leaves no stream behind: which hardware queue the streams that LATER tests of this process
+    create land on depends on the streams alive, wherever the capturing module is collected.  So the capture stream is
+    created through the HIP runtime and destroyed again (``torch.cuda.Stream()`` takes one from torch's pool for good), and the capture
+    is begun and ended by hand (the first ``torch.cuda.graph(...)`` of a process takes a pool stream of its own, whether it is given one
+    or not)."""
+    import torch
+    from quadruped_gym_amd import _abi
+    lib, handle = _abi.load_library(), C.c_void_p()          # (the runtime is a dependency of the library: one lookup serves both)
+    assert lib.hipStreamCreateWithFlags(C.byref(handle), C.c_uint(1)) == 0       # hipStreamNonBlocking
+    try:
+        torch.cuda.synchronize()
+        with torch.cuda.stream(torch.cuda.ExternalStream(handle.value, device=device)):
+            graph.capture_begin()
+            try:
+                yield
+            finally:
+                graph.capture_end()
+    finally:
+        torch.cuda.synchronize()
+        assert lib.hipStreamDestroy(handle) == 0
 
 
 def reference_model(tmp_dir):

@@ -86,3 +86,34 @@ def test_step_shell_exists_once():
     # a load and a store each -- whose listings change with the macros' (7 + j) * n4 + e4 for their 7 * n4 + (j * n4 + e4)
     assert files("P.st.qpos[(7 + j) * n") == []
     assert files("7 * n4 + j4") == ["qg_kernel_link.hip"] * 2 + ["qg_kernel_resident.hip"] * 2
+
+
+def test_rows_shell_exists_once():
+    """The shell of a rows kernel of the policy's backward passes (observation tile staged, hidden layers forward with their record
+    stores, output product, walk back over the transposed image) is text of qg_policy_grad_dev.h that both rows kernels expand around
+    their own heads, not a copy per kernel: each characteristic line occurs once in the .hip / .h / .inc files of csrc/."""
+    csrc = K.CSRC
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".inc"))}
+    shell = ["qg_policy_grad_dev.h"]
+
+    def files(needle):
+        return [f for f, t in text.items() for ln in t.split("\n") if needle in ln]
+
+    for needle in (
+            # the tanh-and-derivative loop of a hidden layer
+            "const double t = tanh(sum[r]);", "dh[r] = (float)(1.0 - t * t);",
+            # the W^T delta product of the walk back, and the delta it forms
+            "qgg_product(packed_t + GL.wt_off, L.nb, m, din, sum, lane);", "d[r] = (float)(sum[r] * (double)dh[r]);",
+            # the record stores: the staged observation, a hidden layer's h and tanh', the output delta, the delta of the walk back
+            "rec[(size_t)(row0 + ee) * G.rec + G.layer[tower][0].h_off + c] = v;", "(myrec + h_next + 16 * m + 4 * g) = h;",
+            "(myrec + d_own + 16 * m + 4 * g) = dh;", "(myrec + G.layer[tower][l].d_off + 4 * g) = D", "(myrec + d_prev + 16 * m + 4 * g) = d;"):
+        assert files(needle) == shell, needle
+    # both rows kernels expand every piece of it, once, in their bodies
+    pieces = ["QGG_ROWS_ENTRY(", "QGG_ROWS_STAGE(", "QGG_ROWS_LAYER(", "QGG_ROWS_HIDDEN(", "QGG_ROWS_OUTPUT(", "QGG_ROWS_DELTA(", "QGG_ROWS_WALK_BACK("]
+    for unit, kernel in (("qg_policy_grad.hip", "qg_policy_grad_rows_kernel"), ("qg_policy_distill.hip", "qg_policy_distill_rows_kernel")):
+        body = text[unit].split("void %s(" % kernel, 1)[1].split("\n}\n", 1)[0]
+        assert [body.count(p) for p in pieces] == [1] * len(pieces), unit
+        assert [text[unit].count(p) for p in pieces] == [1] * len(pieces), unit
+    assert all(text["qg_policy_grad_dev.h"].count("#define " + p) == 1 for p in pieces)
+    # the two row sums stay two (the butterfly and the ascending order round differently), both beside the shell
+    assert files("double qgg_sum_rows(double v)") == shell and files("double qgd_sum_rows(double v, int lane)") == shell

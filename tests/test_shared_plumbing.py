@@ -61,7 +61,7 @@ def test_every_struct_with_a_struct_size_is_sized():
     sized = _sized_classes()
     with_field = [v for v in vars(_abi).values() if isinstance(v, type) and issubclass(v, C.Structure) and v is not _abi._Sized
                   and "struct_size" in [f[0] for f in getattr(v, "_fields_", [])]]
-    assert sorted(c.__name__ for c in with_field) == sorted(c.__name__ for c in sized) and len(sized) == 12
+    assert sorted(c.__name__ for c in with_field) == sorted(c.__name__ for c in sized) and len(sized) == 14
     for cls in sized:
         assert cls._fields_[0][0] == "struct_size"
 
@@ -70,9 +70,10 @@ def test_every_struct_with_a_struct_size_is_sized():
     lambda: _abi.QgPolicyDesc.make(33, (64, 64), 12), lambda: _abi.QgPpoParams.make(), lambda: _abi.QgPpoBatch.make(33, obs=16),
     lambda: _abi.QgAdamParams.make(), lambda: _abi.QgNormDesc.make(33, 8), lambda: _abi.QgRolloutDesc.make(8, 4, 33, 12),
     lambda: _abi.QgRolloutStorage.make(), lambda: _abi.QgRolloutStep.make(done_stride=1), lambda: _abi.QgRolloutBatch.make(),
-    lambda: _abi.QgPerturbDesc.make(8, 33), lambda: _abi.QgContactDesc.make(1.5), lambda: _abi.QgGaitDesc.make()],
+    lambda: _abi.QgPerturbDesc.make(8, 33), lambda: _abi.QgContactDesc.make(1.5), lambda: _abi.QgGaitDesc.make(),
+    lambda: _abi.QgDistillParams.make("kl", 0.25), lambda: _abi.QgDistillBatch.make(33, obs=16)],
     ids=["policy_desc", "ppo_params", "ppo_batch", "adam_params", "norm_desc", "rollout_desc", "rollout_storage", "rollout_step",
-         "rollout_batch", "perturb_desc", "contact_desc", "gait_desc"])
+         "rollout_batch", "perturb_desc", "contact_desc", "gait_desc", "distill_params", "distill_batch"])
 def test_make_fills_struct_size(make):
     d = make()
     assert isinstance(d, _abi._Sized) and d.struct_size == C.sizeof(type(d)) > 0

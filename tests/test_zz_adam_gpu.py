@@ -11,7 +11,6 @@ value or 1e-7, whichever is larger.
 The file name sorts after every other module's on purpose: collected first (as test_adam_gpu.py), the module shifted the state of
 the process in which a resident-mode case of tests/test_resident_gpu.py runs 700 tests later, and that case failed."""
 import collections
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -21,6 +20,7 @@ import torch
 import adam_reference as A
 import policy_reference as R
 import ppo_reference as G
+from helpers import capture_graph
 from policy_checks import DEV
 
 from quadruped_gym_amd import _abi
@@ -30,27 +30,6 @@ pytestmark = pytest.mark.gpu
 F32 = np.float32
 Samples = collections.namedtuple("Samples", G.Batch._fields)
 KW = dict(lr=A.LR, betas=(A.BETA1, A.BETA2), eps=A.EPS)
-
-
-@contextlib.contextmanager
-def _capture(graph):
-    """Captures the body into ``graph`` and leaves no stream behind: which hardware queue the streams that LATER tests of this process
-    create land on depends on the streams alive, wherever this module is collected.  So the capture stream is created through
-    the HIP runtime and destroyed again (``torch.cuda.Stream()`` takes one from torch's pool for good), and the capture is begun and
-    ended by hand (the first ``torch.cuda.graph(...)`` of a process takes a pool stream of its own, whether it is given one or not)."""
-    lib, handle = _abi.load_library(), C.c_void_p()          # (the runtime is a dependency of the library: one lookup serves both)
-    assert lib.hipStreamCreateWithFlags(C.byref(handle), C.c_uint(1)) == 0       # hipStreamNonBlocking
-    try:
-        torch.cuda.synchronize()
-        with torch.cuda.stream(torch.cuda.ExternalStream(handle.value, device=DEV)):
-            graph.capture_begin()
-            try:
-                yield
-            finally:
-                graph.capture_end()
-    finally:
-        torch.cuda.synchronize()
-        assert lib.hipStreamDestroy(handle) == 0
 
 
 def _dev(a):
@@ -199,7 +178,7 @@ def test_replayed_graph_counts_its_steps_on_the_device():
         eager.append(tgrad.cpu().numpy())
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with _capture(graph):
+    with capture_graph(graph, DEV):
         pol.ppo_grad(db, grad, s8)
         pol.adam_step(grad, max_grad_norm=A.MAX_NORM, stats=s4, **KW)
     torch.cuda.synchronize()
@@ -229,7 +208,7 @@ def test_lr_tensor_is_read_at_every_replay():
     lr_t = torch.tensor([A.LR], device=DEV)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with _capture(graph):
+    with capture_graph(graph, DEV):
         pol.ppo_grad(db, grad, None)
         pol.adam_step(grad, lr=123.0, betas=(A.BETA1, A.BETA2), eps=A.EPS, max_grad_norm=A.MAX_NORM, lr_tensor=lr_t, stats=s4)
     lrs, grads, states = [A.LR, float(F32(1e-3)), 0.0], [], []

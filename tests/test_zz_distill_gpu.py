@@ -15,7 +15,6 @@ are different sums, and the last bit may differ; that is not asserted either way
 
 The module's name puts it behind the other modules in collection, as the others that capture hipGraphs."""
 import collections
-import contextlib
 import ctypes as C
 import math
 import os
@@ -28,6 +27,7 @@ import adam_reference as A
 import distill_reference as D
 import policy_reference as R
 import ppo_reference as G
+from helpers import capture_graph
 from policy_checks import DEV
 
 from quadruped_gym_amd import _abi
@@ -43,25 +43,6 @@ def _record(line):
     if out:
         with open(out, "a") as fh:
             fh.write(line + "\n")
-
-
-@contextlib.contextmanager
-def _capture(graph):
-    """Captures the body into ``graph`` and leaves no stream behind (the reason: tests/test_zz_adam_gpu.py): the capture stream is created
-    through the HIP runtime and destroyed again, the capture begun and ended by hand."""
-    lib, handle = _abi.load_library(), C.c_void_p()
-    assert lib.hipStreamCreateWithFlags(C.byref(handle), C.c_uint(1)) == 0       # hipStreamNonBlocking
-    try:
-        torch.cuda.synchronize()
-        with torch.cuda.stream(torch.cuda.ExternalStream(handle.value, device=DEV)):
-            graph.capture_begin()
-            try:
-                yield
-            finally:
-                graph.capture_end()
-    finally:
-        torch.cuda.synchronize()
-        assert lib.hipStreamDestroy(handle) == 0
 
 
 def _dev(a):
@@ -211,7 +192,7 @@ def test_three_replays_of_a_captured_step_leave_the_bits_of_three_eager_steps():
     grad.fill_(float("nan")), stats.fill_(float("nan"))
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with _capture(graph):
+    with capture_graph(graph, DEV):
         pol.distill_grad(obs, target, grad, stats, **kw)
         pol.adam_step(grad, lr=D.REPLAY_RATE)
     torch.cuda.synchronize()
