@@ -1305,6 +1305,132 @@ int qg_priv_read_device(qg_priv *priv, const float *obs, int32_t obs_stride, int
 /* Synchronous, into a host [n][QG_PRIV_DIM] array (no observation in front). */
 int qg_priv_read(qg_priv *priv, float *host_out);
 
+/* ---- commanded gait schedule: a per-env phase oscillator, clock inputs for the policy and rewards that hold the feet to it ------------------
+ * A qg_sched is bound to a qg_contact.  Its launch (qg_sched_advance_device) advances, per env, a phase oscillator with a commanded gait
+ * (which foot is to stand when, at which stepping frequency), writes the oscillator as ten clock columns behind the observation and
+ * reduces four reward terms that compare the feet with the schedule.  The ground forces, the feet's position and velocity and the
+ * contact flags are the contact sensor's, computed by its device code from the simulator's state AS IT STANDS IN MEMORY, with
+ * advance == 0 semantics: THE SENSOR'S TIMERS AND ARMED FLAGS ARE NEITHER READ NOR WRITTEN.  The launch is not the advancing read of
+ * its env-step: it composes with qg_gait_reward_device and qg_contact_read_device in any order.
+ *
+ * State per env, in device memory: phi (u32, the phase as a fraction of 2^32; it wraps by integer overflow) and episode (i64, this
+ * handle's own counter, 0 in a new handle; NOT the simulator's).
+ *
+ * Keys.  Every draw is a pure function of (seed, env_index_base + i, episode_i, stream), through qg_perturb's k(s) -- the same mix64,
+ * the same 24-bit result, the same formula -- in a key space of its own:
+ *   seed_s = seed + 0x5147534348454431                                        (mod 2^64; ASCII "QGSCHED1")
+ *   k(s): x = seed_s + 0xA0761D6478BD642F * s + 0x9E3779B97F4A7C15 * (env + 1) + 0xD1B54A32D192ED03 * (episode + 1);  k = mix64(mix64(x)) >> 40
+ * The parameters of the running episode of env i, recomputed from the key wherever they are needed, never stored:
+ *   g    = (k(0) * n_gaits) >> 24                                             the row of the gait table
+ *   freq = f32(freq_lo + f32(span * f32(k(1) * 2^-24)))                       Hz; span = f32(freq_hi - freq_lo): one product, one add, no fma
+ *   phi0 = random_phase ? k(2) << 8 : 0                                       the phase the episode starts at
+ * Table integers, formed on the host at create from row g's (offset[4], duty):
+ *   off_f = u32(rint(f64(offset_f) * 2^32)) mod 2^32;   D = u32(rint(f64(duty) * 2^32))
+ * Step increment, with dt32 = f32(model.timestep * frame_skip) of the simulator's task at the call, as the sensor forms its dt:
+ *   dphi = u32(rint(f64(freq) * f64(dt32) * 2^32))        a launch with freq_hi * dt32 > 0.5 is refused
+ *
+ * The launch, for env i, in this order:
+ *   1. phi += dphi.
+ *   2. For foot f = 0..3 (bodies 3, 6, 9, 12); every float below is exact in f32:
+ *        q_f = phi + off_f (mod 2^32);  hard_f = q_f < D;  p_f = f32(q_f >> 8) * 2^-24;  d = f32(D >> 8) * 2^-24
+ *        m_f = hard_f ? min(p_f, d - p_f) : -min(p_f - d, 1 - p_f)            the signed distance to the nearer edge of the stance
+ *        s_f = kappa == 0 ? (hard_f ? 1 : 0) : clamp(0.5 + m_f * inv2k, 0, 1)  inv2k = f32(1 / (2 f64(kappa))); one product, one add, no fma
+ *   3. The stand gate.  With command [n] rows (cmd_x, cmd_y): where max(|cmd_x|, |cmd_y|) <= min_command_speed every s_f = 1 and
+ *      every hard_f is true (the schedule says "stand"); the phase and the clock columns keep running.  Without a command no env stands.
+ *   4. F[b], the foot origin's position x and velocity v, and contact_f = F[foot f].z > force_threshold: bit for bit what
+ *      qg_contact_read_device(advance = 0) reports for that state.
+ *   5. The unweighted terms, f32, every product and sum rounded (no fma), sums over feet in ascending f:
+ *        0 swing_force      sum_f (1 - s_f) (1 - expf(-((Fx Fx + Fy Fy) + Fz Fz) * inv_sf2))      inv_sf2 = f32(1 / f64(sigma_force)^2)
+ *        1 stance_velocity  sum_f s_f (1 - expf(-((vx vx + vy vy) + vz vz) * inv_sv2))            inv_sv2 = f32(1 / f64(sigma_velocity)^2)
+ *        2 swing_height     sum_f (1 - s_f) (x_z - swing_height_target)^2
+ *        3 contact_match    the number of feet with contact_f == hard_f, 0..4, exact
+ *   6. components[i][base_terms + k] = f32(w_k * term_k);  shaped_i = their f32 sum in ascending k;  reward_out[i] = reward[i] + shaped_i
+ *      (shaped_i alone where reward is NULL; reward_out may be reward).  reward, reward_out, components, base_components (copied in
+ *      front, or in place where it IS components at the same stride) and the strides follow qg_gait_reward_device's rules, with
+ *      base_terms <= QG_MONITOR_MAX_TERMS - 4.  Here every output is nullable: a launch without any only advances the phase.
+ *   7. The clock columns (QG_SCHED_DIM = 10), of a phase phi, gait row g and frequency freq:
+ *        0-3  sinpif(2 p_f)     4-7  cospif(2 p_f)     8  freq     9  d
+ *      out[i] = [ obs[i][0 : obs_dim] | the 10 columns ], the observation copied as qg_priv_read_device copies it (16-byte accesses
+ *      where alignment allows, the same bits either way).  obs == out at the same stride: the observation is in place already and
+ *      only the ten columns are written; any other overlap is refused.  out is nullable.
+ *   8. Where done names env i (a new episode has begun in the simulator): its four components are exact zeros and its reward passes
+ *      through bit for bit.
+ *        QG_PERTURB_DONE_ROW_TERMINAL (the walking env): the row's clock columns are the old episode's, after its advance;
+ *        QG_PERTURB_DONE_ROW_RESET (the partially observable env): the row's columns are the new episode's at its phi0, with its gait
+ *          and frequency; the rows of terminal_obs / terminal_out (nullable; the same copy and in-place rules) of the FINISHED envs get
+ *          the old episode's columns after its advance; rows of live envs are not touched there;
+ *        both: then episode += 1 and phi = phi0 of the new episode.
+ *
+ * begin (an explicit reset, qg_sched_begin_device): for the envs of the mask (all, when NULL): episode += 1, phi = phi0 of the new
+ * episode, and, where rows are given, rows[i][obs_dim : obs_dim + 10] = the new episode's columns at phi0.  Other rows are not touched.
+ *
+ * qg_sched_advance_device is ONE kernel launch on the caller's stream behind the step whose state it is to see (qg_sched_begin_device is
+ * one launch of its own): no allocation, no wait, no LDS, no atomics; capturable, and a replay advances the phase; bit-reproducible
+ * eagerly and under graph replay; rows depend on their env and key alone, so shards with env_index_base reproduce one big handle.
+ * One lane owns an env's phi and episode: it alone reads and writes them.  Refused while the resident step mode is on
+ * (qg_resident_stop first); every refusal is QG_ERR_ARG and comes before anything is launched.  Outputs for non-finite inputs are
+ * unspecified.  qg_sched_create, _destroy, _set_weights, _get_gaits, _state_bytes, _get_state and _set_state wait for the device and
+ * must not be called during a capture.  Destroy the qg_sched before its qg_contact. */
+#define QG_SCHED_NTERMS 4
+#define QG_SCHED_SWING_FORCE 0
+#define QG_SCHED_STANCE_VELOCITY 1
+#define QG_SCHED_SWING_HEIGHT 2
+#define QG_SCHED_CONTACT_MATCH 3
+#define QG_SCHED_DIM 10
+#define QG_SCHED_SIN 0
+#define QG_SCHED_COS 4
+#define QG_SCHED_FREQ 8
+#define QG_SCHED_DUTY 9
+#define QG_SCHED_MAX_GAITS 8
+typedef struct qg_sched qg_sched;
+typedef struct qg_sched_gait {
+    float offset[4];                   /* per foot, in [0, 1): the fraction of a period by which the foot leads the oscillator */
+    float duty;                        /* in [1/64, 63/64]: the fraction of a period the foot is to stand */
+} qg_sched_gait;
+typedef struct qg_sched_desc {
+    int32_t struct_size;               /* sizeof(qg_sched_desc): checked */
+    int32_t reserved;                  /* 0 */
+    int32_t n_gaits;                   /* 1 .. QG_SCHED_MAX_GAITS rows of `gaits` */
+    int32_t random_phase;              /* 0 or 1 */
+    int32_t done_row;                  /* QG_PERTURB_DONE_ROW_RESET or _TERMINAL */
+    float freq_lo;                     /* Hz; 0 < freq_lo <= freq_hi, finite */
+    float freq_hi;
+    float kappa;                       /* half-width of the stance / swing ramp in phase units, 0 <= kappa <= 1/128 */
+    float sigma_force;                 /* N; finite, > 0 */
+    float sigma_velocity;              /* m/s; finite, > 0 */
+    float swing_height_target;         /* m; finite */
+    float min_command_speed;           /* the command's units; finite, >= 0 */
+    float weights[QG_SCHED_NTERMS];    /* w_k, any sign; finite */
+    qg_sched_gait gaits[QG_SCHED_MAX_GAITS];
+    uint64_t seed;
+    uint64_t env_index_base;           /* env i of this handle is env env_index_base + i of the run */
+} qg_sched_desc;
+/* Validation (QG_ERR_ARG) comes before the handle and the device are looked at.  A new handle has episode = 0 and phi = phi0 of
+ * episode 0 for every env. */
+int qg_sched_create(qg_contact *contact, const qg_sched_desc *desc, qg_sched **out);
+int qg_sched_destroy(qg_sched *sched);
+/* weights [QG_SCHED_NTERMS], host, finite: read by the launches that follow; a captured graph keeps the weights it was captured with. */
+int qg_sched_set_weights(qg_sched *sched, const float *weights);
+/* done: a done vector (QG_DONE_*), nullable.  reward (nullable; only with reward_out), reward_out: f32 [n] at strides >= 1.
+ * components: [n] rows at components_stride >= base_terms + 4; base_components: see above (base_stride >= base_terms; NULL with
+ * base_terms = 0; only with components).  command: nullable, [n] rows of 2 floats at command_stride >= 2.  obs: nullable [n] rows of
+ * obs_dim floats at obs_stride >= obs_dim (NULL: obs_dim must be 0); out: nullable, [n] rows at out_stride >= obs_dim + 10.
+ * terminal_obs / terminal_out: nullable, rows as obs / out at their own strides; terminal_out only with QG_PERTURB_DONE_ROW_RESET. */
+int qg_sched_advance_device(qg_sched *sched, const void *done, int32_t done_kind, int32_t done_stride, const float *reward, int32_t reward_stride,
+                         float *reward_out, int32_t reward_out_stride, float *components, int32_t components_stride,
+                         const float *base_components, int32_t base_stride, int32_t base_terms, const float *command, int32_t command_stride,
+                         const float *obs, int32_t obs_stride, int32_t obs_dim, float *out, int32_t out_stride, const float *terminal_obs,
+                         int32_t terminal_obs_stride, float *terminal_out, int32_t terminal_out_stride, void *stream);
+/* mask: nullable device [n] u8 (non-zero selects); rows: nullable device rows at row_stride >= obs_dim + 10 (obs_dim >= 0). */
+int qg_sched_begin_device(qg_sched *sched, const uint8_t *mask, float *rows, int32_t row_stride, int32_t obs_dim, void *stream);
+/* Host arrays [n], each nullable: the gait row g, freq and phi of the running episodes. */
+int qg_sched_get_gaits(qg_sched *sched, int32_t *gait, float *freq, uint32_t *phi);
+/* The per-env state (phi, episode) as ONE opaque blob of *bytes bytes (host pointer); restoring it into a handle of the same shape
+ * reproduces every later launch bit for bit.  The round trip is exact. */
+int qg_sched_state_bytes(const qg_sched *sched, int64_t *bytes);
+int qg_sched_get_state(qg_sched *sched, void *blob);
+int qg_sched_set_state(qg_sched *sched, const void *blob);
+
 #ifdef __cplusplus
 }
 #endif

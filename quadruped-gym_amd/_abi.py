@@ -372,6 +372,14 @@ PRIV_COLUMNS = (("base_lin_vel", 0, 3), ("base_ang_vel", 3, 3), ("gravity_dir", 
                 ("body_contact", 66, 1), ("dynamics", 67, NDYN), ("frame_wrench", 78, 6), ("episode_time", 84, 1))
 PRIV_DIM = 85
 
+# the commanded gait schedule (qg_sched_*): its reward terms in the order of their columns (QG_SCHED_* of include/quadgym.h), the clock
+# columns behind an observation as (name, first column, width), and the limits of its description
+SCHED_TERMS = ("swing_force", "stance_velocity", "swing_height", "contact_match")
+SCHED_MAX_BASE_TERMS = MONITOR_MAX_TERMS - len(SCHED_TERMS)
+SCHED_COLUMNS = (("clock_sin", 0, 4), ("clock_cos", 4, 4), ("gait_freq", 8, 1), ("gait_duty", 9, 1))
+SCHED_DIM = 10
+SCHED_MAX_GAITS = 8
+
 
 def package_dir() -> str:
     return os.path.dirname(os.path.abspath(__file__))
@@ -540,6 +548,17 @@ PROTOTYPES = {
     "qg_priv_destroy": [_vp],
     "qg_priv_read_device": [_vp, _vp, _i32, _i32, _vp, _i32, _vp],
     "qg_priv_read": [_vp, _vp],
+    # the commanded gait schedule (qg_sched_desc's mirror, QgSchedDesc, lives in schedule.py)
+    "qg_sched_create": [_vp, _vp, _P(_vp)],
+    "qg_sched_destroy": [_vp],
+    "qg_sched_set_weights": [_vp, _P(C.c_float)],
+    "qg_sched_advance_device": [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32,
+                             _vp, _i32, _vp, _i32, _vp],
+    "qg_sched_begin_device": [_vp, _vp, _vp, _i32, _i32, _vp],
+    "qg_sched_get_gaits": [_vp, _vp, _vp, _vp],
+    "qg_sched_state_bytes": [_vp, _P(C.c_int64)],
+    "qg_sched_get_state": [_vp, _vp],
+    "qg_sched_set_state": [_vp, _vp],
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "qg_host.h"
+#include "qg_key_dev.h"
 
 #define QGP_SALT 0x51474E4F49534531ull
 #define QGP_NJ 12
@@ -32,20 +33,7 @@
 #define QGP_NOISY 140
 #define QGP_NCONST 204
 
-// the simulator's stream hash (qg_device.h: uniform24s) as the integer behind it, on both sides of the launch
-__host__ __device__ static inline uint64_t qgp_mix64(uint64_t x) {
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-// what (seed_p, env, episode) contribute to every stream of the key
-__host__ __device__ static inline uint64_t qgp_key(uint64_t seed_p, uint64_t env_index, uint64_t episode) {
-    return seed_p + 0x9E3779B97F4A7C15ull * (env_index + 1) + 0xD1B54A32D192ED03ull * (episode + 1);
-}
-__host__ __device__ static inline uint32_t qgp_k(uint64_t key, uint64_t stream) {
-    return (uint32_t)(qgp_mix64(qgp_mix64(key + 0xA0761D6478BD642Full * stream)) >> 40);
-}
+// (qgp_mix64, qgp_key, qgp_k -- the keyed draw k(s), on both sides of the launch: qg_key_dev.h)
 __host__ __device__ static inline int32_t qgp_delay(uint64_t key, int32_t lo, int32_t hi) {
     return lo + (int32_t)(((uint64_t)qgp_k(key, 0) * (uint64_t)(hi - lo + 1)) >> 24);
 }

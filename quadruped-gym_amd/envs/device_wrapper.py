@@ -1,12 +1,15 @@
 """``DeviceVecEnvWrapper`` -- what the VecEnv wrappers around a device-side layer share (``DeviceVecNormalize``,
-``DevicePerturbedVecEnv``, ``DeviceGaitRewardVecEnv``, ``DevicePrivilegedVecEnv``): the wrapped env and the pass-through to it, the
+``DevicePerturbedVecEnv``, ``DeviceGaitRewardVecEnv``, ``DeviceGaitScheduleVecEnv``, ``DevicePrivilegedVecEnv``): the wrapped env and the pass-through to it, the
 buffers of a ``step_tensor`` call by name, the upload of the NumPy cold path, the finished envs whose info holds a terminal
 observation, checkpoint / resume / close over the layer, and the walk along a stack's ``.venv`` chain by which a wrapper refuses, at
 construction, an order of the stack that cannot work.
 
 The orders that work, inside to outside: ``DevicePerturbedVecEnv`` next to the env (never around ``DevicePrivilegedVecEnv``: its
 noise belongs on the actor's columns); ``DeviceGaitRewardVecEnv`` anywhere, but with ``gate_on_command=True`` inside any
-``DeviceVecNormalize`` that normalises observations (the gate reads the command in m/s); ``DeviceVecNormalize`` outside
+``DeviceVecNormalize`` that normalises observations (the gate reads the command in m/s); ``DeviceGaitScheduleVecEnv`` around the walking
+envs only (the plain env's packed rows have no command and no room for the clock), outside ``DevicePerturbedVecEnv`` (the clock is no
+sensor), on either side of ``DeviceGaitRewardVecEnv``, inside ``DevicePrivilegedVecEnv`` (the actor's window must hold the clock) and,
+with ``gate_on_command=True``, inside a normaliser of observations; ``DeviceVecNormalize`` outside
 ``DevicePrivilegedVecEnv`` around the walking envs, and inside it around the plain env, whose packed step keeps the wide rows apart."""
 from __future__ import annotations
 

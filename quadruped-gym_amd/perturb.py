@@ -171,6 +171,9 @@ class DevicePerturbedVecEnv(DeviceVecEnvWrapper):
         if stack_layer(venv, "privileged") is not None:     # before any handle: the noise would land on the truth columns
             raise ValueError("DevicePerturbedVecEnv around DevicePrivilegedVecEnv: sensor noise, bias and latency belong on the actor's "
                              "columns only; put it inside, DevicePrivilegedVecEnv(DevicePerturbedVecEnv(env))")
+        if stack_layer(venv, "gait_schedule") is not None:  # the clock columns are no sensor, and the rows are no whole frames any more
+            raise ValueError("DevicePerturbedVecEnv around DeviceGaitScheduleVecEnv: the rows are 10 clock columns wider than the env's "
+                             "frames and the clock takes no sensor noise; put it inside, DeviceGaitScheduleVecEnv(DevicePerturbedVecEnv(env))")
         po = hasattr(venv, "obs_window")                    # the stacked frames; its finished rows hold the reset stack
         frame = venv.FRAME if po else venv.obs_dim
         window = venv.obs_window if po else 1
