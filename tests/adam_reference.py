@@ -1,9 +1,12 @@
 """The float64 definition of what FusedMlpPolicy.adam_step and .normalize_advantages compute (include/quadgym.h, "Adam, gradient-norm
 clipping and advantage normalisation"), in NumPy: torch.nn.utils.clip_grad_norm_ + torch.optim.Adam (amsgrad off, no weight decay) and
 SB3's normalize_advantage -- the formulae and nothing cleverer, in float64 or in float32 arithmetic --, the three nets and the gradient
-recipe the CPU and GPU tests share, and the error budget measured by tests/test_adam_reference.py.  No GPU, no torch."""
+recipe the CPU and GPU tests share (the recipe also takes a description ``(obs_dim, hidden, act_dim, critic)`` in place of a net's
+name: tests/test_policy_backward_shapes_gpu.py runs it over policy_reference.SHAPE_TABLE), and the error budget measured by
+tests/test_adam_reference.py.  No GPU, no torch."""
 import functools
 import math
+import zlib
 
 import numpy as np
 
@@ -47,8 +50,13 @@ def derived_m_tolerance(m_old, g, coef64, m64):
 MARGIN = 4.0          # a different but equally valid rounding order: contraction into fma, rsqrt against sqrt and divide
 
 
+def net_of(name):
+    """``(obs_dim, hidden, act_dim, critic)``: a key of ``NETS``, or such a description itself."""
+    return NETS[name] if isinstance(name, str) else (int(name[0]), tuple(int(h) for h in name[1]), int(name[2]), bool(name[3]))
+
+
 def n_params(name):
-    obs_dim, hidden, act_dim, critic = NETS[name]
+    obs_dim, hidden, act_dim, critic = net_of(name)
     layout = FusedMlpPolicy.param_layout(obs_dim, hidden, act_dim, critic)
     off, shape = list(layout.values())[-1]
     return off + math.prod(shape)
@@ -84,12 +92,13 @@ def ulp32(x):
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------------------------
 def _seed(name, *more):
-    return [ord(name)] + [int(x) for x in more]
+    """The seed of a net's draws: a named net's is its letter (as it always was), a description's the CRC of its text."""
+    return [ord(name) if isinstance(name, str) else zlib.crc32(repr(net_of(name)).encode())] + [int(x) for x in more]
 
 
 def initial_params(name):
-    """Random parameters, torch.nn.Linear-like per tensor; ``log_std`` around -1."""
-    obs_dim, hidden, act_dim, critic = NETS[name]
+    """Random parameters, torch.nn.Linear-like per tensor; ``log_std`` around -1.  ``name``: a key of ``NETS`` or a description."""
+    obs_dim, hidden, act_dim, critic = net_of(name)
     rng = np.random.default_rng(_seed(name, 1))
     flat = np.empty(n_params(name), F32)
     for key, (off, shape) in FusedMlpPolicy.param_layout(obs_dim, hidden, act_dim, critic).items():
@@ -101,8 +110,8 @@ def initial_params(name):
 
 def make_gradient(name, seed, norm):
     """Normal draws with a scale per tensor (three decades) and a block of exact zeros, scaled to the Euclidean ``norm``; then a
-    block of magnitude 1e-12; float32."""
-    obs_dim, hidden, act_dim, critic = NETS[name]
+    block of magnitude 1e-12; float32.  ``name``: a key of ``NETS`` or a description."""
+    obs_dim, hidden, act_dim, critic = net_of(name)
     rng = np.random.default_rng(_seed(name, 2, seed))
     n = n_params(name)
     g = np.empty(n, np.float64)

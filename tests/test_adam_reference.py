@@ -1,5 +1,6 @@
 """The float64 checker of the optimiser step (tests/adam_reference.py) against torch on the CPU, and the error budget the GPU tests of
 tests/test_zz_adam_gpu.py use: how far the float32 evaluation of one step lies from the float64 evaluation of the same float32 inputs."""
+import hashlib
 import math
 
 import numpy as np
@@ -7,6 +8,8 @@ import pytest
 import torch
 
 import adam_reference as A
+import policy_backward_shapes as S
+import policy_reference as R
 
 from quadruped_gym_amd.policy import FusedMlpPolicy
 
@@ -72,6 +75,61 @@ def test_error_budget_is_within_the_committed_constants():
     # the constants are the measurement, rounded up: not a looser figure
     assert A.BUDGET_M_ULP <= 1.25 * worst[0] and A.BUDGET_V_ULP <= 1.25 * worst[1] and A.BUDGET_P <= 1.25 * worst[2]
     assert set(A.GPU_STEPS) <= set(A.BUDGET_STEPS)
+
+
+# sha256 of initial_params(name) and of make_gradient(name, seed, norm) for (0, 50.0), (41, 1.0), (1001, 0.1), taken before the three
+# functions learnt to take a description as well as a name: the named nets' arrays have not changed by a bit
+_DIGESTS = {
+    "A": (50, "a5a73936d83ffd847f02bc9d38e2b054b833d53098fd2768d59d5ec04eeaddba",
+          "17e83ca8e635f2ee049201093c7347ddbe1af7febcb93c58a84370b934bce101", "b6c505aa5730846abf17800d780c1aba7bb5c969ef616a85f6ea2097c7cd913c",
+          "e7ea010b693e55d6f394942737f0f9ee7d6bae0feee59704ad4588f1efca6ee1"),
+    "B": (13529, "f93f6286c7813613e288ee93dbbfc4851f99e0c7911488e4b357be14b0546546",
+          "1136acab6174e755345a98d4781f2cbbeeb535cd81e6af6d077b630ddb969a7f", "319d8705564bb6e8a214d951e304c13bd02d242305abd63863c173179c5a4390",
+          "0264a2abeb958397f66c0733609af6b72c1389bb826b86966f751ed52957d87a"),
+    "C": (332697, "07d78091227b5a66d728e485686521f48cce731d470a1f0749861ba08c266aaf",
+          "b6c4c85180cfad2a01d7a43d2c3df075597e0c67892ffc05286bfc662a9bdf4c", "4bef351d37cdcab0c3b7dfe526b7f0ac0a6063361724711bbc91185c39ab72f8",
+          "f1d204e23a2034a1e5b762c15e5727d810f994d2eb0878049460687fd7f3d093"),
+}
+
+
+@pytest.mark.parametrize("name", list(_DIGESTS))
+def test_named_nets_keep_their_bits(name):
+    n, params, *grads = _DIGESTS[name]
+    assert A.n_params(name) == n
+    assert hashlib.sha256(A.initial_params(name).tobytes()).hexdigest() == params
+    for (seed, norm), want in zip(((0, 50.0), (41, 1.0), (1001, 0.1)), grads):
+        assert hashlib.sha256(A.make_gradient(name, seed, norm).tobytes()).hexdigest() == want, (seed, norm)
+
+
+def test_a_description_is_a_net_of_its_own():
+    """A description gives arrays of its own layout and its own draws: the description of net B is not net B's stream."""
+    desc = A.NETS["B"]
+    assert A.n_params(desc) == A.n_params("B") and A.net_of("B") == A.net_of(desc) == desc
+    p, g = A.initial_params(desc), A.make_gradient(desc, 0, 50.0)
+    assert p.dtype == g.dtype == np.float32 and p.shape == g.shape == (13529,)
+    assert not np.array_equal(p, A.initial_params("B")) and np.array_equal(p, A.initial_params(list(desc)))
+    assert abs(float(np.sqrt(np.sum(g.astype(np.float64) ** 2))) - 50.0) < 1e-4
+    for i, critic in S.adam_float64_rows([A.NETS[k] for k in "ABC"]):
+        d = S.adam_desc(i, critic)
+        assert A.n_params(d) == S.n_params(d[:3], critic) == R.param_count(*d[:3], critic)
+        assert A.initial_params(d).shape == A.make_gradient(d, 1, 1.0).shape == (A.n_params(d),)
+
+
+def test_rows_of_the_shape_table_stay_inside_the_budget():
+    """The rows tests/test_policy_backward_shapes_gpu.py holds to the float64 step (those that carry a tail n_params % 4 or a boundary
+    alignment nets A, B, C do not have), at the step and mode it uses (t = 1, clipping active): the NumPy float32 evaluation alone stays
+    inside the committed budgets, which were measured on the three nets and are not raised for these."""
+    rows = S.adam_float64_rows([A.NETS[k] for k in "ABC"])
+    assert rows == [(0, True), (1, False), (2, False), (7, False)]
+    for i, critic in rows:
+        desc = S.adam_desc(i, critic)
+        p, m, v, g, max_norm, ref = A.one_step_case(desc, 1, "active")
+        _, m32, v32, _, info = A.clip_and_adam(p, m, v, 0, g, A.LR, A.BETA1, A.BETA2, A.EPS, max_norm, np.float32)
+        dev = A.deviations(m32, v32, info["dp"], ref)
+        print(f"{S.row_id(i)} critic {int(critic)} ({A.n_params(desc)} parameters): m {dev[0]:.3f} ulp  v {dev[1]:.3f} ulp  "
+              f"|dp32 - dp64| / lr {dev[2]:.3e}")
+        assert float(ref[3]["coef"]) < 1.0
+        assert dev[0] <= A.BUDGET_M_ULP and dev[1] <= A.BUDGET_V_ULP and dev[2] <= A.BUDGET_P, (i, critic, dev)
 
 
 def test_tolerances_follow_the_budget():
