@@ -1431,6 +1431,120 @@ int qg_sched_state_bytes(const qg_sched *sched, int64_t *bytes);
 int qg_sched_get_state(qg_sched *sched, void *blob);
 int qg_sched_set_state(qg_sched *sched, const void *blob);
 
+/* ---- command curriculum: an adaptive grid over (speed, velocity angle) that decides what the robots are asked to do -----------------------
+ * A qg_cmdcur is bound to a qg_walk.  Each env runs a SEGMENT: a commanded (speed, velocity angle alpha, heading angle theta) drawn from
+ * one bin of an n_speed x n_alpha grid, held until the episode ends or, with resample_steps = R > 0, for R env-steps.  The grid's integer
+ * weights say how often a bin is drawn; they grow outward from the bins that start with a weight as the segments drawn from a bin
+ * succeed (the grid-adaptive scheme of Margolis et al., "Rapid Locomotion via Reinforcement Learning", in exact integers).  The launches
+ * of qg_cmdcur_advance_device go BEHIND the env-step (qg_walk_step_device / qg_po_step_device) on the same stream and write the walking
+ * layer's command slots, as the layer's own sampler does after a step's reward and (PO) observation have been produced: the step that
+ * follows rewards, and shows in its PO frames, the new command; the reset row a PO step wrote for a finished env shows, in its command
+ * columns, the command of the segment that finished, as in the reference and with the in-kernel sampler.  No step kernel is involved.
+ *
+ * Grid.  Bin b = si * n_alpha + ai, si = 0 .. n_speed - 1, ai = 0 .. n_alpha - 1, B = n_speed * n_alpha <= 256 bins.  Formed on the host at
+ * create in f64 and rounded once:  ws = f32((f64(speed_hi) - f64(speed_lo)) / n_speed);  wa = f32(2 pi / n_alpha).  Bin (si, ai) covers
+ * speed from edge_s = f32(speed_lo + f32(f32(si) * ws)) and alpha from edge_a = f32(-pi32 + f32(f32(ai) * wa)), pi32 = f32(pi): one
+ * product and one add each, no fma.
+ *
+ * State in device memory.  Per env: bin (i32), steps (i32, env-steps of the running segment), sum[4] (f32, one per criterion), segment
+ * (i64, this handle's own counter, 0 in a new handle; NOT the simulator's episode).  Per handle: weight[2][B] (i32, a ping-pong pair;
+ * the current half is gen & 1), gen (u32, bumped once per advance), episodes[B] and successes[B] (i64, cumulative counts of judged
+ * segments by the bin they were drawn from).
+ *
+ * Keys.  qg_perturb's k(s), in a key space of its own, with the env's segment as the episode:
+ *   seed_c = seed + 0x5147434D44435531                                        (mod 2^64; ASCII "QGCMDCU1")
+ *   k(s): x = seed_c + 0xA0761D6478BD642F * s + 0x9E3779B97F4A7C15 * (env_index_base + i + 1) + 0xD1B54A32D192ED03 * (segment + 1);
+ *         k = mix64(mix64(x)) >> 40
+ * The draw of a new segment from weights w[0 .. B - 1]:
+ *   T = sum w;  r = (k(0) * T) >> 24  (u64);  bin = the smallest b with w[0] + .. + w[b] > r, over ascending b  (a bin of weight 0 is
+ *   never drawn; the share of bin b among the 2^24 values of k(0) is within one count of 2^24 w[b] / T)
+ *   speed = f32(edge_s + f32(ws * f32(k(1) * 2^-24)));   alpha = f32(edge_a + f32(wa * f32(k(2) * 2^-24)))      no fma
+ *   theta = fixed_heading ? heading_angle : f32(pi32 * (2 * f32(k(3) * 2^-24) - 1))
+ *   then the tail of the walking layer's own sampler (one device function, shared): sincosf of theta and alpha, velocity
+ *   (speed cos alpha, speed sin alpha), heading (cos theta, sin theta), global velocity = the velocity rotated by theta.
+ *
+ * qg_cmdcur_advance_device, for env i, in this order:
+ *   1. steps += 1;  for each criterion k: sum[k] = f32(sum[k] + components[i][column_k]).  The done step's row is included.
+ *   2. The segment ends where done names i or steps == R (R = 0: where done names i only).
+ *   3. A segment that ends is judged: it succeeds iff steps >= min_steps and every criterion holds; criterion k holds iff
+ *      sum[k] >= f32(threshold_k * f32(steps)) for sense +1, sum[k] <= that bound for sense -1; a NaN sum (or bound) fails; with
+ *      n_criteria = 0 min_steps alone decides.  Then episodes[bin] += 1 and successes[bin] += success.
+ *   4. Weights: with s_b the successes judged in THIS advance in bin b, every bin c gets
+ *        weight[c] = min(weight_max, weight[c] + delta * sum over b in N(c) of s_b)        (i64)
+ *      N(c) is a SET: c, its speed neighbours (si - 1, ai) and (si + 1, ai) where they exist (no wrap), its angle neighbours
+ *      (si, ai - 1 mod n_alpha) and (si, ai + 1 mod n_alpha) (wrap); with n_alpha = 2 the two angle neighbours are one bin, counted
+ *      once, and with n_alpha = 1 they are c itself.
+ *   5. Every env whose segment ended: segment += 1, steps = 0, sums = 0, and a new draw from the UPDATED weights.
+ *   6. command_out (nullable): row i = (vx, vy, hx, hy), the command in force after the advance, for EVERY env -- bit for bit what
+ *      qg_walk_get_commands reports, without its wait.  The command of an env whose segment did not end keeps its bits.
+ * It is two launches on the caller's stream and nothing else: the first judges and leaves per-block per-bin integer counts, the second
+ * sums them in ascending block order in every block that needs them, forms the new weights and their prefix sums in LDS, draws, and
+ * lets its first block store the new half of the ping-pong.  No floating-point atomics (no float is summed across envs), no workgroup
+ * waits for another, no allocation, no wait for the device; capturable, and a replay advances the curriculum; the same inputs give the
+ * same bits eagerly and under graph replay.  Refused (QG_ERR_ARG, before anything is launched): while the resident step mode is on
+ * (qg_resident_stop first); a criterion column >= n_columns; criteria without components; bad strides or done kind.
+ *
+ * qg_cmdcur_begin_device (an explicit reset; one launch): the envs of the mask (all, when NULL) discard their running segment UNJUDGED --
+ * no count, no weight changes -- and start a new one: segment += 1, steps = 0, sums = 0, a draw from the weights as they stand.
+ *
+ * While a curriculum is bound to a walking layer, qg_walk_set_command_sampler(non-NULL), a second qg_cmdcur_create on that layer and
+ * qg_walk_destroy are refused; a layer with a sampler installed is refused at qg_cmdcur_create (the two would both redraw).  Commands
+ * written by qg_walk_set_commands stand until the env's segment ends.  Shards do NOT reproduce one big handle: the weights depend on
+ * every env's outcomes.  A multi-rank trainer merges its shards' weights through qg_cmdcur_get_weights / qg_cmdcur_set_weights.
+ * Not covered: weight decay on failure, a curriculum over the heading, anything inside a qg_step_device_seq run.  Every entry point
+ * but _advance_device and _begin_device waits for the device and must not be called during a capture.  Destroy the qg_cmdcur before
+ * its qg_walk. */
+#define QG_CMDCUR_MAX_SIDE 16
+#define QG_CMDCUR_MAX_BINS 256
+#define QG_CMDCUR_MAX_WEIGHT 65536
+#define QG_CMDCUR_MAX_CRITERIA 4
+typedef struct qg_cmdcur qg_cmdcur;
+typedef struct qg_cmdcur_criterion {
+    int32_t column;                    /* the column of `components` that is summed over the segment; >= 0, < n_columns at every advance */
+    int32_t sense;                     /* +1: the mean per step must reach the threshold; -1: it must not exceed it */
+    float threshold;                   /* per env-step; finite */
+} qg_cmdcur_criterion;
+typedef struct qg_cmdcur_desc {
+    int32_t struct_size;               /* sizeof(qg_cmdcur_desc): checked */
+    int32_t reserved;                  /* 0 */
+    int32_t n_speed, n_alpha;          /* 1 .. QG_CMDCUR_MAX_SIDE each */
+    float speed_lo, speed_hi;          /* finite, speed_lo <= speed_hi */
+    int32_t fixed_heading;             /* 0: theta is drawn per segment; 1: theta = heading_angle */
+    float heading_angle;               /* rad; finite */
+    int32_t weight_max;                /* W: 1 .. QG_CMDCUR_MAX_WEIGHT */
+    int32_t delta;                     /* 1 .. W */
+    int32_t resample_steps;            /* R >= 0; 0: a segment ends with its episode only */
+    int32_t min_steps;                 /* >= 1 */
+    int32_t n_criteria;                /* 0 .. QG_CMDCUR_MAX_CRITERIA */
+    int32_t reserved2;                 /* 0 */
+    qg_cmdcur_criterion criteria[QG_CMDCUR_MAX_CRITERIA];
+    int32_t initial_weights[QG_CMDCUR_MAX_BINS];     /* the first B: each in [0, W], at least one > 0 */
+    uint64_t seed;
+    uint64_t env_index_base;           /* env i of this handle is env env_index_base + i of the run */
+} qg_cmdcur_desc;
+/* Validation (QG_ERR_ARG) comes before the handle and the device are looked at.  Create draws segment 0 of every env from the initial
+ * weights and writes the commands; it waits for the device. */
+int qg_cmdcur_create(qg_walk *walk, const qg_cmdcur_desc *desc, qg_cmdcur **out);
+int qg_cmdcur_destroy(qg_cmdcur *cur);
+/* done: a done vector (QG_DONE_*), nullable.  components: [n] rows of n_columns floats at components_stride >= n_columns (nullable
+ * where n_criteria is 0).  command_out: nullable, [n] rows of 4 floats at command_out_stride >= 4. */
+int qg_cmdcur_advance_device(qg_cmdcur *cur, const void *done, int32_t done_kind, int32_t done_stride, const float *components,
+                             int32_t components_stride, int32_t n_columns, float *command_out, int32_t command_out_stride, void *stream);
+/* mask: nullable device [n] u8 (non-zero selects). */
+int qg_cmdcur_begin_device(qg_cmdcur *cur, const uint8_t *mask, void *stream);
+/* The current weights, host i32 [B]; set validates as create validates initial_weights and replaces the current half. */
+int qg_cmdcur_get_weights(qg_cmdcur *cur, int32_t *weights);
+int qg_cmdcur_set_weights(qg_cmdcur *cur, const int32_t *weights);
+/* Host i64 [B] each, either nullable: judged segments and successes per bin since create (or the restored state). */
+int qg_cmdcur_get_stats(qg_cmdcur *cur, int64_t *episodes, int64_t *successes);
+/* Host arrays [n], each nullable: the running segments' bin, steps and segment counter. */
+int qg_cmdcur_get_bins(qg_cmdcur *cur, int32_t *bin, int32_t *steps, int64_t *segment);
+/* The whole state (per env and per handle) as ONE opaque blob of *bytes bytes (host pointer); the round trip is exact and a restored
+ * handle of the same shape continues bit for bit.  The commands themselves are the walking layer's (qg_walk_get_state). */
+int qg_cmdcur_state_bytes(const qg_cmdcur *cur, int64_t *bytes);
+int qg_cmdcur_get_state(qg_cmdcur *cur, void *blob);
+int qg_cmdcur_set_state(qg_cmdcur *cur, const void *blob);
+
 #ifdef __cplusplus
 }
 #endif

@@ -380,6 +380,9 @@ SCHED_COLUMNS = (("clock_sin", 0, 4), ("clock_cos", 4, 4), ("gait_freq", 8, 1), 
 SCHED_DIM = 10
 SCHED_MAX_GAITS = 8
 
+# the command curriculum (qg_cmdcur_*): the limits of its description (QG_CMDCUR_* of include/quadgym.h)
+CMDCUR_MAX_SIDE, CMDCUR_MAX_BINS, CMDCUR_MAX_WEIGHT, CMDCUR_MAX_CRITERIA = 16, 256, 65536, 4
+
 
 def package_dir() -> str:
     return os.path.dirname(os.path.abspath(__file__))
@@ -559,6 +562,18 @@ PROTOTYPES = {
     "qg_sched_state_bytes": [_vp, _P(C.c_int64)],
     "qg_sched_get_state": [_vp, _vp],
     "qg_sched_set_state": [_vp, _vp],
+    # the command curriculum (qg_cmdcur_desc's mirror, QgCmdCurDesc, lives in curriculum.py)
+    "qg_cmdcur_create": [_vp, _vp, _P(_vp)],
+    "qg_cmdcur_destroy": [_vp],
+    "qg_cmdcur_advance_device": [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp],
+    "qg_cmdcur_begin_device": [_vp, _vp, _vp],
+    "qg_cmdcur_get_weights": [_vp, _vp],
+    "qg_cmdcur_set_weights": [_vp, _vp],
+    "qg_cmdcur_get_stats": [_vp, _vp, _vp],
+    "qg_cmdcur_get_bins": [_vp, _vp, _vp, _vp],
+    "qg_cmdcur_state_bytes": [_vp, _P(C.c_int64)],
+    "qg_cmdcur_get_state": [_vp, _vp],
+    "qg_cmdcur_set_state": [_vp, _vp],
 }
 EXPORTS = tuple(PROTOTYPES)
 

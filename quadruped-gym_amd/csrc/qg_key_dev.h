@@ -1,6 +1,6 @@
-// qg_key_dev.h -- the keyed 24-bit draw k(s) of include/quadgym.h (qg_perturb_*, qg_sched_*): a pure function of (salted seed, global
-// env index, episode, stream), on both sides of a launch.  Shared by qg_perturb.hip and qg_sched.hip; each adds its own salt to the
-// seed, so their key spaces are apart.  Internal: not installed, nothing in here is exported.
+// qg_key_dev.h -- the keyed 24-bit draw k(s) of include/quadgym.h (qg_perturb_*, qg_sched_*, qg_cmdcur_*): a pure function of (salted
+// seed, global env index, episode, stream), on both sides of a launch.  Shared by qg_perturb.hip, qg_sched.hip and qg_cmdcur.hip;
+// each adds its own salt to the seed, so their key spaces are apart.  Internal: not installed, nothing in here is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

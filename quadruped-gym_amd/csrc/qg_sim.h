@@ -131,6 +131,8 @@ struct qg_walk {
     float *d_obs, *d_reward, *d_comps, *d_actions, *d_tmp;
     uint8_t *d_done;
     size_t ring_slots, summary_blocks;      // allocated extent of the estimator's ring (whole blocks) and of its block summaries
+    struct qg_cmdcur *cmdcur;               // the command curriculum bound to this layer (qg_cmdcur.hip), or NULL: while one is bound
+                                            // the in-kernel sampler, a second curriculum and qg_walk_destroy are refused
 };
 // the walking env-step is one launch with the task layer fused into the step kernel (every mapping but an explicit LANE request)
 bool qg_walk_fused(const qg_sim *s);

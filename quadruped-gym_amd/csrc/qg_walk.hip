@@ -120,6 +120,7 @@ extern "C" int qg_walk_default_params(qg_walk_params *p) {
 
 extern "C" int qg_walk_destroy(qg_walk *w) {
     if (!w) return QG_OK;
+    if (w->cmdcur) return fail(QG_ERR_ARG, "qg_walk_destroy: a command curriculum is bound to this layer (qg_cmdcur_destroy first)");
     (void)hipSetDevice(w->sim->device);
     (void)hipDeviceSynchronize();                  // steps that read the task state may still be in flight on a caller's stream
     if (w->bound) {                                // give the sim back as qg_walk_create found it
@@ -258,6 +259,8 @@ static int walk_sample_commands(qg_walk *w, const uint8_t *select, hipStream_t s
 
 extern "C" int qg_walk_set_command_sampler(qg_walk *w, const qg_command_sampler *c) {
     if (!w) return fail(QG_ERR_ARG, "null handle");
+    if (c && w->cmdcur)
+        return fail(QG_ERR_ARG, "qg_walk_set_command_sampler: a command curriculum is bound to this layer and draws its commands (qg_cmdcur_destroy first)");
     KWalkParams &k = w->kp;
     HIP_TRY(hipSetDevice(w->sim->device), QG_ERR_DEVICE);
     HIP_TRY(hipDeviceSynchronize(), QG_ERR_LAUNCH);   // steps reading the old parameters may be in flight

@@ -383,6 +383,19 @@ __device__ __forceinline__ void walk_channel_terms(const KWalkState &S, int env,
     a.frq = fmaf(fj, fj, a.frq);
 }
 
+// The tail of a command draw: the six command floats of (heading angle theta, velocity angle alpha, speed), written into the env's
+// slots of vel / head / gvel.  Shared by the in-kernel sampler below and by the command curriculum's draw (qg_cmdcur.hip).
+__device__ __forceinline__ void walk_write_command(const KWalkState &S, int n, int env, float theta, float alpha, float speed) {
+    float st, ct, sa, ca;
+    sincosf(theta, &st, &ct);
+    sincosf(alpha, &sa, &ca);
+    const float vx = speed * ca, vy = speed * sa;          // set_velocity_speed_alpha (:45-51)
+    S.vel[env] = vx; S.vel[n + env] = vy;
+    S.head[env] = ct; S.head[n + env] = st;                // set_orientation (:29-36)
+    S.gvel[env] = ct * vx - st * vy;                       // :14-27
+    S.gvel[n + env] = st * vx + ct * vy;
+}
+
 // VelocityHeadingControls.sample (control_inputs.py:74-115) for one env: the command of the episode that has just begun.
 // `episode_key` is the counter of that episode in the env's reset streams -- the one its reset yaw used.
 __device__ __forceinline__ void walk_sample_command(const KWalkParams &P, const KWalkState &S, int n, int env, uint64_t seed,
@@ -393,14 +406,7 @@ __device__ __forceinline__ void walk_sample_command(const KWalkParams &P, const 
     if (!(P.cmd_fixed & 1u)) theta = pi * (2.f * uniform24s(seed, g, c, QG_STREAM_COMMAND + 0u) - 1.f);      // :97-100
     if (!(P.cmd_fixed & 2u)) alpha = pi * (2.f * uniform24s(seed, g, c, QG_STREAM_COMMAND + 1u) - 1.f);      // :106-109
     if (!(P.cmd_fixed & 4u)) speed = fmaf(P.cmd_max_speed - P.cmd_min_speed, uniform24s(seed, g, c, QG_STREAM_COMMAND + 2u), P.cmd_min_speed);   // :112-115
-    float st, ct, sa, ca;
-    sincosf(theta, &st, &ct);
-    sincosf(alpha, &sa, &ca);
-    const float vx = speed * ca, vy = speed * sa;          // set_velocity_speed_alpha (:45-51)
-    S.vel[env] = vx; S.vel[n + env] = vy;
-    S.head[env] = ct; S.head[n + env] = st;                // set_orientation (:29-36)
-    S.gvel[env] = ct * vx - st * vy;                       // :14-27
-    S.gvel[n + env] = st * vx + ct * vy;
+    walk_write_command(S, n, env, theta, alpha, speed);
 }
 
 // what the per-env part of the reward reads from the task state; loaded up front (in the fused kernel: in the prologue, so that

@@ -1,5 +1,6 @@
 """``DeviceVecEnvWrapper`` -- what the VecEnv wrappers around a device-side layer share (``DeviceVecNormalize``,
-``DevicePerturbedVecEnv``, ``DeviceGaitRewardVecEnv``, ``DeviceGaitScheduleVecEnv``, ``DevicePrivilegedVecEnv``): the wrapped env and the pass-through to it, the
+``DevicePerturbedVecEnv``, ``DeviceGaitRewardVecEnv``, ``DeviceGaitScheduleVecEnv``, ``DevicePrivilegedVecEnv``,
+``DeviceCommandCurriculumVecEnv``): the wrapped env and the pass-through to it, the
 buffers of a ``step_tensor`` call by name, the upload of the NumPy cold path, the finished envs whose info holds a terminal
 observation, checkpoint / resume / close over the layer, and the walk along a stack's ``.venv`` chain by which a wrapper refuses, at
 construction, an order of the stack that cannot work.
