@@ -221,8 +221,10 @@ class DeviceCommandCurriculumVecEnv(DeviceVecEnvWrapper):
     ``commands_tensor`` (float32 ``[N, 4]``: vx, vy, hx, hy) holds the commands in force after the latest step, reset or restore.
 
     Refused at construction, before any handle exists: the plain env (no walking layer, no command) and an env with
-    ``random_controls=True`` (its host sampler, or its in-kernel one, would redraw what the curriculum draws).  The wrapper goes on
-    either side of ``DeviceVecNormalize`` and ``DeviceGaitRewardVecEnv``; criteria on gait terms need it outside the gait wrapper.
+    ``random_controls=True`` (its host sampler, or its in-kernel one, would redraw what the curriculum draws).  The wrapper touches no
+    row, reward or component, so no order is refused: it goes on either side of ``DeviceVecNormalize``, ``DevicePerturbedVecEnv``,
+    ``DeviceGaitRewardVecEnv``, ``DeviceGaitScheduleVecEnv`` and ``DevicePrivilegedVecEnv``; criteria on gait or schedule terms need it
+    outside the wrapper that writes those columns (``envs/device_wrapper.py`` has the orders the suite steps).
     ``reset()`` begins a new segment for every env; ``snapshot`` / ``restore`` carry the grid and the segments.  The NumPy
     ``reset()`` / ``step()`` are a cold path built for correctness.  Every other attribute passes through to the wrapped env."""
 

@@ -11,7 +11,13 @@ noise belongs on the actor's columns); ``DeviceGaitRewardVecEnv`` anywhere, but 
 envs only (the plain env's packed rows have no command and no room for the clock), outside ``DevicePerturbedVecEnv`` (the clock is no
 sensor), on either side of ``DeviceGaitRewardVecEnv``, inside ``DevicePrivilegedVecEnv`` (the actor's window must hold the clock) and,
 with ``gate_on_command=True``, inside a normaliser of observations; ``DeviceVecNormalize`` outside
-``DevicePrivilegedVecEnv`` around the walking envs, and inside it around the plain env, whose packed step keeps the wide rows apart."""
+``DevicePrivilegedVecEnv`` around the walking envs, and inside it around the plain env, whose packed step keeps the wide rows apart;
+``DeviceCommandCurriculumVecEnv`` around the walking envs only, built with ``random_controls=False``, and anywhere in the stack: it
+touches no row, reward or component, so it goes on either side of ``DevicePerturbedVecEnv``, ``DeviceGaitRewardVecEnv``,
+``DeviceGaitScheduleVecEnv``, ``DevicePrivilegedVecEnv`` and ``DeviceVecNormalize``.  Its criteria name columns of the layers INSIDE it,
+so criteria on gait or schedule terms put it outside those wrappers; the gates of ``gate_on_command=True`` read the command that was
+in force during the step, wherever the curriculum stands.  ``tests/wrapper_stacks.py`` lists the orders the suite steps: outside the
+perturbation and inside the privileged wrapper, outside the gait and schedule wrappers and inside both."""
 from __future__ import annotations
 
 import numpy as np

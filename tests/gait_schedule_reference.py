@@ -221,6 +221,19 @@ def clock_tolerance(margin=1.0):
     return np.array([margin * BUDGET_CLOCK] * 8 + [0.0, 0.0])
 
 
+def _same(a, b):
+    return np.array_equal(np.ascontiguousarray(a, np.float32).view(np.uint32), np.ascontiguousarray(b, np.float32).view(np.uint32))
+
+
+def check_columns(what, cols, view):
+    """[n, 10] clock columns against a view: freq and d exact, sin / cos within MARGIN x E_clock."""
+    ref = columns(view)
+    assert _same(cols[:, 8:], ref[:, 8:].astype(np.float32)), what
+    err = np.abs(cols[:, :8].astype(np.float64) - ref[:, :8])
+    assert (err <= clock_tolerance(MARGIN)[:8]).all(), (what, err.max())
+    return float(err.max())
+
+
 # ---- the states, extras and the scripted done table ---------------------------------------------------------------------------------------
 def fixture_states(fix):
     """67 indices into tests/golden/contact_cells.npz: 48 states built on a foot's sample points (12 per foot: the foot stands) and 19

@@ -79,13 +79,7 @@ def _check_ints(sched, chk):
     assert _same(got["freq"], want["freq"])
 
 
-def _check_columns(what, cols, view):
-    """[n, 10] clock columns against a view: freq and d exact, sin / cos within MARGIN x E_clock."""
-    ref = R.columns(view)
-    assert _same(cols[:, 8:], ref[:, 8:].astype(np.float32)), what
-    err = np.abs(cols[:, :8].astype(np.float64) - ref[:, :8])
-    assert (err <= R.clock_tolerance(R.MARGIN)[:8]).all(), (what, err.max())
-    return float(err.max())
+_check_columns = R.check_columns                           # shared with tests/test_zz_wrapper_stacks_gpu.py
 
 
 def _check_terms(what, view, comps, reward_out, force, feet, done=None, command=None, reward=None, kappa=R.KAPPA, weights=R.WEIGHTS):
