@@ -380,8 +380,78 @@ SCHED_COLUMNS = (("clock_sin", 0, 4), ("clock_cos", 4, 4), ("gait_freq", 8, 1), 
 SCHED_DIM = 10
 SCHED_MAX_GAITS = 8
 
+
+class QgSchedGait(C.Structure):
+    _fields_ = [("offset", C.c_float * 4), ("duty", C.c_float)]
+
+
+class QgSchedDesc(_Sized):
+    """``qg_sched_desc``: the gait table, the draws' ranges and key, the terms' constants and weights (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("n_gaits", C.c_int32), ("random_phase", C.c_int32),
+                ("done_row", C.c_int32), ("freq_lo", C.c_float), ("freq_hi", C.c_float), ("kappa", C.c_float), ("sigma_force", C.c_float),
+                ("sigma_velocity", C.c_float), ("swing_height_target", C.c_float), ("min_command_speed", C.c_float),
+                ("weights", C.c_float * len(SCHED_TERMS)), ("gaits", QgSchedGait * SCHED_MAX_GAITS), ("seed", C.c_uint64),
+                ("env_index_base", C.c_uint64)]
+
+    @classmethod
+    def make(cls, gaits=(((0.0, 0.0, 0.0, 0.0), 0.5),), freq=(1.0, 1.0), weights=(0.0,) * len(SCHED_TERMS), random_phase=False, done_row=0,
+             kappa=0.0, sigma_force=1.0, sigma_velocity=1.0, swing_height_target=0.0, min_command_speed=0.0, seed=0, env_index_base=0):
+        """``gaits``: up to 8 ``(offsets[4], duty)`` rows."""
+        d = super().make()
+        if len(gaits) > SCHED_MAX_GAITS:
+            raise ValueError(f"gaits: at most {SCHED_MAX_GAITS} rows, got {len(gaits)}")
+        d.n_gaits, d.random_phase, d.done_row = len(gaits), 1 if random_phase else 0, int(done_row)
+        for g, (offsets, duty) in enumerate(gaits):
+            if len(offsets) != 4:
+                raise ValueError(f"gaits[{g}]: four offsets, got {len(offsets)}")
+            for f, off in enumerate(offsets):
+                d.gaits[g].offset[f] = float(off)
+            d.gaits[g].duty = float(duty)
+        d.freq_lo, d.freq_hi, d.kappa = float(freq[0]), float(freq[1]), float(kappa)
+        d.sigma_force, d.sigma_velocity = float(sigma_force), float(sigma_velocity)
+        d.swing_height_target, d.min_command_speed = float(swing_height_target), float(min_command_speed)
+        for k, w in enumerate(weights):
+            d.weights[k] = float(w)
+        d.seed, d.env_index_base = int(seed) % (1 << 64), int(env_index_base)
+        return d
+
+
 # the command curriculum (qg_cmdcur_*): the limits of its description (QG_CMDCUR_* of include/quadgym.h)
 CMDCUR_MAX_SIDE, CMDCUR_MAX_BINS, CMDCUR_MAX_WEIGHT, CMDCUR_MAX_CRITERIA = 16, 256, 65536, 4
+
+
+class QgCmdCurCriterion(C.Structure):
+    _fields_ = [("column", C.c_int32), ("sense", C.c_int32), ("threshold", C.c_float)]
+
+
+class QgCmdCurDesc(_Sized):
+    """``qg_cmdcur_desc``: the grid, the weights' limits, the segment's length and criteria, the key (``struct_size`` is filled in)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("n_speed", C.c_int32), ("n_alpha", C.c_int32), ("speed_lo", C.c_float),
+                ("speed_hi", C.c_float), ("fixed_heading", C.c_int32), ("heading_angle", C.c_float), ("weight_max", C.c_int32),
+                ("delta", C.c_int32), ("resample_steps", C.c_int32), ("min_steps", C.c_int32), ("n_criteria", C.c_int32),
+                ("reserved2", C.c_int32), ("criteria", QgCmdCurCriterion * CMDCUR_MAX_CRITERIA),
+                ("initial_weights", C.c_int32 * CMDCUR_MAX_BINS), ("seed", C.c_uint64), ("env_index_base", C.c_uint64)]
+
+    @classmethod
+    def make(cls, speed=(0.0, 1.0), bins=(1, 1), initial_weights=(1,), weight_max=1, delta=1, resample_steps=0, min_steps=1, criteria=(),
+             fixed_heading=None, seed=0, env_index_base=0):
+        """``criteria``: up to 4 ``(column, sense, threshold)``; ``fixed_heading``: None (theta is drawn) or the angle in rad."""
+        d = super().make()
+        if len(initial_weights) > CMDCUR_MAX_BINS:
+            raise ValueError(f"initial_weights: at most {CMDCUR_MAX_BINS} bins, got {len(initial_weights)}")
+        if len(criteria) > CMDCUR_MAX_CRITERIA:
+            raise ValueError(f"criteria: at most {CMDCUR_MAX_CRITERIA}, got {len(criteria)}")
+        d.n_speed, d.n_alpha = int(bins[0]), int(bins[1])
+        d.speed_lo, d.speed_hi = float(speed[0]), float(speed[1])
+        d.fixed_heading, d.heading_angle = (0, 0.0) if fixed_heading is None else (1, float(fixed_heading))
+        d.weight_max, d.delta, d.resample_steps, d.min_steps = int(weight_max), int(delta), int(resample_steps), int(min_steps)
+        d.n_criteria = len(criteria)
+        for k, (column, sense, threshold) in enumerate(criteria):
+            d.criteria[k].column, d.criteria[k].sense, d.criteria[k].threshold = int(column), int(sense), float(threshold)
+        for b, w in enumerate(initial_weights):
+            d.initial_weights[b] = int(w)
+        d.seed, d.env_index_base = int(seed) % (1 << 64), int(env_index_base)
+        return d
 
 
 def package_dir() -> str:
@@ -395,7 +465,8 @@ def library_path() -> str:
 
 _vp, _i32, _f64, _P = C.c_void_p, C.c_int32, C.c_double, C.POINTER
 # Every entry point include/quadgym.h declares, in its order: name -> argtypes, or (argtypes, restype) where the result is not the int
-# status.  The one list: load_library() applies it, EXPORTS is its keys.
+# status.  The one list: load_library() applies it, EXPORTS is its keys.  (A <prefix>_state_bytes comes in both forms: the size as
+# the int64 result, or the status as the result and the size through an int64 pointer; _TaskLayer.state_bytes reads which from here.)
 PROTOTYPES = {
     # the library, the default robot and task
     "qg_version": ([], C.c_char_p),
@@ -551,8 +622,8 @@ PROTOTYPES = {
     "qg_priv_destroy": [_vp],
     "qg_priv_read_device": [_vp, _vp, _i32, _i32, _vp, _i32, _vp],
     "qg_priv_read": [_vp, _vp],
-    # the commanded gait schedule (qg_sched_desc's mirror, QgSchedDesc, lives in schedule.py)
-    "qg_sched_create": [_vp, _vp, _P(_vp)],
+    # the commanded gait schedule
+    "qg_sched_create": [_vp, _P(QgSchedDesc), _P(_vp)],
     "qg_sched_destroy": [_vp],
     "qg_sched_set_weights": [_vp, _P(C.c_float)],
     "qg_sched_advance_device": [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32,
@@ -562,8 +633,8 @@ PROTOTYPES = {
     "qg_sched_state_bytes": [_vp, _P(C.c_int64)],
     "qg_sched_get_state": [_vp, _vp],
     "qg_sched_set_state": [_vp, _vp],
-    # the command curriculum (qg_cmdcur_desc's mirror, QgCmdCurDesc, lives in curriculum.py)
-    "qg_cmdcur_create": [_vp, _vp, _P(_vp)],
+    # the command curriculum
+    "qg_cmdcur_create": [_vp, _P(QgCmdCurDesc), _P(_vp)],
     "qg_cmdcur_destroy": [_vp],
     "qg_cmdcur_advance_device": [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _vp],
     "qg_cmdcur_begin_device": [_vp, _vp, _vp],

@@ -16,13 +16,12 @@
 #include <stdint.h>
 
 #include "qg_contact_dev.h"
-
-#define QGG_MAX_BASE (QG_MONITOR_MAX_TERMS - QG_GAIT_NTERMS)     // 25: the widest base that still fits a monitor
+#include "qg_shaped_dev.h"
 
 struct KGait {
     float w[QG_GAIT_NTERMS];
     float air_time_target, clearance_target, max_contact_force, min_command_speed;
-    int32_t reward_stride, out_stride, comp_stride, base_stride, base_terms, copy_base, command_stride;
+    KShapedIO io;
 };
 
 template <bool DYN>
@@ -81,40 +80,14 @@ __global__ __launch_bounds__(QGC_ENVS * 16) void qg_gait_kernel(KContact A, KGai
     // ---- the env's terms, weighted; every lane of the group holds them all ----------------------------------------------------------------
     bool moving = true;
     if (command) {
-        const float *c = command + e * (size_t)G.command_stride;
-        moving = fmaxf(fabsf(c[0]), fabsf(c[1])) > G.min_command_speed;
+        const float *c = command + e * (size_t)G.io.command_stride;
+        moving = QG_SHAPED_SPEED(c) > G.min_command_speed;
     }
     const bool finished = done ? qg_done_at(done, A.done_kind, A.done_stride, e) : false;
     const float term[QG_GAIT_NTERMS] = {moving ? s_air : 0.f, s_slip, s_clear, s_down, s_force, (float)bodies_down, feet_down == 0 ? 1.f : 0.f};
-    float comp[QG_GAIT_NTERMS], shaped = 0.f;
-#pragma unroll
-    for (int k = 0; k < QG_GAIT_NTERMS; ++k) {
-        comp[k] = finished ? 0.f : __fmul_rn(G.w[k], term[k]);     // rounded to f32 before the sum: the sum is over the stored columns
-        shaped = k ? __fadd_rn(shaped, comp[k]) : comp[0];
-    }
-
-    // ---- the outputs ------------------------------------------------------------------------------------------------------------------------
-    if (comps) {
-        float *row = comps + e * (size_t)G.comp_stride;
-        if (G.copy_base) {
-            const float *from = base + e * (size_t)G.base_stride;
-            for (int c = lane; c < G.base_terms; c += 16) row[c] = from[c];
-        }
-        if (lane < QG_GAIT_NTERMS) {
-            float mine = comp[0];
-#pragma unroll
-            for (int k = 1; k < QG_GAIT_NTERMS; ++k) mine = lane == k ? comp[k] : mine;
-            row[G.base_terms + lane] = mine;
-        }
-    }
-    if (reward_out && lane == QG_GAIT_NTERMS) {
-        float r = shaped;
-        if (reward) {
-            const float r0 = reward[e * (size_t)G.reward_stride];
-            r = finished ? r0 : __fadd_rn(r0, shaped);         // a finished env's reward passes through bit for bit
-        }
-        reward_out[e * (size_t)G.out_stride] = r;
-    }
+    // ---- the tail of a shaped-reward kernel (qg_shaped_dev.h): comp[], their sum, the component columns and the reward ----------------------
+    QG_SHAPED_WEIGH(QG_GAIT_NTERMS, G.w, term, __fmul_rn, __fadd_rn)
+    QG_SHAPED_STORE(QG_GAIT_NTERMS, G.io, __fadd_rn)
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -125,12 +98,6 @@ struct qg_gait {
     qg_gait_desc desc;
     QgDevMem mem;             // empty: the handle has no device state of its own
 };
-
-static int gait_check_weights(const float *w, const char *who) {
-    for (int k = 0; k < QG_GAIT_NTERMS; ++k)
-        if (!qg_finite32(w[k])) return fail(QG_ERR_ARG, "%s: weights[%d] is not finite", who, k);
-    return QG_OK;
-}
 
 extern "C" int qg_gait_destroy(qg_gait *g) {
     if (g) qg_free_handle(g, g->contact->sim->device);     // launches may still be in flight on a caller's stream
@@ -143,7 +110,7 @@ extern "C" int qg_gait_create(qg_contact *contact, const qg_gait_desc *desc, qg_
     if (!desc) return fail(QG_ERR_ARG, "qg_gait_create: null description");
     QG_CHECK_STRUCT(desc, qg_gait_desc);
     if (desc->reserved != 0) return fail(QG_ERR_ARG, "qg_gait: reserved must be 0");
-    QG_TRY(gait_check_weights(desc->weights, "qg_gait"));
+    QG_TRY(qg_check_weights(desc->weights, QG_GAIT_NTERMS, "qg_gait"));
     const struct { const char *name; float v; } lim[] = {{"air_time_target", desc->air_time_target}, {"clearance_target", desc->clearance_target},
                                                          {"max_contact_force", desc->max_contact_force}, {"min_command_speed", desc->min_command_speed}};
     for (const auto &l : lim)
@@ -159,7 +126,7 @@ extern "C" int qg_gait_create(qg_contact *contact, const qg_gait_desc *desc, qg_
 
 extern "C" int qg_gait_set_weights(qg_gait *g, const float *weights) {
     if (!g || !weights) return fail(QG_ERR_ARG, "qg_gait_set_weights: null argument");
-    QG_TRY(gait_check_weights(weights, "qg_gait_set_weights"));
+    QG_TRY(qg_check_weights(weights, QG_GAIT_NTERMS, "qg_gait_set_weights"));
     memcpy(g->desc.weights, weights, sizeof g->desc.weights);     // read by the next launch; a captured launch keeps its own copy
     return QG_OK;
 }
@@ -172,38 +139,20 @@ extern "C" int qg_gait_reward_device(qg_gait *g, const void *done, int32_t done_
     if (!g) return fail(QG_ERR_ARG, "%s: null handle", who);
     if (!components && !reward_out) return fail(QG_ERR_ARG, "%s: components and reward_out are both NULL", who);
     QG_TRY(qg_check_done(who, done, done_kind, done_stride));
-    if (reward && !reward_out) return fail(QG_ERR_ARG, "%s: reward without reward_out", who);
-    if (reward && reward_stride < 1) return fail(QG_ERR_ARG, "%s: reward_stride %d must be >= 1", who, reward_stride);
-    if (reward_out && reward_out_stride < 1) return fail(QG_ERR_ARG, "%s: reward_out_stride %d must be >= 1", who, reward_out_stride);
-    if (base_terms < 0 || base_terms > QGG_MAX_BASE) return fail(QG_ERR_ARG, "%s: base_terms %d must be 0 .. %d", who, base_terms, QGG_MAX_BASE);
-    if (!base_components && base_terms != 0) return fail(QG_ERR_ARG, "%s: base_terms %d without base_components", who, base_terms);
-    if (base_components && !components) return fail(QG_ERR_ARG, "%s: base_components without components", who);
-    if (components && components_stride < base_terms + QG_GAIT_NTERMS)
-        return fail(QG_ERR_ARG, "%s: components_stride %d must be >= base_terms + %d = %d", who, components_stride, QG_GAIT_NTERMS,
-                    base_terms + QG_GAIT_NTERMS);
-    if (base_components && base_stride < base_terms) return fail(QG_ERR_ARG, "%s: base_stride %d must be >= base_terms %d", who, base_stride, base_terms);
-    if (command && command_stride < 2) return fail(QG_ERR_ARG, "%s: command_stride %d must be >= 2", who, command_stride);
-    if (!qg_aligned(feet, 16)) return fail(QG_ERR_ARG, "%s: feet must be 16-byte aligned", who);
     qg_contact *c = g->contact;
     qg_sim *s = c->sim;
-    // the base columns already at the front of the wide buffer: nothing to copy.  Any other overlap of the two would let a lane read what
-    // another one writes
-    const bool in_place = base_components && base_components == components && base_stride == components_stride;
-    if (base_components && base_terms > 0 && !in_place &&
-        qg_rows_overlap(base_components, base_stride, base_terms, components, components_stride, base_terms + QG_GAIT_NTERMS, s->n))
-        return fail(QG_ERR_ARG, "%s: base_components and components overlap (allowed only as the first base_terms columns of the same rows)", who);
+    KGait G;
+    QG_TRY(qg_shaped_io(who, QG_GAIT_NTERMS, reward, reward_stride, reward_out, reward_out_stride, components, components_stride, base_components,
+                        base_stride, base_terms, command, command_stride, s->n, &G.io));
+    if (!qg_aligned(feet, 16)) return fail(QG_ERR_ARG, "%s: feet must be 16-byte aligned", who);
     if (s->res.active) return fail(QG_ERR_ARG, "%s: the resident step mode is on, the state lives in registers (qg_resident_stop first)", who);
 
     HIP_TRY(hipSetDevice(s->device), QG_ERR_DEVICE);
     qg_note_caller_stream(s, (hipStream_t)stream);               // a later host-pointer call of the simulator waits for this launch
     const KContact A = qgc_args(c, done, done_kind, done_stride, advance);
-    KGait G;
     memcpy(G.w, g->desc.weights, sizeof G.w);
     G.air_time_target = g->desc.air_time_target, G.clearance_target = g->desc.clearance_target;
     G.max_contact_force = g->desc.max_contact_force, G.min_command_speed = g->desc.min_command_speed;
-    G.reward_stride = reward_stride, G.out_stride = reward_out_stride, G.comp_stride = components_stride;
-    G.base_stride = base_stride, G.base_terms = base_terms, G.copy_base = (base_components && base_terms > 0 && !in_place) ? 1 : 0;
-    G.command_stride = command_stride;
     const dim3 grid((unsigned)((s->n + QGC_ENVS - 1) / QGC_ENVS)), block(QGC_ENVS * 16);
     if (s->dyn)
         hipLaunchKernelGGL(qg_gait_kernel<true>, grid, block, 0, (hipStream_t)stream, A, G, (const KModel *)s->d_model, (const float *)s->st.qpos,

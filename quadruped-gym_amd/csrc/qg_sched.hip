@@ -21,11 +21,13 @@
 
 #include "qg_contact_dev.h"
 #include "qg_key_dev.h"
+#include "qg_shaped_dev.h"
 
 #define QGS_SALT 0x5147534348454431ull                            // "QGSCHED1"
-#define QGS_MAX_BASE (QG_MONITOR_MAX_TERMS - QG_SCHED_NTERMS)     // 28: the widest base that still fits a monitor
 #define QGS_ROW 5                                                 // u32 per row of the table in device memory: off_f[4], D
 #define QGS_BLOB 0x48435351u                                      /* "QSCH" */
+#define QGS_MUL(a, b) ((a) * (b))                                 // the shared tail's arithmetic: operators, under the kernel's contract(off)
+#define QGS_ADD(a, b) ((a) + (b))
 
 struct KSched {
     int32_t n, n_gaits, random_phase, done_row;
@@ -33,7 +35,7 @@ struct KSched {
     float freq_lo, span, dt, kappa, inv2k, inv_sf2, inv_sv2, height, min_command_speed, threshold;
     float w[QG_SCHED_NTERMS];
     uint64_t seed_s, base;
-    int32_t reward_stride, out_reward_stride, comp_stride, base_stride, base_terms, copy_base, command_stride;
+    KShapedIO io;
     int32_t obs_stride, obs_dim, out_stride, copy_obs, vec;
     int32_t term_obs_stride, term_out_stride, copy_term, term_vec;
 };
@@ -125,8 +127,8 @@ __global__ __launch_bounds__(QGC_ENVS * 16) void qg_sched_kernel(KSched A, const
     qgc_body<DYN>(M, sq, sv, dyn, b, e, n, x, v, F);
     bool stand = false;
     if (command) {
-        const float *c = command + e * (size_t)A.command_stride;
-        stand = fmaxf(fabsf(c[0]), fabsf(c[1])) <= A.min_command_speed;
+        const float *c = command + e * (size_t)A.io.command_stride;
+        stand = QG_SHAPED_SPEED(c) <= A.min_command_speed;
     }
     const bool foot = live && b != 0 && (b - 1) % 3 == 2;
     float a_force = 0.f, a_vel = 0.f, a_height = 0.f;
@@ -155,35 +157,9 @@ __global__ __launch_bounds__(QGC_ENVS * 16) void qg_sched_kernel(KSched A, const
     }
     const unsigned group = (unsigned)(__ballot(match) >> (threadIdx.x & 48)) & 0xffffu;      // the env's 16 flags (set on foot lanes only)
     const float term[QG_SCHED_NTERMS] = {s_force, s_vel, s_height, (float)__popc(group)};
-    float comp[QG_SCHED_NTERMS], shaped = 0.f;
-#pragma unroll
-    for (int k = 0; k < QG_SCHED_NTERMS; ++k) {
-        comp[k] = finished ? 0.f : A.w[k] * term[k];       // rounded to f32 before the sum: the sum is over the stored columns
-        shaped = k ? shaped + comp[k] : comp[0];
-    }
-
-    // ---- components and reward ------------------------------------------------------------------------------------------------------------------
-    if (comps) {
-        float *row = comps + e * (size_t)A.comp_stride;
-        if (A.copy_base) {
-            const float *from = base + e * (size_t)A.base_stride;
-            for (int c = lane; c < A.base_terms; c += 16) row[c] = from[c];
-        }
-        if (lane < QG_SCHED_NTERMS) {
-            float mine = comp[0];
-#pragma unroll
-            for (int k = 1; k < QG_SCHED_NTERMS; ++k) mine = lane == k ? comp[k] : mine;
-            row[A.base_terms + lane] = mine;
-        }
-    }
-    if (reward_out && lane == QG_SCHED_NTERMS) {
-        float r = shaped;
-        if (reward) {
-            const float r0 = reward[e * (size_t)A.reward_stride];
-            r = finished ? r0 : r0 + shaped;                // a finished env's reward passes through bit for bit
-        }
-        reward_out[e * (size_t)A.out_reward_stride] = r;
-    }
+    // ---- the tail of a shaped-reward kernel (qg_shaped_dev.h): comp[], their sum, the component columns and the reward ----------------------
+    QG_SHAPED_WEIGH(QG_SCHED_NTERMS, A.w, term, QGS_MUL, QGS_ADD)
+    QG_SHAPED_STORE(QG_SCHED_NTERMS, A.io, QGS_ADD)
 
     // ---- the wide rows: the observation in front, the ten clock columns behind it ---------------------------------------------------------------
     if (out) {
@@ -230,12 +206,6 @@ struct qg_sched {
     uint32_t *d_table;        // [QG_SCHED_MAX_GAITS][QGS_ROW]
 };
 
-static int sched_check_weights(const float *w, const char *who) {
-    for (int k = 0; k < QG_SCHED_NTERMS; ++k)
-        if (!qg_finite32(w[k])) return fail(QG_ERR_ARG, "%s: weights[%d] is not finite", who, k);
-    return QG_OK;
-}
-
 static int sched_validate(const qg_sched_desc *d) {
     if (!d) return fail(QG_ERR_ARG, "qg_sched_create: null description");
     QG_CHECK_STRUCT(d, qg_sched_desc);
@@ -253,7 +223,7 @@ static int sched_validate(const qg_sched_desc *d) {
     if (!qg_finite32(d->swing_height_target)) return fail(QG_ERR_ARG, "qg_sched: swing_height_target is not finite");
     if (!qg_finite32(d->min_command_speed) || d->min_command_speed < 0.f)
         return fail(QG_ERR_ARG, "qg_sched: min_command_speed %g must be finite and >= 0", d->min_command_speed);
-    QG_TRY(sched_check_weights(d->weights, "qg_sched"));
+    QG_TRY(qg_check_weights(d->weights, QG_SCHED_NTERMS, "qg_sched"));
     for (int g = 0; g < d->n_gaits; ++g) {
         for (int f = 0; f < 4; ++f)
             if (!qg_finite32(d->gaits[g].offset[f]) || d->gaits[g].offset[f] < 0.f || !(d->gaits[g].offset[f] < 1.f))
@@ -330,7 +300,7 @@ extern "C" int qg_sched_create(qg_contact *contact, const qg_sched_desc *desc, q
 
 extern "C" int qg_sched_set_weights(qg_sched *p, const float *weights) {
     if (!p || !weights) return fail(QG_ERR_ARG, "qg_sched_set_weights: null argument");
-    QG_TRY(sched_check_weights(weights, "qg_sched_set_weights"));
+    QG_TRY(qg_check_weights(weights, QG_SCHED_NTERMS, "qg_sched_set_weights"));
     memcpy(p->desc.weights, weights, sizeof p->desc.weights);     // read by the next launch; a captured launch keeps its own copy
     return QG_OK;
 }
@@ -362,30 +332,17 @@ extern "C" int qg_sched_advance_device(qg_sched *p, const void *done, int32_t do
     const char *who = "qg_sched_advance_device";
     if (!p) return fail(QG_ERR_ARG, "%s: null handle", who);
     QG_TRY(qg_check_done(who, done, done_kind, done_stride));
-    if (reward && !reward_out) return fail(QG_ERR_ARG, "%s: reward without reward_out", who);
-    if (reward && reward_stride < 1) return fail(QG_ERR_ARG, "%s: reward_stride %d must be >= 1", who, reward_stride);
-    if (reward_out && reward_out_stride < 1) return fail(QG_ERR_ARG, "%s: reward_out_stride %d must be >= 1", who, reward_out_stride);
-    if (base_terms < 0 || base_terms > QGS_MAX_BASE) return fail(QG_ERR_ARG, "%s: base_terms %d must be 0 .. %d", who, base_terms, QGS_MAX_BASE);
-    if (!base_components && base_terms != 0) return fail(QG_ERR_ARG, "%s: base_terms %d without base_components", who, base_terms);
-    if (base_components && !components) return fail(QG_ERR_ARG, "%s: base_components without components", who);
-    if (components && components_stride < base_terms + QG_SCHED_NTERMS)
-        return fail(QG_ERR_ARG, "%s: components_stride %d must be >= base_terms + %d = %d", who, components_stride, QG_SCHED_NTERMS,
-                    base_terms + QG_SCHED_NTERMS);
-    if (base_components && base_stride < base_terms) return fail(QG_ERR_ARG, "%s: base_stride %d must be >= base_terms %d", who, base_stride, base_terms);
-    if (command && command_stride < 2) return fail(QG_ERR_ARG, "%s: command_stride %d must be >= 2", who, command_stride);
-    if (obs_dim < 0) return fail(QG_ERR_ARG, "%s: obs_dim %d must be >= 0", who, obs_dim);
-    if (terminal_out && p->desc.done_row != QG_PERTURB_DONE_ROW_RESET)
-        return fail(QG_ERR_ARG, "%s: terminal_out goes with QG_PERTURB_DONE_ROW_RESET (with _TERMINAL the row is the terminal observation)", who);
     qg_contact *c = p->contact;
     qg_sim *s = c->sim;
     KSched A = p->k;
+    QG_TRY(qg_shaped_io(who, QG_SCHED_NTERMS, reward, reward_stride, reward_out, reward_out_stride, components, components_stride, base_components,
+                        base_stride, base_terms, command, command_stride, s->n, &A.io));
+    if (obs_dim < 0) return fail(QG_ERR_ARG, "%s: obs_dim %d must be >= 0", who, obs_dim);
+    if (terminal_out && p->desc.done_row != QG_PERTURB_DONE_ROW_RESET)
+        return fail(QG_ERR_ARG, "%s: terminal_out goes with QG_PERTURB_DONE_ROW_RESET (with _TERMINAL the row is the terminal observation)", who);
     QG_TRY(sched_check_rows(who, "obs", "out", obs, obs_stride, obs_dim, out, out_stride, s->n, &A.copy_obs, &A.vec));
     QG_TRY(sched_check_rows(who, "terminal_obs", "terminal_out", terminal_obs, terminal_obs_stride, obs_dim, terminal_out, terminal_out_stride, s->n,
                             &A.copy_term, &A.term_vec));
-    const bool in_place = base_components && base_components == components && base_stride == components_stride;
-    if (base_components && base_terms > 0 && !in_place &&
-        qg_rows_overlap(base_components, base_stride, base_terms, components, components_stride, base_terms + QG_SCHED_NTERMS, s->n))
-        return fail(QG_ERR_ARG, "%s: base_components and components overlap (allowed only as the first base_terms columns of the same rows)", who);
     A.dt = (float)(s->model.timestep * s->task.frame_skip);       // the sensor's dt (qgc_args), the task as it stands at this call
     if ((double)p->desc.freq_hi * (double)A.dt > 0.5)
         return fail(QG_ERR_ARG, "%s: freq_hi %g Hz x dt %g s > 0.5: the phase would advance by more than half a period per env-step", who,
@@ -397,9 +354,6 @@ extern "C" int qg_sched_advance_device(qg_sched *p, const void *done, int32_t do
     memcpy(A.w, p->desc.weights, sizeof A.w);
     A.threshold = c->desc.force_threshold;
     A.done_kind = done_kind, A.done_stride = done ? done_stride : 1;
-    A.reward_stride = reward_stride, A.out_reward_stride = reward_out_stride, A.comp_stride = components_stride;
-    A.base_stride = base_stride, A.base_terms = base_terms, A.copy_base = (base_components && base_terms > 0 && !in_place) ? 1 : 0;
-    A.command_stride = command_stride;
     A.obs_stride = obs_stride, A.obs_dim = obs_dim, A.out_stride = out_stride;
     A.term_obs_stride = terminal_obs_stride, A.term_out_stride = terminal_out_stride;
     const dim3 grid((unsigned)((s->n + QGC_ENVS - 1) / QGC_ENVS)), block(QGC_ENVS * 16);

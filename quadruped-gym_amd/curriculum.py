@@ -13,44 +13,10 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import CMDCUR_MAX_BINS, CMDCUR_MAX_CRITERIA, CMDCUR_MAX_SIDE, CMDCUR_MAX_WEIGHT, check
+from ._abi import CMDCUR_MAX_CRITERIA, CMDCUR_MAX_SIDE, CMDCUR_MAX_WEIGHT, QgCmdCurDesc, check
+from ._abi import CMDCUR_MAX_BINS, QgCmdCurCriterion                           # (re-exported: names this module has always had)
 from .envs.device_wrapper import STEP_BUFFERS, DeviceVecEnvWrapper, base_env, stack_layers
 from .task_layers import _TaskLayer
-
-
-class QgCmdCurCriterion(C.Structure):
-    _fields_ = [("column", C.c_int32), ("sense", C.c_int32), ("threshold", C.c_float)]
-
-
-class QgCmdCurDesc(C.Structure):
-    """``qg_cmdcur_desc``: the grid, the weights' limits, the segment's length and criteria, the key (``make`` fills ``struct_size``)."""
-    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("n_speed", C.c_int32), ("n_alpha", C.c_int32), ("speed_lo", C.c_float),
-                ("speed_hi", C.c_float), ("fixed_heading", C.c_int32), ("heading_angle", C.c_float), ("weight_max", C.c_int32),
-                ("delta", C.c_int32), ("resample_steps", C.c_int32), ("min_steps", C.c_int32), ("n_criteria", C.c_int32),
-                ("reserved2", C.c_int32), ("criteria", QgCmdCurCriterion * CMDCUR_MAX_CRITERIA),
-                ("initial_weights", C.c_int32 * CMDCUR_MAX_BINS), ("seed", C.c_uint64), ("env_index_base", C.c_uint64)]
-
-    @classmethod
-    def make(cls, speed=(0.0, 1.0), bins=(1, 1), initial_weights=(1,), weight_max=1, delta=1, resample_steps=0, min_steps=1, criteria=(),
-             fixed_heading=None, seed=0, env_index_base=0):
-        """``criteria``: up to 4 ``(column, sense, threshold)``; ``fixed_heading``: None (theta is drawn) or the angle in rad."""
-        d = cls()
-        d.struct_size = C.sizeof(cls)
-        if len(initial_weights) > CMDCUR_MAX_BINS:
-            raise ValueError(f"initial_weights: at most {CMDCUR_MAX_BINS} bins, got {len(initial_weights)}")
-        if len(criteria) > CMDCUR_MAX_CRITERIA:
-            raise ValueError(f"criteria: at most {CMDCUR_MAX_CRITERIA}, got {len(criteria)}")
-        d.n_speed, d.n_alpha = int(bins[0]), int(bins[1])
-        d.speed_lo, d.speed_hi = float(speed[0]), float(speed[1])
-        d.fixed_heading, d.heading_angle = (0, 0.0) if fixed_heading is None else (1, float(fixed_heading))
-        d.weight_max, d.delta, d.resample_steps, d.min_steps = int(weight_max), int(delta), int(resample_steps), int(min_steps)
-        d.n_criteria = len(criteria)
-        for k, (column, sense, threshold) in enumerate(criteria):
-            d.criteria[k].column, d.criteria[k].sense, d.criteria[k].threshold = int(column), int(sense), float(threshold)
-        for b, w in enumerate(initial_weights):
-            d.initial_weights[b] = int(w)
-        d.seed, d.env_index_base = int(seed) % (1 << 64), int(env_index_base)
-        return d
 
 
 def grid_edges(speed, bins):
@@ -124,11 +90,6 @@ class CommandCurriculum(_TaskLayer):
         self.desc = QgCmdCurDesc.make((lo, hi), (ns, na), w.tolist(), weight_max, delta, resample_steps, min_steps, criteria, fixed_heading,
                                       seed, self.env_index_base)
         self._create("qg_cmdcur_create", walk._h, C.byref(self.desc))
-
-    def state_bytes(self) -> int:
-        nbytes = C.c_int64()
-        check(self._lib.qg_cmdcur_state_bytes(self._h, C.byref(nbytes)), "qg_cmdcur_state_bytes")
-        return int(nbytes.value)
 
     def grid(self):
         """``(speed_edges, alpha_edges)`` float32: bin ``(si, ai)`` draws from ``[speed_edges[si], speed_edges[si] + ws)`` and

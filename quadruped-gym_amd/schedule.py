@@ -11,55 +11,22 @@ device code on the simulator's state; the sensor's timers are neither read nor w
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import json
 import os
 
 import numpy as np
 
-from . import _abi
-from ._abi import SCHED_DIM, SCHED_MAX_BASE_TERMS, SCHED_MAX_GAITS, SCHED_TERMS, check
-from .envs.device_wrapper import STEP_BUFFERS, DeviceVecEnvWrapper, stack_layer, stack_layers
+from . import _abi, shaped
+from ._abi import SCHED_DIM, SCHED_MAX_GAITS, SCHED_TERMS, QgSchedDesc, check
+from ._abi import SCHED_MAX_BASE_TERMS, QgSchedGait                            # (re-exported: names this module has always had)
+from .envs.device_wrapper import STEP_BUFFERS, DeviceVecEnvWrapper, stack_layer
+from .envs.device_wrapper import stack_layers                                  # (re-exported)
 from .envs.spaces import Box
 from .task_layers import _TaskLayer
 
 NTERMS = len(SCHED_TERMS)
 DONE_ROWS = {"reset": _abi.PERTURB_DONE_ROW_RESET, "terminal": _abi.PERTURB_DONE_ROW_TERMINAL}
-
-
-class QgSchedGait(C.Structure):
-    _fields_ = [("offset", C.c_float * 4), ("duty", C.c_float)]
-
-
-class QgSchedDesc(C.Structure):
-    """``qg_sched_desc``: the gait table, the draws' ranges and key, the terms' constants and weights (``make`` fills ``struct_size``)."""
-    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("n_gaits", C.c_int32), ("random_phase", C.c_int32),
-                ("done_row", C.c_int32), ("freq_lo", C.c_float), ("freq_hi", C.c_float), ("kappa", C.c_float), ("sigma_force", C.c_float),
-                ("sigma_velocity", C.c_float), ("swing_height_target", C.c_float), ("min_command_speed", C.c_float),
-                ("weights", C.c_float * NTERMS), ("gaits", QgSchedGait * SCHED_MAX_GAITS), ("seed", C.c_uint64),
-                ("env_index_base", C.c_uint64)]
-
-    @classmethod
-    def make(cls, gaits=(((0.0, 0.0, 0.0, 0.0), 0.5),), freq=(1.0, 1.0), weights=(0.0,) * NTERMS, random_phase=False, done_row=0, kappa=0.0,
-             sigma_force=1.0, sigma_velocity=1.0, swing_height_target=0.0, min_command_speed=0.0, seed=0, env_index_base=0):
-        """``gaits``: up to 8 ``(offsets[4], duty)`` rows."""
-        d = cls()
-        d.struct_size = C.sizeof(cls)
-        if len(gaits) > SCHED_MAX_GAITS:
-            raise ValueError(f"gaits: at most {SCHED_MAX_GAITS} rows, got {len(gaits)}")
-        d.n_gaits, d.random_phase, d.done_row = len(gaits), 1 if random_phase else 0, int(done_row)
-        for g, (offsets, duty) in enumerate(gaits):
-            if len(offsets) != 4:
-                raise ValueError(f"gaits[{g}]: four offsets, got {len(offsets)}")
-            for f, off in enumerate(offsets):
-                d.gaits[g].offset[f] = float(off)
-            d.gaits[g].duty = float(duty)
-        d.freq_lo, d.freq_hi, d.kappa = float(freq[0]), float(freq[1]), float(kappa)
-        d.sigma_force, d.sigma_velocity = float(sigma_force), float(sigma_velocity)
-        d.swing_height_target, d.min_command_speed = float(swing_height_target), float(min_command_speed)
-        for k, w in enumerate(weights):
-            d.weights[k] = float(w)
-        d.seed, d.env_index_base = int(seed) % (1 << 64), int(env_index_base)
-        return d
 
 
 # ---- the presets ----------------------------------------------------------------------------------------------------------------------------
@@ -108,18 +75,7 @@ def _packaged_hips():
 GAITS = gait_presets(_packaged_hips())
 
 
-def term_weights(weights) -> list:
-    """``[4]`` floats in the order of ``SCHED_TERMS`` from ``{name: w}`` (missing names weigh 0) or None (all 0).  An unknown name or a
-    non-finite weight raises ``ValueError``."""
-    weights = dict(weights or {})
-    unknown = sorted(set(weights) - set(SCHED_TERMS))
-    if unknown:
-        raise ValueError(f"weights: unknown reward terms {unknown}: one of {', '.join(SCHED_TERMS)}")
-    out = [float(weights.get(name, 0.0)) for name in SCHED_TERMS]
-    for name, w in zip(SCHED_TERMS, out):
-        if not np.isfinite(w):
-            raise ValueError(f"weights[{name!r}] must be finite, got {w}")
-    return out
+term_weights = functools.partial(shaped.term_weights, terms=SCHED_TERMS)      # ``[4]`` floats in the order of ``SCHED_TERMS``
 
 
 def gait_table(gaits) -> list:
@@ -144,7 +100,7 @@ def gait_table(gaits) -> list:
     return rows
 
 
-class GaitSchedule(_TaskLayer):
+class GaitSchedule(shaped.ShapedReward, _TaskLayer):
     """Bound to ``sensor`` (a ``ContactSensor``; this is its ``Handle`` child, so it is destroyed before it).  ``gaits``: preset names
     (``GAITS``) and / or ``(offsets[4], duty)`` rows, 1 to 8 of them; each episode of each env draws one of them, a frequency from
     ``freq = (lo, hi)`` Hz and, with ``random_phase``, its starting phase, keyed by ``(seed, env_index_base + i, episode)``.  The terms,
@@ -192,18 +148,6 @@ class GaitSchedule(_TaskLayer):
                                      **limits)
         self._create("qg_sched_create", sensor._h, C.byref(self.desc))
 
-    def state_bytes(self) -> int:
-        nbytes = C.c_int64()
-        check(self._lib.qg_sched_state_bytes(self._h, C.byref(nbytes)), "qg_sched_state_bytes")
-        return int(nbytes.value)
-
-    def set_weights(self, weights):
-        """New weights ``{name: w}`` for the launches that follow (missing names keep their weight); a captured graph keeps the
-        weights it was captured with."""
-        w = term_weights(dict(self.weights, **dict(weights)))
-        check(self._lib.qg_sched_set_weights(self._h, (C.c_float * NTERMS)(*w)), "qg_sched_set_weights")
-        self.weights = dict(zip(SCHED_TERMS, w))
-
     def gaits(self):
         """NumPy (waits for the device): ``gait`` int32 ``[N]`` (the row of the table), ``freq`` float32 ``[N]`` and ``phi`` uint32
         ``[N]`` of the running episodes."""
@@ -212,11 +156,6 @@ class GaitSchedule(_TaskLayer):
         return {"gait": gait, "freq": freq, "phi": phi}
 
     # -- device path ------------------------------------------------------------------------
-    @staticmethod
-    def _span(t, width, stride):
-        lo = t.data_ptr()
-        return lo, lo + 4 * ((t.shape[0] - 1) * stride + width)
-
     def _wide_pair(self, narrow, wide, names, width=None):
         """The checks of an ``(obs, out)`` pair: ``(obs pointer, obs stride, O, out pointer, out stride)``.  ``narrow`` may be None
         (``O = width or 0``) and may be ``wide[:, :O]`` itself (in place); any other overlap raises."""
@@ -230,10 +169,9 @@ class GaitSchedule(_TaskLayer):
         if wide is None:
             return n_ptr, n_stride, O, None, 0
         w_stride = self._check_rows(wide, O + SCHED_DIM, names[1])
-        if narrow is not None and O and not (n_ptr == wide.data_ptr() and n_stride == w_stride):
-            (a0, a1), (b0, b1) = self._span(narrow, O, n_stride), self._span(wide, O + SCHED_DIM, w_stride)
-            if a0 < b1 and b0 < a1:
-                raise ValueError(f"{names[0]} and {names[1]} overlap: allowed only where {names[0]} is {names[1]}[:, :O]")
+        if narrow is not None:
+            shaped.refuse_overlap(narrow, O, n_stride, wide, O + SCHED_DIM, w_stride,
+                                  f"{names[0]} and {names[1]} overlap: allowed only where {names[0]} is {names[1]}[:, :O]")
         return n_ptr, n_stride, O, wide.data_ptr(), w_stride
 
     def step(self, done=None, reward=None, reward_out=None, components=None, base_components=None, command=None, obs=None, out=None,
@@ -248,28 +186,6 @@ class GaitSchedule(_TaskLayer):
         ``done_row="reset"`` only: the finished envs' rows get the old episode's columns.  A bad argument raises ``ValueError``
         before any launch."""
         import torch
-        n, dev = self.num_envs, self._torch_device()
-        d_ptr, kind, d_stride = self._done_arg(done)
-        r_ptr, r_stride = None, 1
-        if reward is not None:
-            r_stride, r_ptr = self._check_vec(reward, (torch.float32,), "reward"), reward.data_ptr()
-        o_stride = 1 if reward_out is None else self._check_vec(reward_out, (torch.float32,), "reward_out")
-        b_ptr, b_stride, c0 = None, 0, 0
-        if base_components is not None:
-            if base_components.dim() != 2 or not 0 <= base_components.shape[1] <= SCHED_MAX_BASE_TERMS:
-                raise ValueError(f"base_components: expected [N, C0] with C0 <= {SCHED_MAX_BASE_TERMS}, got {tuple(base_components.shape)}")
-            c0 = int(base_components.shape[1])
-            b_stride, b_ptr = self._check_rows(base_components, c0, "base_components"), base_components.data_ptr()
-        c_stride = c0 + NTERMS
-        if components is not None:
-            c_stride = self._check_rows(components, c0 + NTERMS, "components")
-            if c0 and not (b_ptr == components.data_ptr() and b_stride == c_stride):
-                (a0, a1), (b0, b1) = self._span(base_components, c0, b_stride), self._span(components, c0 + NTERMS, c_stride)
-                if a0 < b1 and b0 < a1:
-                    raise ValueError("base_components and components overlap: allowed only where base_components is components[:, :C0]")
-        m_ptr, m_stride = None, 2
-        if command is not None:
-            m_stride, m_ptr = self._check_rows(command, 2, "command"), command.data_ptr()
         if terminal_out is not None and self.done_row != "reset":
             raise ValueError("terminal_out goes with done_row='reset': with 'terminal' the row itself is the terminal observation")
         if terminal_out is None and terminal_obs is not None:
@@ -278,16 +194,12 @@ class GaitSchedule(_TaskLayer):
         t_ptr, t_stride, _, to_ptr, to_stride = self._wide_pair(terminal_obs, terminal_out, ("terminal_obs", "terminal_out"), O)
         if terminal_out is not None and terminal_obs is None and O:
             raise ValueError(f"terminal_out without terminal_obs: the rows in front are {O} wide")
-        if reward_out is None:
-            reward_out = torch.empty(n, device=dev, dtype=torch.float32)
-        if components is None:
-            components = torch.empty((n, c0 + NTERMS), device=dev, dtype=torch.float32)
+        done3, rows11, components, reward_out = self._shaped_args(done, reward, reward_out, components, base_components, command)
         if obs is not None and out is None:
-            out = torch.empty((n, O + SCHED_DIM), device=dev, dtype=torch.float32)
+            out = torch.empty((self.num_envs, O + SCHED_DIM), device=self._torch_device(), dtype=torch.float32)
             out_ptr, out_stride = out.data_ptr(), O + SCHED_DIM
-        check(self._lib.qg_sched_advance_device(self._h, d_ptr, kind, d_stride, r_ptr, r_stride, reward_out.data_ptr(), o_stride, components.data_ptr(),
-                                           c_stride, b_ptr, b_stride, c0, m_ptr, m_stride, obs_ptr, obs_stride, O, out_ptr, out_stride, t_ptr,
-                                           t_stride, to_ptr, to_stride, self._stream_ptr(stream)), "qg_sched_advance_device")
+        check(self._lib.qg_sched_advance_device(self._h, *done3, *rows11, obs_ptr, obs_stride, O, out_ptr, out_stride, t_ptr, t_stride, to_ptr, to_stride,
+                                           self._stream_ptr(stream)), "qg_sched_advance_device")
         return components, reward_out, out
 
     def begin(self, mask=None, rows=None, obs_dim: int | None = None, stream=None):
@@ -324,7 +236,7 @@ def clock_columns(table, gait, freq, phi):
     return cols.astype(np.float32)
 
 
-class DeviceGaitScheduleVecEnv(DeviceVecEnvWrapper):
+class DeviceGaitScheduleVecEnv(shaped.CommandGated, DeviceVecEnvWrapper):
     """The gait schedule around ``WalkingQuadrupedVecEnv`` or ``POWalkingQuadrupedVecEnv`` (or a device-side wrapper around one):
     ``obs_dim`` / ``observation_space`` / ``terminal_obs`` are 10 wider -- the clock columns behind the env's observation --,
     ``step_tensor`` runs the env's launch into the wrapper's own ``[N, O]`` rows, then the schedule's launch on the same stream, and
@@ -345,7 +257,6 @@ class DeviceGaitScheduleVecEnv(DeviceVecEnvWrapper):
     Every other attribute passes through to the wrapped env."""
 
     _snapshot_key = "gait_schedule"
-    PO_COMMAND = 23                        # the command's vx, vy in a partially observable frame (po_walking_quad.py:48-56)
 
     def __init__(self, venv, gaits=("trot",), freq=(1.5, 1.5), weights=None, force_threshold: float = 1.0, gate_on_command: bool = False,
                  seed: int = 0, env_index_base: int | None = None, **options):
@@ -356,12 +267,8 @@ class DeviceGaitScheduleVecEnv(DeviceVecEnvWrapper):
         if stack_layer(venv, "privileged") is not None:
             raise ValueError("DeviceGaitScheduleVecEnv around DevicePrivilegedVecEnv: the actor's window [0 : actor_obs_dim] would miss the "
                              "clock columns; put the schedule inside, DevicePrivilegedVecEnv(DeviceGaitScheduleVecEnv(env))")
-        if gate_on_command and not hasattr(venv, "obs_window"):
-            raise ValueError("gate_on_command: only the partially observable env's observation holds the command")
-        if gate_on_command and any(layer._snapshot_key == "normalizer" and layer.normalizer.norm_obs for layer in stack_layers(venv)):
-            raise ValueError("gate_on_command around a DeviceVecNormalize that normalises observations: the gate would compare normalised "
-                             "command columns with min_command_speed in m/s; put the schedule inside, "
-                             "DeviceVecNormalize(DeviceGaitScheduleVecEnv(env, gate_on_command=True))")
+        self._check_gate(venv, gate_on_command,
+                         "put the schedule inside, DeviceVecNormalize(DeviceGaitScheduleVecEnv(env, gate_on_command=True))")
         po = hasattr(venv, "obs_window")                    # its finished rows hold the new episode's reset stack
         base = venv._sim.env_index_base if env_index_base is None else env_index_base
         self.schedule = GaitSchedule(venv.contact_sensor(force_threshold), gaits, freq, weights, done_row="reset" if po else "terminal",
@@ -377,21 +284,6 @@ class DeviceGaitScheduleVecEnv(DeviceVecEnvWrapper):
     @property
     def reward_keys(self):
         return list(self.venv.reward_keys) + list(SCHED_TERMS)
-
-    def _command(self, obs):
-        """The newest frame's (vx, vy) of the env's stacked observation, as a strided view."""
-        if not self.gate_on_command:
-            return None
-        lo = (self.venv.obs_window - 1) * self.venv.FRAME + self.PO_COMMAND
-        return obs[:, lo:lo + 2]
-
-    def _rows(self, name, width):
-        import torch
-        buf = getattr(self, name)
-        if buf is None or buf.shape[1] != width:
-            buf = torch.empty((self.num_envs, width), device=self.schedule._torch_device(), dtype=torch.float32)
-            setattr(self, name, buf)
-        return buf
 
     # -- device path ------------------------------------------------------------------------
     def step_tensor(self, actions, *args, **kwargs):

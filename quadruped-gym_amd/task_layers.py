@@ -35,10 +35,15 @@ class _TaskLayer(Handle):
 
     def state_bytes(self) -> int:
         what = self._abi_prefix + "_state_bytes"
-        nbytes = int(getattr(self._lib, what)(self._h))
-        if nbytes <= 0:                   # the C side reports errors as small negative numbers
-            check(nbytes if nbytes < 0 else -1, what)
-        return nbytes
+        fn = getattr(self._lib, what)
+        if isinstance(_abi.PROTOTYPES[what], tuple):        # the size is the result
+            nbytes = int(fn(self._h))
+            if nbytes <= 0:               # the C side reports errors as small negative numbers
+                check(nbytes if nbytes < 0 else -1, what)
+            return nbytes
+        nbytes = C.c_int64()                                # the status is the result, the size comes through a pointer
+        check(fn(self._h, C.byref(nbytes)), what)
+        return int(nbytes.value)
 
     def state(self):
         """The layer's per-env state as one ``uint8`` blob; ``load_state(blob)`` on a layer of the same shape continues bit for bit."""

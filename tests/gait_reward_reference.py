@@ -4,6 +4,8 @@ in float64 or in float32 in the stated order; the term names, the parameters, wa
 share, and the error budget measured by tests/test_gait_reward_reference.py.  No GPU, no torch."""
 import numpy as np
 
+import shaped_reward_reference as S
+
 TERMS = ("feet_air_time", "feet_slip", "feet_clearance", "touchdown_speed", "feet_contact_force", "body_contact", "flight")
 NTERMS = len(TERMS)
 FEET = (3, 6, 9, 12)
@@ -55,7 +57,7 @@ MARGIN = 4.0          # a different but equally valid rounding order (contractio
 
 def weight_vector(weights, dtype=np.float64):
     """[7] in the order of TERMS, as the float32 values the C ABI takes."""
-    return np.array([np.float32(weights.get(name, 0.0)) for name in TERMS], np.float32).astype(dtype)
+    return S.weight_vector(weights, TERMS, dtype)
 
 
 def evaluate(body_force, feet, done=None, command=None, reward=None, base=None, *, weights, air_time_target, clearance_target,
@@ -90,37 +92,22 @@ def evaluate(body_force, feet, done=None, command=None, reward=None, base=None, 
         cmd = np.asarray(command, np.float32)
         gate = np.maximum(np.abs(cmd[:, 0]), np.abs(cmd[:, 1])) > np.float32(min_command_speed)
         terms[:, 0] = np.where(gate, terms[:, 0], T(0))
-    comps = (weight_vector(weights, T)[None] * terms).astype(T)
-    finished = np.zeros(n, bool) if done is None else np.asarray(done) != 0
-    comps[finished] = 0
-    shaped = comps[:, 0].copy()
-    for k in range(1, NTERMS):                                    # ascending k
-        shaped = (shaped + comps[:, k]).astype(T)
-    if reward is None:
-        out = shaped.copy()
-    else:
-        rew = np.asarray(reward, np.float32).astype(T)
-        out = np.where(finished, rew, (rew + shaped).astype(T))
-    wide = comps if base is None else np.concatenate([np.asarray(base, np.float32).astype(T), comps], axis=1)
-    return dict(terms=terms, components=comps, shaped=shaped, reward_out=out, wide=wide)
+    return dict(S.tail(terms, weights, TERMS, done, reward, base, T), terms=terms)
 
 
 def term_tolerance(terms64, margin=1.0):
     """[n, 7]: margin x (atol + rtol |t64|) per unweighted term."""
-    t = np.abs(np.asarray(terms64, np.float64))
-    return margin * np.stack([BUDGET_TERM[name][0] + BUDGET_TERM[name][1] * t[:, k] for k, name in enumerate(TERMS)], axis=1)
+    return S.term_tolerance(terms64, TERMS, BUDGET_TERM, margin)
 
 
 def component_tolerance(ref, weights, margin=1.0):
     """[n, 7]: the terms' bounds times |w_k|, and the one rounding of f32(w_k x term_k)."""
-    w = np.abs(weight_vector(weights))
-    return w[None] * term_tolerance(ref["terms"], margin) + margin * 2.0 ** -24 * np.abs(ref["components"])
+    return S.component_tolerance(ref, weights, TERMS, BUDGET_TERM, margin)
 
 
 def reward_tolerance(ref, weights, reward=None, margin=1.0):
     """[n]: the components' bounds summed, and BUDGET_SUM_ULPS roundings of half an ulp of the magnitudes added."""
-    size = np.abs(ref["components"]).sum(1) + (0.0 if reward is None else np.abs(np.asarray(reward, np.float64)))
-    return component_tolerance(ref, weights, margin).sum(1) + margin * BUDGET_SUM_ULPS * 2.0 ** -24 * size
+    return S.reward_tolerance(ref, weights, TERMS, BUDGET_TERM, BUDGET_SUM_ULPS, reward, margin)
 
 
 # ---- synthetic rows on the fixture's states ----------------------------------------------------------------------------------------------

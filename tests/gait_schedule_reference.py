@@ -5,6 +5,7 @@ tests share, and the error budget measured by tests/test_gait_schedule_reference
 import numpy as np
 
 import perturb_reference as P
+import shaped_reward_reference as S
 
 TERMS = ("swing_force", "stance_velocity", "swing_height", "contact_match")
 NTERMS, DIM = len(TERMS), 10
@@ -152,7 +153,7 @@ def columns(view, gaits=TABLE, dtype=np.float64):
 
 
 def weight_vector(weights, dtype=np.float64):
-    return np.array([np.float32(weights.get(name, 0.0)) for name in TERMS], np.float32).astype(dtype)
+    return S.weight_vector(weights, TERMS, dtype)
 
 
 def evaluate(view, body_force, feet, done=None, command=None, reward=None, base=None, *, gaits=TABLE, weights=WEIGHTS, kappa=KAPPA,
@@ -185,35 +186,20 @@ def evaluate(view, body_force, feet, done=None, command=None, reward=None, base=
             acc = (acc + a[:, f]).astype(T)
         terms[:, j] = acc
     terms[:, 3] = (contact == hard).sum(1)
-    comps = (weight_vector(weights, T)[None] * terms).astype(T)
-    finished = np.zeros(n, bool) if done is None else np.asarray(done) != 0
-    comps[finished] = 0
-    shaped = comps[:, 0].copy()
-    for j in range(1, NTERMS):                                    # ascending k
-        shaped = (shaped + comps[:, j]).astype(T)
-    if reward is None:
-        out = shaped.copy()
-    else:
-        rew = np.asarray(reward, np.float32).astype(T)
-        out = np.where(finished, rew, (rew + shaped).astype(T))
-    wide = comps if base is None else np.concatenate([np.asarray(base, np.float32).astype(T), comps], axis=1)
-    return dict(hard=hard, s=s, contact=contact, terms=terms, components=comps, shaped=shaped, reward_out=out, wide=wide)
+    return dict(S.tail(terms, weights, TERMS, done, reward, base, T), hard=hard, s=s, contact=contact, terms=terms)
 
 
 def term_tolerance(terms64, margin=1.0):
-    t = np.abs(np.asarray(terms64, np.float64))
-    return margin * np.stack([BUDGET_TERM[name][0] + BUDGET_TERM[name][1] * t[:, j] for j, name in enumerate(TERMS)], axis=1)
+    return S.term_tolerance(terms64, TERMS, BUDGET_TERM, margin)
 
 
 def component_tolerance(ref, weights=WEIGHTS, margin=1.0):
     """[n, 4]: the terms' bounds times |w_k|, and the one rounding of f32(w_k x term_k)."""
-    w = np.abs(weight_vector(weights))
-    return w[None] * term_tolerance(ref["terms"], margin) + margin * 2.0 ** -24 * np.abs(ref["components"])
+    return S.component_tolerance(ref, weights, TERMS, BUDGET_TERM, margin)
 
 
 def reward_tolerance(ref, weights=WEIGHTS, reward=None, margin=1.0):
-    size = np.abs(ref["components"]).sum(1) + (0.0 if reward is None else np.abs(np.asarray(reward, np.float64)))
-    return component_tolerance(ref, weights, margin).sum(1) + margin * BUDGET_SUM_ULPS * 2.0 ** -24 * size
+    return S.reward_tolerance(ref, weights, TERMS, BUDGET_TERM, BUDGET_SUM_ULPS, reward, margin)
 
 
 def clock_tolerance(margin=1.0):
